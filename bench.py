@@ -82,6 +82,10 @@ def parse(argv=None):
                          "<= 6e-11 relative at worst; the measured max |dt| is in the line) or accurate (the library's default tier)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (by rank 0; at --gpus > 1 the table "
+                         "all-gathered from every rank's rows; arrays over their share of 64 MB as a fixed seeded sample, with the "
+                         "flat indices in DIR/<name>_sample_index.npy)")
     args = ap.parse_args(argv)
     if args.workload == "auto":
         args.workload = "cfg3_planar" if args.gpus <= 1 else "cfg4_lens_f32"
@@ -254,6 +258,44 @@ class Timed:
         return dt, ev0.elapsed_time(ev1) / self.steps
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # --dump-outputs: all files together stay under 64 MB (room left for the .npy headers)
+
+
+def dump_sample_index(size, n, seed=0):
+    """Flat indices of a fixed, seeded sample of `n` of `size` elements: one per stratum of `size / n` consecutive elements,
+    so the sample is sorted, free of duplicates and spread over the whole array.  `n >= size` -> every element."""
+    if n >= size:
+        return np.arange(size, dtype=np.int64)
+    edges = (np.arange(n + 1, dtype=np.int64) * size) // n
+    rng = np.random.default_rng(seed)
+    return edges[:-1] + (rng.random(n) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(torch, arrays, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: write each device array of `arrays` ({name: tensor}) as out_dir/<name>.npy, floats in their own precision,
+    integer arrays as float64 (exact).  An array bigger than its share of `budget` is written as a seeded sample of its
+    flattened elements (dump_sample_index), with the flat indices beside it as <name>_sample_index.npy (float64, exact).
+    -> {name: what was written}, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        dt = np.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.uint8, torch.int8, torch.bool) else np.float64
+        word = np.dtype(dt).itemsize
+        flat = t.reshape(-1)
+        if flat.numel() * word <= share:
+            idx = None
+            vals = flat.cpu().numpy().astype(dt)
+        else:
+            idx = dump_sample_index(flat.numel(), share // (word + 8), seed)
+            vals = flat[torch.as_tensor(idx, device=flat.device)].cpu().numpy().astype(dt)
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), vals)
+        written[name] = {"shape": list(t.shape), "dtype": np.dtype(dt).name,
+                         "sampled": None if idx is None else f"{idx.size} of {flat.numel()} elements (seed {seed})"}
+    return written
+
+
 def load_profile_json(name):
     """profiles/<name>: the newest round's file wins (r04 over r03 over ...)."""
     for tag in ("r04", "r03", "r02", "r01"):
@@ -370,6 +412,13 @@ def main(argv=None):
 
         def reassemble():               # the one exchange of the path: RCCL all-gather of the row blocks over xGMI
             m.gather(0)
+
+        def last_outputs():             # what the caller of the path receives, from the last step's slot: the whole table, reassembled
+            b = (args.steps - 1) % slots  # from every rank's rows at N > 1 (a collective: every rank calls it)
+            if world == 1:
+                return {"tt": m.local(b)[:n_e]}, "the whole table"
+            m.gather(b)
+            return {"tt": m.matrix(b)}, f"the whole table, all-gathered from {world} ranks' rows"
     else:
         R = ref_inputs(wl)
         G, T, N = R["geoms"].shape[0], R["xa"].size, R["n"]
@@ -390,6 +439,9 @@ def main(argv=None):
 
         def reassemble():
             pass
+
+        def last_outputs():
+            return dict(plan.out), "rank 0's outputs (every rank runs the whole sweep)"
 
         gather_step = gather_end = gather_after = False     # independent rows per rank, no table to reassemble
 
@@ -434,6 +486,12 @@ def main(argv=None):
         except Exception as exc:
             gather_error = repr(exc)
             print(f"[bench] all-gather failed: {gather_error}", file=sys.stderr)
+    dumped = None
+    if args.dump_outputs:                           # after the timed region (and the timed reassembly): what its last step computed
+        arrays, what = last_outputs()
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs, "what": what, "arrays": dump_outputs(torch, arrays, args.dump_outputs)}
+        barrier()
 
     total_units = total_units_per_step * args.steps
     value = total_units / dt / 1e6
@@ -466,6 +524,8 @@ def main(argv=None):
                        f" (after ~{PREWARM_MS:.0f} ms of untimed replays: clock ramp)") if graph_on else "eager launches",
         },
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if reassembly_ms is not None:
         shard_bytes = m.per * n_f * word
         per_step_s = dt / args.steps

@@ -58,3 +58,20 @@ def test_refuses_to_run_without_a_gpu():
     if p.returncode == 0:            # a GPU box that ignores the masking variables: nothing to check here
         return
     assert "needs a GPU" in (p.stderr + p.stdout)
+
+
+def test_dump_outputs_flag_and_sample(tmp_path):
+    import torch
+    assert bench.parse([]).dump_outputs is None and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    idx = bench.dump_sample_index(10 ** 9 + 7, 1000, seed=0)
+    assert idx.size == 1000 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 10 ** 9 + 7
+    assert np.array_equal(idx, bench.dump_sample_index(10 ** 9 + 7, 1000, seed=0))
+    assert np.array_equal(bench.dump_sample_index(5, 9), np.arange(5))
+    t = torch.arange(4000, dtype=torch.float64).reshape(40, 100)
+    w = bench.dump_outputs(torch, {"tt": t, "hit": (t < 7).to(torch.uint8), "first": t.to(torch.int32)[:2]}, str(tmp_path),
+                           budget=3 * 16000)
+    assert w["first"]["sampled"] is None and w["hit"]["sampled"] is None and w["tt"]["sampled"]
+    assert np.load(tmp_path / "hit.npy").dtype == np.float32 and np.load(tmp_path / "hit.npy").sum() == 7
+    assert np.array_equal(np.load(tmp_path / "first.npy"), np.arange(200.0))
+    v, i = np.load(tmp_path / "tt.npy"), np.load(tmp_path / "tt_sample_index.npy")
+    assert v.size == 16000 // 16 and np.array_equal(v, i)

@@ -142,6 +142,25 @@ def test_bench_reference_sweep_workload_two_ranks():
     assert "true>" in d["roofline"]["kernel"] and "reference sweep" in d["config"]["workload"] and "no exchange" in d["config"]["sharding"]
 
 
+def test_bench_dump_outputs_two_ranks_is_the_one_process_table(tmp_path):
+    """--dump-outputs at N = 2 writes the table every rank holds after the reassembly, not rank 0's shard: the same bits as the
+    one-process run of the same (rehearsal-sized) workload."""
+    import json
+    import subprocess
+    d = _run_bench_two_ranks(["--no-extra", "--dump-outputs", str(tmp_path / "two")])
+    assert d["dump_outputs"]["what"].startswith("the whole table, all-gathered from 2 ranks")
+    env = dict(os.environ, RTUS_BENCH_SMALL="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg4_lens_f32", "--steps", "4",
+                        "--warmup", "2", "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "one")],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    one = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["dump_outputs"]
+    assert one["arrays"]["tt"]["shape"] == d["dump_outputs"]["arrays"]["tt"]["shape"]
+    assert sorted(os.listdir(tmp_path / "two")) == sorted(os.listdir(tmp_path / "one")) == ["tt.npy"]
+    a, b = np.load(tmp_path / "two" / "tt.npy"), np.load(tmp_path / "one" / "tt.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b, equal_nan=True)
+
+
 def _tfm_worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
