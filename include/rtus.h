@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 103 /* 0.1.2: rtus_solve_workspace_bytes takes n_rx */
+#define RTUS_VERSION 104 /* 0.1.3: rtus_tt_surface* (one curved interface from a sampled profile) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -452,6 +452,46 @@ int rtus_tt_lens_f32_multi_dev(const rtus_lens *lens, double alpha_lo, double al
                                const float *const *d_xe, const float *const *d_ze, int n_e,
                                const float *const *d_xf, const float *const *d_zf, int n_f, float *const *d_tt,
                                const int *devices, int n_dev, void *const *streams, int gather);
+
+/* ------------------------------------------------------------------------------------------
+ * Element x focal-point Fermat travel times through ONE curved interface given as a measured profile (immersion through a
+ * pipe wall, a weld cap, a machined contour).  NOT IN THE REFERENCE — the build's own solver, "parity unpinned"; checked against
+ * tests/surface_numpy.py (itself checked against mpmath at 40 digits) and, on a flat profile, against rtus_tt_layers.
+ *
+ *   x0, dx        the profile's grid: sample k at x_k = x0 + k dx, dx > 0
+ *   zs   [n_s]    depths of the samples, n_s >= 4 (DEVICE memory in the _dev entry).  z points down.  The interface s(x) is the
+ *                 NATURAL cubic spline through (x_k, zs[k]) on the extent [x0, x0 + (n_s - 1) dx]
+ *   c1, c2        speed above the surface (medium 1, the couplant) and below it (medium 2, the part)
+ *   xe,ze [n_e]   elements, in medium 1: an element that is not strictly above s over the whole extent (ze >= min s) gets a NaN
+ *                 row.  Elements may lie horizontally outside the extent
+ *   xf,zf [n_f]   focal points: x0 <= xf <= x0 + (n_s - 1) dx and zf > s(xf), else NaN.  There is no direct path through medium 1
+ *   tt   [n_e][n_f]       travel times [s]: with S(x) = (x, s(x)) and, for x strictly inside the extent,
+ *                         T(x) = |E - S(x)| / c1 + |S(x) - F| / c2,  the LEAST T OVER THE INTERIOR LOCAL MINIMA of T — the first
+ *                         arriving ray that obeys Snell's law at the surface.  NaN when T has no interior local minimum (total
+ *                         internal reflection, minima outside the extent).  Occlusion is NOT checked: on a wavy profile either leg
+ *                         may cross the surface elsewhere.
+ *   x_entry [n_e][n_f]    nullable: x of the winning entry point
+ *
+ * Guarantee: every interior local minimum whose basin spans at least one profile segment dx centred on it is found — the basin
+ * running from the minimum to its neighbouring stationary points of T or to the ends of the extent; a minimum qualifies when
+ * each neighbouring STATIONARY point is at least dx / 2 away (an end of the extent always does).  Narrower minima may be
+ * missed; a missed minimum can only make the reported time later (or NaN), never earlier.
+ * Determinism: an entry depends only on its element, its focal point, the profile and the speeds — not on which other elements
+ * or focal points share the call (the bits of a row block or a focal-point subset are those of the whole table).
+ *
+ * The _dev entry runs a set-up kernel (the spline, into d_workspace: rtus_tt_surface_workspace_bytes(n_s) bytes, 256-byte
+ * aligned) and the table kernel on `stream`: no allocation, no host synchronisation (capturable).  n_s <= 2^22, n_e <= 524280.
+ * The host-buffer twin rtus_tt_surface stages everything through the device's arena.
+ * ---------------------------------------------------------------------------------------- */
+size_t rtus_tt_surface_workspace_bytes(int n_s);   /* 0 when n_s is out of range */
+int rtus_tt_surface_dev(double x0, double dx, const double *d_zs, int n_s, double c1, double c2,
+                        const double *d_xe, const double *d_ze, int n_e,
+                        const double *d_xf, const double *d_zf, int n_f,
+                        double *d_tt, double *d_x_entry, void *d_workspace, size_t workspace_bytes, void *stream);
+int rtus_tt_surface(double x0, double dx, const double *zs, int n_s, double c1, double c2,
+                    const double *xe, const double *ze, int n_e,
+                    const double *xf, const double *zf, int n_f,
+                    double *tt, double *x_entry, int device);
 
 /* ------------------------------------------------------------------------------------------
  * Consumers of a travel-time table.  NOT IN THE REFERENCE, which stops at the travel times

@@ -157,6 +157,12 @@ def lib():
     for name in ("rtus_tt_layers_rows_dev", "rtus_tt_lens_rows_dev", "rtus_tt_lens_f32_rows_dev", "rtus_tt_layers_multi",
                  "rtus_tt_lens_f32_multi", "rtus_tt_layers_multi_dev", "rtus_tt_lens_f32_multi_dev"):
         getattr(L, name).restype = ip
+    dd = C.c_double
+    L.rtus_tt_surface_workspace_bytes.argtypes = [ip]
+    L.rtus_tt_surface_workspace_bytes.restype = C.c_size_t
+    L.rtus_tt_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, vp, C.c_size_t, vp]
+    L.rtus_tt_surface.argtypes = [dd, dd, dp, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, ip]
+    L.rtus_tt_surface_dev.restype = L.rtus_tt_surface.restype = ip
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -179,4 +185,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_lens_f32_rows_dev", "rtus_tt_layers_multi", "rtus_tt_lens_f32_multi", "rtus_tt_layers_multi_dev",
            "rtus_tt_lens_f32_multi_dev", "rtus_sweep_workspace_bytes", "rtus_sweep_dev", "rtus_sweep",
            "rtus_tt_layers_ex_dev", "rtus_tt_layers_ex", "rtus_tt_layers_batch_ex_dev", "rtus_tt_layers_multi_ex",
-           "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev")
+           "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev",
+           "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface")

@@ -399,6 +399,31 @@ def solve_travel_times(x_a, z_a, x_rx, alpha, geoms=None, *, z_land=None, params
     return (tt, ar, ta, aa, nr) if all_roots else (tt, ar)
 
 
+def travel_time_surface(x0, dx, zs, c1, c2, xe, ze, xf, zf, *, return_entry=False, out=None, device=0):
+    """Element x focal-point Fermat travel times through ONE curved interface given as a sampled depth profile -> tt[n_e, n_f].
+
+    The interface is the natural cubic spline through ``zs[k]`` at ``x0 + k*dx`` (z down); speed ``c1`` above it (couplant),
+    ``c2`` below it (part).  An entry is the least travel time over the interior local minima of
+    T(x) = |E - S(x)|/c1 + |S(x) - F|/c2 — the first-arriving ray obeying Snell's law at the surface — and NaN without one
+    (total internal reflection, a minimum outside the extent), for an element not strictly above the whole profile, or for a
+    focal point outside the extent or not below the surface.  Occlusion is not checked.  ``return_entry``: also the x of the
+    winning entry point, -> (tt, x_entry).  ``out``: optional float64 [n_e, n_f] result buffer.  The table feeds
+    focal_delays / tfm_image as it is.  Definition and guarantee: include/rtus.h (rtus_tt_surface).
+
+    NOT in the reference (no measured profiles there): parity unpinned, see DESIGN.md.
+    """
+    zs = _f64(zs, "zs")
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    tt = _out(out, (xe.size, xf.size), np.float64)
+    xn = np.empty((xe.size, xf.size), dtype=np.float64) if return_entry else None
+    st = _lib.lib().rtus_tt_surface(float(x0), float(dx), _ptr(zs), zs.size, float(c1), float(c2), _ptr(xe), _ptr(ze), xe.size,
+                                    _ptr(xf), _ptr(zf), xf.size, _ptr(tt), _ptr(xn), int(device))
+    _lib.check(st, "rtus_tt_surface")
+    return (tt, xn) if return_entry else tt
+
+
 def focal_delays(tt, *, out=None, device=0):
     """Transmit focal law from a travel-time table tt[n_elem, n_focal]: the delay each element must be fired with so that
     all wavefronts reach the focal point together, delays[e, f] = max_e' tt[e', f] - tt[e, f] (elements without a ray

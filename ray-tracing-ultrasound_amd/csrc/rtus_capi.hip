@@ -54,6 +54,10 @@ hipError_t rtus_launch_tt_lens_f32(const rtus_lens& L, double a_lo, double a_hi,
                                    int n_e, const float* xf, const float* zf, int n_f, float* tt, float* alpha_out,
                                    int row0, long long n_rows_total, hipStream_t s, unsigned long long* stats = nullptr);
 
+hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* xe,
+                                  const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt, double* xent,
+                                  void* ws, hipStream_t s);
+size_t rtus_surface_ws_bytes(int n_s);
 hipError_t rtus_launch_focal_delays(const double* tt, int n_e, int n_f, double* delays, hipStream_t s);
 hipError_t rtus_launch_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                            const double* tt_rx, int n_f, float* image, hipStream_t s);
@@ -771,6 +775,58 @@ int rtus_tt_layers(const double* z_if, const double* c, int n_if, const double* 
                    const double* xf, const double* zf, int n_f, double* tt, uint8_t* iters, int device)
 {
     return rtus_tt_layers_ex(z_if, c, n_if, xe, ze, n_e, xf, zf, n_f, tt, iters, 0u, device);
+}
+
+// ---------------------------------------------------------------------------- one curved interface: a sampled profile
+#define RTUS_SURFACE_MAX_SAMPLES (1 << 22)
+static int check_surface(double x0, double dx, const void* zs, int n_s, double c1, double c2, const void* xe, const void* ze, int n_e,
+                         const void* xf, const void* zf, int n_f, const void* tt)
+{
+    if (!zs || !xe || !ze || !xf || !zf || !tt || n_s < 4 || n_e <= 0 || n_f <= 0) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(x0) || !isfinite(dx) || !(dx > 0) || !isfinite(c1) || !(c1 > 0) || !isfinite(c2) || !(c2 > 0)) return RTUS_ERR_INVALID_ARG;
+    if (n_s > RTUS_SURFACE_MAX_SAMPLES || n_e > 65535 * 8) return RTUS_ERR_UNSUPPORTED;   // grid.y: 8 elements per workgroup
+    return RTUS_OK;
+}
+
+size_t rtus_tt_surface_workspace_bytes(int n_s) { return n_s >= 4 && n_s <= RTUS_SURFACE_MAX_SAMPLES ? rtus_surface_ws_bytes(n_s) : 0; }
+
+int rtus_tt_surface_dev(double x0, double dx, const double* d_zs, int n_s, double c1, double c2, const double* d_xe, const double* d_ze,
+                        int n_e, const double* d_xf, const double* d_zf, int n_f, double* d_tt, double* d_x_entry, void* d_workspace,
+                        size_t workspace_bytes, void* stream)
+{
+    int st = check_surface(x0, dx, d_zs, n_s, c1, c2, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    LAUNCH_TRY(rtus_launch_tt_surface(x0, dx, d_zs, n_s, c1, c2, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, d_x_entry, d_workspace,
+                                      (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tt_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* xe, const double* ze, int n_e,
+                    const double* xf, const double* zf, int n_f, double* tt, double* x_entry, int device)
+{
+    int st = check_surface(x0, dx, zs, n_s, c1, c2, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_e * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    Session S;
+    if ((st = S.open(device, al256(8 * (size_t)n_s) + 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) + (x_entry ? 2 : 1) * al256(8 * tot) +
+                                 al256(wsb))))
+        return st;
+    double *dzs, *dxe, *dze, *dxf, *dzf;
+    S.upload(dzs, zs, n_s);
+    S.upload(dxe, xe, n_e);
+    S.upload(dze, ze, n_e);
+    S.upload(dxf, xf, n_f);
+    S.upload(dzf, zf, n_f);
+    double* dtt = S.take<double>(tot);
+    double* dxn = x_entry ? S.take<double>(tot) : nullptr;
+    void* ws = S.take<char>(wsb);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_tt_surface(x0, dx, dzs, n_s, c1, c2, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, ws, S.a->stream));
+    S.download(tt, dtt, tot);
+    S.download(x_entry, dxn, tot);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
 }
 
 // ---------------------------------------------------------------------------- consumers: focal laws, TFM

@@ -1,0 +1,335 @@
+// rtus_surface.hip — element x focal-point Fermat travel times through ONE curved interface given as a sampled depth
+// profile (natural cubic spline through zs[k] at x0 + k dx).  NOT IN THE REFERENCE (parity unpinned): checked against
+// tests/surface_numpy.py (itself checked against mpmath) and, on a flat profile, against the planar solver.
+//
+// T(x) = |E - S(x)| / c1 + |S(x) - F| / c2,  S(x) = (x, s(x));  the entry is the least T over the interior local minima of T.
+//
+//   1. rtus_surface_setup_kernel (one workgroup): the spline's second derivatives (Thomas solve of the natural-spline system,
+//      one lane: n_s - 2 unknowns), the per-segment cubic coefficients, the profile's minimum depth and the scan points
+//      P_j = x0 + j dx / 4, j = 0 .. 4 (n_s - 1), as fp32 (x, s, s') relative to the profile's centre — all into the caller's
+//      workspace, on the stream (graph-capturable).
+//   2. rtus_surface_kernel: lanes are consecutive focal points, a workgroup owns SURF_EB elements.  A local minimum of T is a
+//      sign change - -> + of T'(x) = g1(x) / c1 + g2(x) / c2, g_i = (unit vector from the surface point to E / F) . (1, s'),
+//      so the scan tests the SIGN of T' at every P_j:  g2 (the focal point's term: one v_rsq_f32 per lane and point) is shared
+//      by the workgroup's elements, -(c2 / c1) g1 (the element's term) is computed once per (element, point) into LDS and read
+//      as a broadcast.  Per (element, point) that is one compare plus lane-mask logic on the scalar unit; a lane whose sign
+//      goes from - to + ranks the bracket [P_j, P_j+1] by an fp32 estimate of T there and keeps the SURF_K best.
+//   3. Each kept bracket within the fp32 ranking margin of the best (and always the best two) is refined in fp64: safeguarded
+//      Newton (bisection when a step leaves the bracket or T'' <= 0) on T'(x) = 0 with the cubic's analytic s' and s''.  The
+//      entry is the least refined time.  Where the fp32 sign at a bracket end was wrong (|T'| below fp32 resolution: within
+//      ~1e-8 m of the root) the fp64 signs pick the neighbouring interval instead.
+//
+// Guarantee: a minimum whose neighbouring stationary points are at least dx / 2 away on both sides (the ends of the extent do
+// not count) has a scan point in its decreasing part and the next one in its increasing part (spacing dx / 4: a quarter of
+// margin for the fp32 signs) and is found.  Narrower minima may be missed, which can only make the entry later (or NaN).
+//
+// Determinism: every value an entry is made of is computed from its own element, focal point, the profile and the speeds,
+// by code that does not depend on the element's slot in the workgroup or on the lane: the entry has the same bits whatever
+// else shares the call.
+#include "rtus_device.h"
+
+// no implicit contraction: the fma()s are written out, so every element slot's inlined copy of the arithmetic rounds alike
+#pragma clang fp contract(off)
+
+#define SURF_EB 8           // elements per workgroup (register block: the focal point's leg is shared by them)
+#define SURF_TILE 64        // scan points per LDS tile
+#define SURF_K 3            // brackets kept per (element, focal point)
+#define SURF_SUB 4          // scan points per profile segment
+
+struct SurfArgs {
+    double x0, dx, hq, inv_dx, xend;   // hq = dx / SURF_SUB
+    double c1, c2, xo, zo;             // (xo, zo): origin of the fp32 scan coordinates
+    float ic1f, ic2f, k21f;            // 1 / c1, 1 / c2, c2 / c1
+    int n_s, m, n_e, n_f;
+    const double* __restrict__ xe;
+    const double* __restrict__ ze;
+    const double* __restrict__ xf;
+    const double* __restrict__ zf;
+    double* __restrict__ tt;
+    double* __restrict__ xent;         // nullable
+    const double* __restrict__ coef;   // [n_s - 1][4]: a, b, c, d of s(x0 + k dx + t) = a + b t + c t^2 + d t^3
+    const float4* __restrict__ pts;    // [m]: (x - xo, s - zo, s', 0)
+    const double* __restrict__ smin;   // the profile's least depth
+};
+
+// workspace layout (256-byte aligned pieces): M [n_s] | Thomas scratch [n_s] | coef [4 (n_s - 1)] | pts [m] | smin
+static inline size_t al256s(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline __host__ __device__ int surf_points(int n_s) { return SURF_SUB * (n_s - 1) + 1; }
+size_t rtus_surface_ws_bytes(int n_s)
+{
+    return 2 * al256s(8 * (size_t)n_s) + al256s(32 * (size_t)(n_s - 1)) + al256s(16 * (size_t)surf_points(n_s)) + 256;
+}
+
+struct SurfWs {
+    double *M, *cp, *coef, *smin;
+    float4* pts;
+};
+static SurfWs surf_ws(void* ws, int n_s)
+{
+    char* p = (char*)ws;
+    SurfWs w;
+    w.M = (double*)p;  p += al256s(8 * (size_t)n_s);
+    w.cp = (double*)p; p += al256s(8 * (size_t)n_s);
+    w.coef = (double*)p; p += al256s(32 * (size_t)(n_s - 1));
+    w.pts = (float4*)p; p += al256s(16 * (size_t)surf_points(n_s));
+    w.smin = (double*)p;
+    return w;
+}
+
+// s, s', s'' at x (x clamped to the extent's segments: outside it the end segments' cubics continue)
+__device__ __forceinline__ void spline_eval(const double* __restrict__ coef, int n_s, double x0, double dx, double inv_dx, double x,
+                                            double& s, double& s1, double& s2)
+{
+    double kf = floor((x - x0) * inv_dx);
+    kf = !(kf >= 0.0) ? 0.0 : (kf > (double)(n_s - 2) ? (double)(n_s - 2) : kf);       // (NaN -> segment 0: never out of bounds)
+    const int k = (int)kf;
+    const double t = x - fma(kf, dx, x0);
+    const double a = coef[4 * k], b = coef[4 * k + 1], c = coef[4 * k + 2], d = coef[4 * k + 3];
+    s = fma(fma(fma(d, t, c), t, b), t, a);
+    s1 = fma(fma(3.0 * d, t, 2.0 * c), t, b);
+    s2 = fma(6.0 * d, t, 2.0 * c);
+}
+
+__global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_setup_kernel(const double* __restrict__ zs, int n_s, double x0, double dx,
+                                                                          double xo, double zo, SurfWs w)
+{
+    const int tid = threadIdx.x;
+    // natural spline: M_0 = M_{n-1} = 0,  M_{i-1} + 4 M_i + M_{i+1} = 6 (z_{i+1} - 2 z_i + z_{i-1}) / dx^2
+    if (tid == 0) {
+        const double r6 = 6.0 / (dx * dx);
+        double cprev = 0.0, dprev = 0.0;
+        for (int i = 1; i <= n_s - 2; ++i) {
+            const double rhs = r6 * ((zs[i + 1] - zs[i]) - (zs[i] - zs[i - 1]));
+            const double inv = 1.0 / (4.0 - cprev);
+            cprev = inv;
+            dprev = (rhs - dprev) * inv;
+            w.cp[i] = cprev;
+            w.M[i] = dprev;
+        }
+        w.M[0] = 0.0;
+        w.M[n_s - 1] = 0.0;
+        for (int i = n_s - 3; i >= 1; --i) w.M[i] = fma(-w.cp[i], w.M[i + 1], w.M[i]);
+    }
+    __syncthreads();
+    __shared__ double red[RTUS_BLOCK];
+    double lo = INFINITY;
+    for (int k = tid; k < n_s - 1; k += RTUS_BLOCK) {
+        const double Mk = w.M[k], Mk1 = w.M[k + 1], z0 = zs[k], z1 = zs[k + 1];
+        const double a = z0, b = (z1 - z0) / dx - dx * (2.0 * Mk + Mk1) / 6.0, c = 0.5 * Mk, d = (Mk1 - Mk) / (6.0 * dx);
+        w.coef[4 * k] = a; w.coef[4 * k + 1] = b; w.coef[4 * k + 2] = c; w.coef[4 * k + 3] = d;
+        // least depth on the segment: its ends and the roots of s' = b + 2 c t + 3 d t^2 inside it
+        double m = fmin(a, fma(fma(fma(d, dx, c), dx, b), dx, a));
+        const double A = 3.0 * d, B = 2.0 * c, disc = B * B - 4.0 * A * b;
+        double r[2] = {NAN, NAN};
+        if (A != 0.0) {
+            if (disc >= 0.0) { const double q = sqrt(disc); r[0] = (-B - q) / (2.0 * A); r[1] = (-B + q) / (2.0 * A); }
+        } else if (B != 0.0) {
+            r[0] = -b / B;
+        }
+        for (int i = 0; i < 2; ++i)
+            if (r[i] > 0.0 && r[i] < dx) m = fmin(m, fma(fma(fma(d, r[i], c), r[i], b), r[i], a));
+        lo = fmin(lo, m);
+    }
+    red[tid] = lo;
+    __syncthreads();
+    for (int h = RTUS_BLOCK / 2; h > 0; h >>= 1) {
+        if (tid < h) red[tid] = fmin(red[tid], red[tid + h]);
+        __syncthreads();
+    }
+    if (tid == 0) *w.smin = red[0];
+    const int m = surf_points(n_s);
+    const double hq = dx / SURF_SUB;
+    for (int j = tid; j < m; j += RTUS_BLOCK) {
+        const int k = j / SURF_SUB < n_s - 2 ? j / SURF_SUB : n_s - 2;
+        const double t = (double)(j - SURF_SUB * k) * hq;
+        const double* cf = w.coef + 4 * k;
+        const double s = fma(fma(fma(cf[3], t, cf[2]), t, cf[1]), t, cf[0]);
+        const double s1 = fma(fma(3.0 * cf[3], t, 2.0 * cf[2]), t, cf[1]);
+        w.pts[j] = make_float4((float)(fma((double)j, hq, x0) - xo), (float)(s - zo), (float)s1, 0.0f);
+    }
+}
+
+// T'(x) and T''(x) (and T) in fp64
+struct Tder { double t, d1, d2; };
+__device__ __forceinline__ Tder surf_T(const double* __restrict__ coef, int n_s, double x0, double dx, double inv_dx, double inv_c1,
+                                       double inv_c2, double xe, double ze, double xf, double zf, double x)
+{
+    double s, s1, s2;
+    spline_eval(coef, n_s, x0, dx, inv_dx, x, s, s1, s2);
+    const double ux = x - xe, uz = s - ze, vx = x - xf, vz = s - zf;
+    const double q1 = fma(ux, ux, uz * uz), q2 = fma(vx, vx, vz * vz);
+    const double r1 = 1.0 / sqrt(q1), r2 = 1.0 / sqrt(q2);
+    const double l1 = q1 * r1, l2 = q2 * r2;                     // the two leg lengths
+    const double A1 = fma(uz, s1, ux), A2 = fma(vz, s1, vx);     // (S - E) . S',  (S - F) . S'
+    const double B = fma(s1, s1, 1.0);                           // |S'|^2
+    Tder o;
+    o.t = fma(l1, inv_c1, l2 * inv_c2);
+    o.d1 = fma(A1 * r1, inv_c1, A2 * r2 * inv_c2);
+    o.d2 = fma((fma(uz, s2, B) - A1 * A1 * r1 * r1) * r1, inv_c1, (fma(vz, s2, B) - A2 * A2 * r2 * r2) * r2 * inv_c2);
+    return o;
+}
+
+// the least refined time over the kept brackets of one (element, focal point); written to tt (and xent)
+__device__ __forceinline__ void surf_refine(const double* __restrict__ coef, int n_s, int m, double x0, double dx, double hq, double inv_dx,
+                                         double c1, double c2, double xe, double ze, double xf, double zf, bool ok, float t0, float t1,
+                                         float t2, int j0, int j1, int j2, double* __restrict__ tt_out, double* __restrict__ xent_out)
+{
+    const double inv_c1 = 1.0 / c1, inv_c2 = 1.0 / c2;
+    // fp32 ranking margin: the estimates carry ~1e-7 relative error (fp32 coordinates and legs); keep what might be the best
+    const float margin = 4e-6f * t0;
+    double best = NAN, bx = NAN;
+    for (int k = 0; k < SURF_K; ++k) {
+        const int j = k == 0 ? j0 : (k == 1 ? j1 : j2);
+        const float tk = k == 0 ? t0 : (k == 1 ? t1 : t2);
+        if (!ok || j < 0 || (k >= 2 && !(tk <= t0 + margin))) continue;
+        // the fp32 scan saw T' < 0 at P_j and > 0 at P_j+1; find the fp64 bracket (P_j-1 .. P_j+2 at most)
+        double lo = fma((double)j, hq, x0), hi = fma((double)(j + 1), hq, x0);
+        const double dlo = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, lo).d1;
+        const double dhi = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, hi).d1;
+        if (!(dlo < 0.0)) {                                  // the root is left of P_j
+            if (!(dhi > 0.0) || j == 0) continue;
+            hi = lo;
+            lo = fma((double)(j - 1), hq, x0);
+            if (!(surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, lo).d1 < 0.0)) continue;
+        } else if (!(dhi > 0.0)) {                           // ... or right of P_j+1
+            if (j + 2 >= m) continue;
+            lo = hi;
+            hi = fma((double)(j + 2), hq, x0);
+            if (!(surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, hi).d1 > 0.0)) continue;
+        }
+        // safeguarded Newton on T' = 0 inside [lo, hi], T'(lo) < 0 < T'(hi)
+        double x = 0.5 * (lo + hi);
+        const double tol = 1e-10 * hq;
+        Tder v = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x);
+        for (int it = 0; it < 100; ++it) {
+            if (v.d1 == 0.0) break;
+            if (v.d1 < 0.0) lo = x; else hi = x;
+            const double step = -v.d1 / v.d2;
+            // converged: the last Newton step is taken even when it rounds onto x (a bisection there would jump away from the root)
+            const bool done = (v.d2 > 0.0 && fabs(step) <= tol) || !(hi - lo > tol);
+            double xn = x + step;
+            if (!(v.d2 > 0.0) || !(xn >= lo && xn <= hi)) xn = done ? x : 0.5 * (lo + hi);
+            x = xn;
+            v = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x);
+            if (done) break;
+        }
+        if (isnan(best) || v.t < best) { best = v.t; bx = x; }
+    }
+    *tt_out = best;
+    if (xent_out) *xent_out = bx;
+}
+
+// insert (t, j) into the sorted triple (t0 <= t1 <= t2): selects on values (references invite a phi of pointers -> scratch)
+#define SURF_KEEP(t, j, T, J)                                                                               \
+    do {                                                                                                    \
+        const bool c0_ = (t) < T[0], c1_ = (t) < T[1], c2_ = (t) < T[2];                                    \
+        T[2] = c1_ ? T[1] : (c2_ ? (t) : T[2]);  J[2] = c1_ ? J[1] : (c2_ ? (j) : J[2]);                    \
+        T[1] = c0_ ? T[0] : (c1_ ? (t) : T[1]);  J[1] = c0_ ? J[0] : (c1_ ? (j) : J[1]);                    \
+        T[0] = c0_ ? (t) : T[0];                 J[0] = c0_ ? (j) : J[0];                                   \
+    } while (0)
+
+__global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
+{
+    __shared__ float4 sp[SURF_TILE];                                    // the tile's scan points
+    __shared__ float4 sng[SURF_TILE][SURF_EB / 4];                      // -(c2 / c1) g1 per (point, element)
+    __shared__ float4 st1[SURF_TILE][SURF_EB / 4];                      // |P - E| / c1 per (point, element)
+    __shared__ float sxe[SURF_EB], sze[SURF_EB];
+    const int tid = threadIdx.x;
+    const int f = blockIdx.x * RTUS_BLOCK + tid;
+    const int e0 = blockIdx.y * SURF_EB;
+    if (tid < SURF_EB) {
+        const int e = e0 + tid < a.n_e ? e0 + tid : a.n_e - 1;
+        sxe[tid] = (float)(a.xe[e] - a.xo);
+        sze[tid] = (float)(a.ze[e] - a.zo);
+    }
+    // the focal point: inside the extent and below the surface, else no path (NaN coordinates fail every test)
+    double xf = 0.0, zf = 0.0;
+    bool fok = false;
+    if (f < a.n_f) {
+        xf = a.xf[f];
+        zf = a.zf[f];
+        if (xf >= a.x0 && xf <= a.xend) {
+            double s, s1, s2;
+            spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, xf, s, s1, s2);
+            fok = zf > s;
+        }
+    }
+    const float xfr = fok ? (float)(xf - a.xo) : NAN, zfr = fok ? (float)(zf - a.zo) : NAN;
+
+    float bt[SURF_EB][SURF_K];
+    int bj[SURF_EB][SURF_K];
+    bool neg[SURF_EB];
+#pragma unroll
+    for (int e = 0; e < SURF_EB; ++e) {
+        neg[e] = false;
+#pragma unroll
+        for (int k = 0; k < SURF_K; ++k) { bt[e][k] = INFINITY; bj[e][k] = -1; }
+    }
+    for (int base = 0; base < a.m; base += SURF_TILE) {
+        const int n = a.m - base < SURF_TILE ? a.m - base : SURF_TILE;
+        __syncthreads();
+        for (int i = tid; i < SURF_TILE * SURF_EB; i += RTUS_BLOCK) {
+            const int j = i / SURF_EB, e = i % SURF_EB;
+            const float4 P = j < n ? a.pts[base + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float ux = P.x - sxe[e], uz = P.y - sze[e];
+            const float q = fmaf(uz, uz, ux * ux);
+            const float r = __builtin_amdgcn_rsqf(q);
+            ((float*)&sng[j][0])[e] = -(fmaf(uz, P.z, ux) * r) * a.k21f;
+            ((float*)&st1[j][0])[e] = q * r * a.ic1f;
+            if (e == 0) sp[j] = P;
+        }
+        __syncthreads();
+        for (int jj = 0; jj < n; ++jj) {
+            const float4 P = sp[jj];
+            const float vx = P.x - xfr, vz = P.y - zfr;
+            const float q = fmaf(vz, vz, vx * vx);
+            const float r = __builtin_amdgcn_rsqf(q);
+            const float g2 = fmaf(vz, P.z, vx) * r;                     // T' c2 = g2 - ng: T' > 0 <=> g2 > ng
+            const float4 ng0 = sng[jj][0], ng1 = sng[jj][1];
+            const float ng[SURF_EB] = {ng0.x, ng0.y, ng0.z, ng0.w, ng1.x, ng1.y, ng1.z, ng1.w};
+            const int j = base + jj;
+#pragma unroll
+            for (int e = 0; e < SURF_EB; ++e) {
+                const bool pos = g2 > ng[e];
+                if (pos && neg[e]) {                                    // - -> + between P_j-1 and P_j: a minimum
+                    const float t = fmaf(q * r, a.ic2f, ((const float*)&st1[jj][0])[e]);
+                    SURF_KEEP(t, j - 1, bt[e], bj[e]);
+                }
+                neg[e] = !pos;                                          // (T' = 0 counts as -; NaN: never +)
+            }
+        }
+    }
+    if (f >= a.n_f) return;
+    const double smin = *a.smin;
+#pragma unroll
+    for (int e = 0; e < SURF_EB; ++e) {
+        const int row = e0 + e;
+        if (row < a.n_e) {
+            const double xe = a.xe[row], ze = a.ze[row];
+            const size_t o = (size_t)row * a.n_f + f;
+            surf_refine(a.coef, a.n_s, a.m, a.x0, a.dx, a.hq, a.inv_dx, a.c1, a.c2, xe, ze, xf, zf, fok && ze < smin, bt[e][0], bt[e][1],
+                        bt[e][2], bj[e][0], bj[e][1], bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
+        }
+    }
+}
+
+hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* xe,
+                                  const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt, double* xent,
+                                  void* ws, hipStream_t s)
+{
+    const SurfWs w = surf_ws(ws, n_s);
+    SurfArgs a;
+    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
+    a.c1 = c1; a.c2 = c2;
+    a.xo = x0 + 0.5 * (double)(n_s - 1) * dx;
+    a.zo = 0.0;                                   // (zs is device memory: depths stay absolute; a few cm of depth is ~4e-9 m in fp32)
+    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1);
+    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_e; a.n_f = n_f;
+    a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
+    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
+    const long long gy = ((long long)n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
+    hipLaunchKernelGGL(rtus_surface_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}

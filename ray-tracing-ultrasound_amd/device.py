@@ -287,6 +287,30 @@ def tt_layers_batch_dev(z_if, c, xe, ze, xf, zf, out=None, taup=False):
     return out
 
 
+def tt_surface_dev(x0, dx, zs, c1, c2, xe, ze, xf, zf, out=None, x_entry=None):
+    """Travel times through one curved interface (rtus_tt_surface_dev; api.travel_time_surface's definition) on float64 CUDA
+    tensors -> out [n_e, n_f] (and x_entry [n_e, n_f] when a tensor is given for it).  The spline's workspace is allocated here;
+    asynchronous on the current stream."""
+    for t, n in ((zs, "zs"), (xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
+        _chk(t, n)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    if out is None:
+        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
+    _chk(out, "out")
+    if x_entry is not None:
+        _chk(x_entry, "x_entry")
+    if out.numel() != n_e * n_f or (x_entry is not None and x_entry.numel() != n_e * n_f):
+        raise ValueError("out / x_entry must hold n_e * n_f values")
+    need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)      # (the caching allocator's blocks are 512-byte aligned)
+    st = _lib.lib().rtus_tt_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c2), _p(xe), _p(ze), n_e, _p(xf),
+                                        _p(zf), n_f, _p(out), _p(x_entry), _p(ws), need, _stream(xe))
+    _lib.check(st, "rtus_tt_surface_dev")
+    return out
+
+
 def focal_delays_dev(tt, out=None):
     """delays[e, f] = max_e' tt[e', f] - tt[e, f] on device (NaN-aware); ``out`` may be ``tt`` itself."""
     _chk(tt, "tt")
