@@ -163,6 +163,12 @@ def lib():
     L.rtus_tt_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, vp, C.c_size_t, vp]
     L.rtus_tt_surface.argtypes = [dd, dd, dp, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, ip]
     L.rtus_tt_surface_dev.restype = L.rtus_tt_surface.restype = ip
+    L.rtus_fmc_analytic_dev.argtypes = [dp, ip, ip, ip, ip, dp, vp]
+    L.rtus_fmc_analytic.argtypes = [dp, ip, ip, ip, ip, dp, ip]
+    L.rtus_surface_find_dev.argtypes = [dp, ip, ip, dd, dd, dp, dp, dd, dd, dd, ip, dd, dd, ip, dp, dp, dp, vp]
+    L.rtus_surface_find.argtypes = [dp, ip, ip, dd, dd, dp, dp, dd, dd, dd, ip, dd, dd, ip, dp, dp, dp, ip]
+    for name in ("rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find"):
+        getattr(L, name).restype = ip
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -186,4 +192,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_lens_f32_multi_dev", "rtus_sweep_workspace_bytes", "rtus_sweep_dev", "rtus_sweep",
            "rtus_tt_layers_ex_dev", "rtus_tt_layers_ex", "rtus_tt_layers_batch_ex_dev", "rtus_tt_layers_multi_ex",
            "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev",
-           "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface")
+           "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface",
+           "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find")

@@ -458,3 +458,94 @@ def tfm_image(fmc, fs, tt_tx, tt_rx=None, *, t0=0.0, out=None, device=0):
                              tt_tx.shape[1], _ptr(img), int(device))
     _lib.check(st, "rtus_tfm")
     return img
+
+
+def fmc_analytic(fmc, n_taps=63, *, out=None, device=0):
+    """Analytic signal of every A-scan of an FMC block by an FIR Hilbert transformer -> complex64 [n_tx, n_rx, n_t]:
+    real part = the A-scan, imaginary part = sum_m h[m] x[n - m] with h[m] = 2/(pi m) * Hamming(m) for odd m and 0 for even m,
+    ``n_taps`` = 2M + 1 odd in [3, 255]; samples outside the record count as zero.  The envelope is ``np.abs`` of the result.
+    Definition: include/rtus.h (rtus_fmc_analytic).  Not in the reference."""
+    fmc = np.ascontiguousarray(fmc, dtype=np.float32)
+    if fmc.ndim != 3:
+        raise ValueError("fmc must be [n_tx, n_rx, n_t]")
+    a = _out(out, fmc.shape, np.complex64)
+    st = _lib.lib().rtus_fmc_analytic(_ptr(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], int(n_taps), _ptr(a), int(device))
+    _lib.check(st, "rtus_fmc_analytic")
+    return a
+
+
+def _depths(z_lo, z_hi, dz):
+    """number of depths z_lo + j dz up to z_hi (inclusive, to within 1e-9 dz)"""
+    if not (np.isfinite(z_lo) and np.isfinite(z_hi) and np.isfinite(dz) and dz > 0 and z_hi >= z_lo):
+        raise ValueError("need finite z_lo <= z_hi and dz > 0")
+    return int(np.floor((z_hi - z_lo) / dz + 1e-9)) + 1
+
+
+def surface_profile(x0, dx, z_peak, amp, threshold=0.1):
+    """The post-processing of measure_surface on the host: valid = finite z_peak and amp >= threshold * max amp; trimmed to the
+    first through last valid column; interior invalid columns filled by linear interpolation in x between the nearest valid ones.
+    -> dict(x0, dx, zs, valid).  ValueError when fewer than 4 columns remain."""
+    z_peak = np.asarray(z_peak, dtype=np.float64)
+    amp = np.asarray(amp, dtype=np.float64)
+    fin = np.isfinite(amp)
+    top = amp[fin].max() if fin.any() else np.nan
+    with np.errstate(invalid="ignore"):
+        valid = np.isfinite(z_peak) & fin & (amp >= threshold * top)
+    idx = np.nonzero(valid)[0]
+    if idx.size == 0 or idx[-1] - idx[0] + 1 < 4:
+        raise ValueError(f"the surface was found in too few columns ({idx.size} valid; a profile needs 4 after trimming)")
+    lo, hi = int(idx[0]), int(idx[-1])
+    k = np.arange(lo, hi + 1)
+    zs = np.interp(x0 + k * dx, x0 + idx * dx, z_peak[idx])
+    zs[valid[lo:hi + 1]] = z_peak[lo:hi + 1][valid[lo:hi + 1]]        # (the valid columns exactly as measured)
+    return dict(x0=float(x0 + lo * dx), dx=float(dx), zs=zs, valid=valid)
+
+
+def measure_surface(fmc, fs, xe, ze, c1, x0, dx, n_s, z_lo, z_hi, dz, *, t0=0.0, threshold=0.1, n_taps=63, analytic=None,
+                    return_image=False, device=0):
+    """The surface profile under the couplant, measured from a square FMC block fmc[n_e, n_e, n_t] (element e transmits and
+    receives; first sample at ``t0``, ``fs`` samples per second): an envelope TFM of the couplant (speed ``c1``, straight rays) over
+    the columns x0 + k dx (k < n_s) and the depths z_lo + j dz up to z_hi, and in every column the depth of the brightest pixel,
+    refined by a parabolic step (rtus_surface_find; definition and limits in include/rtus.h).  ``analytic``: an analytic FMC
+    from fmc_analytic to re-use (fmc is then not read); otherwise it is formed with ``n_taps`` Hilbert taps.
+
+    Post-processing (host): a column is valid where its peak lies inside the depth window and its amplitude is at least
+    ``threshold`` times the largest; the profile is trimmed to the first through last valid column, and interior invalid columns
+    are filled by linear interpolation in x.  ValueError when fewer than 4 columns remain.
+    -> dict(x0, dx, zs: the profile for travel_time_surface, z_peak [n_s], amplitude [n_s], valid [n_s] bool, image [n_s, n_z]
+    float32 when ``return_image``).
+
+    The measurement assumes an aperture without grating lobes (pitch below half a wavelength in the couplant), a window that
+    holds the surface echo and no other strong echo, and moderate slopes; dim columns are unreliable, hence the threshold."""
+    if analytic is None:
+        analytic = fmc_analytic(fmc, n_taps, device=device)
+    a = np.ascontiguousarray(analytic)
+    if a.dtype == np.float32 and a.ndim == 4 and a.shape[3] == 2:
+        a = a.view(np.complex64)[..., 0]
+    if a.dtype != np.complex64 or a.ndim != 3 or a.shape[0] != a.shape[1]:
+        raise ValueError("the analytic FMC must be complex64 [n_e, n_e, n_t] (or float32 [n_e, n_e, n_t, 2])")
+    xe, ze = _f64(xe, "xe"), _f64(ze, "ze")
+    if xe.size != a.shape[0] or ze.size != a.shape[0]:
+        raise ValueError("xe / ze must hold one position per element of the FMC")
+    n_s, n_z = int(n_s), _depths(z_lo, z_hi, dz)
+    z_peak = np.empty(n_s, dtype=np.float64)
+    amp = np.empty(n_s, dtype=np.float32)
+    img = np.empty((n_s, n_z), dtype=np.float32) if return_image else None
+    st = _lib.lib().rtus_surface_find(_ptr(a), a.shape[0], a.shape[2], float(fs), float(t0), _ptr(xe), _ptr(ze), float(c1), float(x0),
+                                      float(dx), n_s, float(z_lo), float(dz), n_z, _ptr(z_peak), _ptr(amp), _ptr(img), int(device))
+    _lib.check(st, "rtus_surface_find")
+    r = surface_profile(x0, dx, z_peak, amp, threshold)
+    r.update(z_peak=z_peak, amplitude=amp)
+    if return_image:
+        r["image"] = img
+    return r
+
+
+def adaptive_tfm(fmc, fs, xe, ze, c1, c2, x0, dx, n_s, z_lo, z_hi, dz, xf, zf, *, t0=0.0, threshold=0.1, n_taps=63, device=0):
+    """Adaptive TFM: measure the surface from the FMC (measure_surface), build the travel times through it
+    (travel_time_surface, couplant ``c1`` over the part ``c2``) and image the part at the focal points (xf, zf) with the RF
+    delay-and-sum tfm_image.  Focal points outside the trimmed profile's extent get NaN times and contribute nothing.
+    -> (image float32 [n_f], surface dict of measure_surface)."""
+    surf = measure_surface(fmc, fs, xe, ze, c1, x0, dx, n_s, z_lo, z_hi, dz, t0=t0, threshold=threshold, n_taps=n_taps, device=device)
+    tt = travel_time_surface(surf["x0"], surf["dx"], surf["zs"], c1, c2, xe, ze, xf, zf, device=device)
+    return tfm_image(fmc, fs, tt, t0=t0, device=device), surf

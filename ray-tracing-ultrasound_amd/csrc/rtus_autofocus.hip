@@ -1,0 +1,208 @@
+// rtus_autofocus.hip — measuring the surface profile from the FMC data that is later imaged ("adaptive TFM"): an analytic
+// (complex) FMC by an FIR Hilbert transform, and an envelope image of the couplant above the part, reduced to the depth of the
+// surface echo in every column.  NOT IN THE REFERENCE: checked against tests/autofocus_numpy.py.  Definitions in include/rtus.h
+// (rtus_fmc_analytic, rtus_surface_find).
+//
+//   * rtus_analytic_kernel: one workgroup = RTUS_ANA_TILE samples of one A-scan plus the filter's halo in LDS; streams the FMC
+//     (4 B in, 8 B out per sample) -> HBM roofline, a small share of the chain.
+//   * rtus_surface_find_kernel: the rtus_tfm gather loop on complex samples, with straight-ray delays formed in the kernel instead
+//     of read from a table: 16 B of L2 traffic per (pair, pixel).  The roof is the L2 gather rate, as for rtus_tfm.
+#include "rtus_device.h"
+
+// ---------------------------------------------------------------------------------------------- analytic FMC
+// out[pair][n] = (x[n], sum_m h[m] x[n - m]).  h is odd-symmetric and zero at even m, so the sum is
+// sum over odd m = 1..M of h[m] (x[n - m] - x[n + m]), in that order (fixed: the result does not depend on the launch).
+#define RTUS_ANA_TILE 1024                                   // output samples per workgroup: 4 per lane
+#define RTUS_ANA_MAX_HALF 127                                // M = (n_taps - 1) / 2, n_taps <= 255
+
+struct AnaArgs {
+    const float* __restrict__ x;                             // [n_pairs][n_t]
+    float2* __restrict__ out;                                // [n_pairs][n_t]: (re, im)
+    int n_t, n_tiles, M;
+    float h[(RTUS_ANA_MAX_HALF + 1) / 2];                    // h[i] = tap 2 i + 1
+};
+
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_analytic_kernel(AnaArgs a)
+{
+    __shared__ float xs[RTUS_ANA_TILE + 2 * RTUS_ANA_MAX_HALF];
+    const size_t pair = blockIdx.x / (unsigned)a.n_tiles;
+    const int n0 = (int)(blockIdx.x % (unsigned)a.n_tiles) * RTUS_ANA_TILE;
+    const float* rec = a.x + pair * (size_t)a.n_t;
+    const int M = a.M;
+    for (int i = threadIdx.x; i < RTUS_ANA_TILE + 2 * M; i += RTUS_BLOCK) {   // samples outside the record are zero
+        const int n = n0 - M + i;
+        xs[i] = (n >= 0 && n < a.n_t) ? rec[n] : 0.0f;
+    }
+    __syncthreads();
+    float2* o = a.out + pair * (size_t)a.n_t;
+#pragma unroll
+    for (int q = 0; q < RTUS_ANA_TILE / RTUS_BLOCK; ++q) {
+        const int l = q * RTUS_BLOCK + threadIdx.x, n = n0 + l;
+        if (n >= a.n_t) break;
+        const float* c = xs + l + M;                         // c[0] = x[n]
+        float y = 0.0f;
+        for (int i = 0; 2 * i + 1 <= M; ++i) y = fmaf(a.h[i], c[-(2 * i + 1)] - c[2 * i + 1], y);
+        o[n] = make_float2(c[0], y);
+    }
+}
+
+hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t, int n_taps, float2* out, hipStream_t s)
+{
+    AnaArgs a;
+    a.x = fmc; a.out = out; a.n_t = n_t;
+    a.n_tiles = (n_t + RTUS_ANA_TILE - 1) / RTUS_ANA_TILE;
+    a.M = (n_taps - 1) / 2;
+    for (int i = 0; i < (RTUS_ANA_MAX_HALF + 1) / 2; ++i) {
+        const int m = 2 * i + 1;                             // h[m] = 2 / (pi m) w[m], w the Hamming window over -M..M
+        a.h[i] = m <= a.M ? (float)(2.0 / (M_PI * m) * (0.54 + 0.46 * cos(M_PI * m / a.M))) : 0.0f;
+    }
+    hipLaunchKernelGGL(rtus_analytic_kernel, dim3((unsigned)(n_pairs * a.n_tiles)), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- couplant envelope + peak
+// A[k][j] = | sum_tx sum_rx a[tx][rx](s) |, s = (|E_tx - P| + |E_rx - P|) / c1 fs - t0 fs, P = (x0 + k dx, z_lo + j dz); real
+// and imaginary parts interpolated linearly and separately, rtus_tfm's edge rules.  Then the first index of the column's
+// maximum and a parabolic step.
+//
+// One workgroup = one column, lanes over depths (n_z > 256: the workgroup walks the column in chunks of 256).  Each element's
+// half of the sample position (fp64, rounded once to fp32, as rtus_tfm's tfm_tau) sits in LDS for a tile of RTUS_SF_TILE
+// elements; sixteen receive elements per trip, all sixteen 16-byte gathers issued before the first is used (rtus_tfm's reasoning:
+// a 256-column image is one wave per SIMD, and only the wave's own loads hide the gather latency).
+#define RTUS_SF_TILE 64
+#define RTUS_SF_GROUP 16
+#define RTUS_SF_MAX_Z 1024
+typedef unsigned int sf_u32x4 __attribute__((ext_vector_type(4)));
+
+struct SfArgs {
+    const float* __restrict__ a;         // [n_e][n_e][n_t][2]
+    const double* __restrict__ xe;
+    const double* __restrict__ ze;
+    double* __restrict__ z_peak;         // [n_s]
+    float* __restrict__ amp;             // [n_s]
+    float* __restrict__ image;           // [n_s][n_z] or null
+    int n_e, n_t, n_s, n_z;
+    double c1, fs, half_t0s, x0, dx, z_lo, dz;
+};
+
+__device__ __forceinline__ float sf_tau(double xe, double ze, double px, double pz, double c1, double fs, double half_t0s)
+{
+    const double ux = xe - px, uz = ze - pz;
+    const float v = (float)(sqrt(ux * ux + uz * uz) / c1 * fs - half_t0s);
+    return fabsf(v) < 1.0e8f ? v : -1.0e8f;                  // (positions are finite; absurd ones read nothing)
+}
+
+// Two neighbouring complex samples i, i + 1 of one analytic A-scan (wave-uniform base) in one 16-byte load; the descriptor's range
+// check zeroes what lies outside the record.  Negative indices are clamped to one that is out of range with all four dwords (as
+// unsigned they are >= 2^31; times 8 they would wrap): |i| < 2^28 (sf_tau clamps to +-1e8 samples per leg), n_t <= 2^26.
+__device__ __forceinline__ sf_u32x4 sf_load2(const float* rec, int n_t, int i)
+{
+    const __amdgpu_buffer_rsrc_t q = __builtin_amdgcn_make_buffer_rsrc((void*)rec, 0, (unsigned)n_t * 8u, 0x00020000);
+    return __builtin_amdgcn_raw_buffer_load_b128(q, min((unsigned)i, 0x1ffffff0u) * 8u, 0, 0);
+}
+
+__device__ __forceinline__ void sf_accum(sf_u32x4 v, float w, float& re, float& im)
+{
+    const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
+    re += fmaf(w, r1 - r0, r0);
+    im += fmaf(w, i1 - i0, i0);
+}
+
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_surface_find_kernel(SfArgs a)
+{
+    __shared__ float tau[RTUS_SF_TILE][RTUS_BLOCK];          // 64 KB
+    __shared__ float col[RTUS_SF_MAX_Z];                     // the column's amplitudes, for the parabolic step
+    __shared__ float red_v[RTUS_BLOCK];
+    __shared__ int red_i[RTUS_BLOCK];
+    // XCD k takes a contiguous share of the columns: neighbouring columns read the same sample windows (rtus_tfm_kernel)
+    const int nblk = gridDim.x, per = (nblk + 7) >> 3;
+    int k = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if (nblk & 7) k = blockIdx.x;
+    const int t = threadIdx.x;
+    const double px = a.x0 + k * a.dx;
+    const size_t pair_len = (size_t)a.n_t * 2;               // floats per analytic A-scan
+    const bool tx_in_tile = a.n_e <= RTUS_SF_TILE;
+    float best = -1.0f;                                      // this lane's maximum (first index), and whether it saw a NaN / inf
+    int best_j = a.n_z;
+    bool bad = false;
+    for (int j0 = 0; j0 < a.n_z; j0 += RTUS_BLOCK) {
+        const int j_raw = j0 + t;
+        const bool live = j_raw < a.n_z;
+        const int j = live ? j_raw : a.n_z - 1;
+        const double pz = a.z_lo + j * a.dz;
+        float re = 0.0f, im = 0.0f;
+        for (int r0 = 0; r0 < a.n_e; r0 += RTUS_SF_TILE) {
+            const int nr = min(RTUS_SF_TILE, a.n_e - r0);
+            __syncthreads();                                 // the previous tile is no longer read
+            for (int r = 0; r < nr; ++r) tau[r][t] = sf_tau(a.xe[r0 + r], a.ze[r0 + r], px, pz, a.c1, a.fs, a.half_t0s);
+            __syncthreads();
+            for (int tx = 0; tx < a.n_e; ++tx) {
+                const float tt = tx_in_tile ? tau[tx][t] : sf_tau(a.xe[tx], a.ze[tx], px, pz, a.c1, a.fs, a.half_t0s);
+                const float* rec = a.a + ((size_t)tx * a.n_e + r0) * pair_len;   // wave-uniform
+                int r = 0;
+                for (; r + RTUS_SF_GROUP <= nr; r += RTUS_SF_GROUP) {
+                    sf_u32x4 v[RTUS_SF_GROUP];
+                    float w[RTUS_SF_GROUP];
+#pragma unroll
+                    for (int q = 0; q < RTUS_SF_GROUP; ++q) {
+                        const float s = tt + tau[r + q][t];
+                        const float fl = floorf(s);
+                        w[q] = s - fl;
+                        v[q] = sf_load2(rec + (size_t)(r + q) * pair_len, a.n_t, (int)fl);
+                    }
+#pragma unroll
+                    for (int q = 0; q < RTUS_SF_GROUP; ++q) sf_accum(v[q], w[q], re, im);
+                }
+                for (; r < nr; ++r) {                        // receive elements past the last full group
+                    const float s = tt + tau[r][t];
+                    const float fl = floorf(s);
+                    sf_accum(sf_load2(rec + (size_t)r * pair_len, a.n_t, (int)fl), s - fl, re, im);
+                }
+            }
+        }
+        const float A = sqrtf(re * re + im * im);
+        if (live) {
+            col[j] = A;
+            if (a.image) a.image[(size_t)k * a.n_z + j] = A;
+            bad |= !(A <= 3.402823466e38f);                  // NaN or inf
+            if (A > best) { best = A; best_j = j; }          // ascending j: strict > keeps the first index
+        }
+    }
+    red_v[t] = best;
+    red_i[t] = bad ? -1 : best_j;                            // -1: this lane saw a non-finite amplitude
+    for (int h = RTUS_BLOCK / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (t < h) {
+            const float v1 = red_v[t], v2 = red_v[t + h];
+            const int i1 = red_i[t], i2 = red_i[t + h];
+            if (i1 < 0 || i2 < 0) red_i[t] = -1;
+            else if (v2 > v1 || (v2 == v1 && i2 < i1)) { red_v[t] = v2; red_i[t] = i2; }
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const float m = red_v[0];
+        const int js = red_i[0];
+        double z = NAN;
+        if (js > 0 && js < a.n_z - 1 && m > 0.0f) {         // inside the window, a finite, non-zero maximum
+            const double am = col[js - 1], a0 = col[js], ap = col[js + 1];
+            double d = (am - ap) / (2.0 * (am - 2.0 * a0 + ap)); // am < a0 (first index of the maximum), ap <= a0: denominator < 0
+            d = fmin(fmax(d, -0.5), 0.5);
+            z = a.z_lo + (js + d) * a.dz;
+        }
+        a.z_peak[k] = z;
+        a.amp[k] = js < 0 ? NAN : m;
+    }
+}
+
+hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs, double t0, const double* xe, const double* ze,
+                                    double c1, double x0, double dx, int n_s, double z_lo, double dz, int n_z, double* z_peak,
+                                    float* amp, float* image, hipStream_t s)
+{
+    SfArgs a;
+    a.a = an; a.xe = xe; a.ze = ze; a.z_peak = z_peak; a.amp = amp; a.image = image;
+    a.n_e = n_e; a.n_t = n_t; a.n_s = n_s; a.n_z = n_z;
+    a.c1 = c1; a.fs = fs; a.half_t0s = 0.5 * t0 * fs; a.x0 = x0; a.dx = dx; a.z_lo = z_lo; a.dz = dz;
+    hipLaunchKernelGGL(rtus_surface_find_kernel, dim3(n_s), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}

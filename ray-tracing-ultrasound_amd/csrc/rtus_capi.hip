@@ -61,6 +61,10 @@ size_t rtus_surface_ws_bytes(int n_s);
 hipError_t rtus_launch_focal_delays(const double* tt, int n_e, int n_f, double* delays, hipStream_t s);
 hipError_t rtus_launch_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                            const double* tt_rx, int n_f, float* image, hipStream_t s);
+hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t, int n_taps, float2* out, hipStream_t s);
+hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs, double t0, const double* xe, const double* ze,
+                                    double c1, double x0, double dx, int n_s, double z_lo, double dz, int n_z, double* z_peak,
+                                    float* amp, float* image, hipStream_t s);
 
 static thread_local int g_last_hip = 0;
 static int hip_fail(hipError_t e) { g_last_hip = (int)e; return RTUS_ERR_HIP; }
@@ -890,6 +894,97 @@ int rtus_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0
     HIP_TRY(S.flush());
     LAUNCH_TRY(rtus_launch_tfm(dfmc, n_tx, n_rx, n_t, fs, t0, dtx, drx, n_f, dimg, S.a->stream));
     S.download(image, dimg, (size_t)n_f);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+// ---------------------------------------------------------------------------- adaptive TFM: analytic FMC, surface from the couplant image
+#define RTUS_ANALYTIC_MAX_TAPS 255
+#define RTUS_ANALYTIC_MAX_SAMPLES (1 << 26)
+static int check_analytic(const void* fmc, int n_tx, int n_rx, int n_t, int n_taps, const void* out)
+{
+    if (!fmc || !out || n_tx <= 0 || n_rx <= 0 || n_t <= 0) return RTUS_ERR_INVALID_ARG;
+    if (n_taps < 3 || n_taps > RTUS_ANALYTIC_MAX_TAPS || !(n_taps & 1)) return RTUS_ERR_INVALID_ARG;
+    if (n_t > RTUS_ANALYTIC_MAX_SAMPLES) return RTUS_ERR_UNSUPPORTED;
+    const long long n_pairs = (long long)n_tx * n_rx, n_tiles = (n_t + 1023) / 1024;
+    if (n_pairs * n_tiles > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;          // one workgroup per (pair, 1024 samples)
+    const uintptr_t i0 = (uintptr_t)fmc, i1 = i0 + (uintptr_t)(4 * n_pairs * n_t), o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(8 * n_pairs * n_t);
+    if (i0 < o1 && o0 < i1) return RTUS_ERR_INVALID_ARG;                        // the output must not overlap the input
+    return RTUS_OK;
+}
+
+int rtus_fmc_analytic_dev(const float* d_fmc, int n_tx, int n_rx, int n_t, int n_taps, float* d_out, void* stream)
+{
+    int st = check_analytic(d_fmc, n_tx, n_rx, n_t, n_taps, d_out);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_fmc_analytic(d_fmc, (long long)n_tx * n_rx, n_t, n_taps, (float2*)d_out, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_fmc_analytic(const float* fmc, int n_tx, int n_rx, int n_t, int n_taps, float* out, int device)
+{
+    int st = check_analytic(fmc, n_tx, n_rx, n_t, n_taps, out);
+    if (st) return st;
+    const size_t n = (size_t)n_tx * n_rx * n_t;
+    Session S;
+    if ((st = S.open(device, al256(4 * n) + al256(8 * n)))) return st;
+    float* din;
+    S.upload(din, fmc, n);
+    float* dout = S.take<float>(2 * n);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_fmc_analytic(din, (long long)n_tx * n_rx, n_t, n_taps, (float2*)dout, S.a->stream));
+    S.download(out, dout, 2 * n);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+#define RTUS_SURFACE_FIND_MAX_E 4096
+#define RTUS_SURFACE_FIND_MAX_Z 1024
+#define RTUS_SURFACE_FIND_MAX_S (1 << 24)
+static int check_surface_find(const void* a, int n_e, int n_t, double fs, double t0, const void* xe, const void* ze, double c1, double x0,
+                              double dx, int n_s, double z_lo, double dz, int n_z, const void* z_peak, const void* amp)
+{
+    if (!a || !xe || !ze || !z_peak || !amp || n_e <= 0 || n_t < 2 || n_s <= 0 || n_z < 3) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(fs) || !(fs > 0) || !isfinite(t0) || !isfinite(c1) || !(c1 > 0)) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(x0) || !isfinite(dx) || !(dx > 0) || !isfinite(z_lo) || !isfinite(dz) || !(dz > 0)) return RTUS_ERR_INVALID_ARG;
+    if (n_e > RTUS_SURFACE_FIND_MAX_E || n_z > RTUS_SURFACE_FIND_MAX_Z || n_s > RTUS_SURFACE_FIND_MAX_S || n_t > RTUS_ANALYTIC_MAX_SAMPLES)
+        return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+int rtus_surface_find_dev(const float* d_a, int n_e, int n_t, double fs, double t0, const double* d_xe, const double* d_ze, double c1,
+                          double x0, double dx, int n_s, double z_lo, double dz, int n_z, double* d_z_peak, float* d_amp, float* d_image,
+                          void* stream)
+{
+    int st = check_surface_find(d_a, n_e, n_t, fs, t0, d_xe, d_ze, c1, x0, dx, n_s, z_lo, dz, n_z, d_z_peak, d_amp);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_surface_find(d_a, n_e, n_t, fs, t0, d_xe, d_ze, c1, x0, dx, n_s, z_lo, dz, n_z, d_z_peak, d_amp, d_image,
+                                        (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_surface_find(const float* a, int n_e, int n_t, double fs, double t0, const double* xe, const double* ze, double c1, double x0,
+                      double dx, int n_s, double z_lo, double dz, int n_z, double* z_peak, float* amp, float* image, int device)
+{
+    int st = check_surface_find(a, n_e, n_t, fs, t0, xe, ze, c1, x0, dx, n_s, z_lo, dz, n_z, z_peak, amp);
+    if (st) return st;
+    const size_t na = (size_t)n_e * n_e * n_t * 2, ni = image ? (size_t)n_s * n_z : 0;
+    Session S;
+    if ((st = S.open(device, al256(4 * na) + 2 * al256(8 * (size_t)n_e) + al256(8 * (size_t)n_s) + al256(4 * (size_t)n_s) + al256(4 * ni))))
+        return st;
+    float* da;
+    double *dxe, *dze;
+    S.upload(da, a, na);
+    S.upload(dxe, xe, n_e);
+    S.upload(dze, ze, n_e);
+    double* dzp = S.take<double>(n_s);
+    float* damp = S.take<float>(n_s);
+    float* dimg = S.take<float>(ni);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_surface_find(da, n_e, n_t, fs, t0, dxe, dze, c1, x0, dx, n_s, z_lo, dz, n_z, dzp, damp, dimg, S.a->stream));
+    S.download(z_peak, dzp, n_s);
+    S.download(amp, damp, n_s);
+    S.download(image, dimg, ni);
     HIP_TRY(S.finish());
     return RTUS_OK;
 }

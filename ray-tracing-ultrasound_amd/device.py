@@ -346,6 +346,48 @@ def tfm_dev(fmc, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
     return out
 
 
+def fmc_analytic_dev(fmc, n_taps=63, out=None):
+    """Analytic FMC on device (rtus_fmc_analytic_dev; api.fmc_analytic's definition): fmc float32 [n_tx, n_rx, n_t] -> out float32
+    [n_tx, n_rx, n_t, 2] (real, imaginary), which must not overlap fmc.  Asynchronous on the current stream."""
+    _chk(fmc, "fmc", torch.float32)
+    if fmc.dim() != 3:
+        raise ValueError("fmc must be [n_tx, n_rx, n_t]")
+    if out is None:
+        out = torch.empty((*fmc.shape, 2), dtype=torch.float32, device=fmc.device)
+    _chk(out, "out", torch.float32)
+    if out.numel() != 2 * fmc.numel() or out.device != fmc.device:
+        raise ValueError("out must hold 2 * fmc.numel() float32 values on the device of fmc")
+    st = _lib.lib().rtus_fmc_analytic_dev(_p(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], int(n_taps), _p(out), _stream(fmc))
+    _lib.check(st, "rtus_fmc_analytic_dev")
+    return out
+
+
+def surface_find_dev(analytic, fs, xe, ze, c1, x0, dx, n_s, z_lo, dz, n_z, t0=0.0, z_peak=None, amp=None, image=None):
+    """Couplant envelope image and column peak on device (rtus_surface_find_dev; include/rtus.h): analytic float32
+    [n_e, n_e, n_t, 2], xe / ze float64 [n_e] -> (z_peak float64 [n_s], amp float32 [n_s]); ``image``: an optional float32
+    [n_s, n_z] tensor that receives the envelope image.  Outputs not given are allocated here; asynchronous on the current
+    stream (capturable with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(xe, "xe"); _chk(ze, "ze")
+    if analytic.dim() != 4 or analytic.shape[0] != analytic.shape[1] or analytic.shape[3] != 2:
+        raise ValueError("analytic must be [n_e, n_e, n_t, 2]")
+    n_e, n_t, n_s, n_z = analytic.shape[0], analytic.shape[2], int(n_s), int(n_z)
+    if xe.numel() != n_e or ze.numel() != n_e:
+        raise ValueError("xe / ze must hold one position per element")
+    if z_peak is None:
+        z_peak = torch.empty(n_s, dtype=torch.float64, device=analytic.device)
+    if amp is None:
+        amp = torch.empty(n_s, dtype=torch.float32, device=analytic.device)
+    _chk(z_peak, "z_peak"); _chk(amp, "amp", torch.float32)
+    if image is not None:
+        _chk(image, "image", torch.float32)
+    if z_peak.numel() != n_s or amp.numel() != n_s or (image is not None and image.numel() != n_s * n_z):
+        raise ValueError("z_peak / amp must hold n_s values, image n_s * n_z")
+    st = _lib.lib().rtus_surface_find_dev(_p(analytic), n_e, n_t, float(fs), float(t0), _p(xe), _p(ze), float(c1), float(x0), float(dx),
+                                          n_s, float(z_lo), float(dz), n_z, _p(z_peak), _p(amp), _p(image), _stream(analytic))
+    _lib.check(st, "rtus_surface_find_dev")
+    return z_peak, amp
+
+
 class LayersPlan:
     """Pre-bound ``rtus_tt_layers_dev`` call for repeated solves of one shape: ``run()`` is a single
     ctypes call (no argument checking, no allocation, no sync) — capturable in a hipGraph."""
