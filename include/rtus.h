@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 105 /* 0.1.4: rtus_fmc_analytic*, rtus_surface_find* (surface profile from the FMC: adaptive TFM) */
+#define RTUS_VERSION 106 /* 0.1.5: rtus_tfm_analytic* (envelope TFM + coherence factor over an analytic FMC) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -563,6 +563,41 @@ int rtus_surface_find_dev(const float *d_a, int n_e, int n_t, double fs, double 
 int rtus_surface_find(const float *a, int n_e, int n_t, double fs, double t0, const double *xe, const double *ze,
                       double c1, double x0, double dx, int n_s, double z_lo, double dz, int n_z,
                       double *z_peak, float *amp, float *image, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_analytic: the envelope TFM — rtus_tfm's delay-and-sum over an analytic (complex) FMC, through any travel-time table of
+ * this library (rtus_tt_layers*, rtus_tt_lens*, rtus_tt_surface*) — and, optionally, the coherence factor.  NOT IN THE
+ * REFERENCE; checked against tests/tfm_analytic_numpy.py.
+ *   a       [n_tx][n_rx][n_t][2]  interleaved complex float32 (rtus_fmc_analytic's output, or any complex FMC); fs, t0,
+ *                                 tt_tx [n_tx][n_f], tt_rx [n_rx][n_f] exactly as in rtus_tfm (the two tables may be one table)
+ *   Sample position and edge rules: rtus_tfm's.  Each leg becomes (t fs - t0 fs / 2) in fp64, rounded once to fp32; a leg that is
+ *           not finite or has |.| >= 1e8 samples has no path; the pair's position is s = tau_tx + tau_rx in fp32, i = floor(s),
+ *           w = s - i; a position below 0 or at / past n_t contributes nothing, sample n_t counts as zero.  The real and imaginary
+ *           parts are interpolated separately, each as fmaf(w, x[i + 1] - x[i], x[i]).
+ *   image   [n_f][2]  S = (sum re, sum im) in fp32, accumulated in rtus_tfm's order (receive tiles of 64 elements, then tx
+ *           ascending, then rx ascending inside the tile).  Consequence: image[f].re is bit-identical to rtus_tfm on the real
+ *           parts of a, image[f].im to rtus_tfm on the imaginary parts.  The envelope is |S|.
+ *   cf      [n_f] float32, nullable (null: nothing extra is computed).  The coherence factor (Mallart & Fink)
+ *           cf = |S|^2 / (N E):  N = T R, T the number of tx with a path at f, R the number of rx with a path at f (a pair has a
+ *           path iff both legs have one); E = the sum over the pairs of |interpolated complex sample|^2, fp32, in the same fixed
+ *           order.  Formed in fp64 from the fp32 sums, clamped to [0, 1], rounded once to fp32.  cf = NaN when N = 0, 0 when
+ *           E = 0 < N.  Pairs whose position falls outside the record count in N with value zero (so cf <= 1 by Cauchy-Schwarz).
+ *           A CF-weighted envelope is |S| cf^p.
+ *   Determinism: the bits of a focal point depend only on its own columns of the tables, not on n_f or on which other focal
+ *           points share the call; passing cf does not change the bits of image.
+ *   Limits: check_tfm's (image required, cf nullable) and 2 <= n_t <= 2^26 (16-byte samples addressed with 32-bit byte offsets):
+ *           -1 for invalid arguments, -5 past a limit, before any HIP call.  The _dev entry allocates nothing and does not
+ *           synchronise (capturable).  The host twin stages through the arena as rtus_tfm does (one table uploaded when
+ *           tt_tx == tt_rx, cf downloaded only when asked for).
+ * Measured on MI355X: 64 elements x 2048 samples, 256^2 focal points: 284 us, 281 us with cf (9.5e11 gathers/s,
+ * 0.73x two rtus_tfm launches over split planes); 1024^2: 1.90 ms, 1.95 ms with cf (2.2e12 gathers/s).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tfm_analytic_dev(const float *d_a, int n_tx, int n_rx, int n_t, double fs, double t0,
+                          const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                          float *d_image, float *d_cf, void *stream);
+int rtus_tfm_analytic(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
+                      const double *tt_tx, const double *tt_rx, int n_f,
+                      float *image, float *cf, int device);
 
 #ifdef __cplusplus
 }

@@ -167,7 +167,10 @@ def lib():
     L.rtus_fmc_analytic.argtypes = [dp, ip, ip, ip, ip, dp, ip]
     L.rtus_surface_find_dev.argtypes = [dp, ip, ip, dd, dd, dp, dp, dd, dd, dd, ip, dd, dd, ip, dp, dp, dp, vp]
     L.rtus_surface_find.argtypes = [dp, ip, ip, dd, dd, dp, dp, dd, dd, dd, ip, dd, dd, ip, dp, dp, dp, ip]
-    for name in ("rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find"):
+    L.rtus_tfm_analytic_dev.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, ip, dp, dp, vp]
+    L.rtus_tfm_analytic.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip]
+    for name in ("rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find", "rtus_tfm_analytic_dev",
+                 "rtus_tfm_analytic"):
         getattr(L, name).restype = ip
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
@@ -193,4 +196,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_layers_ex_dev", "rtus_tt_layers_ex", "rtus_tt_layers_batch_ex_dev", "rtus_tt_layers_multi_ex",
            "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev",
            "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface",
-           "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find")
+           "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find",
+           "rtus_tfm_analytic_dev", "rtus_tfm_analytic")

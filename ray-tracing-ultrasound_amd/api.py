@@ -541,11 +541,53 @@ def measure_surface(fmc, fs, xe, ze, c1, x0, dx, n_s, z_lo, z_hi, dz, *, t0=0.0,
     return r
 
 
-def adaptive_tfm(fmc, fs, xe, ze, c1, c2, x0, dx, n_s, z_lo, z_hi, dz, xf, zf, *, t0=0.0, threshold=0.1, n_taps=63, device=0):
+def _complex_fmc(a):
+    """complex64 [n_tx, n_rx, n_t] (a float32 [..., 2] array is viewed as one)"""
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float32 and a.ndim == 4 and a.shape[3] == 2:
+        a = a.view(np.complex64)[..., 0]
+    if a.dtype != np.complex64 or a.ndim != 3:
+        raise ValueError("the analytic FMC must be complex64 [n_tx, n_rx, n_t] (or float32 [n_tx, n_rx, n_t, 2])")
+    return a
+
+
+def tfm_analytic(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, out=None, device=0):
+    """Envelope TFM: tfm_image's delay-and-sum over an analytic FMC (complex64 [n_tx, n_rx, n_t], e.g. from fmc_analytic, or float32
+    [n_tx, n_rx, n_t, 2]) through any travel-time table of this library; tt_rx defaults to tt_tx.  Real and imaginary parts are
+    interpolated separately with tfm_image's sample positions, edge rules and order, so ``image.real`` is tfm_image of
+    ``analytic.real`` bit for bit (and ``image.imag`` of ``analytic.imag``).  The envelope is ``np.abs(image)``.
+    -> complex64 image [n_f]; with ``coherence=True`` -> (image, cf float32 [n_f]): the coherence factor |S|^2 / (N E) of every
+    focal point (Mallart & Fink; S the complex sum, E the sum of |sample|^2 over the N = T R pairs whose legs both have a path; NaN
+    when N = 0).  A CF-weighted image is ``np.abs(image) * cf**p`` (p = 1 is usual).  Definition: include/rtus.h
+    (rtus_tfm_analytic).  Not in the reference."""
+    a = _complex_fmc(analytic)
+    tt_tx = np.ascontiguousarray(tt_tx, dtype=np.float64)
+    same = tt_rx is None or tt_rx is tt_tx
+    tt_rx = tt_tx if same else np.ascontiguousarray(tt_rx, dtype=np.float64)
+    if tt_tx.ndim != 2 or tt_rx.ndim != 2 or tt_tx.shape[1] != tt_rx.shape[1]:
+        raise ValueError("tt_tx / tt_rx must be [n_tx, n_focal] / [n_rx, n_focal]")
+    if tt_tx.shape[0] != a.shape[0] or tt_rx.shape[0] != a.shape[1]:
+        raise ValueError("the analytic FMC's first two dimensions must match the rows of tt_tx and tt_rx")
+    n_f = tt_tx.shape[1]
+    img = _out(out, (n_f,), np.complex64)
+    cf = np.empty(n_f, dtype=np.float32) if coherence else None
+    st = _lib.lib().rtus_tfm_analytic(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx),
+                                      n_f, _ptr(img), _ptr(cf), int(device))
+    _lib.check(st, "rtus_tfm_analytic")
+    return (img, cf) if coherence else img
+
+
+def adaptive_tfm(fmc, fs, xe, ze, c1, c2, x0, dx, n_s, z_lo, z_hi, dz, xf, zf, *, t0=0.0, threshold=0.1, n_taps=63, envelope=False,
+                 device=0):
     """Adaptive TFM: measure the surface from the FMC (measure_surface), build the travel times through it
-    (travel_time_surface, couplant ``c1`` over the part ``c2``) and image the part at the focal points (xf, zf) with the RF
-    delay-and-sum tfm_image.  Focal points outside the trimmed profile's extent get NaN times and contribute nothing.
-    -> (image float32 [n_f], surface dict of measure_surface)."""
-    surf = measure_surface(fmc, fs, xe, ze, c1, x0, dx, n_s, z_lo, z_hi, dz, t0=t0, threshold=threshold, n_taps=n_taps, device=device)
+    (travel_time_surface, couplant ``c1`` over the part ``c2``) and image the part at the focal points (xf, zf).  By default the
+    image is the RF delay-and-sum tfm_image; with ``envelope=True`` it is the envelope ``np.abs(tfm_analytic(...))`` of the analytic
+    FMC, which is formed once (``n_taps`` Hilbert taps) and serves the surface measurement too.  Focal points outside the trimmed
+    profile's extent get NaN times and contribute nothing.  -> (image float32 [n_f], surface dict of measure_surface)."""
+    analytic = fmc_analytic(fmc, n_taps, device=device) if envelope else None
+    surf = measure_surface(fmc, fs, xe, ze, c1, x0, dx, n_s, z_lo, z_hi, dz, t0=t0, threshold=threshold, n_taps=n_taps,
+                           analytic=analytic, device=device)
     tt = travel_time_surface(surf["x0"], surf["dx"], surf["zs"], c1, c2, xe, ze, xf, zf, device=device)
+    if envelope:
+        return np.abs(tfm_analytic(analytic, fs, tt, t0=t0, device=device)), surf
     return tfm_image(fmc, fs, tt, t0=t0, device=device), surf

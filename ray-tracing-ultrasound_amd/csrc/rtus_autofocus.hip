@@ -72,7 +72,6 @@ hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t
 #define RTUS_SF_TILE 64
 #define RTUS_SF_GROUP 16
 #define RTUS_SF_MAX_Z 1024
-typedef unsigned int sf_u32x4 __attribute__((ext_vector_type(4)));
 
 struct SfArgs {
     const float* __restrict__ a;         // [n_e][n_e][n_t][2]
@@ -90,15 +89,6 @@ __device__ __forceinline__ float sf_tau(double xe, double ze, double px, double 
     const double ux = xe - px, uz = ze - pz;
     const float v = (float)(sqrt(ux * ux + uz * uz) / c1 * fs - half_t0s);
     return fabsf(v) < 1.0e8f ? v : -1.0e8f;                  // (positions are finite; absurd ones read nothing)
-}
-
-// Two neighbouring complex samples i, i + 1 of one analytic A-scan (wave-uniform base) in one 16-byte load; the descriptor's range
-// check zeroes what lies outside the record.  Negative indices are clamped to one that is out of range with all four dwords (as
-// unsigned they are >= 2^31; times 8 they would wrap): |i| < 2^28 (sf_tau clamps to +-1e8 samples per leg), n_t <= 2^26.
-__device__ __forceinline__ sf_u32x4 sf_load2(const float* rec, int n_t, int i)
-{
-    const __amdgpu_buffer_rsrc_t q = __builtin_amdgcn_make_buffer_rsrc((void*)rec, 0, (unsigned)n_t * 8u, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(q, min((unsigned)i, 0x1ffffff0u) * 8u, 0, 0);
 }
 
 __device__ __forceinline__ void sf_accum(sf_u32x4 v, float w, float& re, float& im)

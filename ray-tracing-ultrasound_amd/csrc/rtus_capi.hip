@@ -65,6 +65,8 @@ hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t
 hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs, double t0, const double* xe, const double* ze,
                                     double c1, double x0, double dx, int n_s, double z_lo, double dz, int n_z, double* z_peak,
                                     float* amp, float* image, hipStream_t s);
+hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                                    const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 
 static thread_local int g_last_hip = 0;
 static int hip_fail(hipError_t e) { g_last_hip = (int)e; return RTUS_ERR_HIP; }
@@ -985,6 +987,51 @@ int rtus_surface_find(const float* a, int n_e, int n_t, double fs, double t0, co
     S.download(z_peak, dzp, n_s);
     S.download(amp, damp, n_s);
     S.download(image, dimg, ni);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+// ---------------------------------------------------------------------------- envelope TFM + coherence factor over an analytic FMC
+static int check_tfm_analytic(const void* a, int n_tx, int n_rx, int n_t, double fs, double t0, const void* tt_tx, const void* tt_rx,
+                              int n_f, const void* image)
+{
+    int st = check_tfm(a, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, image);   // (cf is nullable)
+    if (st) return st;
+    if (n_t > RTUS_ANALYTIC_MAX_SAMPLES) return RTUS_ERR_UNSUPPORTED;           // 16-byte samples, 32-bit byte offsets
+    return RTUS_OK;
+}
+
+int rtus_tfm_analytic_dev(const float* d_a, int n_tx, int n_rx, int n_t, double fs, double t0, const double* d_tt_tx,
+                          const double* d_tt_rx, int n_f, float* d_image, float* d_cf, void* stream)
+{
+    int st = check_tfm_analytic(d_a, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_analytic(d_a, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, d_cf, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                      int n_f, float* image, float* cf, int device)
+{
+    int st = check_tfm_analytic(a, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, image);
+    if (st) return st;
+    const size_t na = (size_t)n_tx * n_rx * n_t * 2;
+    const bool same = tt_tx == tt_rx && n_tx == n_rx;
+    Session S;
+    if ((st = S.open(device, al256(4 * na) + (same ? 1 : 2) * al256(8 * (size_t)(n_tx > n_rx ? n_tx : n_rx) * n_f) +
+                                 al256(8 * (size_t)n_f) + (cf ? al256(4 * (size_t)n_f) : 0))))
+        return st;
+    float* da;
+    double *dtx, *drx;
+    S.upload(da, a, na);
+    S.upload(dtx, tt_tx, (size_t)n_tx * n_f);
+    if (same) drx = dtx; else S.upload(drx, tt_rx, (size_t)n_rx * n_f);
+    float* dimg = S.take<float>(2 * (size_t)n_f);
+    float* dcf = cf ? S.take<float>(n_f) : nullptr;
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, n_f, dimg, dcf, S.a->stream));
+    S.download(image, dimg, 2 * (size_t)n_f);
+    if (cf) S.download(cf, dcf, (size_t)n_f);
     HIP_TRY(S.finish());
     return RTUS_OK;
 }

@@ -204,3 +204,113 @@ hipError_t rtus_launch_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double
     hipLaunchKernelGGL(rtus_tfm_kernel, dim3((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------- envelope TFM + coherence factor
+// The same delay-and-sum over an analytic (complex) FMC: S[f] = sum over (tx, rx) of a[tx][rx] at rtus_tfm's sample position, real
+// and imaginary parts interpolated separately with rtus_tfm's arithmetic, edge rules and order — so S.re is rtus_tfm on the real
+// parts and S.im rtus_tfm on the imaginary parts, bit for bit.  With CF, also E[f] = sum over the pairs of |a(s)|^2 and
+// N[f] = T[f] R[f], the legs with a path counted while the delays are formed (none of it in the gather loop but two FMAs);
+// cf = |S|^2 / (N E) in fp64.  Definition: include/rtus.h (rtus_tfm_analytic).
+//
+// rtus_tfm_kernel's structure (256 focal points per workgroup, the XCD-contiguous order, the 64-element receive tile in LDS,
+// sixteen gathers in flight per lane) with rtus_surface_find_kernel's 16-byte gathers: two neighbouring complex samples in one
+// range-checked buffer load, 16 B of L2 traffic per (pair, focal point).
+struct TfmaArgs {
+    const float* __restrict__ a;         // [n_tx][n_rx][n_t][2]
+    const double* __restrict__ tt_tx;    // [n_tx][n_f]
+    const double* __restrict__ tt_rx;    // [n_rx][n_f]
+    float2* __restrict__ image;          // [n_f]
+    float* __restrict__ cf;              // [n_f] (read by the CF instantiation only)
+    int n_tx, n_rx, n_t, n_f;
+    double fs, half_t0s;
+};
+
+__device__ __forceinline__ int tfm_has_path(float tau) { return tau > -1.0e8f; }   // tfm_tau's no-path value is -1e8, a path's |tau| < 1e8
+
+template <bool CF>
+__device__ __forceinline__ void tfma_accum(sf_u32x4 v, float w, float& re, float& im, float& en)
+{
+    const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
+    const float pr = fmaf(w, r1 - r0, r0), pi = fmaf(w, i1 - i0, i0);
+    re += pr;
+    im += pi;
+    if (CF) en = fmaf(pi, pi, fmaf(pr, pr, en));
+}
+
+template <bool CF>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs a)
+{
+    __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB, as rtus_tfm_kernel
+    const int nblk = gridDim.x, per = (nblk + 7) >> 3;                // XCD k takes a contiguous share (rtus_tfm_kernel)
+    int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if (nblk & 7) blk = blockIdx.x;
+    const int f_raw = blk * RTUS_BLOCK + threadIdx.x;
+    const bool live = f_raw < a.n_f;
+    const int f = live ? f_raw : a.n_f - 1;
+    const size_t nf = (size_t)a.n_f;
+    const size_t pair_len = (size_t)a.n_t * 2;                        // floats per analytic A-scan
+    const bool tx_in_tile = a.tt_tx == a.tt_rx && a.n_tx == a.n_rx && a.n_rx <= RTUS_TFM_RX_TILE;
+    float re = 0.0f, im = 0.0f, en = 0.0f;
+    int n_tx_ok = 0, n_rx_ok = 0;                                     // T[f], R[f] (CF only)
+    for (int r0 = 0; r0 < a.n_rx; r0 += RTUS_TFM_RX_TILE) {
+        const int nr = min(RTUS_TFM_RX_TILE, a.n_rx - r0);
+        __syncthreads();                                              // the previous tile is no longer read
+        for (int r = 0; r < nr; ++r) {
+            const float v = tfm_tau(a.tt_rx[(size_t)(r0 + r) * nf + f], a.fs, a.half_t0s);
+            tau_rx[r][threadIdx.x] = v;
+            if (CF) n_rx_ok += tfm_has_path(v);
+        }
+        __syncthreads();
+        for (int tx = 0; tx < a.n_tx; ++tx) {
+            const float tt = tx_in_tile ? tau_rx[tx][threadIdx.x] : tfm_tau(a.tt_tx[(size_t)tx * nf + f], a.fs, a.half_t0s);
+            if (CF && r0 == 0) n_tx_ok += tfm_has_path(tt);
+            const float* rec = a.a + ((size_t)tx * a.n_rx + r0) * pair_len;   // wave-uniform
+            int r = 0;
+            for (; r + RTUS_TFM_GROUP <= nr; r += RTUS_TFM_GROUP) {
+                sf_u32x4 v[RTUS_TFM_GROUP];
+                float w[RTUS_TFM_GROUP];
+#pragma unroll
+                for (int k = 0; k < RTUS_TFM_GROUP; ++k) {           // all sixteen gathers issued before the first is used
+                    const float s = tt + tau_rx[r + k][threadIdx.x];
+                    const float fl = floorf(s);
+                    w[k] = s - fl;
+                    v[k] = sf_load2(rec + (size_t)(r + k) * pair_len, a.n_t, (int)fl);
+                }
+#pragma unroll
+                for (int k = 0; k < RTUS_TFM_GROUP; ++k) tfma_accum<CF>(v[k], w[k], re, im, en);
+            }
+            for (; r < nr; ++r) {                                     // receive elements past the last full group
+                const float s = tt + tau_rx[r][threadIdx.x];
+                const float fl = floorf(s);
+                tfma_accum<CF>(sf_load2(rec + (size_t)r * pair_len, a.n_t, (int)fl), s - fl, re, im, en);
+            }
+        }
+    }
+    if (!live) return;
+    a.image[f] = make_float2(re, im);
+    if (CF) {
+        // |S|^2 is exact in fp64 (squares of fp32 values); pairs outside the record count in N with value 0, so |S|^2 <= N E up
+        // to the rounding of the fp32 sums (Cauchy-Schwarz): clamped to 1
+        const double n = (double)n_tx_ok * (double)n_rx_ok;
+        double c = NAN;                                               // no pair with a path
+        if (n > 0.0) {
+            const double s2 = (double)re * (double)re + (double)im * (double)im;
+            c = en > 0.0f ? s2 / (n * (double)en) : 0.0;
+            c = c > 1.0 ? 1.0 : c;
+        }
+        a.cf[f] = (float)c;
+    }
+}
+
+hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                                    const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s)
+{
+    TfmaArgs a;
+    a.a = an; a.tt_tx = tt_tx; a.tt_rx = tt_rx; a.image = (float2*)image; a.cf = cf;
+    a.n_tx = n_tx; a.n_rx = n_rx; a.n_t = n_t; a.n_f = n_f;
+    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    if (cf) hipLaunchKernelGGL(rtus_tfm_analytic_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(rtus_tfm_analytic_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}

@@ -388,6 +388,32 @@ def surface_find_dev(analytic, fs, xe, ze, c1, x0, dx, n_s, z_lo, dz, n_z, t0=0.
     return z_peak, amp
 
 
+def tfm_analytic_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None):
+    """Envelope TFM on device (rtus_tfm_analytic_dev; api.tfm_analytic's definition): analytic float32 [n_tx, n_rx, n_t, 2] (as
+    fmc_analytic_dev makes it), tt_tx [n_tx, n_f], tt_rx [n_rx, n_f] (default: tt_tx) -> out float32 [n_f, 2] (the complex sum);
+    ``cf``: an optional float32 [n_f] tensor that receives the coherence factor (then -> (out, cf)).  Asynchronous on the current
+    stream (capturable with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    if analytic.dim() != 4 or analytic.shape[3] != 2 or tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] \
+            or analytic.shape[0] != tt_tx.shape[0] or analytic.shape[1] != tt_rx.shape[0]:
+        raise ValueError("need analytic [n_tx, n_rx, n_t, 2], tt_tx [n_tx, n_f], tt_rx [n_rx, n_f]")
+    n_f = tt_tx.shape[1]
+    if out is None:
+        out = torch.empty((n_f, 2), dtype=torch.float32, device=analytic.device)
+    _chk(out, "out", torch.float32)
+    if cf is not None:
+        _chk(cf, "cf", torch.float32)
+    if out.numel() != 2 * n_f or (cf is not None and cf.numel() != n_f):
+        raise ValueError("out must hold 2 * n_focal float32 values, cf n_focal")
+    if not (out.device == analytic.device == tt_tx.device == tt_rx.device and (cf is None or cf.device == analytic.device)):
+        raise ValueError("analytic, tt_tx, tt_rx, out and cf must be on one device")
+    st = _lib.lib().rtus_tfm_analytic_dev(_p(analytic), analytic.shape[0], analytic.shape[1], analytic.shape[2], float(fs), float(t0),
+                                          _p(tt_tx), _p(tt_rx), n_f, _p(out), _p(cf), _stream(analytic))
+    _lib.check(st, "rtus_tfm_analytic_dev")
+    return out if cf is None else (out, cf)
+
+
 class LayersPlan:
     """Pre-bound ``rtus_tt_layers_dev`` call for repeated solves of one shape: ``run()`` is a single
     ctypes call (no argument checking, no allocation, no sync) — capturable in a hipGraph."""
