@@ -270,8 +270,8 @@ def travel_time_layers(z_if, c, xe, ze, xf, zf, *, return_iters=False, out=None,
     ``out``: optional float64 [n_e, n_f] result buffer, returned as ``tt``.
     ``devices``: a list of GPU indices — the table's rows are solved in contiguous blocks on all of them at once and each
     GPU copies its block straight into ``tt`` (rtus_tt_layers_multi_ex); the result is bit for bit the one-GPU table.
-    ``taup``: the faster accuracy tier (RTUS_TT_TAUP_TAIL: the tau-p form of the travel time, <= 6e-11 relative at worst,
-    measured 3e-17 s on BASELINE configs[2]; the default tier: <= 1e-13 relative) — the tier bench.py's headline times.
+    ``taup``: the faster accuracy tier (RTUS_TT_TAUP_TAIL: the tau-p form of the travel time, <= 1.3e-10 relative at worst
+    (include/rtus.h), measured 3e-17 s on BASELINE configs[2]; the default tier: <= 1e-13 relative) — the tier bench.py's headline times.
     The aperture may come in any order: the rows are solved in (depth, position) order and stored where they belong, so an
     element's bits do not depend on it (``return_iters`` takes the elements as given: it is a diagnostic of that).
 

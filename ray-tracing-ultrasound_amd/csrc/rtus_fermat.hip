@@ -90,7 +90,7 @@ struct __attribute__((aligned(16))) ElemRec {
 typedef const __attribute__((address_space(3))) ElemRec* RecPtr;   // a record where it lives: LDS (ds_read at a register + immediate offset)
 
 // Relative size of the Newton step at which a lane stops (and does not take it).  A HELD solve of the tau-p tier (HOLD = 2) forms its
-// second-order term from quantities good to ~0.1 % (3.6 % at worst): its error is that fraction of (tau^2 / 8) T, so it stops at a third.
+// second-order term from quantities good to ~0.1 % (8.4 % at worst): its error is that fraction of (tau^2 / 8) T, so it stops at a third.
 #define RTUS_PLANAR_TAU 3e-4f
 
 // Per-lane solver state: the layer table of this lane's target, PERMUTED so that slot 0 is the lane's fastest
@@ -182,7 +182,7 @@ __device__ __forceinline__ void layer_setup(const LayerArgs& a, double ze, const
 template <int NL, bool ITERS, bool FAST, bool TAUP, int HOLD = 0>
 __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL>& L, RecPtr R, int hist, double xf,
                                             float h1, float h2, float h3, float h4, bool live, size_t row, unsigned f8,
-                                            __amdgpu_buffer_rsrc_t rs, unsigned soff, float hold_age_rcp = 0.0f, bool* hold_ok = nullptr)
+                                            __amdgpu_buffer_rsrc_t rs, unsigned soff, bool after_held = false, bool* hold_ok = nullptr)
 {
     static_assert(HOLD == 0 || (FAST && TAUP), "HOLD is a mode of the tau-p tier's four-history runs");
     const double dxs = xf - R->xe;
@@ -256,7 +256,8 @@ __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL
             if (__ballot(relw > 1e-4f) && l0) atomicAdd(&planar_dbg[4], 1ull);
         }
 #endif
-        // (a prediction of the wrong sign is never "small": the step it asks for is larger than itself)
+        // (a prediction of the wrong sign is never "small": the step it asks for is larger than itself).  A held solve stops at tau / 3
+        // on the second-evaluation path too: its error bound is one at the stopping threshold, whatever the predictor left it.
         const float tau_f = HOLD == 2 ? L.tau * (1.0f / 3.0f) : L.tau;   // (loop-invariant: one register, no instruction per solve)
         const bool big = fabsf(dq) > tau_f * fabsf(q);
         if (__builtin_amdgcn_ballot_w64(big)) {             // wave-uniform: some lane wants a second evaluation
@@ -269,7 +270,7 @@ __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL
             if (ITERS) it += big ? 1 : 0;
             for (int trip = 0; trip < 64; ++trip) {         // wave-uniform trip count, ballot exit
                 eval(q, true);
-                const bool bigger = fabsf(dq) > L.tau * fabsf(q);
+                const bool bigger = fabsf(dq) > tau_f * fabsf(q);
                 if (!__builtin_amdgcn_ballot_w64(bigger)) break;
                 q = bigger ? __builtin_amdgcn_fmed3f(q + dq, lbs, sinf) : q;
                 if (ITERS) it += bigger ? 1 : 0;
@@ -322,15 +323,20 @@ __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL
         }
         // the second-order term = G dXf^2 with G = u^3 / (2 cm X'(q)); HOLD = 2: the G of the group's first element (see the kernel)
         float G;
-        if (HOLD == 2) G = L.G = L.G + L.dG;                // one element further along the line through the last two G formed
+        if (HOLD == 2) G = L.G = L.G + L.dG;                // one element further along the secant through the last two G formed exactly
         else {
             G = ((L.hic * us) * (us * us)) * L.rS3;
             if (HOLD == 1) {
-                L.dG = (G - L.G) * hold_age_rcp;                // hold_age_rcp here: 1 / (elements since L.G was formed)
-                // G is a smooth function of q (|d ln G / dq| <= 3, |G'' / G| <= ~20 along the aperture): a step of the root of <= 0.02
-                // per element keeps the line through the last two G within 10 (3 x 0.02)^2 = 3.6 % of G over the three elements ahead
-                // (typically ~0.1 %), and rules out a group that straddles the extremum of G under a target (first difference ~0,
-                // second difference not).  (A separate test on the first difference of G was redundant with this one: dropped.)
+                // the secant through the two latest EXACTLY formed G.  After a held group L.G is the extrapolated G of the element
+                // before this one, and L.G - 3 dG the exact G of the previous group's first element, four elements back; otherwise
+                // L.G is the exact G of the element before this one.  (after_held is wave-uniform: two scalar selects, one FMA.)
+                L.dG = fmaf(after_held ? 3.0f : 0.0f, L.dG, G - L.G) * (after_held ? 0.25f : 1.0f);
+                // G is a smooth function of q (|d ln G / dq| <= 3, |G'' / G| <= ~20 along the aperture).  With the root moving by
+                // Dq <= 0.02 per element, the secant through the G of elements -s and 0 misses the G of element j by at most
+                // |G''| (j + s) j Dq^2 / 2: over the three elements ahead (j <= 3) 10.5 |G''| Dq^2 <= 8.4 % of G after a held group
+                // (s = 4), 6 |G''| Dq^2 <= 4.8 % after one that was not (s = 1) — typically ~0.1 %.  The test also rules out a
+                // group that straddles the extremum of G under a target (first difference ~0, second difference not).  (A separate
+                // test on the first difference of G was redundant with this one: dropped.)
                 *hold_ok = !__builtin_amdgcn_ballot_w64(fabsf(h1 - h2) > 0.02f) &&   // (lanes without a path: NaN, never true)
                            (__builtin_amdgcn_readfirstlane(R->info) & 16);            // the pitch is uniform around this group
             }
@@ -499,14 +505,15 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
             // HOLD (tau-p tier).  The untaken Newton step dq = dXf / X' and the tail's second-order term G dXf^2 need X'(q) and u^3
             // only to a few per cent — dq moves the history by <= tau q, the term is <= (tau^2 / 8) T — and both drift by ~1-2 % from
             // one element to the next.  So the FIRST solve of a group of four forms them exactly (HOLD = 1: the sum for X', v_rcp_f32,
-            // u^3) and, where the root moves by <= 0.02 per element (wave-uniform test: |d ln G / dq| <= 3 and its curvature bound the
-            // line through the last two G to within ~3.6 % of G over three elements) and the pitch is uniform around the group (bit 4
-            // of the record: the line runs along the element index), the other three reuse them (HOLD = 2: eleven fp32 instructions
-            // fewer per solve, stopping at tau / 3); otherwise they form their own (HOLD = 0).  Error of the held term: <= 3.6 % of
-            // ((tau / 3)^2 / 8) T = 4.5e-11 T at the stopping threshold, 1e-15 T typically.
+            // u^3) and, where the root moves by <= 0.02 per element (wave-uniform test: the curvature of G bounds the secant through
+            // the last two exactly formed G to within 8.4 % of G over three elements, see HOLD = 1) and the pitch is uniform around the
+            // group (bit 4 of the record: the secant runs along the element index), the other three reuse them (HOLD = 2: eleven fp32
+            // instructions fewer per solve, stopping at tau / 3); otherwise they form their own (HOLD = 0).  Error of the held term:
+            // <= 8.4 % of ((tau / 3)^2 / 8) T = 1.05e-10 T at the stopping threshold, 1e-15 T typically; with the fp32 residual's
+            // (tau / 3) 2e-7 T a held solve is within 1.25e-10 T.
             // A row's bits stay a function of the table (the groups start where the four-history run starts: a function of the
             // aperture and of the rows per block).
-            bool held = false;                              // L.G is one element old (else: four)
+            bool held = false;                              // the previous group of this run was held: L.G is extrapolated (see HOLD = 1)
             for (int r = 0; r < run4; r += 4) {
 #ifdef RTUS_EXP_NO_HOLD
                 if (false) {
@@ -514,7 +521,7 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
                 if (TAUP) {
 #endif
                     bool ok = false;
-                    qd = solve_elem<NL, ITERS, true, TAUP, TAUP ? 1 : 0>(it_p, L, rp + 0, 4, xf, qa, qb, qc, qd, live, dest_o(li + r, o), f8, dest_rs(li + r, o), dest_so(so), held ? 0.25f : 1.0f, &ok);
+                    qd = solve_elem<NL, ITERS, true, TAUP, TAUP ? 1 : 0>(it_p, L, rp + 0, 4, xf, qa, qb, qc, qd, live, dest_o(li + r, o), f8, dest_rs(li + r, o), dest_so(so), held, &ok);
                     if (ok) {
                         qc = solve_elem<NL, ITERS, true, TAUP, TAUP ? 2 : 0>(it_p, L, rp + 1, 4, xf, qd, qa, qb, qc, live, dest_o(li + r + 1, o + nf), f8, dest_rs(li + r + 1, o + nf), dest_so(so + row_bytes));
                         qb = solve_elem<NL, ITERS, true, TAUP, TAUP ? 2 : 0>(it_p, L, rp + 2, 4, xf, qc, qd, qa, qb, live, dest_o(li + r + 2, o + 2 * nf), f8, dest_rs(li + r + 2, o + 2 * nf), dest_so(so + 2 * row_bytes));

@@ -260,7 +260,12 @@ __global__ __launch_bounds__(RTUS_BLOCK, sizeof(R) == 4 ? 8 : 3) void rtus_tt_le
 #endif
         r.mode = lin ? 2 : (hist >= 1 ? 1 : 0);
         const unsigned long long m2 = __builtin_amdgcn_ballot_w64(r.mode == 2 && idx < ne);
-        float xmn = (float)xe_v, xmx = (float)xe_v;          // (idx >= ne repeats the last element: no effect on the extent)
+        // the block's OWN elements only: a thread with idx >= ne reads an element of the next block (or, in a row shard, the shard's
+        // last one), which would make reach — and the fast rows' g' threshold below — depend on where the launch ends.  An element at
+        // a non-finite position makes the block's reach infinite (fminf / fmaxf would drop a NaN): the rows behind it take the
+        // generic step, whose history handling tests/test_gpu_edge_sizes.py checks; the fast rows' extrapolation does not survive it
+        const bool fin = isfinite(xe_v);
+        float xmn = idx < ne ? (fin ? (float)xe_v : -INFINITY) : INFINITY, xmx = idx < ne ? (fin ? (float)xe_v : INFINITY) : -INFINITY;
         for (int sh = 32; sh > 0; sh >>= 1) { xmn = fminf(xmn, __shfl_xor(xmn, sh)); xmx = fmaxf(xmx, __shfl_xor(xmx, sh)); }
         if (lane == 0) { m2s[idx >> 6] = m2; xext[2 * (idx >> 6)] = xmn; xext[2 * (idx >> 6) + 1] = xmx; }
     }
