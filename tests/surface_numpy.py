@@ -121,10 +121,10 @@ def stationary(x0, dx, zs, c1, c2, xe, ze, xf, zf, coef=None):
     return ent[o], x[o], kind[o], t[o]
 
 
-def table(x0, dx, zs, c1, c2, xe, ze, xf, zf):
+def table(x0, dx, zs, c1, c2, xe, ze, xf, zf, coef=None):
     """-> dict(t, x, basin, gap), each [n_e, n_f]: travel time, winning entry point, winner's basin width, runner-up gap"""
     zs = np.asarray(zs, dtype=np.float64)
-    coef = spline(x0, dx, zs)
+    coef = spline(x0, dx, zs) if coef is None else coef
     xe, ze, xf, zf = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (xe, ze, xf, zf))
     n_e, n_f = xe.size, xf.size
     ent, x, kind, t = stationary(x0, dx, zs, c1, c2, xe, ze, xf, zf, coef)
@@ -158,6 +158,28 @@ def table(x0, dx, zs, c1, c2, xe, ze, xf, zf):
     out_x[~ok] = np.nan
     shp = (n_e, n_f)
     return dict(t=out_t.reshape(shp), x=out_x.reshape(shp), basin=out_b.reshape(shp), gap=out_g.reshape(shp))
+
+
+def table_chunked(x0, dx, zs, c1, c2, xe, ze, xf, zf, chunk=256):
+    """table() over the focal points in chunks of ``chunk`` (stationary()'s arrays are [chunk, 64 (n_s - 1)] doubles), the spline
+    solved once"""
+    coef = spline(x0, dx, zs)
+    xf, zf = np.atleast_1d(np.asarray(xf, dtype=np.float64)), np.atleast_1d(np.asarray(zf, dtype=np.float64))
+    parts = [table(x0, dx, zs, c1, c2, xe, ze, xf[i:i + chunk], zf[i:i + chunk], coef) for i in range(0, xf.size, chunk)]
+    return {k: np.concatenate([p[k] for p in parts], axis=1) for k in parts[0]}
+
+
+def count_minima(x0, dx, zs, c1, c2, xe, ze, xf, zf, chunk=256):
+    """[n_e, n_f] number of interior local minima of T per entry (validity not applied), over the focal points in chunks"""
+    coef = spline(x0, dx, zs)
+    xe = np.atleast_1d(np.asarray(xe, dtype=np.float64))
+    xf, zf = np.atleast_1d(np.asarray(xf, dtype=np.float64)), np.atleast_1d(np.asarray(zf, dtype=np.float64))
+    out = np.zeros((xe.size, xf.size), dtype=np.int64)
+    for i in range(0, xf.size, chunk):
+        n = min(chunk, xf.size - i)
+        ent, _, kind, _ = stationary(x0, dx, zs, c1, c2, xe, ze, xf[i:i + n], zf[i:i + n], coef)
+        out[:, i:i + n] = np.bincount(ent[kind == 1], minlength=xe.size * n).reshape(xe.size, n)
+    return out
 
 
 def minima(x0, dx, zs, c1, c2, xe, ze, xf, zf):

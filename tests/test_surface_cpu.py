@@ -108,6 +108,22 @@ def test_oracle_validity_rules():
     assert np.isfinite(r["t"][0, 0])
 
 
+def test_chunked_oracle_equals_the_whole_table():
+    """table_chunked / count_minima (the GPU suite's memory-bounded forms) are table / stationary over slices of the focal points"""
+    zs = _wavy()
+    xe, ze = np.linspace(-0.01, 0.01, 3), np.zeros(3)
+    rng = np.random.default_rng(3)
+    xf, zf = rng.uniform(-0.018, 0.018, 70), rng.uniform(0.015, 0.04, 70)
+    whole = S.table(X0, DX, zs, C1, C2, xe, ze, xf, zf)
+    parts = S.table_chunked(X0, DX, zs, C1, C2, xe, ze, xf, zf, chunk=16)
+    for k in whole:
+        assert np.array_equal(whole[k], parts[k], equal_nan=True), k
+    ent, _, kind, _ = S.stationary(X0, DX, zs, C1, C2, xe, ze, xf, zf)
+    n = np.bincount(ent[kind == 1], minlength=xe.size * xf.size).reshape(xe.size, xf.size)
+    assert np.array_equal(S.count_minima(X0, DX, zs, C1, C2, xe, ze, xf, zf, chunk=16), n)
+    assert n.max() >= 2
+
+
 def test_invalid_arguments_are_status_codes(rtus):
     """argument checks return -1 / -4 before any HIP call (no GPU here)"""
     L = rtus.lib()
