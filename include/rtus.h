@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 106 /* 0.1.5: rtus_tfm_analytic* (envelope TFM + coherence factor over an analytic FMC) */
+#define RTUS_VERSION 107 /* 0.1.6: rtus_pw_layers*, rtus_pw_surface*, rtus_fmc_synth_tx* (plane-wave imaging) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -600,6 +600,73 @@ int rtus_tfm_analytic_dev(const float *d_a, int n_tx, int n_rx, int n_t, double 
 int rtus_tfm_analytic(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
                       const double *tt_tx, const double *tt_rx, int n_f,
                       float *image, float *cf, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Plane-wave imaging (PWI): a few dozen plane waves, each fired by the whole aperture with a linear delay law and received on every
+ * element.  The transmit leg is a table with one row per angle, tt_pw [n_a][n_f]; the receive leg is an element table (rtus_tt_*)
+ * and the delay-and-sum is rtus_tfm / rtus_tfm_analytic with tt_tx = tt_pw.  NOT IN THE REFERENCE; checked against
+ * tests/pwi_numpy.py (itself checked against mpmath at 40 digits and a brute-force Huygens minimum).
+ *
+ * Array and angle.  The array is linear and horizontal at depth z_a, spanning [x_lo, x_hi], in medium 1 (speed c1; c[0] for
+ * layers).  A plane wave has angle t, measured in medium 1 from +z towards +x, with |t| < pi/2.  Let u = (sin t, cos t) and
+ * x_ref = x_lo if sin t >= 0, else x_hi.  Element e fires at d_e(t) = (x_e - x_ref) sin t / c1 >= 0, so time zero is the first
+ * firing.  These are the delays the user loads into the instrument (the Python layer's pw_delays returns them).
+ *
+ * rtus_pw_layers: planar layers (z_if, c as in rtus_tt_layers, HOST memory; z_a < z_if[0]).  With p = sin t / c[0] and h_i the
+ *   vertical extent of layer i between z_a and zf:
+ *       t(F) = (xf - x_ref) p + sum_i h_i sqrt(1/c_i^2 - p^2)
+ *   The entry is NaN when any of these holds: zf <= z_a; p c_i >= 1 in a layer the path crosses (evanescent); t is not finite or
+ *   |t| >= pi/2; F is not insonified.  F is insonified when the ray traced back from F meets the array line inside the aperture:
+ *   x_back = xf - sum_i h_i p c_i / sqrt(1 - p^2 c_i^2) must lie in [x_lo, x_hi] (inclusive).  A focal point on an interface
+ *   depth belongs to the layer above it.  The square roots are formed once per (angle, layer) in the kernel.
+ *
+ * rtus_pw_surface: a measured surface (the spline, grid, extent and focal-point rules of rtus_tt_surface; c1 above, c2 below).
+ *   With S(x) = (x, s(x)):
+ *       T(x) = ((x - x_ref) sin t + (s(x) - z_a) cos t) / c1 + |S(x) - F| / c2
+ *   An entry x is insonified when x - (s(x) - z_a) tan t lies in [x_lo, x_hi].  The table entry is the least T over the interior
+ *   local minima of T at insonified entries.  It is NaN when there is none, when the profile is not strictly below z_a (z_a >=
+ *   min s: the whole table is NaN), for an angle that is not finite or has |t| >= pi/2, and under rtus_tt_surface's focal-point
+ *   rules.  x_entry [n_a][n_f] is optional, as in rtus_tt_surface.
+ *   Guarantee: rtus_tt_surface's, with the band edges counting like stationary points: a minimum is found when its neighbouring
+ *   stationary points and band edges are at least dx / 2 away.
+ *   Determinism: an entry's bits depend only on its angle, its focal point, the profile, the array and the speeds; subsets or
+ *   reorderings of angles or focal points give the same bits.
+ *   d_workspace: rtus_tt_surface_workspace_bytes(n_s) bytes, 256-byte aligned (-4 otherwise).
+ *
+ * rtus_fmc_synth_tx: synthesis of any transmit delay law from an FMC,
+ *       out[v][rx][n] = sum over tx ascending of x_{tx,rx}(n - d[v][tx] fs)
+ *   fmc [n_tx][n_rx][n_t] float32 (fs samples per second), delays [n_v][n_tx] in seconds (DEVICE memory in the _dev entry): plane
+ *   waves, diverging waves and sub-apertures all fit.  x is the record, linearly interpolated; indices outside [0, n_t) count as
+ *   zero.  For each (v, tx) the shift s = d fs is formed once in fp64: m = ceil(s), the position n - s lies between samples
+ *   i = n - m and i + 1 with weight w = m - s, rounded once to fp32 (so a whole-sample delay shifts the record exactly); the term
+ *   is fmaf(w, x[i + 1] - x[i], x[i]) and the sum is fp32 in tx order.  A tx with a non-finite delay or |d fs| >= 1e8 is not
+ *   fired (skipped).  The bits of out[v] do not depend on which other v share the call.  out [n_v][n_rx][n_t] float32 has the
+ *   FMC's layout, so rtus_fmc_analytic, rtus_tfm and rtus_tfm_analytic take it as it is; it must not overlap fmc or delays (-1).
+ *
+ * Argument checks run before any HIP call: -1 for a null pointer, a non-positive size, x_lo > x_hi, a non-finite scalar, a speed
+ * <= 0, a non-ascending z_if, z_a >= z_if[0], fs <= 0, an overlapping synthesis output; -5 past a limit: n_a <= 65535,
+ * n_if <= RTUS_MAX_LAYERS, n_s <= 2^22 (rtus_tt_surface's), n_v <= 65535, n_rx <= 65535, n_t <= 2^28.  The _dev entries allocate
+ * nothing and do not synchronise (capturable).  The host twins take host buffers, stage them through the device's arena, last
+ * argument `device`.
+ * Measured on MI355X: see DESIGN.md §4 (plane-wave imaging).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_pw_layers_dev(const double *z_if, const double *c, int n_if, const double *d_angles, int n_a,
+                       double x_lo, double x_hi, double z_a, const double *d_xf, const double *d_zf, int n_f,
+                       double *d_tt, void *stream);
+int rtus_pw_layers(const double *z_if, const double *c, int n_if, const double *angles, int n_a,
+                   double x_lo, double x_hi, double z_a, const double *xf, const double *zf, int n_f,
+                   double *tt, int device);
+int rtus_pw_surface_dev(double x0, double dx, const double *d_zs, int n_s, double c1, double c2,
+                        const double *d_angles, int n_a, double x_lo, double x_hi, double z_a,
+                        const double *d_xf, const double *d_zf, int n_f, double *d_tt, double *d_x_entry,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
+int rtus_pw_surface(double x0, double dx, const double *zs, int n_s, double c1, double c2,
+                    const double *angles, int n_a, double x_lo, double x_hi, double z_a,
+                    const double *xf, const double *zf, int n_f, double *tt, double *x_entry, int device);
+int rtus_fmc_synth_tx_dev(const float *d_fmc, int n_tx, int n_rx, int n_t, double fs, const double *d_delays, int n_v,
+                          float *d_out, void *stream);
+int rtus_fmc_synth_tx(const float *fmc, int n_tx, int n_rx, int n_t, double fs, const double *delays, int n_v,
+                      float *out, int device);
 
 #ifdef __cplusplus
 }

@@ -172,6 +172,19 @@ def lib():
     for name in ("rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find", "rtus_tfm_analytic_dev",
                  "rtus_tfm_analytic"):
         getattr(L, name).restype = ip
+    try:
+        L.rtus_pw_layers_dev.argtypes = [dp, dp, ip, dp, ip, dd, dd, dd, dp, dp, ip, dp, vp]
+        L.rtus_pw_layers.argtypes = [dp, dp, ip, dp, ip, dd, dd, dd, dp, dp, ip, dp, ip]
+        L.rtus_pw_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dp, ip, dd, dd, dd, dp, dp, ip, dp, dp, vp, C.c_size_t, vp]
+        L.rtus_pw_surface.argtypes = [dd, dd, dp, ip, dd, dd, dp, ip, dd, dd, dd, dp, dp, ip, dp, dp, ip]
+        L.rtus_fmc_synth_tx_dev.argtypes = [dp, ip, ip, ip, dd, dp, ip, dp, vp]
+        L.rtus_fmc_synth_tx.argtypes = [dp, ip, ip, ip, dd, dp, ip, dp, ip]
+        for name in ("rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev",
+                     "rtus_fmc_synth_tx"):
+            getattr(L, name).restype = ip
+    except AttributeError:                # a build from before version 107, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -197,4 +210,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev",
            "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface",
            "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find",
-           "rtus_tfm_analytic_dev", "rtus_tfm_analytic")
+           "rtus_tfm_analytic_dev", "rtus_tfm_analytic",
+           "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx")

@@ -591,3 +591,112 @@ def adaptive_tfm(fmc, fs, xe, ze, c1, c2, x0, dx, n_s, z_lo, z_hi, dz, xf, zf, *
     if envelope:
         return np.abs(tfm_analytic(analytic, fs, tt, t0=t0, device=device)), surf
     return tfm_image(fmc, fs, tt, t0=t0, device=device), surf
+
+
+# ---------------------------------------------------------------------------------------------- plane-wave imaging
+def _aperture(xe, ze):
+    """(x_lo, x_hi, z_a) of a linear horizontal array: all elements at one depth"""
+    xe, ze = _f64(xe, "xe"), _f64(ze, "ze")
+    if xe.shape != ze.shape or xe.size == 0:
+        raise ValueError("xe/ze must pair up and hold at least one element")
+    if not (np.all(np.isfinite(xe)) and np.all(np.isfinite(ze))):
+        raise ValueError("element positions must be finite")
+    if np.any(ze != ze[0]):
+        raise ValueError("plane waves need a horizontal array: all ze equal")
+    return float(xe.min()), float(xe.max()), float(ze[0])
+
+
+def pw_delays(xe, ze, angles, c1):
+    """Firing delays of plane waves -> float64 [n_a, n_e]: element e fires at (xe[e] - x_ref) sin(angle) / c1 >= 0 with
+    x_ref = min(xe) for sin(angle) >= 0, else max(xe) (time zero: the first firing).  Angles in radians, measured in medium 1
+    (speed ``c1``) from +z towards +x.  The array must be horizontal (equal ``ze``).  Computed on the host; a non-finite angle or
+    |angle| >= pi/2 gives a NaN row (the synthesis skips NaN delays).  Definition: include/rtus.h (plane-wave imaging)."""
+    x_lo, x_hi, _ = _aperture(xe, ze)
+    xe = _f64(xe, "xe")
+    a = _f64(angles, "angles")
+    if not (np.isfinite(c1) and c1 > 0):
+        raise ValueError("c1 must be a positive finite speed")
+    ok = np.abs(a) < np.pi / 2
+    sn = np.sin(np.where(ok, a, 0.0))
+    xref = np.where(sn >= 0.0, x_lo, x_hi)
+    d = (xe[None, :] - xref[:, None]) * sn[:, None] / float(c1)
+    d[~ok] = np.nan
+    return d
+
+
+def pw_travel_time_layers(z_if, c, angles, xe, ze, xf, zf, *, out=None, device=0):
+    """Plane-wave transmit times through horizontal layers -> tt[n_a, n_f]: the time from the first firing until the plane wave of
+    each angle reaches each focal point.  The aperture is taken from ``xe``/``ze`` (a horizontal array above z_if[0]).  NaN where
+    the wave is evanescent in a crossed layer, the focal point is not below the array, the angle is not finite or |angle| >= pi/2,
+    or the focal point is not insonified (its ray traced back misses the aperture).  The table is ``tt_tx`` of tfm_image /
+    tfm_analytic / pwi_image with element tables as ``tt_rx``.  Definition: include/rtus.h (rtus_pw_layers).  Not in the reference."""
+    z_if = _f64(z_if, "z_if") if np.size(z_if) else np.zeros(0)
+    c = _f64(c, "c")
+    if c.size != z_if.size + 1:
+        raise ValueError("need len(c) == len(z_if) + 1")
+    x_lo, x_hi, z_a = _aperture(xe, ze)
+    ang = _f64(angles, "angles")
+    xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
+    if xf.shape != zf.shape:
+        raise ValueError("xf/zf must pair up")
+    tt = _out(out, (ang.size, xf.size), np.float64)
+    st = _lib.lib().rtus_pw_layers(_ptr(z_if) if z_if.size else None, _ptr(c), z_if.size, _ptr(ang), ang.size, x_lo, x_hi, z_a,
+                                   _ptr(xf), _ptr(zf), xf.size, _ptr(tt), int(device))
+    _lib.check(st, "rtus_pw_layers")
+    return tt
+
+
+def pw_travel_time_surface(x0, dx, zs, c1, c2, angles, xe, ze, xf, zf, *, return_entry=False, out=None, device=0):
+    """Plane-wave transmit times through ONE curved interface given as a sampled depth profile -> tt[n_a, n_f] (travel_time_surface's
+    spline, extent and focal-point rules; ``c1`` above, ``c2`` below).  The aperture is taken from ``xe``/``ze`` (a horizontal
+    array strictly above the whole profile, else the table is NaN).  An entry is the least time over the interior local minima of
+    T(x) = ((x - x_ref) sin a + (s(x) - z_a) cos a)/c1 + |S(x) - F|/c2 at insonified entry points (x - (s(x) - z_a) tan a inside the
+    aperture).  ``return_entry``: also the winning entry points, -> (tt, x_entry).  Definition and guarantee: include/rtus.h
+    (rtus_pw_surface).  Not in the reference."""
+    zs = _f64(zs, "zs")
+    x_lo, x_hi, z_a = _aperture(xe, ze)
+    ang = _f64(angles, "angles")
+    xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
+    if xf.shape != zf.shape:
+        raise ValueError("xf/zf must pair up")
+    tt = _out(out, (ang.size, xf.size), np.float64)
+    xn = np.empty((ang.size, xf.size), dtype=np.float64) if return_entry else None
+    st = _lib.lib().rtus_pw_surface(float(x0), float(dx), _ptr(zs), zs.size, float(c1), float(c2), _ptr(ang), ang.size, x_lo, x_hi, z_a,
+                                    _ptr(xf), _ptr(zf), xf.size, _ptr(tt), _ptr(xn), int(device))
+    _lib.check(st, "rtus_pw_surface")
+    return (tt, xn) if return_entry else tt
+
+
+def fmc_synth_tx(fmc, fs, delays, *, out=None, device=0):
+    """Data of any transmit delay law from an FMC -> float32 [n_v, n_rx, n_t]:
+    out[v, rx, n] = sum over tx of fmc[tx, rx](n - delays[v, tx] fs), linearly interpolated, samples outside the record zero.
+    ``delays`` [n_v, n_tx] in seconds: plane waves (pw_delays), diverging waves, sub-apertures; a NaN (or absurd) delay does not
+    fire that tx.  The output has the FMC's layout: tfm_image / fmc_analytic / tfm_analytic take it as it is.  Definition:
+    include/rtus.h (rtus_fmc_synth_tx).  Not in the reference."""
+    fmc = np.ascontiguousarray(fmc, dtype=np.float32)
+    if fmc.ndim != 3:
+        raise ValueError("fmc must be [n_tx, n_rx, n_t]")
+    d = _f64(delays, "delays", ndim=2)
+    if d.shape[1] != fmc.shape[0]:
+        raise ValueError("delays must be [n_v, n_tx] with n_tx = fmc.shape[0]")
+    o = _out(out, (d.shape[0], fmc.shape[1], fmc.shape[2]), np.float32)
+    st = _lib.lib().rtus_fmc_synth_tx(_ptr(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], float(fs), _ptr(d), d.shape[0], _ptr(o),
+                                      int(device))
+    _lib.check(st, "rtus_fmc_synth_tx")
+    return o
+
+
+def pwi_image(pw, fs, tt_pw, tt_rx, *, t0=0.0, envelope=False, coherence=False, n_taps=63, device=0):
+    """Plane-wave image: the delay-and-sum of plane-wave data ``pw`` [n_a, n_rx, n_t] (float32, e.g. fmc_synth_tx(fmc, fs,
+    pw_delays(...)) or recorded by an instrument with those delays) through the plane-wave table ``tt_pw`` [n_a, n_f]
+    (pw_travel_time_*) and an element table ``tt_rx`` [n_rx, n_f].  RF: tfm_image(pw, fs, tt_pw, tt_rx) -> float32 [n_f].  With
+    ``envelope=True``: |tfm_analytic(fmc_analytic(pw, n_taps), ...)| -> float32 [n_f], and with ``coherence=True`` also the coherence
+    factor, -> (envelope, cf)."""
+    if coherence and not envelope:
+        raise ValueError("the coherence factor needs envelope=True")
+    tt_pw = np.ascontiguousarray(tt_pw, dtype=np.float64)
+    tt_rx = np.ascontiguousarray(tt_rx, dtype=np.float64)
+    if not envelope:
+        return tfm_image(pw, fs, tt_pw, tt_rx, t0=t0, device=device)
+    r = tfm_analytic(fmc_analytic(pw, n_taps, device=device), fs, tt_pw, tt_rx, t0=t0, coherence=coherence, device=device)
+    return (np.abs(r[0]), r[1]) if coherence else np.abs(r)

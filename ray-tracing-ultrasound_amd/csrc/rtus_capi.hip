@@ -67,6 +67,13 @@ hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs
                                     float* amp, float* image, hipStream_t s);
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
+hipError_t rtus_launch_pw_layers(const double* z_if, const double* c, int n_if, const double* ang, int n_a, double xlo, double xhi,
+                                 double za, const double* xf, const double* zf, int n_f, double* tt, hipStream_t s);
+hipError_t rtus_launch_pw_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* ang, int n_a,
+                                  double xlo, double xhi, double za, const double* xf, const double* zf, int n_f, double* tt, double* xent,
+                                  void* ws, hipStream_t s);
+hipError_t rtus_launch_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, const double* d, int n_v, float* out,
+                                    hipStream_t s);
 
 static thread_local int g_last_hip = 0;
 static int hip_fail(hipError_t e) { g_last_hip = (int)e; return RTUS_ERR_HIP; }
@@ -1032,6 +1039,153 @@ int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, n_f, dimg, dcf, S.a->stream));
     S.download(image, dimg, 2 * (size_t)n_f);
     if (cf) S.download(cf, dcf, (size_t)n_f);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+// ---------------------------------------------------------------------------- plane-wave imaging
+#define RTUS_PW_MAX_ANGLES 65535
+#define RTUS_SYNTH_MAX_LAWS 65535
+#define RTUS_SYNTH_MAX_RX 65535
+static int check_aperture(const void* ang, int n_a, double x_lo, double x_hi, double z_a, const void* xf, const void* zf, int n_f,
+                          const void* tt)
+{
+    if (!ang || !xf || !zf || !tt || n_a <= 0 || n_f <= 0) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(x_lo) || !isfinite(x_hi) || !isfinite(z_a) || x_lo > x_hi) return RTUS_ERR_INVALID_ARG;
+    if (n_a > RTUS_PW_MAX_ANGLES) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+static int check_pw_layers(const double* z_if, const double* c, int n_if, const void* ang, int n_a, double x_lo, double x_hi, double z_a,
+                           const void* xf, const void* zf, int n_f, const void* tt)
+{
+    if (!c || (n_if > 0 && !z_if) || n_if < 0) return RTUS_ERR_INVALID_ARG;
+    int st = check_aperture(ang, n_a, x_lo, x_hi, z_a, xf, zf, n_f, tt);
+    if (st) return st;
+    if (n_if > RTUS_MAX_LAYERS) return RTUS_ERR_UNSUPPORTED;
+    for (int i = 0; i <= n_if; ++i) if (!(c[i] > 0) || !isfinite(c[i])) return RTUS_ERR_INVALID_ARG;
+    for (int i = 0; i < n_if; ++i) {
+        if (!isfinite(z_if[i])) return RTUS_ERR_INVALID_ARG;
+        if (i && !(z_if[i] > z_if[i - 1])) return RTUS_ERR_INVALID_ARG;
+    }
+    if (n_if > 0 && !(z_a < z_if[0])) return RTUS_ERR_INVALID_ARG;
+    return RTUS_OK;
+}
+
+int rtus_pw_layers_dev(const double* z_if, const double* c, int n_if, const double* d_angles, int n_a, double x_lo, double x_hi,
+                       double z_a, const double* d_xf, const double* d_zf, int n_f, double* d_tt, void* stream)
+{
+    int st = check_pw_layers(z_if, c, n_if, d_angles, n_a, x_lo, x_hi, z_a, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_pw_layers(z_if, c, n_if, d_angles, n_a, x_lo, x_hi, z_a, d_xf, d_zf, n_f, d_tt, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_pw_layers(const double* z_if, const double* c, int n_if, const double* angles, int n_a, double x_lo, double x_hi, double z_a,
+                   const double* xf, const double* zf, int n_f, double* tt, int device)
+{
+    int st = check_pw_layers(z_if, c, n_if, angles, n_a, x_lo, x_hi, z_a, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_a * n_f;
+    Session S;
+    if ((st = S.open(device, al256(8 * (size_t)n_a) + 2 * al256(8 * (size_t)n_f) + al256(8 * tot)))) return st;
+    double *dang, *dxf, *dzf;
+    S.upload(dang, angles, n_a);
+    S.upload(dxf, xf, n_f);
+    S.upload(dzf, zf, n_f);
+    double* dtt = S.take<double>(tot);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_pw_layers(z_if, c, n_if, dang, n_a, x_lo, x_hi, z_a, dxf, dzf, n_f, dtt, S.a->stream));
+    S.download(tt, dtt, tot);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+static int check_pw_surface(double x0, double dx, const void* zs, int n_s, double c1, double c2, const void* ang, int n_a, double x_lo,
+                            double x_hi, double z_a, const void* xf, const void* zf, int n_f, const void* tt)
+{
+    if (!zs || n_s < 4) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(x0) || !isfinite(dx) || !(dx > 0) || !isfinite(c1) || !(c1 > 0) || !isfinite(c2) || !(c2 > 0)) return RTUS_ERR_INVALID_ARG;
+    int st = check_aperture(ang, n_a, x_lo, x_hi, z_a, xf, zf, n_f, tt);
+    if (st) return st;
+    if (n_s > RTUS_SURFACE_MAX_SAMPLES) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+int rtus_pw_surface_dev(double x0, double dx, const double* d_zs, int n_s, double c1, double c2, const double* d_angles, int n_a,
+                        double x_lo, double x_hi, double z_a, const double* d_xf, const double* d_zf, int n_f, double* d_tt,
+                        double* d_x_entry, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int st = check_pw_surface(x0, dx, d_zs, n_s, c1, c2, d_angles, n_a, x_lo, x_hi, z_a, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    LAUNCH_TRY(rtus_launch_pw_surface(x0, dx, d_zs, n_s, c1, c2, d_angles, n_a, x_lo, x_hi, z_a, d_xf, d_zf, n_f, d_tt, d_x_entry,
+                                      d_workspace, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_pw_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* angles, int n_a, double x_lo,
+                    double x_hi, double z_a, const double* xf, const double* zf, int n_f, double* tt, double* x_entry, int device)
+{
+    int st = check_pw_surface(x0, dx, zs, n_s, c1, c2, angles, n_a, x_lo, x_hi, z_a, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_a * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    Session S;
+    if ((st = S.open(device, al256(8 * (size_t)n_s) + al256(8 * (size_t)n_a) + 2 * al256(8 * (size_t)n_f) + (x_entry ? 2 : 1) * al256(8 * tot) +
+                                 al256(wsb))))
+        return st;
+    double *dzs, *dang, *dxf, *dzf;
+    S.upload(dzs, zs, n_s);
+    S.upload(dang, angles, n_a);
+    S.upload(dxf, xf, n_f);
+    S.upload(dzf, zf, n_f);
+    double* dtt = S.take<double>(tot);
+    double* dxn = x_entry ? S.take<double>(tot) : nullptr;
+    void* ws = S.take<char>(wsb);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_pw_surface(x0, dx, dzs, n_s, c1, c2, dang, n_a, x_lo, x_hi, z_a, dxf, dzf, n_f, dtt, dxn, ws, S.a->stream));
+    S.download(tt, dtt, tot);
+    S.download(x_entry, dxn, tot);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+static int check_synth(const void* fmc, int n_tx, int n_rx, int n_t, double fs, const void* d, int n_v, const void* out)
+{
+    if (!fmc || !d || !out || n_tx <= 0 || n_rx <= 0 || n_t <= 0 || n_v <= 0) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(fs) || !(fs > 0)) return RTUS_ERR_INVALID_ARG;
+    if (n_t > (1 << 28) || n_rx > RTUS_SYNTH_MAX_RX || n_v > RTUS_SYNTH_MAX_LAWS) return RTUS_ERR_UNSUPPORTED;
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(4 * (size_t)n_v * n_rx * n_t);
+    const uintptr_t i0 = (uintptr_t)fmc, i1 = i0 + (uintptr_t)(4 * (size_t)n_tx * n_rx * n_t);
+    const uintptr_t d0 = (uintptr_t)d, d1 = d0 + (uintptr_t)(8 * (size_t)n_v * n_tx);
+    if ((i0 < o1 && o0 < i1) || (d0 < o1 && o0 < d1)) return RTUS_ERR_INVALID_ARG;   // the output must not overlap an input
+    return RTUS_OK;
+}
+
+int rtus_fmc_synth_tx_dev(const float* d_fmc, int n_tx, int n_rx, int n_t, double fs, const double* d_delays, int n_v, float* d_out,
+                          void* stream)
+{
+    int st = check_synth(d_fmc, n_tx, n_rx, n_t, fs, d_delays, n_v, d_out);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_fmc_synth_tx(d_fmc, n_tx, n_rx, n_t, fs, d_delays, n_v, d_out, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, const double* delays, int n_v, float* out, int device)
+{
+    int st = check_synth(fmc, n_tx, n_rx, n_t, fs, delays, n_v, out);
+    if (st) return st;
+    const size_t nin = (size_t)n_tx * n_rx * n_t, nout = (size_t)n_v * n_rx * n_t, nd = (size_t)n_v * n_tx;
+    Session S;
+    if ((st = S.open(device, al256(4 * nin) + al256(8 * nd) + al256(4 * nout)))) return st;
+    float* din;
+    double* dd;
+    S.upload(din, fmc, nin);
+    S.upload(dd, delays, nd);
+    float* dout = S.take<float>(nout);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_fmc_synth_tx(din, n_tx, n_rx, n_t, fs, dd, n_v, dout, S.a->stream));
+    S.download(out, dout, nout);
     HIP_TRY(S.finish());
     return RTUS_OK;
 }

@@ -26,6 +26,13 @@
 // Determinism: every value an entry is made of is computed from its own element, focal point, the profile and the speeds,
 // by code that does not depend on the element's slot in the workgroup or on the lane: the entry has the same bits whatever
 // else shares the call.
+//
+// Plane waves (rtus_pw_surface): the same kernel with ANGLES in the elements' place (template argument PW).  The first leg is
+// the plane wave's time to S(x), ((x - x_ref) sin t + (s(x) - z_a) cos t) / c1, so -(c2 / c1) g1 becomes -(c2 / c1)(sin t +
+// s' cos t) and T'' loses the first leg's curvature term (s'' cos t / c1 remains).  Only entry points whose ray traced back
+// along the incident direction meets the aperture count (insonified): an out-of-band scan point carries NaN in LDS and never
+// becomes the "-" side of a bracket (a NaN term would otherwise read as - and fake a - -> + change at every band edge), and the
+// refined root is tested against the band in fp64.
 #include "rtus_device.h"
 
 // no implicit contraction: the fma()s are written out, so every element slot's inlined copy of the arithmetic rounds alike
@@ -50,6 +57,9 @@ struct SurfArgs {
     const double* __restrict__ coef;   // [n_s - 1][4]: a, b, c, d of s(x0 + k dx + t) = a + b t + c t^2 + d t^3
     const float4* __restrict__ pts;    // [m]: (x - xo, s - zo, s', 0)
     const double* __restrict__ smin;   // the profile's least depth
+    // plane waves (PW instantiation): n_e counts angles; the aperture [x_lo, x_hi] at depth z_a
+    const double* __restrict__ ang;
+    double xlo, xhi, za;
 };
 
 // workspace layout (256-byte aligned pieces): M [n_s] | Thomas scratch [n_s] | coef [4 (n_s - 1)] | pts [m] | smin
@@ -169,12 +179,45 @@ __device__ __forceinline__ Tder surf_T(const double* __restrict__ coef, int n_s,
     return o;
 }
 
-// the least refined time over the kept brackets of one (element, focal point); written to tt (and xent)
-__device__ __forceinline__ void surf_refine(const double* __restrict__ coef, int n_s, int m, double x0, double dx, double hq, double inv_dx,
-                                         double c1, double c2, double xe, double ze, double xf, double zf, bool ok, float t0, float t1,
+// the same for a plane wave: first leg ((x - x_ref) sn + (s - z_a) cs) / c1
+__device__ __forceinline__ Tder surf_T_pw(const double* __restrict__ coef, int n_s, double x0, double dx, double inv_dx, double inv_c1,
+                                          double inv_c2, double sn, double cs, double xref, double za, double xf, double zf, double x)
+{
+    double s, s1, s2;
+    spline_eval(coef, n_s, x0, dx, inv_dx, x, s, s1, s2);
+    const double vx = x - xf, vz = s - zf;
+    const double q2 = fma(vx, vx, vz * vz);
+    const double r2 = 1.0 / sqrt(q2);
+    const double l2 = q2 * r2;
+    const double A2 = fma(vz, s1, vx);
+    const double B = fma(s1, s1, 1.0);
+    Tder o;
+    o.t = fma(fma(x - xref, sn, (s - za) * cs), inv_c1, l2 * inv_c2);
+    o.d1 = fma(fma(s1, cs, sn), inv_c1, A2 * r2 * inv_c2);
+    o.d2 = fma(s2 * cs, inv_c1, (fma(vz, s2, B) - A2 * A2 * r2 * r2) * r2 * inv_c2);
+    return o;
+}
+
+// per-angle constants of a plane wave (fp64, from the angle alone: the same bits in every slot and call); false when the angle is
+// not finite or |angle| >= pi / 2
+struct PwAngle { double sn, cs, tn, xref; bool ok; };
+__device__ __forceinline__ PwAngle pw_angle(double th, double xlo, double xhi)
+{
+    PwAngle p;
+    p.ok = fabs(th) < RTUS_PI_2;                                     // (NaN fails)
+    const double t = p.ok ? th : 0.0;
+    sincos(t, &p.sn, &p.cs);
+    p.tn = p.sn / p.cs;
+    p.xref = p.sn >= 0.0 ? xlo : xhi;
+    return p;
+}
+
+// the least refined time over the kept brackets of one (element, focal point); written to tt (and xent).  T(x): the travel time
+// and its derivatives at x; band(x): whether a root at x counts (always, for elements)
+template <class TF, class BF>
+__device__ __forceinline__ void surf_refine(TF T_at, BF band, int m, double x0, double hq, bool ok, float t0, float t1,
                                          float t2, int j0, int j1, int j2, double* __restrict__ tt_out, double* __restrict__ xent_out)
 {
-    const double inv_c1 = 1.0 / c1, inv_c2 = 1.0 / c2;
     // fp32 ranking margin: the estimates carry ~1e-7 relative error (fp32 coordinates and legs); keep what might be the best
     const float margin = 4e-6f * t0;
     double best = NAN, bx = NAN;
@@ -184,23 +227,23 @@ __device__ __forceinline__ void surf_refine(const double* __restrict__ coef, int
         if (!ok || j < 0 || (k >= 2 && !(tk <= t0 + margin))) continue;
         // the fp32 scan saw T' < 0 at P_j and > 0 at P_j+1; find the fp64 bracket (P_j-1 .. P_j+2 at most)
         double lo = fma((double)j, hq, x0), hi = fma((double)(j + 1), hq, x0);
-        const double dlo = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, lo).d1;
-        const double dhi = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, hi).d1;
+        const double dlo = T_at(lo).d1;
+        const double dhi = T_at(hi).d1;
         if (!(dlo < 0.0)) {                                  // the root is left of P_j
             if (!(dhi > 0.0) || j == 0) continue;
             hi = lo;
             lo = fma((double)(j - 1), hq, x0);
-            if (!(surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, lo).d1 < 0.0)) continue;
+            if (!(T_at(lo).d1 < 0.0)) continue;
         } else if (!(dhi > 0.0)) {                           // ... or right of P_j+1
             if (j + 2 >= m) continue;
             lo = hi;
             hi = fma((double)(j + 2), hq, x0);
-            if (!(surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, hi).d1 > 0.0)) continue;
+            if (!(T_at(hi).d1 > 0.0)) continue;
         }
         // safeguarded Newton on T' = 0 inside [lo, hi], T'(lo) < 0 < T'(hi)
         double x = 0.5 * (lo + hi);
         const double tol = 1e-10 * hq;
-        Tder v = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x);
+        Tder v = T_at(x);
         for (int it = 0; it < 100; ++it) {
             if (v.d1 == 0.0) break;
             if (v.d1 < 0.0) lo = x; else hi = x;
@@ -210,9 +253,10 @@ __device__ __forceinline__ void surf_refine(const double* __restrict__ coef, int
             double xn = x + step;
             if (!(v.d2 > 0.0) || !(xn >= lo && xn <= hi)) xn = done ? x : 0.5 * (lo + hi);
             x = xn;
-            v = surf_T(coef, n_s, x0, dx, inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x);
+            v = T_at(x);
             if (done) break;
         }
+        if (!band(x)) continue;
         if (isnan(best) || v.t < best) { best = v.t; bx = x; }
     }
     *tt_out = best;
@@ -228,19 +272,36 @@ __device__ __forceinline__ void surf_refine(const double* __restrict__ coef, int
         T[0] = c0_ ? (t) : T[0];                 J[0] = c0_ ? (j) : J[0];                                   \
     } while (0)
 
+template <bool PW>
 __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
 {
     __shared__ float4 sp[SURF_TILE];                                    // the tile's scan points
-    __shared__ float4 sng[SURF_TILE][SURF_EB / 4];                      // -(c2 / c1) g1 per (point, element)
-    __shared__ float4 st1[SURF_TILE][SURF_EB / 4];                      // |P - E| / c1 per (point, element)
+    __shared__ float4 sng[SURF_TILE][SURF_EB / 4];                      // -(c2 / c1) g1 per (point, element); PW: NaN out of band
+    __shared__ float4 st1[SURF_TILE][SURF_EB / 4];                      // |P - E| / c1 per (point, element); PW: the plane wave's time
     __shared__ float sxe[SURF_EB], sze[SURF_EB];
+    // PW: per angle (fp32, scan coordinates): -(c2/c1) sin, -(c2/c1) cos, sin / c1, cos / c1, the time's offset, tan, band edges
+    __shared__ float spw[8][SURF_EB];
     const int tid = threadIdx.x;
     const int f = blockIdx.x * RTUS_BLOCK + tid;
     const int e0 = blockIdx.y * SURF_EB;
     if (tid < SURF_EB) {
         const int e = e0 + tid < a.n_e ? e0 + tid : a.n_e - 1;
-        sxe[tid] = (float)(a.xe[e] - a.xo);
-        sze[tid] = (float)(a.ze[e] - a.zo);
+        if constexpr (PW) {
+            const PwAngle w = pw_angle(a.ang[e], a.xlo, a.xhi);
+            const double k21 = a.c2 / a.c1, nan = w.ok ? 0.0 : NAN;      // (an invalid angle: no bracket anywhere)
+            spw[0][tid] = (float)(-k21 * w.sn + nan);
+            spw[1][tid] = (float)(-k21 * w.cs + nan);
+            spw[2][tid] = (float)(w.sn / a.c1);
+            spw[3][tid] = (float)(w.cs / a.c1);
+            spw[4][tid] = (float)(((a.xo - w.xref) * w.sn + (a.zo - a.za) * w.cs) / a.c1);
+            spw[5][tid] = (float)w.tn;
+            spw[6][tid] = (float)(a.xlo - a.xo);
+            spw[7][tid] = (float)(a.xhi - a.xo);
+            sze[tid] = (float)(a.za - a.zo);
+        } else {
+            sxe[tid] = (float)(a.xe[e] - a.xo);
+            sze[tid] = (float)(a.ze[e] - a.zo);
+        }
     }
     // the focal point: inside the extent and below the surface, else no path (NaN coordinates fail every test)
     double xf = 0.0, zf = 0.0;
@@ -271,11 +332,19 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
         for (int i = tid; i < SURF_TILE * SURF_EB; i += RTUS_BLOCK) {
             const int j = i / SURF_EB, e = i % SURF_EB;
             const float4 P = j < n ? a.pts[base + j] : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float ux = P.x - sxe[e], uz = P.y - sze[e];
-            const float q = fmaf(uz, uz, ux * ux);
-            const float r = __builtin_amdgcn_rsqf(q);
-            ((float*)&sng[j][0])[e] = -(fmaf(uz, P.z, ux) * r) * a.k21f;
-            ((float*)&st1[j][0])[e] = q * r * a.ic1f;
+            if constexpr (PW) {
+                // insonified: the point traced back along the incident direction lands on the aperture
+                const float xb = fmaf(-(P.y - sze[e]), spw[5][e], P.x);
+                const bool in = xb >= spw[6][e] && xb <= spw[7][e];
+                ((float*)&sng[j][0])[e] = in ? fmaf(P.z, spw[1][e], spw[0][e]) : NAN;
+                ((float*)&st1[j][0])[e] = fmaf(P.x, spw[2][e], fmaf(P.y, spw[3][e], spw[4][e]));
+            } else {
+                const float ux = P.x - sxe[e], uz = P.y - sze[e];
+                const float q = fmaf(uz, uz, ux * ux);
+                const float r = __builtin_amdgcn_rsqf(q);
+                ((float*)&sng[j][0])[e] = -(fmaf(uz, P.z, ux) * r) * a.k21f;
+                ((float*)&st1[j][0])[e] = q * r * a.ic1f;
+            }
             if (e == 0) sp[j] = P;
         }
         __syncthreads();
@@ -295,20 +364,40 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
                     const float t = fmaf(q * r, a.ic2f, ((const float*)&st1[jj][0])[e]);
                     SURF_KEEP(t, j - 1, bt[e], bj[e]);
                 }
-                neg[e] = !pos;                                          // (T' = 0 counts as -; NaN: never +)
+                if constexpr (PW) neg[e] = !pos && ng[e] == ng[e];       // out of band (NaN): neither side of a bracket
+                else neg[e] = !pos;                                     // (T' = 0 counts as -; NaN: never +)
             }
         }
     }
     if (f >= a.n_f) return;
     const double smin = *a.smin;
+    const double inv_c1 = 1.0 / a.c1, inv_c2 = 1.0 / a.c2;
 #pragma unroll
     for (int e = 0; e < SURF_EB; ++e) {
         const int row = e0 + e;
         if (row < a.n_e) {
-            const double xe = a.xe[row], ze = a.ze[row];
             const size_t o = (size_t)row * a.n_f + f;
-            surf_refine(a.coef, a.n_s, a.m, a.x0, a.dx, a.hq, a.inv_dx, a.c1, a.c2, xe, ze, xf, zf, fok && ze < smin, bt[e][0], bt[e][1],
-                        bt[e][2], bj[e][0], bj[e][1], bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
+            if constexpr (PW) {
+                const PwAngle w = pw_angle(a.ang[row], a.xlo, a.xhi);
+                const double za = a.za;
+                auto T_at = [&](double x) {
+                    return surf_T_pw(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, w.sn, w.cs, w.xref, za, xf, zf, x);
+                };
+                auto band = [&](double x) {
+                    double s, s1, s2;
+                    spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, x, s, s1, s2);
+                    const double xb = fma(-(s - za), w.tn, x);
+                    return xb >= a.xlo && xb <= a.xhi;
+                };
+                surf_refine(T_at, band, a.m, a.x0, a.hq, fok && w.ok && za < smin, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1],
+                            bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
+            } else {
+                const double xe = a.xe[row], ze = a.ze[row];
+                auto T_at = [&](double x) { return surf_T(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x); };
+                auto band = [](double) { return true; };
+                surf_refine(T_at, band, a.m, a.x0, a.hq, fok && ze < smin, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1], bj[e][2],
+                            a.tt + o, a.xent ? a.xent + o : nullptr);
+            }
         }
     }
 }
@@ -327,9 +416,33 @@ hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_
     a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_e; a.n_f = n_f;
     a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
     a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
+    a.ang = nullptr; a.xlo = a.xhi = a.za = 0.0;
     const long long gy = ((long long)n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
     if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
-    hipLaunchKernelGGL(rtus_surface_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(rtus_surface_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// plane waves: angles in the elements' place (the set-up kernel and its workspace as above)
+hipError_t rtus_launch_pw_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* ang, int n_a,
+                                  double xlo, double xhi, double za, const double* xf, const double* zf, int n_f, double* tt, double* xent,
+                                  void* ws, hipStream_t s)
+{
+    const SurfWs w = surf_ws(ws, n_s);
+    SurfArgs a;
+    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
+    a.c1 = c1; a.c2 = c2;
+    a.xo = x0 + 0.5 * (double)(n_s - 1) * dx;
+    a.zo = 0.0;
+    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1);
+    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_a; a.n_f = n_f;
+    a.xe = nullptr; a.ze = nullptr; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
+    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
+    a.ang = ang; a.xlo = xlo; a.xhi = xhi; a.za = za;
+    const long long gy = ((long long)n_a + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
+    hipLaunchKernelGGL(rtus_surface_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }

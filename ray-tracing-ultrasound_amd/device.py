@@ -447,3 +447,70 @@ class LayersPlan:
         if st:
             _lib.check(st, "rtus_tt_layers_dev")
         return self.out
+
+
+def pw_layers_dev(z_if, c, angles, x_lo, x_hi, z_a, xf, zf, out=None):
+    """Plane-wave transmit times through horizontal layers on device (rtus_pw_layers_dev; api.pw_travel_time_layers's definition):
+    z_if / c small HOST sequences, angles / xf / zf float64 CUDA tensors, the aperture [x_lo, x_hi] at depth z_a -> out [n_a, n_f].
+    Asynchronous on the current stream."""
+    import numpy as np
+    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+    if c.size != z_if.size + 1:               # the C layer reads c[0 .. n_if] from this host pointer
+        raise ValueError("need len(c) == len(z_if) + 1")
+    _chk(angles, "angles"); _chk(xf, "xf"); _chk(zf, "zf")
+    n_a, n_f = angles.numel(), xf.numel()
+    if zf.numel() != n_f:
+        raise ValueError("xf/zf must pair up")
+    if out is None:
+        out = torch.empty((n_a, n_f), dtype=torch.float64, device=xf.device)
+    _chk(out, "out")
+    if out.numel() != n_a * n_f:
+        raise ValueError("out must hold n_a * n_f values")
+    st = _lib.lib().rtus_pw_layers_dev(z_if.ctypes.data if z_if.size else None, c.ctypes.data, z_if.size, _p(angles), n_a, float(x_lo),
+                                       float(x_hi), float(z_a), _p(xf), _p(zf), n_f, _p(out), _stream(xf))
+    _lib.check(st, "rtus_pw_layers_dev")
+    return out
+
+
+def pw_surface_dev(x0, dx, zs, c1, c2, angles, x_lo, x_hi, z_a, xf, zf, out=None, x_entry=None):
+    """Plane-wave transmit times through one curved interface on device (rtus_pw_surface_dev; api.pw_travel_time_surface's
+    definition) on float64 CUDA tensors -> out [n_a, n_f] (and x_entry [n_a, n_f] when a tensor is given for it).  The spline's
+    workspace is allocated here; asynchronous on the current stream."""
+    for t, n in ((zs, "zs"), (angles, "angles"), (xf, "xf"), (zf, "zf")):
+        _chk(t, n)
+    n_a, n_f = angles.numel(), xf.numel()
+    if zf.numel() != n_f:
+        raise ValueError("xf/zf must pair up")
+    if out is None:
+        out = torch.empty((n_a, n_f), dtype=torch.float64, device=xf.device)
+    _chk(out, "out")
+    if x_entry is not None:
+        _chk(x_entry, "x_entry")
+    if out.numel() != n_a * n_f or (x_entry is not None and x_entry.numel() != n_a * n_f):
+        raise ValueError("out / x_entry must hold n_a * n_f values")
+    need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xf.device)      # (the caching allocator's blocks are 512-byte aligned)
+    st = _lib.lib().rtus_pw_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c2), _p(angles), n_a, float(x_lo),
+                                        float(x_hi), float(z_a), _p(xf), _p(zf), n_f, _p(out), _p(x_entry), _p(ws), need, _stream(xf))
+    _lib.check(st, "rtus_pw_surface_dev")
+    return out
+
+
+def fmc_synth_tx_dev(fmc, fs, delays, out=None):
+    """Synthesis of transmit delay laws on device (rtus_fmc_synth_tx_dev; api.fmc_synth_tx's definition): fmc float32
+    [n_tx, n_rx, n_t], delays float64 [n_v, n_tx] (seconds) -> out float32 [n_v, n_rx, n_t], which must not overlap fmc or delays.
+    Asynchronous on the current stream."""
+    _chk(fmc, "fmc", torch.float32); _chk(delays, "delays")
+    if fmc.dim() != 3 or delays.dim() != 2 or delays.shape[1] != fmc.shape[0]:
+        raise ValueError("need fmc [n_tx, n_rx, n_t] and delays [n_v, n_tx]")
+    n_v = delays.shape[0]
+    if out is None:
+        out = torch.empty((n_v, fmc.shape[1], fmc.shape[2]), dtype=torch.float32, device=fmc.device)
+    _chk(out, "out", torch.float32)
+    if out.numel() != n_v * fmc.shape[1] * fmc.shape[2] or not (out.device == fmc.device == delays.device):
+        raise ValueError("out must hold n_v * n_rx * n_t float32 values on the device of fmc / delays")
+    st = _lib.lib().rtus_fmc_synth_tx_dev(_p(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], float(fs), _p(delays), n_v, _p(out),
+                                          _stream(fmc))
+    _lib.check(st, "rtus_fmc_synth_tx_dev")
+    return out
