@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 107 /* 0.1.6: rtus_pw_layers*, rtus_pw_surface*, rtus_fmc_synth_tx* (plane-wave imaging) */
+#define RTUS_VERSION 108 /* 0.1.7: rtus_tt_surface_skip* (multi-view TFM: backwall skip legs) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -667,6 +667,53 @@ int rtus_fmc_synth_tx_dev(const float *d_fmc, int n_tx, int n_rx, int n_t, doubl
                           float *d_out, void *stream);
 int rtus_fmc_synth_tx(const float *fmc, int n_tx, int n_rx, int n_t, double fs, const double *delays, int n_v,
                       float *out, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Multi-view TFM: legs that reflect once off the backwall, with or without a mode conversion there.  NOT IN THE REFERENCE;
+ * checked against tests/skip_numpy.py (itself checked against mpmath at 40 digits), against rtus_tt_layers on a flat profile and
+ * against rtus_tt_surface at the mirrored depth when c_down = c_up.
+ *
+ * Conventions.  The part has a planar, horizontal backwall at depth z_back and is laterally unbounded; c_l and c_t are its
+ * longitudinal and transverse speeds.  A LEG is named by its modes, read from the element towards the point: "L" and "T" are the
+ * direct legs; "XY" (X, Y in {L, T}) is a skip leg: element -> couplant -> front surface -> down in mode X to the backwall ->
+ * reflects -> up in mode Y to the point.  Its time is the direct time to F' = (xf, 2 z_back - zf) through the stack that has one
+ * more interface at z_back (speed c_X above it, c_Y below it).  A point is valid for a skip leg only if front(xf) < zf < z_back;
+ * otherwise the entry is NaN.  A VIEW "A-B" is written in propagation order: transmit leg A from the transmitter to the point,
+ * then receive leg B from the point to the receiver; its image is TFM with tt_tx = leg[A] and tt_rx = leg[reverse(B)]
+ * (reciprocity: path B read backwards is the element-to-point leg reverse(B)).  Through planar layers a skip leg is
+ * rtus_tt_layers on the stack z_if + [z_back], c + [c_up] at the mirrored depth (composed in the Python layer).
+ *
+ * rtus_tt_surface_skip: a skip leg through a measured surface (the spline, grid, extent, element rules and workspace of
+ *   rtus_tt_surface; c1 above the surface, c_down below it down to the backwall, c_up from the backwall up to the point).
+ *   With S(x) = (x, s(x)) and B = (xb, z_back):
+ *       T(x) = |E - S(x)| / c1 + T_in(S(x)),   T_in(S) = min over xb of |S - B| / c_down + |B - F'| / c_up
+ *   The entry is the least T over the interior local minima of T.  It is NaN under rtus_tt_surface's element and focal-point
+ *   rules, when zf >= z_back, when z_back <= max s (the whole table is NaN; this is known only on the device), and when T has no
+ *   interior local minimum.
+ *   Guarantee: every interior local minimum whose basin spans at least one profile segment dx centred on it is found — the basin
+ *   running from the minimum to its neighbouring stationary points of T or to the ends of the extent; a minimum qualifies when
+ *   each neighbouring STATIONARY point is at least dx / 2 away (an end of the extent always does).  Narrower minima may be
+ *   missed; a missed minimum can only make the reported time later (or NaN), never earlier.
+ *   Determinism: an entry depends only on its element, its focal point, the profile and the speeds — not on which other elements
+ *   or focal points share the call (the bits of a row block or a focal-point subset are those of the whole table).
+ *   x_entry [n_e][n_f] (nullable): x of the winning entry point; x_back [n_e][n_f] (nullable): x of its backwall reflection
+ *   point, so that a caller can mask views whose reflection falls outside a finite part.
+ *   Method: rtus_tt_surface's scan and refine.  Below the surface, with p the horizontal slowness, q_d = sqrt(1/c_down^2 - p^2),
+ *   q_u = sqrt(1/c_up^2 - p^2), h1 = z_back - s(x), h2 = z_back - zf, X = xf - x, the ray solves
+ *       f(p) = h1 p / q_d + h2 p / q_u - X = 0   (one root with |p| < 1 / max(c_down, c_up): h1, h2 > 0),
+ *   T_in = p X + h1 q_d + h2 q_u and dT_in/dx = -(p + q_d s').  The fp32 scan takes a fixed number of safeguarded Newton steps
+ *   per scan point, warm-started from the previous one; the fp64 refine solves p to convergence.
+ *   Argument checks run before any HIP call, with rtus_tt_surface's codes: -1 also for a non-finite or non-positive speed or a
+ *   non-finite z_back.  d_workspace: rtus_tt_surface_workspace_bytes(n_s) bytes, 256-byte aligned (-4 otherwise).
+ *   Measured on MI355X: see DESIGN.md §4 (multi-view TFM).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tt_surface_skip_dev(double x0, double dx, const double *d_zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                             const double *d_xe, const double *d_ze, int n_e, const double *d_xf, const double *d_zf, int n_f,
+                             double *d_tt, double *d_x_entry, double *d_x_back, void *d_workspace, size_t workspace_bytes,
+                             void *stream);
+int rtus_tt_surface_skip(double x0, double dx, const double *zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                         const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
+                         double *tt, double *x_entry, double *x_back, int device);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,13 @@ def lib():
     except AttributeError:                # a build from before version 107, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        L.rtus_tt_surface_skip_dev.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, vp, C.c_size_t, vp]
+        L.rtus_tt_surface_skip.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, ip]
+        L.rtus_tt_surface_skip_dev.restype = L.rtus_tt_surface_skip.restype = ip
+    except AttributeError:                # a build from before version 108, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -211,4 +218,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface",
            "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find",
            "rtus_tfm_analytic_dev", "rtus_tfm_analytic",
-           "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx")
+           "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx",
+           "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip")

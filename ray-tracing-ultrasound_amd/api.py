@@ -700,3 +700,142 @@ def pwi_image(pw, fs, tt_pw, tt_rx, *, t0=0.0, envelope=False, coherence=False, 
         return tfm_image(pw, fs, tt_pw, tt_rx, t0=t0, device=device)
     r = tfm_analytic(fmc_analytic(pw, n_taps, device=device), fs, tt_pw, tt_rx, t0=t0, coherence=coherence, device=device)
     return (np.abs(r[0]), r[1]) if coherence else np.abs(r)
+
+
+# ---------------------------------------------------------------------------------------------- multi-view TFM
+MAX_LAYERS = 8              # RTUS_MAX_LAYERS (include/rtus.h)
+LEGS = ("L", "T", "LL", "LT", "TL", "TT")
+VIEWS = ("L-L", "L-T", "T-T",
+         "LL-L", "LL-T", "LT-L", "LT-T", "TL-L", "TL-T", "TT-L", "TT-T",
+         "LL-LL", "LL-LT", "LL-TL", "LL-TT", "LT-LT", "LT-TL", "LT-TT", "TL-LT", "TL-TT", "TT-TT")
+
+
+def reverse_leg(leg):
+    """the leg read the other way: the time of path ``leg`` from the point to an element is the element-to-point leg
+    ``reverse_leg(leg)`` ("LT" -> "TL"; direct legs are their own reverse)"""
+    if leg not in LEGS:
+        raise ValueError(f"unknown leg {leg!r}: legs are {LEGS}")
+    return leg[::-1]
+
+
+def view_tables(view):
+    """(transmit leg, receive leg) of a view "A-B" as tfm_image takes them: (A, reverse_leg(B))"""
+    parts = view.split("-") if isinstance(view, str) else ()
+    if len(parts) != 2 or parts[0] not in LEGS or parts[1] not in LEGS:
+        raise ValueError(f"unknown view {view!r}: a view is 'A-B' with A, B in {LEGS}")
+    return parts[0], reverse_leg(parts[1])
+
+
+def skip_travel_time_layers(z_if, c, z_back, xe, ze, xf, zf, *, c_up=None, taup=False, out=None, device=0, devices=None):
+    """Element x focal-point times of a SKIP leg through horizontal layers -> tt[n_e, n_f]: the ray goes down through the layers
+    ``z_if`` / ``c`` (``c[-1]``: the down-going speed in the part), reflects off the planar backwall at ``z_back`` and comes up to
+    the point at speed ``c_up`` (default ``c[-1]``; another speed is a mode conversion at the backwall).  The time is
+    travel_time_layers(z_if + [z_back], c + [c_up], ..., 2 z_back - zf) — the direct time to the mirrored point — and NaN outside
+    z_if[-1] < zf < z_back.  ``taup``, ``out``, ``device``, ``devices``: travel_time_layers's.  Conventions: include/rtus.h
+    (multi-view TFM)."""
+    z_if = _f64(z_if, "z_if") if np.size(z_if) else np.zeros(0)
+    c = _f64(c, "c")
+    if c.size != z_if.size + 1:
+        raise ValueError("need len(c) == len(z_if) + 1")
+    z_back = float(z_back)
+    c_up = float(c[-1]) if c_up is None else float(c_up)
+    front = float(z_if[-1]) if z_if.size else -np.inf
+    if not (z_back > front):
+        raise ValueError("the backwall must lie below the last interface (z_back > z_if[-1])")
+    if z_if.size + 1 > MAX_LAYERS:
+        raise ValueError(f"a skip leg adds an interface: at most {MAX_LAYERS - 1} interfaces above the backwall")
+    xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
+    if xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    tt = travel_time_layers(np.r_[z_if, z_back], np.r_[c, c_up], xe, ze, xf, 2.0 * z_back - zf, out=out, device=device,
+                            devices=devices, taup=taup)
+    tt[:, ~((zf > front) & (zf < z_back))] = np.nan
+    return tt
+
+
+def skip_travel_time_surface(x0, dx, zs, c1, c2, z_back, xe, ze, xf, zf, *, c_up=None, return_entry=False, out=None, device=0):
+    """Element x focal-point times of a SKIP leg through ONE curved front surface -> tt[n_e, n_f]: element -> couplant (``c1``) ->
+    the surface (travel_time_surface's spline, extent and element rules) -> down at ``c2`` to the planar backwall at ``z_back`` ->
+    up at ``c_up`` (default ``c2``; another speed is a mode conversion) to the point.  An entry is the least time over the
+    interior local minima of T(x) = |E - S(x)|/c1 + T_in(S(x)), T_in the Fermat time below the surface via the backwall; NaN
+    without one, for a point outside the extent or not strictly between the surface and the backwall, and everywhere when the
+    backwall is not strictly below the whole profile.  ``return_entry``: -> (tt, x_entry, x_back), the winning entry point and
+    backwall reflection point.  Definition and guarantee: include/rtus.h (rtus_tt_surface_skip).  Not in the reference."""
+    zs = _f64(zs, "zs")
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    c_up = float(c2) if c_up is None else float(c_up)
+    tt = _out(out, (xe.size, xf.size), np.float64)
+    xn = np.empty((xe.size, xf.size), dtype=np.float64) if return_entry else None
+    xb = np.empty((xe.size, xf.size), dtype=np.float64) if return_entry else None
+    st = _lib.lib().rtus_tt_surface_skip(float(x0), float(dx), _ptr(zs), zs.size, float(c1), float(c2), c_up, float(z_back), _ptr(xe),
+                                         _ptr(ze), xe.size, _ptr(xf), _ptr(zf), xf.size, _ptr(tt), _ptr(xn), _ptr(xb), int(device))
+    _lib.check(st, "rtus_tt_surface_skip")
+    return (tt, xn, xb) if return_entry else tt
+
+
+def _legs_wanted(legs):
+    legs = tuple(legs)
+    bad = [g for g in legs if g not in LEGS]
+    if bad:
+        raise ValueError(f"unknown legs {bad}: legs are {LEGS}")
+    return legs
+
+
+def view_legs_layers(z_if, c_above, c_l, c_t, z_back, xe, ze, xf, zf, *, legs=LEGS, device=0):
+    """The leg tables of multi-view TFM through horizontal layers -> {leg: tt [n_e, n_f]} for ``legs`` (default all six:
+    L, T, LL, LT, TL, TT).  ``z_if`` / ``c_above``: the interfaces and the speeds above the part (len(c_above) == len(z_if)); the
+    part below z_if[-1] has speeds ``c_l`` / ``c_t`` and a planar backwall at ``z_back``.  Direct legs: travel_time_layers; skip
+    legs: skip_travel_time_layers.  Conventions: include/rtus.h (multi-view TFM)."""
+    legs = _legs_wanted(legs)
+    z_if = list(np.atleast_1d(np.asarray(z_if, dtype=np.float64)))
+    c_above = list(np.atleast_1d(np.asarray(c_above, dtype=np.float64)))
+    if len(c_above) != len(z_if):
+        raise ValueError("need len(c_above) == len(z_if)")
+    sp = {"L": float(c_l), "T": float(c_t)}
+    out = {}
+    for g in legs:
+        if len(g) == 1:
+            out[g] = travel_time_layers(z_if, c_above + [sp[g]], xe, ze, xf, zf, device=device)
+        else:
+            out[g] = skip_travel_time_layers(z_if, c_above + [sp[g[0]]], z_back, xe, ze, xf, zf, c_up=sp[g[1]], device=device)
+    return out
+
+
+def view_legs_surface(x0, dx, zs, c1, c_l, c_t, z_back, xe, ze, xf, zf, *, legs=LEGS, device=0):
+    """The leg tables of multi-view TFM through ONE measured front surface (travel_time_surface's profile; couplant ``c1``) ->
+    {leg: tt [n_e, n_f]} for ``legs`` (default all six).  The part has speeds ``c_l`` / ``c_t`` and a planar backwall at
+    ``z_back``.  Direct legs: travel_time_surface; skip legs: skip_travel_time_surface.  Conventions: include/rtus.h."""
+    legs = _legs_wanted(legs)
+    sp = {"L": float(c_l), "T": float(c_t)}
+    out = {}
+    for g in legs:
+        if len(g) == 1:
+            out[g] = travel_time_surface(x0, dx, zs, c1, sp[g], xe, ze, xf, zf, device=device)
+        else:
+            out[g] = skip_travel_time_surface(x0, dx, zs, c1, sp[g[0]], z_back, xe, ze, xf, zf, c_up=sp[g[1]], device=device)
+    return out
+
+
+def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=False, n_taps=63, device=0):
+    """Multi-view TFM: one image per view -> {view: image float32 [n_f]}.  ``legs``: {leg: tt [n_e, n_f]} (view_legs_layers /
+    view_legs_surface); a view "A-B" (transmit leg A, then receive leg B from the point to the receiver) is imaged with
+    tt_tx = legs[A] and tt_rx = legs[reverse_leg(B)].  RF: tfm_image.  With ``envelope=True``: |tfm_analytic| over the analytic FMC,
+    formed once for all views (``n_taps`` Hilbert taps); with ``coherence=True`` too, each value is (envelope, cf).  An unknown view
+    or a leg missing from ``legs`` raises ValueError before any GPU call."""
+    if coherence and not envelope:
+        raise ValueError("the coherence factor needs envelope=True")
+    views = (views,) if isinstance(views, str) else tuple(views)
+    pairs = {v: view_tables(v) for v in views}
+    missing = sorted({g for p in pairs.values() for g in p if g not in legs})
+    if missing:
+        raise ValueError(f"legs {missing} are needed by the views and missing from ``legs``")
+    if not envelope:
+        return {v: tfm_image(fmc, fs, legs[a], legs[b], t0=t0, device=device) for v, (a, b) in pairs.items()}
+    analytic = fmc_analytic(fmc, n_taps, device=device)
+    out = {}
+    for v, (a, b) in pairs.items():
+        r = tfm_analytic(analytic, fs, legs[a], legs[b], t0=t0, coherence=coherence, device=device)
+        out[v] = (np.abs(r[0]), r[1]) if coherence else np.abs(r)
+    return out

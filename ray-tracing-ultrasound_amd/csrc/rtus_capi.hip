@@ -58,6 +58,9 @@ hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_
                                   const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt, double* xent,
                                   void* ws, hipStream_t s);
 size_t rtus_surface_ws_bytes(int n_s);
+hipError_t rtus_launch_tt_surface_skip(double x0, double dx, const double* zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                                       const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                                       double* xent, double* xback, void* ws, hipStream_t s);
 hipError_t rtus_launch_focal_delays(const double* tt, int n_e, int n_f, double* delays, hipStream_t s);
 hipError_t rtus_launch_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                            const double* tt_rx, int n_f, float* image, hipStream_t s);
@@ -838,6 +841,57 @@ int rtus_tt_surface(double x0, double dx, const double* zs, int n_s, double c1, 
     LAUNCH_TRY(rtus_launch_tt_surface(x0, dx, dzs, n_s, c1, c2, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, ws, S.a->stream));
     S.download(tt, dtt, tot);
     S.download(x_entry, dxn, tot);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+// skip legs through the surface: rtus_tt_surface's checks, c_down in c2's place, and the leg's own speed and backwall
+static int check_surface_skip(double x0, double dx, const void* zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                              const void* xe, const void* ze, int n_e, const void* xf, const void* zf, int n_f, const void* tt)
+{
+    if (!isfinite(c_up) || !(c_up > 0) || !isfinite(z_back)) return RTUS_ERR_INVALID_ARG;
+    return check_surface(x0, dx, zs, n_s, c1, c_down, xe, ze, n_e, xf, zf, n_f, tt);
+}
+
+int rtus_tt_surface_skip_dev(double x0, double dx, const double* d_zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                             const double* d_xe, const double* d_ze, int n_e, const double* d_xf, const double* d_zf, int n_f, double* d_tt,
+                             double* d_x_entry, double* d_x_back, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int st = check_surface_skip(x0, dx, d_zs, n_s, c1, c_down, c_up, z_back, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    LAUNCH_TRY(rtus_launch_tt_surface_skip(x0, dx, d_zs, n_s, c1, c_down, c_up, z_back, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, d_x_entry,
+                                           d_x_back, d_workspace, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tt_surface_skip(double x0, double dx, const double* zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                         const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                         double* x_entry, double* x_back, int device)
+{
+    int st = check_surface_skip(x0, dx, zs, n_s, c1, c_down, c_up, z_back, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_e * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    Session S;
+    if ((st = S.open(device, al256(8 * (size_t)n_s) + 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) +
+                                 (1 + (x_entry ? 1 : 0) + (x_back ? 1 : 0)) * al256(8 * tot) + al256(wsb))))
+        return st;
+    double *dzs, *dxe, *dze, *dxf, *dzf;
+    S.upload(dzs, zs, n_s);
+    S.upload(dxe, xe, n_e);
+    S.upload(dze, ze, n_e);
+    S.upload(dxf, xf, n_f);
+    S.upload(dzf, zf, n_f);
+    double* dtt = S.take<double>(tot);
+    double* dxn = x_entry ? S.take<double>(tot) : nullptr;
+    double* dxb = x_back ? S.take<double>(tot) : nullptr;
+    void* ws = S.take<char>(wsb);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_tt_surface_skip(x0, dx, dzs, n_s, c1, c_down, c_up, z_back, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, dxb, ws,
+                                           S.a->stream));
+    S.download(tt, dtt, tot);
+    S.download(x_entry, dxn, tot);
+    S.download(x_back, dxb, tot);
     HIP_TRY(S.finish());
     return RTUS_OK;
 }

@@ -27,12 +27,19 @@
 // by code that does not depend on the element's slot in the workgroup or on the lane: the entry has the same bits whatever
 // else shares the call.
 //
-// Plane waves (rtus_pw_surface): the same kernel with ANGLES in the elements' place (template argument PW).  The first leg is
+// Plane waves (rtus_pw_surface): the same kernel with ANGLES in the elements' place (template argument SURF_PW).  The first leg is
 // the plane wave's time to S(x), ((x - x_ref) sin t + (s(x) - z_a) cos t) / c1, so -(c2 / c1) g1 becomes -(c2 / c1)(sin t +
 // s' cos t) and T'' loses the first leg's curvature term (s'' cos t / c1 remains).  Only entry points whose ray traced back
 // along the incident direction meets the aperture count (insonified): an out-of-band scan point carries NaN in LDS and never
 // becomes the "-" side of a bracket (a NaN term would otherwise read as - and fake a - -> + change at every band edge), and the
 // refined root is tested against the band in fp64.
+//
+// Skip legs (rtus_tt_surface_skip, SURF_SKIP): elements as in SURF_ELEM, the leg below the surface reflected once off a planar
+// backwall at zb (down at c_down = c2, up at c_up).  Only the lane term changes: per scan point the lane solves the leg below the
+// surface for its horizontal slowness (u = c_down p, SKIP_NEWTON safeguarded fp32 Newton steps warm-started from the previous
+// scan point) and tests -(u + a_d s') > ng (T_in' = -(p + q_d s'), envelope theorem); the bracket estimate is T_in + st1.  The
+// refine solves u to convergence in fp64 (skip_inner) inside surf_T_skip.  The set-up kernel also reduces max s (smin[1]) for
+// the rule zb > max s.
 #include "rtus_device.h"
 
 // no implicit contraction: the fma()s are written out, so every element slot's inlined copy of the arithmetic rounds alike
@@ -56,13 +63,17 @@ struct SurfArgs {
     double* __restrict__ xent;         // nullable
     const double* __restrict__ coef;   // [n_s - 1][4]: a, b, c, d of s(x0 + k dx + t) = a + b t + c t^2 + d t^3
     const float4* __restrict__ pts;    // [m]: (x - xo, s - zo, s', 0)
-    const double* __restrict__ smin;   // the profile's least depth
+    const double* __restrict__ smin;   // the profile's least depth (smin[1]: its greatest)
     // plane waves (PW instantiation): n_e counts angles; the aperture [x_lo, x_hi] at depth z_a
     const double* __restrict__ ang;
     double xlo, xhi, za;
+    // skip legs (SKIP instantiation): c2 is c_down; the backwall at zb, kap = c_down / c_up, umax = min(1, kap)
+    double zb, kap, umax;
+    float zbr, kap2f, umaxf;           // zb - zo, kap^2, umax less a margin (fp32 scan)
+    double* __restrict__ xback;        // nullable
 };
 
-// workspace layout (256-byte aligned pieces): M [n_s] | Thomas scratch [n_s] | coef [4 (n_s - 1)] | pts [m] | smin
+// workspace layout (256-byte aligned pieces): M [n_s] | Thomas scratch [n_s] | coef [4 (n_s - 1)] | pts [m] | smin, smax
 static inline size_t al256s(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline __host__ __device__ int surf_points(int n_s) { return SURF_SUB * (n_s - 1) + 1; }
 size_t rtus_surface_ws_bytes(int n_s)
@@ -121,14 +132,15 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_setup_kernel(const do
         for (int i = n_s - 3; i >= 1; --i) w.M[i] = fma(-w.cp[i], w.M[i + 1], w.M[i]);
     }
     __syncthreads();
-    __shared__ double red[RTUS_BLOCK];
-    double lo = INFINITY;
+    __shared__ double red[RTUS_BLOCK], red_hi[RTUS_BLOCK];
+    double lo = INFINITY, up = -INFINITY;
     for (int k = tid; k < n_s - 1; k += RTUS_BLOCK) {
         const double Mk = w.M[k], Mk1 = w.M[k + 1], z0 = zs[k], z1 = zs[k + 1];
         const double a = z0, b = (z1 - z0) / dx - dx * (2.0 * Mk + Mk1) / 6.0, c = 0.5 * Mk, d = (Mk1 - Mk) / (6.0 * dx);
         w.coef[4 * k] = a; w.coef[4 * k + 1] = b; w.coef[4 * k + 2] = c; w.coef[4 * k + 3] = d;
         // least depth on the segment: its ends and the roots of s' = b + 2 c t + 3 d t^2 inside it
-        double m = fmin(a, fma(fma(fma(d, dx, c), dx, b), dx, a));
+        const double zend = fma(fma(fma(d, dx, c), dx, b), dx, a);
+        double m = fmin(a, zend), mx = fmax(a, zend);
         const double A = 3.0 * d, B = 2.0 * c, disc = B * B - 4.0 * A * b;
         double r[2] = {NAN, NAN};
         if (A != 0.0) {
@@ -137,16 +149,22 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_setup_kernel(const do
             r[0] = -b / B;
         }
         for (int i = 0; i < 2; ++i)
-            if (r[i] > 0.0 && r[i] < dx) m = fmin(m, fma(fma(fma(d, r[i], c), r[i], b), r[i], a));
+            if (r[i] > 0.0 && r[i] < dx) {
+                const double zr = fma(fma(fma(d, r[i], c), r[i], b), r[i], a);
+                m = fmin(m, zr);
+                mx = fmax(mx, zr);
+            }
         lo = fmin(lo, m);
+        up = fmax(up, mx);
     }
     red[tid] = lo;
+    red_hi[tid] = up;
     __syncthreads();
     for (int h = RTUS_BLOCK / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] = fmin(red[tid], red[tid + h]);
+        if (tid < h) { red[tid] = fmin(red[tid], red[tid + h]); red_hi[tid] = fmax(red_hi[tid], red_hi[tid + h]); }
         __syncthreads();
     }
-    if (tid == 0) *w.smin = red[0];
+    if (tid == 0) { w.smin[0] = red[0]; w.smin[1] = red_hi[0]; }     // least and greatest depth (the slot holds 256 bytes)
     const int m = surf_points(n_s);
     const double hq = dx / SURF_SUB;
     for (int j = tid; j < m; j += RTUS_BLOCK) {
@@ -198,6 +216,66 @@ __device__ __forceinline__ Tder surf_T_pw(const double* __restrict__ coef, int n
     return o;
 }
 
+// skip leg below the surface, in the down-going slowness scaled by c_down: u = c_down p, a_d = sqrt(1 - u^2), a_u = sqrt(kap^2 - u^2)
+// (kap = c_down / c_up).  The ray from S down to the backwall and up to F has f(u) = h1 u / a_d + h2 u / a_u - X = 0 (h1 = zb - s,
+// h2 = zb - zf, X = xf - x): f is odd, increasing and infinite at +-umax = +-min(1, kap), so the root is unique for h1, h2 > 0.
+// Safeguarded Newton from u0 (bisection of the bracket when a step leaves it) until the step is below 1e-15; the last step is taken.
+__host__ __device__ __forceinline__ double skip_inner(double h1, double h2, double X, double kap2, double umax, double u0, double& fu_out)
+{
+    double lo = -umax, hi = umax, u = u0, fu = NAN;
+    for (int it = 0; it < 80; ++it) {
+        const double ad2 = fma(-u, u, 1.0), au2 = fma(-u, u, kap2);
+        const double rd = 1.0 / sqrt(ad2), ru = 1.0 / sqrt(au2);
+        const double f = fma(u, fma(h1, rd, h2 * ru), -X);
+        fu = fma(h1, rd * rd * rd, h2 * kap2 * (ru * ru * ru));
+        if (f < 0.0) lo = u; else if (f > 0.0) hi = u; else break;
+        const double step = -f / fu;
+        const bool done = fabs(step) <= 1e-15 || !(hi - lo > 1e-15);
+        // (a converged step that rounds onto u — now a bracket end — is kept: a bisection there would jump away from the root)
+        double un = u + step;
+        if (!(un >= lo && un <= hi)) un = done ? u : 0.5 * (lo + hi);
+        u = un;
+        if (done) break;
+    }
+    fu_out = fu;
+    return u;
+}
+
+// the straight line from S to the mirrored point F' = (xf, 2 zb - zf), as a start for skip_inner
+__host__ __device__ __forceinline__ double skip_u0(double h1, double h2, double X, double umax)
+{
+    const double h = h1 + h2;
+    return umax * X / sqrt(fma(X, X, h * h));
+}
+
+// T, T', T'' of a skip leg: the element's leg as in surf_T, then T_in = (u X + h1 a_d + h2 a_u) / c_down with u solved in fp64;
+// T_in' = -(u + a_d s') / c_down (envelope theorem), T_in'' = (1 - s' u / a_d)^2 / (c_down f_u) - a_d s'' / c_down (implicit
+// differentiation of f = 0).  uw: the previous call's root (warm start), NaN for none; it is updated.
+__device__ __forceinline__ Tder surf_T_skip(const double* __restrict__ coef, int n_s, double x0, double dx, double inv_dx, double inv_c1,
+                                            double inv_cd, double kap2, double umax, double zb, double xe, double ze, double xf, double zf,
+                                            double x, double& uw)
+{
+    double s, s1, s2;
+    spline_eval(coef, n_s, x0, dx, inv_dx, x, s, s1, s2);
+    const double ux = x - xe, uz = s - ze;
+    const double q1 = fma(ux, ux, uz * uz);
+    const double r1 = 1.0 / sqrt(q1);
+    const double l1 = q1 * r1;
+    const double A1 = fma(uz, s1, ux);
+    const double B = fma(s1, s1, 1.0);
+    const double h1 = zb - s, h2 = zb - zf, X = xf - x;
+    double fu;
+    const double u = skip_inner(h1, h2, X, kap2, umax, isnan(uw) ? skip_u0(h1, h2, X, umax) : uw, fu);
+    uw = u;
+    const double ad = sqrt(fma(-u, u, 1.0)), au = sqrt(fma(-u, u, kap2));
+    const double w = fma(-s1 * u, 1.0 / ad, 1.0);
+    Tder o;
+    o.t = fma(l1, inv_c1, fma(u, X, fma(h1, ad, h2 * au)) * inv_cd);
+    o.d1 = fma(A1 * r1, inv_c1, -fma(ad, s1, u) * inv_cd);
+    o.d2 = fma((fma(uz, s2, B) - A1 * A1 * r1 * r1) * r1, inv_c1, (w * w / fu - ad * s2) * inv_cd);
+    return o;
+}
+
 // per-angle constants of a plane wave (fp64, from the angle alone: the same bits in every slot and call); false when the angle is
 // not finite or |angle| >= pi / 2
 struct PwAngle { double sn, cs, tn, xref; bool ok; };
@@ -215,7 +293,7 @@ __device__ __forceinline__ PwAngle pw_angle(double th, double xlo, double xhi)
 // the least refined time over the kept brackets of one (element, focal point); written to tt (and xent).  T(x): the travel time
 // and its derivatives at x; band(x): whether a root at x counts (always, for elements)
 template <class TF, class BF>
-__device__ __forceinline__ void surf_refine(TF T_at, BF band, int m, double x0, double hq, bool ok, float t0, float t1,
+__device__ __forceinline__ double surf_refine(TF T_at, BF band, int m, double x0, double hq, bool ok, float t0, float t1,
                                          float t2, int j0, int j1, int j2, double* __restrict__ tt_out, double* __restrict__ xent_out)
 {
     // fp32 ranking margin: the estimates carry ~1e-7 relative error (fp32 coordinates and legs); keep what might be the best
@@ -261,6 +339,7 @@ __device__ __forceinline__ void surf_refine(TF T_at, BF band, int m, double x0, 
     }
     *tt_out = best;
     if (xent_out) *xent_out = bx;
+    return bx;
 }
 
 // insert (t, j) into the sorted triple (t0 <= t1 <= t2): selects on values (references invite a phi of pointers -> scratch)
@@ -272,11 +351,16 @@ __device__ __forceinline__ void surf_refine(TF T_at, BF band, int m, double x0, 
         T[0] = c0_ ? (t) : T[0];                 J[0] = c0_ ? (j) : J[0];                                   \
     } while (0)
 
-template <bool PW>
+// the kernel's instantiations: element rows, plane-wave rows, element rows of a skip leg
+enum SurfMode { SURF_ELEM = 0, SURF_PW = 1, SURF_SKIP = 2 };
+#define SKIP_NEWTON 2       // fp32 Newton steps of the skip leg's inner slowness per (lane, scan point): scripts/skip_newton_study.py
+
+template <int MODE>
 __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
 {
     __shared__ float4 sp[SURF_TILE];                                    // the tile's scan points
     __shared__ float4 sng[SURF_TILE][SURF_EB / 4];                      // -(c2 / c1) g1 per (point, element); PW: NaN out of band
+                                                                        // (SKIP: c2 is c_down)
     __shared__ float4 st1[SURF_TILE][SURF_EB / 4];                      // |P - E| / c1 per (point, element); PW: the plane wave's time
     __shared__ float sxe[SURF_EB], sze[SURF_EB];
     // PW: per angle (fp32, scan coordinates): -(c2/c1) sin, -(c2/c1) cos, sin / c1, cos / c1, the time's offset, tan, band edges
@@ -286,7 +370,7 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
     const int e0 = blockIdx.y * SURF_EB;
     if (tid < SURF_EB) {
         const int e = e0 + tid < a.n_e ? e0 + tid : a.n_e - 1;
-        if constexpr (PW) {
+        if constexpr (MODE == SURF_PW) {
             const PwAngle w = pw_angle(a.ang[e], a.xlo, a.xhi);
             const double k21 = a.c2 / a.c1, nan = w.ok ? 0.0 : NAN;      // (an invalid angle: no bracket anywhere)
             spw[0][tid] = (float)(-k21 * w.sn + nan);
@@ -313,9 +397,19 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
             double s, s1, s2;
             spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, xf, s, s1, s2);
             fok = zf > s;
+            if constexpr (MODE == SURF_SKIP) fok = fok && zf < a.zb;
         }
     }
     const float xfr = fok ? (float)(xf - a.xo) : NAN, zfr = fok ? (float)(zf - a.zo) : NAN;
+    // SKIP: the lane's leg below the surface; u (= c_down p) is carried from scan point to scan point (fixed order: its bits depend
+    // on the focal point and the profile alone), starting from the straight line to the mirrored point at the first one
+    float h2f = 0.0f, uf = 0.0f;
+    if constexpr (MODE == SURF_SKIP) {
+        h2f = a.zbr - zfr;
+        const float4 P = a.pts[0];
+        const float X = xfr - P.x, h = (a.zbr - P.y) + h2f;
+        uf = a.umaxf * X * __builtin_amdgcn_rsqf(fmaf(X, X, h * h));
+    }
 
     float bt[SURF_EB][SURF_K];
     int bj[SURF_EB][SURF_K];
@@ -332,7 +426,7 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
         for (int i = tid; i < SURF_TILE * SURF_EB; i += RTUS_BLOCK) {
             const int j = i / SURF_EB, e = i % SURF_EB;
             const float4 P = j < n ? a.pts[base + j] : make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (PW) {
+            if constexpr (MODE == SURF_PW) {
                 // insonified: the point traced back along the incident direction lands on the aperture
                 const float xb = fmaf(-(P.y - sze[e]), spw[5][e], P.x);
                 const bool in = xb >= spw[6][e] && xb <= spw[7][e];
@@ -350,10 +444,29 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
         __syncthreads();
         for (int jj = 0; jj < n; ++jj) {
             const float4 P = sp[jj];
-            const float vx = P.x - xfr, vz = P.y - zfr;
-            const float q = fmaf(vz, vz, vx * vx);
-            const float r = __builtin_amdgcn_rsqf(q);
-            const float g2 = fmaf(vz, P.z, vx) * r;                     // T' c2 = g2 - ng: T' > 0 <=> g2 > ng
+            float g2, tin;                                              // T' c2 = g2 - ng: T' > 0 <=> g2 > ng; the leg's time
+            if constexpr (MODE == SURF_SKIP) {
+                // f(u) = h1 u / a_d + h2 u / a_u - X = 0; T_in c_down = u X + h1 a_d + h2 a_u, T_in' c_down = -(u + a_d s')
+                const float h1 = a.zbr - P.y, X = xfr - P.x;
+#pragma unroll
+                for (int it = 0; it < SKIP_NEWTON; ++it) {
+                    const float rd = __builtin_amdgcn_rsqf(fmaf(-uf, uf, 1.0f)), ru = __builtin_amdgcn_rsqf(fmaf(-uf, uf, a.kap2f));
+                    const float fv = fmaf(uf, fmaf(h1, rd, h2f * ru), -X);
+                    const float fu = fmaf(h1 * rd, rd * rd, h2f * a.kap2f * (ru * ru * ru));
+                    const float un = fmaf(-fv, __builtin_amdgcn_rcpf(fu), uf);
+                    uf = fabsf(un) < a.umaxf ? un : 0.5f * (uf + (fv < 0.0f ? a.umaxf : -a.umaxf));   // (NaN: toward an end)
+                }
+                const float ad2 = fmaf(-uf, uf, 1.0f), au2 = fmaf(-uf, uf, a.kap2f);
+                const float ad = ad2 * __builtin_amdgcn_rsqf(ad2), au = au2 * __builtin_amdgcn_rsqf(au2);
+                g2 = -fmaf(ad, P.z, uf);
+                tin = fmaf(uf, X, fmaf(h1, ad, h2f * au));
+            } else {
+                const float vx = P.x - xfr, vz = P.y - zfr;
+                const float q = fmaf(vz, vz, vx * vx);
+                const float r = __builtin_amdgcn_rsqf(q);
+                g2 = fmaf(vz, P.z, vx) * r;
+                tin = q * r;
+            }
             const float4 ng0 = sng[jj][0], ng1 = sng[jj][1];
             const float ng[SURF_EB] = {ng0.x, ng0.y, ng0.z, ng0.w, ng1.x, ng1.y, ng1.z, ng1.w};
             const int j = base + jj;
@@ -361,23 +474,23 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
             for (int e = 0; e < SURF_EB; ++e) {
                 const bool pos = g2 > ng[e];
                 if (pos && neg[e]) {                                    // - -> + between P_j-1 and P_j: a minimum
-                    const float t = fmaf(q * r, a.ic2f, ((const float*)&st1[jj][0])[e]);
+                    const float t = fmaf(tin, a.ic2f, ((const float*)&st1[jj][0])[e]);
                     SURF_KEEP(t, j - 1, bt[e], bj[e]);
                 }
-                if constexpr (PW) neg[e] = !pos && ng[e] == ng[e];       // out of band (NaN): neither side of a bracket
+                if constexpr (MODE == SURF_PW) neg[e] = !pos && ng[e] == ng[e];       // out of band (NaN): neither side of a bracket
                 else neg[e] = !pos;                                     // (T' = 0 counts as -; NaN: never +)
             }
         }
     }
     if (f >= a.n_f) return;
-    const double smin = *a.smin;
+    const double smin = a.smin[0], smax = MODE == SURF_SKIP ? a.smin[1] : 0.0;
     const double inv_c1 = 1.0 / a.c1, inv_c2 = 1.0 / a.c2;
 #pragma unroll
     for (int e = 0; e < SURF_EB; ++e) {
         const int row = e0 + e;
         if (row < a.n_e) {
             const size_t o = (size_t)row * a.n_f + f;
-            if constexpr (PW) {
+            if constexpr (MODE == SURF_PW) {
                 const PwAngle w = pw_angle(a.ang[row], a.xlo, a.xhi);
                 const double za = a.za;
                 auto T_at = [&](double x) {
@@ -391,12 +504,32 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
                 };
                 surf_refine(T_at, band, a.m, a.x0, a.hq, fok && w.ok && za < smin, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1],
                             bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
-            } else {
+            } else if constexpr (MODE == SURF_ELEM) {
                 const double xe = a.xe[row], ze = a.ze[row];
                 auto T_at = [&](double x) { return surf_T(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x); };
                 auto band = [](double) { return true; };
                 surf_refine(T_at, band, a.m, a.x0, a.hq, fok && ze < smin, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1], bj[e][2],
                             a.tt + o, a.xent ? a.xent + o : nullptr);
+            } else {                                                    // SURF_SKIP
+                const double xe = a.xe[row], ze = a.ze[row], inv_cd = inv_c2, kap2 = a.kap * a.kap;
+                double uw = NAN;
+                auto T_at = [&](double x) {
+                    return surf_T_skip(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_cd, kap2, a.umax, a.zb, xe, ze, xf, zf, x, uw);
+                };
+                auto band = [](double) { return true; };
+                const double bx = surf_refine(T_at, band, a.m, a.x0, a.hq, fok && ze < smin && a.zb > smax, bt[e][0], bt[e][1], bt[e][2],
+                                              bj[e][0], bj[e][1], bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
+                if (a.xback) {                                          // the reflection point of the winning root
+                    double xb = NAN;
+                    if (!isnan(bx)) {
+                        double s, s1, s2, fu;
+                        spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, bx, s, s1, s2);
+                        const double h1 = a.zb - s, h2 = a.zb - zf, X = xf - bx;
+                        const double u = skip_inner(h1, h2, X, kap2, a.umax, skip_u0(h1, h2, X, a.umax), fu);
+                        xb = fma(h1, u / sqrt(fma(-u, u, 1.0)), bx);
+                    }
+                    a.xback[o] = xb;
+                }
             }
         }
     }
@@ -417,10 +550,11 @@ hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_
     a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
     a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
     a.ang = nullptr; a.xlo = a.xhi = a.za = 0.0;
+    a.zb = a.kap = a.umax = 0.0; a.zbr = a.kap2f = a.umaxf = 0.0f; a.xback = nullptr;
     const long long gy = ((long long)n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
     if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
-    hipLaunchKernelGGL(rtus_surface_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(rtus_surface_kernel<SURF_ELEM>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -440,9 +574,37 @@ hipError_t rtus_launch_pw_surface(double x0, double dx, const double* zs, int n_
     a.xe = nullptr; a.ze = nullptr; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
     a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
     a.ang = ang; a.xlo = xlo; a.xhi = xhi; a.za = za;
+    a.zb = a.kap = a.umax = 0.0; a.zbr = a.kap2f = a.umaxf = 0.0f; a.xback = nullptr;
     const long long gy = ((long long)n_a + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
     if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
-    hipLaunchKernelGGL(rtus_surface_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(rtus_surface_kernel<SURF_PW>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// skip legs: elements, the leg below the surface down in c_down to the backwall at z_back and up in c_up to the point
+hipError_t rtus_launch_tt_surface_skip(double x0, double dx, const double* zs, int n_s, double c1, double c_down, double c_up, double z_back,
+                                       const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                                       double* xent, double* xback, void* ws, hipStream_t s)
+{
+    const SurfWs w = surf_ws(ws, n_s);
+    SurfArgs a;
+    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
+    a.c1 = c1; a.c2 = c_down;
+    a.xo = x0 + 0.5 * (double)(n_s - 1) * dx;
+    a.zo = 0.0;
+    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c_down); a.k21f = (float)(c_down / c1);
+    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_e; a.n_f = n_f;
+    a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
+    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
+    a.ang = nullptr; a.xlo = a.xhi = a.za = 0.0;
+    a.zb = z_back; a.kap = c_down / c_up; a.umax = a.kap < 1.0 ? a.kap : 1.0;
+    a.zbr = (float)(z_back - a.zo); a.kap2f = (float)(a.kap * a.kap);
+    a.umaxf = (float)a.umax * (1.0f - 1e-6f);                 // (the fp32 scan stays off the ends, where a_d or a_u is 0)
+    a.xback = xback;
+    const long long gy = ((long long)n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
+    hipLaunchKernelGGL(rtus_surface_kernel<SURF_SKIP>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }

@@ -8,6 +8,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from . import api as _api
 from .api import Params, _resolve
 
 
@@ -494,6 +495,58 @@ def pw_surface_dev(x0, dx, zs, c1, c2, angles, x_lo, x_hi, z_a, xf, zf, out=None
     st = _lib.lib().rtus_pw_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c2), _p(angles), n_a, float(x_lo),
                                         float(x_hi), float(z_a), _p(xf), _p(zf), n_f, _p(out), _p(x_entry), _p(ws), need, _stream(xf))
     _lib.check(st, "rtus_pw_surface_dev")
+    return out
+
+
+def skip_layers_dev(z_if, c, z_back, xe, ze, xf, zf, c_up=None, out=None, taup=False):
+    """Skip-leg times through horizontal layers on device (api.skip_travel_time_layers's definition): tt_layers_dev on the stack
+    z_if + [z_back], c + [c_up] at the mirrored depth 2 z_back - zf, then NaN outside z_if[-1] < zf < z_back.  z_if / c are small
+    HOST sequences; asynchronous on the current stream (no host synchronisation)."""
+    import numpy as np
+    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+    if c.size != z_if.size + 1:
+        raise ValueError("need len(c) == len(z_if) + 1")
+    z_back = float(z_back)
+    front = float(z_if[-1]) if z_if.size else -float("inf")
+    if not (z_back > front):
+        raise ValueError("the backwall must lie below the last interface (z_back > z_if[-1])")
+    if z_if.size + 1 > _api.MAX_LAYERS:
+        raise ValueError(f"a skip leg adds an interface: at most {_api.MAX_LAYERS - 1} interfaces above the backwall")
+    _chk(zf, "zf")
+    c_up = float(c[-1]) if c_up is None else float(c_up)
+    zm = (2.0 * z_back) - zf
+    out = tt_layers_dev(np.r_[z_if, z_back], np.r_[c, c_up], xe, ze, xf, zm, out=out, taup=taup)
+    ok = (zf > front) & (zf < z_back)
+    out.view(-1, zf.numel()).masked_fill_(~ok.view(1, -1), float("nan"))
+    return out
+
+
+def tt_surface_skip_dev(x0, dx, zs, c1, c_down, c_up, z_back, xe, ze, xf, zf, out=None, x_entry=None, x_back=None):
+    """Skip-leg times through one curved interface on device (rtus_tt_surface_skip_dev; api.skip_travel_time_surface's definition)
+    on float64 CUDA tensors -> out [n_e, n_f] (and x_entry / x_back [n_e, n_f] when tensors are given for them).  The spline's
+    workspace is allocated here; asynchronous on the current stream."""
+    for t, n in ((zs, "zs"), (xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
+        _chk(t, n)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    if out is None:
+        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
+    _chk(out, "out")
+    for t, n in ((x_entry, "x_entry"), (x_back, "x_back")):
+        if t is not None:
+            _chk(t, n)
+            if t.numel() != n_e * n_f:
+                raise ValueError(f"{n} must hold n_e * n_f values")
+    if out.numel() != n_e * n_f:
+        raise ValueError("out must hold n_e * n_f values")
+    need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)      # (the caching allocator's blocks are 512-byte aligned)
+    st = _lib.lib().rtus_tt_surface_skip_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c_down), float(c_up),
+                                             float(z_back), _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(out), _p(x_entry), _p(x_back),
+                                             _p(ws), need, _stream(xe))
+    _lib.check(st, "rtus_tt_surface_skip_dev")
     return out
 
 
