@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 108 /* 0.1.7: rtus_tt_surface_skip* (multi-view TFM: backwall skip legs) */
+#define RTUS_VERSION 109 /* 0.1.8: rtus_leg_amp_surface*, rtus_tfm_weighted* (ray amplitudes, sensitivity-normalised views) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -714,6 +714,86 @@ int rtus_tt_surface_skip_dev(double x0, double dx, const double *d_zs, int n_s, 
 int rtus_tt_surface_skip(double x0, double dx, const double *zs, int n_s, double c1, double c_down, double c_up, double z_back,
                          const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
                          double *tt, double *x_entry, double *x_back, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Ray amplitudes and sensitivity-normalised multi-view TFM (the ray model of Budyn, Bevan, Zhang, Croxford and Wilcox, IEEE UFFC
+ * 2019).  NOT IN THE REFERENCE; checked against tests/amplitude_numpy.py, itself checked against a 40-digit mpmath solve of the
+ * boundary conditions, energy balance, reciprocity and a finite-difference ray tube (tests/test_amplitude_cpu.py).
+ *
+ * Media.  Couplant: a fluid, density rho1, speed c1.  Part: an isotropic elastic solid, density rho2, speeds c_l > c_t, with a planar
+ * traction-free backwall at z_back.  Front surface: rtus_tt_surface's natural cubic spline s(x), local normal n = (-s', 1) / sqrt(1 +
+ * s'^2) (z points down).  Elements are horizontal and face +z.
+ * Legs (the multi-view conventions above): E = (xe, ze) the element, S = (x_entry, s(x_entry)) the entry point, B = (x_back, z_back)
+ * the backwall point (skip legs), F = (xf, zf) the point; x_entry / x_back are what rtus_tt_surface[_skip] return, no solve is made.
+ * Direction: DOWN — the wave travels E -> S -> (B) -> F; UP — F -> (B) -> S -> E along the same path (for "XY": down in Y to the
+ * backwall, up in X to the surface).  View "A-B": transmit weight from DOWN of leg A, receive weight from UP of leg reverse(B) (the
+ * table the view already uses for tt_rx).
+ *
+ * Amplitude A = D C_S [C_B] G, formed in fp64, stored as complex64:
+ *   D    directivity sinc(w sin(theta_E) / lambda1), sinc(u) = sin(pi u) / (pi u), lambda1 = c1 / f_c, theta_E the angle of E - S to
+ *        +z, w the element width (w = 0: D = 1).
+ *   C_S  the plane-wave DISPLACEMENT-amplitude coefficient at the surface at the local incidence angle on n: DOWN fluid -> solid into
+ *        the leg's first mode; UP solid -> fluid from the mode that arrives at the surface.
+ *   C_B  (skip legs) the free-surface displacement reflection coefficient, incoming mode -> outgoing mode in propagation order (DOWN
+ *        X -> Y, UP Y -> X).
+ *        Boundary conditions: fluid-solid — continuity of the normal displacement and of the normal traction (sigma_nn = -p), zero
+ *        shear traction; backwall — zero normal and shear traction.  Polarisation: L along the propagation direction d, T along
+ *        (-d_z, d_x).  The other modes may be evanescent (past a critical angle): the coefficients are complex.  Each coefficient is
+ *        the horizontal slowness p of the segment that arrives at the interface.
+ *   G    2-D geometric spreading of the ray tube, G = sqrt( prod_k (cos theta_out,k / cos theta_in,k) / |J| ), J = dq / dphi the tube's
+ *        width at the end point (measured perpendicular to the last segment) per radian of launch angle at the start (the element
+ *        DOWN, the point UP), the product over the surface crossing and the backwall reflection with angles on the local normals.
+ *        Closed form: the width W and the direction change Th per launch radian start at (0, 1); a segment of length l adds l Th to W;
+ *        at an interface with incidence / exit cosines ci, co, speeds c_in, c_out and normal turning at K per arc length (K = -+ s'' /
+ *        (1 + s'^2)^{3/2} at the surface, for a ray going down / up; 0 at the backwall): ds = W / ci, dtin = Th - K ds, dtout = c_out ci
+ *        / (c_in co) dtin, then transmission W = ds co, Th = K ds + dtout; reflection W = -ds co, Th = K ds - dtout.  J is the final W.
+ *        (Homogeneous: G = 1 / sqrt(r); a flat interface: G = 1 / sqrt(r1 + r2 (c2 / c1) cos^2 theta1 / cos^2 theta2).)
+ *   Phase convention: the entry is the factor that multiplies the ANALYTIC signal of the wave (rtus_fmc_analytic's positive-frequency
+ *   phasor e^{+iwt}) — the complex conjugate of the coefficients as derived in the e^{i(k.x - wt)} convention.
+ *   Invalid entries: NaN + NaN i exactly where x_entry (or, for skip legs, x_back) is NaN — where the time table is NaN.  A stationary
+ *   path that does not cross the surface from the couplant into the part (E - S or the segment below S not pointing along +n: the
+ *   time solvers do not check occlusion, and on a steep facet a point may lie above the local tangent) carries no ray: 0 + 0 i.  At
+ *   a caustic (J = 0) ray theory fails and the entry is +inf + inf i (rtus_tfm_weighted drops such a leg).
+ *
+ * rtus_leg_amp_surface: amp [n_e][n_f] complex64 (interleaved float32 pairs) of one leg in one direction.
+ *   x0, dx, zs, n_s, xe, ze, xf, zf: rtus_tt_surface's; x_entry [n_e][n_f] the leg's entry points; x_back [n_e][n_f] its backwall points
+ *   (skip legs; nullable for L and T).  leg: RTUS_LEG_*; direction: RTUS_AMP_DOWN / RTUS_AMP_UP; element_width >= 0 [m] and f_c > 0
+ *   [Hz] (f_c is read only when element_width > 0).  Determinism: an entry depends only on its own inputs (subsets give the same bits).
+ *   Argument checks run before any HIP call: -1 for a null pointer, a non-positive size, a bad leg or direction, a non-finite or
+ *   non-positive speed or density, c_t >= c_l, a non-finite z_back, a negative width, f_c <= 0 with a width; -5 past n_s <= 2^22 or
+ *   n_e <= 65535.  d_workspace: rtus_tt_surface_workspace_bytes(n_s) bytes, 256-byte aligned (-4 otherwise); the spline is set up in it
+ *   by rtus_tt_surface's set-up kernel.
+ *
+ * rtus_tfm_weighted: S[f] = sum over (tx, rx) of w_tx[tx][f] w_rx[rx][f] a[tx][rx](tau_tx + tau_rx) — rtus_tfm_analytic's arguments,
+ *   sample positions, interpolation, edge rules and no-path rule, plus complex64 weights w_tx [n_tx][n_f], w_rx [n_rx][n_f].  A leg
+ *   whose weight is not finite also contributes nothing (it cannot poison the pixel).  image [n_f] complex64, fp32 sums: per tx the
+ *   receive tiles of 16 elements are summed with their weights, then multiplied by the transmit weight.
+ *   sens [n_f] float32, nullable: P[f] = (sum over tx with a path of |w_tx|^2) (sum over rx with a path of |w_rx|^2), fp32 sums, the
+ *   product in fp64 rounded once.  With w = conj(A) (A the leg amplitudes), P is the sensitivity — the image at f of a unit isotropic
+ *   point scatterer at f — and |S| / P reads the scatterer's own amplitude; views become comparable.  Passing sens does not change the
+ *   bits of image; the bits of a focal point do not depend on which other focal points share the call.
+ *   Limits and codes: rtus_tfm_analytic's (w_tx, w_rx required, sens nullable).
+ *
+ * The _dev entries allocate nothing and do not synchronise (capturable); the host twins stage through the device's arena.
+ * Measured on MI355X: see DESIGN.md §4 (ray amplitudes).
+ * ---------------------------------------------------------------------------------------- */
+enum { RTUS_LEG_L = 0, RTUS_LEG_T = 1, RTUS_LEG_LL = 2, RTUS_LEG_LT = 3, RTUS_LEG_TL = 4, RTUS_LEG_TT = 5 };
+enum { RTUS_AMP_DOWN = 0, RTUS_AMP_UP = 1 };
+int rtus_leg_amp_surface_dev(double x0, double dx, const double *d_zs, int n_s, double c1, double rho1, double c_l, double c_t,
+                             double rho2, double z_back, int leg, int direction, double element_width, double f_c,
+                             const double *d_xe, const double *d_ze, int n_e, const double *d_xf, const double *d_zf, int n_f,
+                             const double *d_x_entry, const double *d_x_back, float *d_amp, void *d_workspace, size_t workspace_bytes,
+                             void *stream);
+int rtus_leg_amp_surface(double x0, double dx, const double *zs, int n_s, double c1, double rho1, double c_l, double c_t,
+                         double rho2, double z_back, int leg, int direction, double element_width, double f_c,
+                         const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
+                         const double *x_entry, const double *x_back, float *amp, int device);
+int rtus_tfm_weighted_dev(const float *d_a, int n_tx, int n_rx, int n_t, double fs, double t0,
+                          const double *d_tt_tx, const double *d_tt_rx, const float *d_w_tx, const float *d_w_rx, int n_f,
+                          float *d_image, float *d_sens, void *stream);
+int rtus_tfm_weighted(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
+                      const double *tt_tx, const double *tt_rx, const float *w_tx, const float *w_rx, int n_f,
+                      float *image, float *sens, int device);
 
 #ifdef __cplusplus
 }

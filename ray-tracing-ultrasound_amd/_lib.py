@@ -192,6 +192,17 @@ def lib():
     except AttributeError:                # a build from before version 108, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        L.rtus_leg_amp_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dd, dd, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, vp,
+                                               C.c_size_t, vp]
+        L.rtus_leg_amp_surface.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dd, dd, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, ip]
+        L.rtus_tfm_weighted_dev.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, dp, dp, ip, dp, dp, vp]
+        L.rtus_tfm_weighted.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, dp, dp, ip, dp, dp, ip]
+        for name in ("rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted"):
+            getattr(L, name).restype = ip
+    except AttributeError:                # a build from before version 109, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -219,4 +230,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find",
            "rtus_tfm_analytic_dev", "rtus_tfm_analytic",
            "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx",
-           "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip")
+           "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip",
+           "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted")

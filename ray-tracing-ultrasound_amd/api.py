@@ -818,24 +818,143 @@ def view_legs_surface(x0, dx, zs, c1, c_l, c_t, z_back, xe, ze, xf, zf, *, legs=
     return out
 
 
-def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=False, n_taps=63, device=0):
+def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=False, n_taps=63, amplitudes=None, device=0):
     """Multi-view TFM: one image per view -> {view: image float32 [n_f]}.  ``legs``: {leg: tt [n_e, n_f]} (view_legs_layers /
     view_legs_surface); a view "A-B" (transmit leg A, then receive leg B from the point to the receiver) is imaged with
     tt_tx = legs[A] and tt_rx = legs[reverse_leg(B)].  RF: tfm_image.  With ``envelope=True``: |tfm_analytic| over the analytic FMC,
-    formed once for all views (``n_taps`` Hilbert taps); with ``coherence=True`` too, each value is (envelope, cf).  An unknown view
-    or a leg missing from ``legs`` raises ValueError before any GPU call."""
+    formed once for all views (``n_taps`` Hilbert taps); with ``coherence=True`` too, each value is (envelope, cf).
+    ``amplitudes``: {leg: (down, up)} complex64 [n_e, n_f] (view_amplitudes_surface; needs ``envelope=True``, excludes ``coherence``):
+    each view is beamformed by tfm_weighted with w_tx = conj(down[A]) and w_rx = conj(up[reverse_leg(B)]) and the value is |S| / P,
+    P the view's sensitivity (NaN where P = 0): a unit point scatterer reads 1 in every view that sees it, so views share one scale.
+    An unknown view or a leg missing from ``legs`` (or ``amplitudes``) raises ValueError before any GPU call."""
     if coherence and not envelope:
         raise ValueError("the coherence factor needs envelope=True")
+    if amplitudes is not None and not envelope:
+        raise ValueError("amplitude weighting needs envelope=True")
+    if amplitudes is not None and coherence:
+        raise ValueError("amplitude weighting and the coherence factor are exclusive")
     views = (views,) if isinstance(views, str) else tuple(views)
     pairs = {v: view_tables(v) for v in views}
     missing = sorted({g for p in pairs.values() for g in p if g not in legs})
     if missing:
         raise ValueError(f"legs {missing} are needed by the views and missing from ``legs``")
+    if amplitudes is not None:
+        missing = sorted({g for p in pairs.values() for g in p if g not in amplitudes})
+        if missing:
+            raise ValueError(f"legs {missing} are needed by the views and missing from ``amplitudes``")
     if not envelope:
         return {v: tfm_image(fmc, fs, legs[a], legs[b], t0=t0, device=device) for v, (a, b) in pairs.items()}
     analytic = fmc_analytic(fmc, n_taps, device=device)
     out = {}
     for v, (a, b) in pairs.items():
+        if amplitudes is not None:
+            w_tx = np.conj(np.asarray(amplitudes[a][0], dtype=np.complex64))
+            w_rx = np.conj(np.asarray(amplitudes[b][1], dtype=np.complex64))
+            img, sens = tfm_weighted(analytic, fs, legs[a], w_tx, legs[b], w_rx, t0=t0, sensitivity=True, device=device)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[v] = np.where(sens > 0, np.abs(img) / sens, np.float32(np.nan)).astype(np.float32)
+            continue
         r = tfm_analytic(analytic, fs, legs[a], legs[b], t0=t0, coherence=coherence, device=device)
         out[v] = (np.abs(r[0]), r[1]) if coherence else np.abs(r)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- ray amplitudes, weighted TFM
+LEG_CODES = {"L": 0, "T": 1, "LL": 2, "LT": 3, "TL": 4, "TT": 5}      # RTUS_LEG_* (include/rtus.h)
+
+
+def leg_amplitudes_surface(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, leg, xe, ze, xf, zf, x_entry, x_back=None, *, up=False,
+                           element_width=0.0, f_c=None, out=None, device=0):
+    """Ray amplitudes of one multi-view leg through a measured surface -> complex64 [n_e, n_f]: A = D C_S [C_B] G (element
+    directivity, surface and backwall displacement coefficients, 2-D ray-tube spreading), in the analytic signal's phase convention.
+    ``x_entry`` (and ``x_back`` for skip legs) are the leg's points as travel_time_surface(return_entry=True) /
+    skip_travel_time_surface(return_entry=True) return them.  ``up``: the wave travels point -> element along the leg's path (the
+    receive direction) instead of element -> point.  ``element_width`` [m] > 0 needs ``f_c`` [Hz], the centre frequency of the
+    directivity.  The couplant has speed ``c1`` and density ``rho1``, the part ``c_l`` > ``c_t`` and ``rho2`` with a traction-free
+    backwall at ``z_back``.  NaN where x_entry (or x_back) is NaN.  Definition: include/rtus.h (rtus_leg_amp_surface).  Not in the
+    reference."""
+    if leg not in LEGS:
+        raise ValueError(f"unknown leg {leg!r}: legs are {LEGS}")
+    skip = len(leg) == 2
+    zs = _f64(zs, "zs")
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    shape = (xe.size, xf.size)
+    xn = _f64(x_entry, "x_entry", 2)
+    if xn.shape != shape:
+        raise ValueError(f"x_entry must be [n_e, n_f] = {shape}")
+    xb = None
+    if skip:
+        if x_back is None:
+            raise ValueError(f"the skip leg {leg!r} needs x_back")
+        xb = _f64(x_back, "x_back", 2)
+        if xb.shape != shape:
+            raise ValueError(f"x_back must be [n_e, n_f] = {shape}")
+    if element_width > 0 and f_c is None:
+        raise ValueError("an element width needs the centre frequency f_c")
+    amp = _out(out, shape, np.complex64)
+    st = _lib.lib().rtus_leg_amp_surface(float(x0), float(dx), _ptr(zs), zs.size, float(c1), float(rho1), float(c_l), float(c_t),
+                                         float(rho2), float(z_back), LEG_CODES[leg], 1 if up else 0, float(element_width),
+                                         float(f_c or 0.0), _ptr(xe), _ptr(ze), xe.size, _ptr(xf), _ptr(zf), xf.size, _ptr(xn), _ptr(xb),
+                                         _ptr(amp), int(device))
+    _lib.check(st, "rtus_leg_amp_surface")
+    return amp
+
+
+def view_amplitudes_surface(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, xe, ze, xf, zf, *, legs=LEGS, element_width=0.0, f_c=None,
+                            device=0):
+    """The leg tables of multi-view TFM through ONE measured front surface with their ray amplitudes -> (legs_tt, amps):
+    legs_tt = {leg: tt [n_e, n_f]} as view_legs_surface makes them, amps = {leg: (down, up)} complex64 [n_e, n_f]
+    (leg_amplitudes_surface in both directions on the tables' own entry and backwall points).  Feed both to
+    ``tfm_views(..., envelope=True, amplitudes=amps)``."""
+    legs = _legs_wanted(legs)
+    sp = {"L": float(c_l), "T": float(c_t)}
+    tts, amps = {}, {}
+    for g in legs:
+        if len(g) == 1:
+            tt, xn = travel_time_surface(x0, dx, zs, c1, sp[g], xe, ze, xf, zf, return_entry=True, device=device)
+            xb = None
+        else:
+            tt, xn, xb = skip_travel_time_surface(x0, dx, zs, c1, sp[g[0]], z_back, xe, ze, xf, zf, c_up=sp[g[1]], return_entry=True,
+                                                  device=device)
+        tts[g] = tt
+        amps[g] = tuple(leg_amplitudes_surface(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, g, xe, ze, xf, zf, xn, xb, up=u,
+                                               element_width=element_width, f_c=f_c, device=device) for u in (False, True))
+    return tts, amps
+
+
+def _weights(w, n, n_f, name):
+    w = np.ascontiguousarray(w, dtype=np.complex64)
+    if w.shape != (n, n_f):
+        raise ValueError(f"{name} must be complex64 [{n}, {n_f}]")
+    return w
+
+
+def tfm_weighted(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, *, t0=0.0, sensitivity=False, out=None, device=0):
+    """Weighted envelope TFM: S[f] = sum over (tx, rx) of w_tx[tx, f] w_rx[rx, f] a[tx, rx](tau_tx + tau_rx), with tfm_analytic's
+    sample positions, interpolation, edge rules and no-path rule; a leg with a non-finite weight contributes nothing.  ``w_tx`` /
+    ``w_rx``: complex64 [n_tx, n_f] / [n_rx, n_f]; tt_rx and w_rx default to tt_tx and w_tx.  -> complex64 image [n_f]; with
+    ``sensitivity=True`` -> (image, P float32 [n_f]), P = (sum over tx with a path of |w_tx|^2) (sum over rx with a path of |w_rx|^2).
+    With the weights conj(amplitude) P is the image of a unit point scatterer and |S| / P is sensitivity-normalised.  Definition:
+    include/rtus.h (rtus_tfm_weighted).  Not in the reference."""
+    a = _complex_fmc(analytic)
+    tt_tx = np.ascontiguousarray(tt_tx, dtype=np.float64)
+    if tt_rx is None:
+        tt_rx = tt_tx
+        w_rx = w_tx if w_rx is None else w_rx
+    tt_rx = np.ascontiguousarray(tt_rx, dtype=np.float64)
+    if w_rx is None:
+        raise ValueError("w_rx is needed with tt_rx")
+    if tt_tx.ndim != 2 or tt_rx.ndim != 2 or tt_tx.shape[1] != tt_rx.shape[1]:
+        raise ValueError("tt_tx / tt_rx must be [n_tx, n_focal] / [n_rx, n_focal]")
+    if tt_tx.shape[0] != a.shape[0] or tt_rx.shape[0] != a.shape[1]:
+        raise ValueError("the analytic FMC's first two dimensions must match the rows of tt_tx and tt_rx")
+    n_f = tt_tx.shape[1]
+    w_tx, w_rx = _weights(w_tx, a.shape[0], n_f, "w_tx"), _weights(w_rx, a.shape[1], n_f, "w_rx")
+    img = _out(out, (n_f,), np.complex64)
+    sens = np.empty(n_f, dtype=np.float32) if sensitivity else None
+    st = _lib.lib().rtus_tfm_weighted(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx),
+                                      _ptr(w_tx), _ptr(w_rx), n_f, _ptr(img), _ptr(sens), int(device))
+    _lib.check(st, "rtus_tfm_weighted")
+    return (img, sens) if sensitivity else img

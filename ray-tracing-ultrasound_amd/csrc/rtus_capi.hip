@@ -70,6 +70,13 @@ hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs
                                     float* amp, float* image, hipStream_t s);
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
+hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                                    const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
+                                    hipStream_t s);
+hipError_t rtus_launch_leg_amp_surface(double x0, double dx, const double* zs, int n_s, double c1, double rho1, double c_l, double c_t,
+                                       double rho2, double z_back, int leg, int up, double width, double f_c, const double* xe,
+                                       const double* ze, int n_e, const double* xf, const double* zf, int n_f, const double* x_entry,
+                                       const double* x_back, float* amp, void* ws, hipStream_t s);
 hipError_t rtus_launch_pw_layers(const double* z_if, const double* c, int n_if, const double* ang, int n_a, double xlo, double xhi,
                                  double za, const double* xf, const double* zf, int n_f, double* tt, hipStream_t s);
 hipError_t rtus_launch_pw_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* ang, int n_a,
@@ -1093,6 +1100,116 @@ int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, n_f, dimg, dcf, S.a->stream));
     S.download(image, dimg, 2 * (size_t)n_f);
     if (cf) S.download(cf, dcf, (size_t)n_f);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+// ---------------------------------------------------------------------------- weighted envelope TFM + sensitivity
+static int check_tfm_weighted(const void* a, int n_tx, int n_rx, int n_t, double fs, double t0, const void* tt_tx, const void* tt_rx,
+                              const void* w_tx, const void* w_rx, int n_f, const void* image)
+{
+    if (!w_tx || !w_rx) return RTUS_ERR_INVALID_ARG;
+    return check_tfm_analytic(a, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, image);   // (sens is nullable)
+}
+
+int rtus_tfm_weighted_dev(const float* d_a, int n_tx, int n_rx, int n_t, double fs, double t0, const double* d_tt_tx,
+                          const double* d_tt_rx, const float* d_w_tx, const float* d_w_rx, int n_f, float* d_image, float* d_sens,
+                          void* stream)
+{
+    int st = check_tfm_weighted(d_a, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, d_w_tx, d_w_rx, n_f, d_image);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_weighted(d_a, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, d_w_tx, d_w_rx, n_f, d_image, d_sens,
+                                        (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_weighted(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                      const float* w_tx, const float* w_rx, int n_f, float* image, float* sens, int device)
+{
+    int st = check_tfm_weighted(a, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, w_tx, w_rx, n_f, image);
+    if (st) return st;
+    const size_t na = (size_t)n_tx * n_rx * n_t * 2, ntx = (size_t)n_tx * n_f, nrx = (size_t)n_rx * n_f;
+    Session S;
+    if ((st = S.open(device, al256(4 * na) + al256(8 * ntx) + al256(8 * nrx) + al256(8 * ntx) + al256(8 * nrx) + al256(8 * (size_t)n_f) +
+                                 (sens ? al256(4 * (size_t)n_f) : 0))))
+        return st;
+    float *da, *dwt, *dwr;
+    double *dtx, *drx;
+    S.upload(da, a, na);
+    S.upload(dtx, tt_tx, ntx);
+    S.upload(drx, tt_rx, nrx);
+    S.upload(dwt, w_tx, 2 * ntx);
+    S.upload(dwr, w_rx, 2 * nrx);
+    float* dimg = S.take<float>(2 * (size_t)n_f);
+    float* dsens = sens ? S.take<float>(n_f) : nullptr;
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_tfm_weighted(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, dwt, dwr, n_f, dimg, dsens, S.a->stream));
+    S.download(image, dimg, 2 * (size_t)n_f);
+    if (sens) S.download(sens, dsens, (size_t)n_f);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}
+
+// ---------------------------------------------------------------------------- ray amplitude tables through a measured surface
+static int check_leg_amp(double x0, double dx, const void* zs, int n_s, double c1, double rho1, double c_l, double c_t, double rho2,
+                         double z_back, int leg, int dir, double width, double f_c, const void* xe, const void* ze, int n_e,
+                         const void* xf, const void* zf, int n_f, const void* x_entry, const void* x_back, const void* amp)
+{
+    if (!zs || !xe || !ze || !xf || !zf || !x_entry || !amp || n_s < 4 || n_e <= 0 || n_f <= 0) return RTUS_ERR_INVALID_ARG;
+    if (leg < RTUS_LEG_L || leg > RTUS_LEG_TT || (dir != RTUS_AMP_DOWN && dir != RTUS_AMP_UP)) return RTUS_ERR_INVALID_ARG;
+    if (leg >= RTUS_LEG_LL && !x_back) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(x0) || !isfinite(dx) || !(dx > 0) || !isfinite(z_back)) return RTUS_ERR_INVALID_ARG;
+    const double sp[5] = {c1, rho1, c_l, c_t, rho2};
+    for (double v : sp)
+        if (!isfinite(v) || !(v > 0)) return RTUS_ERR_INVALID_ARG;
+    if (!(c_t < c_l) || !isfinite(width) || width < 0 || (width > 0 && (!isfinite(f_c) || !(f_c > 0)))) return RTUS_ERR_INVALID_ARG;
+    if (n_s > RTUS_SURFACE_MAX_SAMPLES || n_e > 65535) return RTUS_ERR_UNSUPPORTED;       // grid.y: one element per row of workgroups
+    return RTUS_OK;
+}
+
+int rtus_leg_amp_surface_dev(double x0, double dx, const double* d_zs, int n_s, double c1, double rho1, double c_l, double c_t,
+                             double rho2, double z_back, int leg, int direction, double element_width, double f_c, const double* d_xe,
+                             const double* d_ze, int n_e, const double* d_xf, const double* d_zf, int n_f, const double* d_x_entry,
+                             const double* d_x_back, float* d_amp, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int st = check_leg_amp(x0, dx, d_zs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, d_xe, d_ze, n_e, d_xf,
+                           d_zf, n_f, d_x_entry, d_x_back, d_amp);
+    if (st) return st;
+    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    LAUNCH_TRY(rtus_launch_leg_amp_surface(x0, dx, d_zs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, d_xe,
+                                           d_ze, n_e, d_xf, d_zf, n_f, d_x_entry, leg >= RTUS_LEG_LL ? d_x_back : nullptr, d_amp,
+                                           d_workspace, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_leg_amp_surface(double x0, double dx, const double* zs, int n_s, double c1, double rho1, double c_l, double c_t, double rho2,
+                         double z_back, int leg, int direction, double element_width, double f_c, const double* xe, const double* ze,
+                         int n_e, const double* xf, const double* zf, int n_f, const double* x_entry, const double* x_back, float* amp,
+                         int device)
+{
+    int st = check_leg_amp(x0, dx, zs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, xe, ze, n_e, xf, zf,
+                           n_f, x_entry, x_back, amp);
+    if (st) return st;
+    const bool skip = leg >= RTUS_LEG_LL;
+    const size_t tot = (size_t)n_e * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    Session S;
+    if ((st = S.open(device, al256(8 * (size_t)n_s) + 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) + (skip ? 2 : 1) * al256(8 * tot) +
+                                 al256(8 * tot) + al256(wsb))))
+        return st;
+    double *dzs, *dxe, *dze, *dxf, *dzf, *dxn, *dxb = nullptr;
+    S.upload(dzs, zs, n_s);
+    S.upload(dxe, xe, n_e);
+    S.upload(dze, ze, n_e);
+    S.upload(dxf, xf, n_f);
+    S.upload(dzf, zf, n_f);
+    S.upload(dxn, x_entry, tot);
+    if (skip) S.upload(dxb, x_back, tot);
+    float* damp = S.take<float>(2 * tot);
+    void* ws = S.take<char>(wsb);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_leg_amp_surface(x0, dx, dzs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, dxe, dze,
+                                           n_e, dxf, dzf, n_f, dxn, dxb, damp, ws, S.a->stream));
+    S.download(amp, damp, 2 * tot);
     HIP_TRY(S.finish());
     return RTUS_OK;
 }

@@ -608,3 +608,14 @@ hipError_t rtus_launch_tt_surface_skip(double x0, double dx, const double* zs, i
     hipLaunchKernelGGL(rtus_surface_kernel<SURF_SKIP>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }
+
+// the set-up kernel alone, for the consumers of a surface table in other files (rtus_amp.hip): the spline's coefficients land in
+// the workspace at *coef (the scan points are written too, as for a table launch)
+hipError_t rtus_launch_surface_setup(const double* zs, int n_s, double x0, double dx, void* ws, const double** coef, hipStream_t s)
+{
+    const SurfWs w = surf_ws(ws, n_s);
+    *coef = w.coef;
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, x0 + 0.5 * (double)(n_s - 1) * dx,
+                       0.0, w);
+    return hipGetLastError();
+}

@@ -314,3 +314,116 @@ hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t
     else hipLaunchKernelGGL(rtus_tfm_analytic_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------- weighted envelope TFM + sensitivity
+// S[f] = sum over (tx, rx) of w_tx[tx][f] w_rx[rx][f] a[tx][rx](s), with rtus_tfm_analytic's sample positions, interpolation and edge
+// rules; a leg without a path or with a non-finite weight contributes nothing.  With SENS, also P[f] = (sum over tx with a path of
+// |w_tx|^2) (sum over rx with a path of |w_rx|^2), counted while the tiles are filled.  Definition: include/rtus.h (rtus_tfm_weighted).
+//
+// rtus_tfm_analytic_kernel's structure with a receive tile of 16 elements: the tile holds the fp32 delays AND the complex receive
+// weights (16 x 256 x 12 B = 48 KiB of LDS: three workgroups per CU; 64 elements would need 192 KiB, past the CU's 160 KiB).  One
+// tile is one group of sixteen gathers in flight per lane; per transmit element the tile's weighted sum goes into a partial that is
+// multiplied by the transmit weight once (4 FMAs per tx and tile, not per pair).  The transmit delay and weight are re-read per tile
+// (16 B per tx and focal point, against 16 x 16 B of gathers).
+#define RTUS_TFMW_RX_TILE 16
+
+struct TfmwArgs {
+    const float* __restrict__ a;         // [n_tx][n_rx][n_t][2]
+    const double* __restrict__ tt_tx;    // [n_tx][n_f]
+    const double* __restrict__ tt_rx;    // [n_rx][n_f]
+    const float2* __restrict__ w_tx;     // [n_tx][n_f]
+    const float2* __restrict__ w_rx;     // [n_rx][n_f]
+    float2* __restrict__ image;          // [n_f]
+    float* __restrict__ sens;            // [n_f] (read by the SENS instantiation only)
+    int n_tx, n_rx, n_t, n_f;
+    double fs, half_t0s;
+};
+
+__device__ __forceinline__ bool tfmw_finite(float2 w) { return fabsf(w.x) <= 3.4e38f && fabsf(w.y) <= 3.4e38f; }   // NaN fails
+
+__device__ __forceinline__ void tfmw_accum(sf_u32x4 v, float w, float2 g, float& pr, float& pi)
+{
+    const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
+    const float sr = fmaf(w, r1 - r0, r0), si = fmaf(w, i1 - i0, i0);
+    pr = fmaf(g.x, sr, fmaf(-g.y, si, pr));
+    pi = fmaf(g.x, si, fmaf(g.y, sr, pi));
+}
+
+template <bool SENS>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_weighted_kernel(TfmwArgs a)
+{
+    __shared__ float tau_rx[RTUS_TFMW_RX_TILE][RTUS_BLOCK];           // 16 KiB
+    __shared__ float2 wr[RTUS_TFMW_RX_TILE][RTUS_BLOCK];              // 32 KiB
+    const int nblk = gridDim.x, per = (nblk + 7) >> 3;                // XCD k takes a contiguous share (rtus_tfm_kernel)
+    int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if (nblk & 7) blk = blockIdx.x;
+    const int f_raw = blk * RTUS_BLOCK + threadIdx.x;
+    const bool live = f_raw < a.n_f;
+    const int f = live ? f_raw : a.n_f - 1;
+    const size_t nf = (size_t)a.n_f;
+    const size_t pair_len = (size_t)a.n_t * 2;
+    float re = 0.0f, im = 0.0f, ptx = 0.0f, prx = 0.0f;
+    for (int r0 = 0; r0 < a.n_rx; r0 += RTUS_TFMW_RX_TILE) {
+        const int nr = min(RTUS_TFMW_RX_TILE, a.n_rx - r0);
+        __syncthreads();                                              // the previous tile is no longer read
+        for (int r = 0; r < nr; ++r) {
+            const size_t o = (size_t)(r0 + r) * nf + f;
+            const float v = tfm_tau(a.tt_rx[o], a.fs, a.half_t0s);
+            const float2 g = a.w_rx[o];
+            const bool ok = tfm_has_path(v) && tfmw_finite(g);
+            tau_rx[r][threadIdx.x] = ok ? v : -1.0e8f;                // no path: every position of the pair is negative
+            wr[r][threadIdx.x] = ok ? g : make_float2(0.0f, 0.0f);
+            if (SENS && ok) prx = fmaf(g.y, g.y, fmaf(g.x, g.x, prx));
+        }
+        __syncthreads();
+        for (int tx = 0; tx < a.n_tx; ++tx) {
+            const size_t o = (size_t)tx * nf + f;
+            float tt = tfm_tau(a.tt_tx[o], a.fs, a.half_t0s);
+            float2 gt = a.w_tx[o];
+            const bool ok = tfm_has_path(tt) && tfmw_finite(gt);
+            if (!ok) { tt = -1.0e8f; gt = make_float2(0.0f, 0.0f); }
+            if (SENS && r0 == 0 && ok) ptx = fmaf(gt.y, gt.y, fmaf(gt.x, gt.x, ptx));
+            const float* rec = a.a + ((size_t)tx * a.n_rx + r0) * pair_len;   // wave-uniform
+            float pr = 0.0f, pi = 0.0f;
+            int r = 0;
+            for (; r + RTUS_TFM_GROUP <= nr; r += RTUS_TFM_GROUP) {
+                sf_u32x4 v[RTUS_TFM_GROUP];
+                float w[RTUS_TFM_GROUP];
+#pragma unroll
+                for (int k = 0; k < RTUS_TFM_GROUP; ++k) {           // all sixteen gathers issued before the first is used
+                    const float s = tt + tau_rx[r + k][threadIdx.x];
+                    const float fl = floorf(s);
+                    w[k] = s - fl;
+                    v[k] = sf_load2(rec + (size_t)(r + k) * pair_len, a.n_t, (int)fl);
+                }
+#pragma unroll
+                for (int k = 0; k < RTUS_TFM_GROUP; ++k) tfmw_accum(v[k], w[k], wr[r + k][threadIdx.x], pr, pi);
+            }
+            for (; r < nr; ++r) {                                     // a ragged last tile
+                const float s = tt + tau_rx[r][threadIdx.x];
+                const float fl = floorf(s);
+                tfmw_accum(sf_load2(rec + (size_t)r * pair_len, a.n_t, (int)fl), s - fl, wr[r][threadIdx.x], pr, pi);
+            }
+            re = fmaf(gt.x, pr, fmaf(-gt.y, pi, re));
+            im = fmaf(gt.x, pi, fmaf(gt.y, pr, im));
+        }
+    }
+    if (!live) return;
+    a.image[f] = make_float2(re, im);
+    if (SENS) a.sens[f] = (float)((double)ptx * (double)prx);
+}
+
+hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                                    const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
+                                    hipStream_t s)
+{
+    TfmwArgs a;
+    a.a = an; a.tt_tx = tt_tx; a.tt_rx = tt_rx; a.w_tx = (const float2*)w_tx; a.w_rx = (const float2*)w_rx;
+    a.image = (float2*)image; a.sens = sens;
+    a.n_tx = n_tx; a.n_rx = n_rx; a.n_t = n_t; a.n_f = n_f;
+    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    if (sens) hipLaunchKernelGGL(rtus_tfm_weighted_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(rtus_tfm_weighted_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}

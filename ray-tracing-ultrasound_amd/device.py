@@ -567,3 +567,75 @@ def fmc_synth_tx_dev(fmc, fs, delays, out=None):
                                           _stream(fmc))
     _lib.check(st, "rtus_fmc_synth_tx_dev")
     return out
+
+
+def leg_amp_surface_dev(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, leg, xe, ze, xf, zf, x_entry, x_back=None, *, up=False,
+                        element_width=0.0, f_c=None, out=None, ws=None):
+    """Ray amplitudes of one leg on device (rtus_leg_amp_surface_dev; api.leg_amplitudes_surface's definition): float64 CUDA tensors
+    in, out float32 [n_e, n_f, 2] (interleaved complex64).  ``ws``: an optional uint8 tensor of rtus_tt_surface_workspace_bytes(n_s)
+    bytes (allocated here otherwise; pass one to capture the call in a graph).  Asynchronous on the current stream."""
+    if leg not in _api.LEG_CODES:
+        raise ValueError(f"unknown leg {leg!r}: legs are {_api.LEGS}")
+    for t, n in ((zs, "zs"), (xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf"), (x_entry, "x_entry")):
+        _chk(t, n)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f or x_entry.numel() != n_e * n_f:
+        raise ValueError("xe/ze and xf/zf must pair up, x_entry hold n_e * n_f values")
+    if len(leg) == 2:
+        if x_back is None:
+            raise ValueError(f"the skip leg {leg!r} needs x_back")
+        _chk(x_back, "x_back")
+        if x_back.numel() != n_e * n_f:
+            raise ValueError("x_back must hold n_e * n_f values")
+    if element_width > 0 and f_c is None:
+        raise ValueError("an element width needs the centre frequency f_c")
+    if out is None:
+        out = torch.empty((n_e, n_f, 2), dtype=torch.float32, device=xe.device)
+    _chk(out, "out", torch.float32)
+    if out.numel() != 2 * n_e * n_f:
+        raise ValueError("out must hold 2 * n_e * n_f float32 values")
+    need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)
+    _chk(ws, "ws", torch.uint8)
+    st = _lib.lib().rtus_leg_amp_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(rho1), float(c_l), float(c_t),
+                                             float(rho2), float(z_back), _api.LEG_CODES[leg], 1 if up else 0, float(element_width),
+                                             float(f_c or 0.0), _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(x_entry),
+                                             _p(x_back if len(leg) == 2 else None), _p(out), _p(ws), ws.numel(), _stream(xe))
+    _lib.check(st, "rtus_leg_amp_surface_dev")
+    return out
+
+
+def tfm_weighted_dev(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, t0=0.0, out=None, sens=None):
+    """Weighted envelope TFM on device (rtus_tfm_weighted_dev; api.tfm_weighted's definition): analytic float32 [n_tx, n_rx, n_t, 2],
+    tt_tx [n_tx, n_f] / tt_rx [n_rx, n_f] float64 (tt_rx, w_rx default to tt_tx, w_tx), w_tx / w_rx float32 [n, n_f, 2] (complex)
+    -> out float32 [n_f, 2]; ``sens``: an optional float32 [n_f] tensor that receives the sensitivity (then -> (out, sens)).
+    Asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx"); _chk(w_tx, "w_tx", torch.float32)
+    if tt_rx is None:
+        tt_rx = tt_tx
+        w_rx = w_tx if w_rx is None else w_rx
+    _chk(tt_rx, "tt_rx")
+    if w_rx is None:
+        raise ValueError("w_rx is needed with tt_rx")
+    _chk(w_rx, "w_rx", torch.float32)
+    if analytic.dim() != 4 or analytic.shape[3] != 2 or tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] \
+            or analytic.shape[0] != tt_tx.shape[0] or analytic.shape[1] != tt_rx.shape[0]:
+        raise ValueError("need analytic [n_tx, n_rx, n_t, 2], tt_tx [n_tx, n_f], tt_rx [n_rx, n_f]")
+    n_f = tt_tx.shape[1]
+    if w_tx.numel() != 2 * tt_tx.numel() or w_rx.numel() != 2 * tt_rx.numel():
+        raise ValueError("w_tx / w_rx must hold 2 * n_tx * n_f / 2 * n_rx * n_f float32 values")
+    if out is None:
+        out = torch.empty((n_f, 2), dtype=torch.float32, device=analytic.device)
+    _chk(out, "out", torch.float32)
+    if sens is not None:
+        _chk(sens, "sens", torch.float32)
+    if out.numel() != 2 * n_f or (sens is not None and sens.numel() != n_f):
+        raise ValueError("out must hold 2 * n_focal float32 values, sens n_focal")
+    devs = {t.device for t in (analytic, tt_tx, tt_rx, w_tx, w_rx, out) + ((sens,) if sens is not None else ())}
+    if len(devs) != 1:
+        raise ValueError("analytic, the tables, the weights, out and sens must be on one device")
+    st = _lib.lib().rtus_tfm_weighted_dev(_p(analytic), analytic.shape[0], analytic.shape[1], analytic.shape[2], float(fs), float(t0),
+                                          _p(tt_tx), _p(tt_rx), _p(w_tx), _p(w_rx), n_f, _p(out), _p(sens), _stream(analytic))
+    _lib.check(st, "rtus_tfm_weighted_dev")
+    return out if sens is None else (out, sens)

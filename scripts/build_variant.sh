@@ -8,7 +8,10 @@ EXTRA="$*"
 SRC=$ROOT/ray-tracing-ultrasound_amd/csrc
 OUT=$ROOT/variants; mkdir -p $OUT/obj_$NAME
 COMMON="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -fno-fast-math -fno-slp-vectorize"
-for f in rtus_shoot rtus_solve rtus_match rtus_fermat rtus_lens_fermat rtus_tfm rtus_surface rtus_autofocus rtus_pwi rtus_capi; do
+# the library's sources are the Makefile's SRCS: a variant links exactly what librtus.so links
+SRCS=$(sed -n 's/^SRCS *:= *//p' $SRC/Makefile)
+[ -n "$SRCS" ] || { echo "no SRCS in $SRC/Makefile" >&2; exit 1; }
+for f in ${SRCS//.hip/}; do
   fl=""
   [ $f = rtus_shoot ] && fl="-ffp-contract=off -mllvm -disable-machine-licm"
   [ $f = rtus_solve ] && fl="-ffp-contract=off -mllvm -disable-machine-licm"
