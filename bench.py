@@ -23,10 +23,13 @@ main_rt.py:464-501: 210 geometries x 905 rays forward trace + 65-element matcher
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against the HBM roof as the contract asks
 (algorithmic bytes per launch / HIP-event launch time; `traffic` = PMC-measured HBM bytes per launch from profiles/);
-`roofline_valu` carries what actually binds this scalar root-find (VALU issue; SQ counters from profiles/);
-`cpu_baseline` is the oracle's fp64 CPU port timed on this box's host cores on the whole workload, and `accuracy` the
-measured max |dt| of the GPU result against the long-double oracle on a seeded sample (rank 0, N = 1 only);
-`extra` holds side measurements of the other configs and of the reference-parity path.
+`roofline_valu` carries what actually binds this scalar root-find (VALU issue; SQ counters from profiles/).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, --dump-outputs if asked, print the line.
+--full adds everything else, after the timed region: `cpu_baseline` (the oracle's fp64 CPU port timed on the host's cores
+on the whole workload) and `accuracy` (the measured max |dt| of the GPU result against the long-double oracle on a seeded
+sample; rank 0, N = 1 only), and `extra`, the side measurements of the other configs and of the reference-parity path.
+--no-cpu-baseline / --no-extra leave either part out of a --full run.
 """
 import argparse
 import json
@@ -79,9 +82,12 @@ def parse(argv=None):
                          "own output buffer (default 1: K back-to-back launches on one stream)")
     ap.add_argument("--tier", default="taup", choices=["taup", "accurate"],
                     help="planar workloads: accuracy tier of the solver — taup (RTUS_TT_TAUP_TAIL: the travel time from the tau-p form, "
-                         "<= 6e-11 relative at worst; the measured max |dt| is in the line) or accurate (the library's default tier)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+                         "<= 6e-11 relative at worst; the measured max |dt| is in the --full line) or accurate (the library's default tier)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline + accuracy check against the oracle and the side "
+                         "measurements (`extra`); off by default: a plain run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and accuracy check")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step computed as DIR/<name>.npy (by rank 0; at --gpus > 1 the table "
                          "all-gathered from every rank's rows; arrays over their share of 64 MB as a fixed seeded sample, with the "
@@ -512,10 +518,10 @@ def main(argv=None):
             "numerics": {"cfg4_lens_f32": "fp32 throughout (|dt| < 2e-10 s vs fp64 where both follow the same ray path; DESIGN section 4 on minima at the end of the search interval)"}.get(
                 wl, ("fp64 results, tier RTUS_TT_TAUP_TAIL: Newton PRE-iteration on the fp32 pipe, the travel time from the tau-p form "
                      "p X + sum (h/c) cos(theta) in fp64 (stationary in p) + its second-order term from the fp32 residual — <= 6e-11 "
-                     "relative by construction, measured max |dt| vs the long-double oracle: see `accuracy`; the library's default tier "
-                     "(fp64 residual, <= 1e-13 relative) is timed in extra.cfg3_planar_accurate_tier" if args.tier == "taup" else
+                     "relative by construction, measured max |dt| vs the long-double oracle: see `accuracy` (--full); the library's default tier "
+                     "(fp64 residual, <= 1e-13 relative) is timed in extra.cfg3_planar_accurate_tier (--full)" if args.tier == "taup" else
                      "fp64 results, default tier: Newton PRE-iteration on the fp32 pipe, the result from an fp64 evaluation + Fermat "
-                     "expansion (measured max |dt| vs the long-double oracle: see `accuracy`)")
+                     "expansion (measured max |dt| vs the long-double oracle: see `accuracy`, --full)")
                 if wl in PLANAR else "fp64, reference-compatible arithmetic"),
             "sharding": (f"tx-element rows x{world}" if m is not None else f"{world} rank(s), each its own (geometry, tx) rows: no exchange") + (", RCCL all-gather every step (overlapped)" if gather_step else
                                                        ", RCCL all-gather of the final matrix inside the timed region" if gather_end else
@@ -545,10 +551,10 @@ def main(argv=None):
         out["config"]["numerics"] = (f"VALUE = {out['value']} Mrays/s is the COLLECTIVE-FREE solve rate; with ONE RCCL all-gather of the table after the "
                                      f"K steps: {rs} Mrays/s (value_with_reassembly), reassembled every step: {out.get('value_reassembled_every_step')} "
                                      f"Mrays/s — the table's reassembly, not the solve, decides those (DESIGN.md section 6); the workload that "
-                                     f"scales WITH its collective inside the timed region is extra.tfm_columns.  " + out["config"]["numerics"])
+                                     f"scales WITH its collective inside the timed region is extra.tfm_columns (--full).  " + out["config"]["numerics"])
     if world > 1:
         out["multi_gpu_note"] = ("RCCL over xGMI first ran in the driver's scaling job (the build pool has one GPU per box); compare "
-                                 "this line with `extra.cfg4_lens_f32_full` (the same table on one GPU) of the N = 1 line" if wl == "cfg4_lens_f32"
+                                 "this line with `extra.cfg4_lens_f32_full` (the same table on one GPU) of the N = 1 --full line" if wl == "cfg4_lens_f32"
                                  else "per-GPU work fixed (weak scaling): no data-path collective")
 
     ach = alg_bytes / (kern_ms * 1e-3) / 1e9
@@ -573,24 +579,26 @@ def main(argv=None):
             v["frac_of_issue_bound"] = round(t_issue * 1e3 / kern_ms, 4)
         out["roofline_valu"] = v
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    cpu_leg = args.full and not args.no_cpu_baseline         # --full only: everything below is beside the headline
+    extra_leg = args.full and not args.no_extra
+    if rank == 0 and world == 1 and cpu_leg:
         gpu_table = m.local(0)[:n_e] if m is not None else None
         out["cpu_baseline"], acc = cpu_baseline(wl, gpu_table, torch)
         if acc is not None:
             out["accuracy"] = acc
             out["max_abs_dt_s"] = acc["max_abs_dt_s"]
-    if rank == 0 and world == 1 and not args.no_extra and wl == "cfg3_planar":
+    if rank == 0 and world == 1 and extra_leg and wl == "cfg3_planar":
         out["extra"] = extra_measurements(dev_api, dist_api, rtus, t64, torch, dev)
         lens_samples = out["extra"].pop("_lens_samples", {})
-        if not args.no_cpu_baseline:
+        if cpu_leg:
             out["extra"]["cpu_ref_path"] = cpu_ref_path()
             out["extra"]["lens_tables_accuracy"] = lens_tables_accuracy(lens_samples)
-    if world > 1 and not args.no_extra and wl == "cfg4_lens_f32" and args.gather != "step":
+    if world > 1 and extra_leg and wl == "cfg4_lens_f32" and args.gather != "step":
         fm = fmc_strong(dev_api, dist_api, t64, torch, dev, rank, world, barrier, max_over_ranks, args)
         tc = tfm_columns(dev_api, dist_api, t64, torch, dev, rank, world, barrier, max_over_ranks, args)
         if rank == 0:
             out["extra"] = {"cfg5_fmc": fm, "tfm_columns": tc}
-    if world == 1 and rank == 0 and not args.no_extra and "extra" in out:
+    if world == 1 and rank == 0 and extra_leg and "extra" in out:
         out["extra"]["tfm_columns"] = tfm_columns(dev_api, dist_api, t64, torch, dev, 0, 1, barrier, max_over_ranks, args)
     if rank == 0:
         print(json.dumps(out), flush=True)

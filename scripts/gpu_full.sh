@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/full; mkdir -p "$OUT"
 cd $ROOT
 timeout -k 10 900 python3 -m pytest tests -x -q -m gpu > $OUT/pytest.log 2>&1 || { tail -40 $OUT/pytest.log; exit 1; }
 tail -3 $OUT/pytest.log
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err || { tail -20 $OUT/bench20.err; exit 1; }
+timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench20.json 2> $OUT/bench20.err || { tail -20 $OUT/bench20.err; exit 1; }
 python3 - <<PY
 import json
 d = json.loads(open("$OUT/bench20.json").read().strip().splitlines()[-1])

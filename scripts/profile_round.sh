@@ -17,10 +17,10 @@ SQ2="SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_
 SQSH="SQ_INSTS_SMEM SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE"
 SQ3="SQ_INSTS_VALU_INT32 SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAIT_ANY GRBM_GUI_ACTIVE"
 echo "[1] un-profiled bench lines: the driver's K (20 / 5) and the default K"
-python3 $B --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err
+python3 $B --steps 20 --warmup 5 --full > $OUT/bench_k20.json 2> $OUT/bench_k20.err
 python3 $B --no-extra --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "[2] kernel trace of the driver's command"
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $B --steps 20 --warmup 5 --no-cpu-baseline > $OUT/kt.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python3 $B --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/kt.log 2>&1
 echo "[3] HBM traffic of the headline launch (separate passes)"
 rocprofv3 --pmc WRITE_SIZE -d $OUT/wr -o wr --output-format csv -- python3 $B $PMC > $OUT/wr.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $OUT/rd -o rd --output-format csv -- python3 $B $PMC > $OUT/rd.log 2>&1

@@ -80,7 +80,7 @@ for name in ("bench_k20", "bench_default"):
 bench = json.load(open(os.path.join(dst, f"{tag}_bench_k20.json")))
 
 # ---- kernel trace of the driver's command ------------------------------------------------------------------------
-kt = kernel_rows("kt", "python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline (rocprofv3 --kernel-trace --stats)")
+kt = kernel_rows("kt", "python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline (rocprofv3 --kernel-trace --stats)")
 head = [r for r in kt if HEAD in r["kernel"]][0]
 # the K timed launches alone: the headline kernel's dispatches in time order are W warm-up launches, the ~30 ms of untimed
 # graph replays (clock ramp), the K timed ones and one more inside `extra`; the driver's command has K = 20

@@ -28,6 +28,14 @@ def test_defaults_and_flags(monkeypatch):
     assert a.workload == "cfg3_planar"
 
 
+def test_full_is_off_by_default():
+    # a plain run times the headline alone; the CPU baseline, the accuracy check and `extra` run with --full
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and not a.no_extra and not a.no_cpu_baseline
+    a = bench.parse(["--full", "--no-cpu-baseline"])
+    assert a.full and a.no_cpu_baseline and not a.no_extra
+
+
 def test_config_inputs_shapes_and_shards():
     w = bench.planar_inputs("cfg2_planar", 0, 1)
     assert w["n_e"] == 128 and w["n_f"] == 128 * 128 and len(w["c"]) == len(w["z_if"]) + 1 == 2

@@ -115,8 +115,8 @@ def _run_bench_two_ranks(extra_args):
 
 def test_bench_default_multi_gpu_line_strong_scaled_with_reassembly():
     """The N > 1 control flow of bench.py: BASELINE configs[3] strong-scaled (tx rows / N), collective-free timed region,
-    the reassembly all-gather timed on its own and folded into value_with_reassembly, configs[4] under extra."""
-    d = _run_bench_two_ranks([])
+    the reassembly all-gather timed on its own and folded into value_with_reassembly, configs[4] under extra (--full)."""
+    d = _run_bench_two_ranks(["--full"])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["dtype"] == "f32" and d["steps"] == 4
     assert "configs[3]" in d["config"]["workload"] and d["config"]["solves_per_step_all_gpus"] == 2 * d["config"]["solves_per_step_per_gpu"]
     assert d["value"] > 0 and d["reassembly"]["ms"] > 0
