@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 109 /* 0.1.8: rtus_leg_amp_surface*, rtus_tfm_weighted* (ray amplitudes, sensitivity-normalised views) */
+#define RTUS_VERSION 110 /* 0.1.9: rtus_tt_pipe* (lens to pipe-wall travel times) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -794,6 +794,53 @@ int rtus_tfm_weighted_dev(const float *d_a, int n_tx, int n_rx, int n_t, double 
 int rtus_tfm_weighted(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
                       const double *tt_tx, const double *tt_rx, const float *w_tx, const float *w_rx, int n_f,
                       float *image, float *sens, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Element x focal-point travel times from elements behind the curved lens INTO THE PIPE WALL: two curved refractions, the lens
+ * surface and then the pipe's outer circle.  NOT IN THE REFERENCE (it defines the wall speed c3 = 5600 and never uses it); checked
+ * against tests/pipe_numpy.py, itself checked against a 40-digit joint solve in (alpha, beta) (tests/test_pipe_cpu.py).
+ *
+ * Geometry is the reference's (z up, elements in the lens at ze, normally d): lens surface P(alpha) = h(alpha)(sin alpha, cos alpha)
+ * (rtus_tt_lens's), pipe centre Cp = (x_off, 0), outer surface Q(beta) = (x_off + r_outer sin beta, r_outer cos beta) (the angle of
+ * main_rt.py:250-252).  The wall is r_inner < |F - Cp| < r_outer, 0 <= r_inner < r_outer (0: a solid bar).
+ *     T(beta)      = T_lens(E, Q(beta)) + |Q(beta) - F| / c3
+ *     T_lens(E, Q) = rtus_tt_lens's entry for the target Q: the least time over alpha in [alpha_lo, alpha_hi], pinned ends included
+ *     tt[e][f]     = the least T over the interior local minima of T on (beta_lo, beta_hi) whose path qualifies:
+ *       1. the water segment L(alpha*) -> Q arrives from outside the circle, (Q - L) . (Q - Cp) < 0;
+ *       2. the wall segment Q -> F keeps a distance of at least r_inner from Cp (it does not cross the bore).
+ * NaN for an F outside the wall, without a qualifying interior minimum (total reflection past the critical angle included), and for
+ * the rows of elements with a non-finite position.  alpha_out, beta_out [n_e][n_f] (nullable): the lens refraction point's and the
+ * pipe entry point's angles.
+ * Guarantee: beta_lo .. beta_hi is scanned at n_scan equally spaced points; every interior local minimum whose neighbouring
+ * stationary points of T(beta) lie at least one scan step away is found.  A missed minimum can only make an entry later (or NaN),
+ * never earlier.
+ * Determinism: an entry depends only on its element, its focal point and the parameters, not on which other elements or points
+ * share the call.
+ * Rejected: a pipe that touches the lens, r_outer >= min over alpha in [alpha_lo, alpha_hi] of |P(alpha) - Cp| (RTUS_ERR_INVALID_ARG,
+ * checked on the host before any HIP call).
+ * Argument checks run before any HIP call: -1 for a null pointer, a non-positive size, a speed that is not finite and positive,
+ * r_inner outside [0, r_outer), non-finite x_off or interval ends, alpha_lo >= alpha_hi, beta_lo >= beta_hi, n_scan < 4 or a pipe
+ * touching the lens; -5 past n_e <= 65535 * 8, n_scan <= 65536, n_e * n_scan <= 2^26.  d_workspace:
+ * rtus_tt_pipe_workspace_bytes(n_e, n_scan) bytes, 256-byte aligned (-4 otherwise; the function returns 0 for sizes it rejects).
+ * The _dev entry allocates nothing and does not synchronise (capturable); the host twin stages through the device's arena.
+ * Method and measured figures on MI355X: DESIGN.md section 4 (pipe wall).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct rtus_pipe {
+    double r_outer; /* outer radius [m]                       main_rt.py:466 */
+    double r_inner; /* bore radius [m], 0 <= r_inner < r_outer (0: a solid bar) */
+    double x_off;   /* x of the pipe's centre [m]             main_rt.py:467 (pipe_offset) */
+    double c3;      /* speed in the wall [m/s]                main_rt.py:451 */
+} rtus_pipe;
+size_t rtus_tt_pipe_workspace_bytes(int n_e, int n_scan);
+int rtus_tt_pipe_dev(const rtus_lens *lens, double alpha_lo, double alpha_hi, const rtus_pipe *pipe,
+                     double beta_lo, double beta_hi, int n_scan,
+                     const double *d_xe, const double *d_ze, int n_e, const double *d_xf, const double *d_zf, int n_f,
+                     double *d_tt, double *d_alpha_out, double *d_beta_out,
+                     void *d_workspace, size_t workspace_bytes, void *stream);
+int rtus_tt_pipe(const rtus_lens *lens, double alpha_lo, double alpha_hi, const rtus_pipe *pipe,
+                 double beta_lo, double beta_hi, int n_scan,
+                 const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
+                 double *tt, double *alpha_out, double *beta_out, int device);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,11 @@ class Lens(C.Structure):
                 ("d", C.c_double)]
 
 
+class Pipe(C.Structure):
+    """rtus_pipe — the pipe of the reference's probe (main_rt.py:451, 466-467) plus its bore."""
+    _fields_ = [("r_outer", C.c_double), ("r_inner", C.c_double), ("x_off", C.c_double), ("c3", C.c_double)]
+
+
 def build(force: bool = False) -> str:
     """Compile librtus.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     args = ["make", "-C", CSRC, "-j4"]
@@ -203,6 +208,16 @@ def lib():
     except AttributeError:                # a build from before version 109, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        PP = C.POINTER(Pipe)
+        L.rtus_tt_pipe_workspace_bytes.argtypes = [ip, ip]
+        L.rtus_tt_pipe_workspace_bytes.restype = C.c_size_t
+        L.rtus_tt_pipe_dev.argtypes = [LP, dd, dd, PP, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, vp, C.c_size_t, vp]
+        L.rtus_tt_pipe.argtypes = [LP, dd, dd, PP, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, ip]
+        L.rtus_tt_pipe_dev.restype = L.rtus_tt_pipe.restype = ip
+    except AttributeError:                # a build from before version 110, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -231,4 +246,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tfm_analytic_dev", "rtus_tfm_analytic",
            "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx",
            "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip",
-           "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted")
+           "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted",
+           "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe")

@@ -16,7 +16,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib
-from ._lib import Lens
+from ._lib import Lens, Pipe
 
 KEYS = ("lens_1_x", "lens_1_z", "pipe_x", "pipe_z", "lens_2_x", "lens_2_z", "target_x", "target_z")
 
@@ -958,3 +958,54 @@ def tfm_weighted(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, *, t0=0.0, se
                                       _ptr(w_tx), _ptr(w_rx), n_f, _ptr(img), _ptr(sens), int(device))
     _lib.check(st, "rtus_tfm_weighted")
     return (img, sens) if sensitivity else img
+
+
+PIPE_SCAN_ARC = 0.25e-3     # default spacing of travel_time_pipe's scan points along the pipe's outer surface [m]
+
+
+def _pipe_args(params, c3, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan):
+    p = _resolve(params)
+    a_lo = -ALPHA_MAX if alpha_lo is None else float(alpha_lo)
+    a_hi = ALPHA_MAX if alpha_hi is None else float(alpha_hi)
+    b_lo, b_hi = float(beta_lo), float(beta_hi)
+    if n_scan is None:
+        n_scan = int(np.ceil(float(p.r_outer) * (b_hi - b_lo) / PIPE_SCAN_ARC)) + 1 if b_hi > b_lo else 4
+        n_scan = max(n_scan, 4)
+    pipe = Pipe(float(p.r_outer), float(r_inner), float(p.pipe_offset), float(c3))
+    return p.lens(), a_lo, a_hi, pipe, b_lo, b_hi, int(n_scan)
+
+
+def travel_time_pipe(xe, ze, xf, zf, *, c3=5600.0, r_inner=0.0, params: Params = None, alpha_lo=None, alpha_hi=None,
+                     beta_lo=-np.pi / 2, beta_hi=np.pi / 2, n_scan=None, return_path=False, out=None, device=0):
+    """Element x focal-point Fermat travel times from elements behind the curved lens (c1), through the water (c2), into the
+    WALL of the pipe (c3) -> tt[n_e, n_f]: two curved refractions, the lens surface and the pipe's outer circle.  The pipe is the
+    reference's: radius ``params.r_outer``, centre (``params.pipe_offset``, 0) (main_rt.py:466-467); ``r_inner`` is the bore (0: a
+    solid bar).  An entry is the least time over the interior local minima of T(beta), beta the angle of the pipe entry point on
+    [``beta_lo``, ``beta_hi``], scanned at ``n_scan`` points (default: at most 0.25 mm of arc apart); NaN for a point outside the
+    wall or without a qualifying path.  ``return_path``: -> (tt, alpha, beta), the lens refraction point's and the pipe entry
+    point's angles.  Definition, rules and guarantee: include/rtus.h (rtus_tt_pipe).  Not in the reference."""
+    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _pipe_args(params, c3, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    tt = _out(out, (xe.size, xf.size), np.float64)
+    al = np.empty((xe.size, xf.size), dtype=np.float64) if return_path else None
+    be = np.empty((xe.size, xf.size), dtype=np.float64) if return_path else None
+    st = _lib.lib().rtus_tt_pipe(C.byref(lens), a_lo, a_hi, C.byref(pipe), b_lo, b_hi, n_scan, _ptr(xe), _ptr(ze), xe.size, _ptr(xf),
+                                 _ptr(zf), xf.size, _ptr(tt), _ptr(al), _ptr(be), int(device))
+    _lib.check(st, "rtus_tt_pipe")
+    return (tt, al, be) if return_path else tt
+
+
+def pipe_wall_grid(r_inner, r_outer, n_r, n_theta, theta_lo, theta_hi, *, params: Params = None):
+    """Focal points over the pipe wall in polar coordinates about the pipe's centre (``params.pipe_offset``, 0): ``n_r`` radii
+    evenly over [r_inner, r_outer] and ``n_theta`` angles over [theta_lo, theta_hi] (radians from +z, travel_time_pipe's beta
+    convention) -> (xf, zf), radius-major, so that ``tfm_image(...).reshape(n_r, n_theta)`` is the unrolled wall image (row 0 at
+    r_inner).  Pass radii strictly inside the wall to keep the edge rows out of NaN: the wall is open, r_inner < r < r_outer."""
+    p = _resolve(params)
+    if int(n_r) < 1 or int(n_theta) < 1:
+        raise ValueError("n_r and n_theta must be positive")
+    r = np.linspace(float(r_inner), float(r_outer), int(n_r))
+    th = np.linspace(float(theta_lo), float(theta_hi), int(n_theta))
+    rr, tt = np.meshgrid(r, th, indexing="ij")
+    return (float(p.pipe_offset) + rr * np.sin(tt)).ravel(), (rr * np.cos(tt)).ravel()

@@ -82,6 +82,10 @@ hipError_t rtus_launch_pw_layers(const double* z_if, const double* c, int n_if, 
 hipError_t rtus_launch_pw_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* ang, int n_a,
                                   double xlo, double xhi, double za, const double* xf, const double* zf, int n_f, double* tt, double* xent,
                                   void* ws, hipStream_t s);
+hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double b_lo, double b_hi, int n_scan,
+                               const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                               double* alpha_out, double* beta_out, void* ws, hipStream_t s);
+size_t rtus_pipe_ws_bytes(int n_e, int m);
 hipError_t rtus_launch_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, const double* d, int n_v, float* out,
                                     hipStream_t s);
 
@@ -1697,3 +1701,101 @@ int rtus_tt_lens_f32_multi_dev(const rtus_lens* lens, double alpha_lo, double al
 }
 
 }   // extern "C"
+
+// ---------------------------------------------------------------------------- lens -> pipe wall
+// The least distance from the pipe's centre to the lens surface over [a_lo, a_hi] (h(alpha): main_rt.py:180-189, root [1]):
+// 4097 even samples, then golden-section search on the cells either side of the least one.  Samples where the lens is not
+// defined (NaN) do not count.
+static double lens_clearance(const rtus_lens& L, double a_lo, double a_hi, double x_off)
+{
+    const double T = L.l0 / L.c1 + L.h0 / L.c2, c1sq = L.c1 * L.c1;
+    const double A = c1sq / (L.c2 * L.c2) - 1.0, C = c1sq * (T * T) - L.d * L.d;
+    auto dist = [&](double al) {
+        const double B = 2.0 * L.d * cos(al) - 2.0 * T * c1sq / L.c2;
+        const double h = (-B - sqrt(B * B - 4.0 * A * C)) / (2.0 * A);
+        const double px = h * sin(al) - x_off, pz = h * cos(al);
+        return sqrt(px * px + pz * pz);
+    };
+    const int N = 4096;
+    int jb = -1;
+    double best = INFINITY;
+    for (int j = 0; j <= N; ++j) {
+        const double v = dist(j == N ? a_hi : a_lo + (a_hi - a_lo) * j / N);
+        if (v < best) { best = v; jb = j; }
+    }
+    if (jb < 0) return NAN;
+    double lo = a_lo + (a_hi - a_lo) * (jb > 0 ? jb - 1 : 0) / N, hi = a_lo + (a_hi - a_lo) * (jb < N ? jb + 1 : N) / N;
+    const double g = 0.5 * (sqrt(5.0) - 1.0);
+    for (int it = 0; it < 80; ++it) {
+        const double x1 = hi - g * (hi - lo), x2 = lo + g * (hi - lo);
+        const double d1 = dist(x1), d2 = dist(x2);
+        best = fmin(best, fmin(d1, d2));
+        if (d1 < d2) hi = x2; else lo = x1;
+    }
+    return best;
+}
+
+#define RTUS_PIPE_MAX_SCAN 65536
+static int check_pipe(const rtus_lens* lens, double a_lo, double a_hi, const rtus_pipe* pipe, double b_lo, double b_hi, int n_scan,
+                      const void* xe, const void* ze, int n_e, const void* xf, const void* zf, int n_f, const void* tt)
+{
+    const int st = check_lens(lens, a_lo, a_hi, xe, ze, n_e > 0 ? 1 : n_e, xf, zf, n_f, tt);   // (the pipe's own limit on n_e is below)
+    if (st) return st;
+    if (!pipe || !isfinite(lens->c1) || !isfinite(lens->c2)) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(pipe->c3) || !(pipe->c3 > 0) || !isfinite(pipe->r_outer) || !(pipe->r_outer > 0) || !isfinite(pipe->x_off))
+        return RTUS_ERR_INVALID_ARG;
+    if (!(pipe->r_inner >= 0) || !(pipe->r_inner < pipe->r_outer)) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(b_lo) || !isfinite(b_hi) || !(b_hi > b_lo) || n_scan < 4) return RTUS_ERR_INVALID_ARG;
+    if (n_e > 65535 * 8 || n_scan > RTUS_PIPE_MAX_SCAN || (long long)n_e * n_scan > (1LL << 26)) return RTUS_ERR_UNSUPPORTED;
+    if (!(pipe->r_outer < lens_clearance(*lens, a_lo, a_hi, pipe->x_off))) return RTUS_ERR_INVALID_ARG;   // touches the lens
+    return RTUS_OK;
+}
+
+extern "C" size_t rtus_tt_pipe_workspace_bytes(int n_e, int n_scan)
+{
+    if (n_e <= 0 || n_scan < 4 || n_e > 65535 * 8 || n_scan > RTUS_PIPE_MAX_SCAN || (long long)n_e * n_scan > (1LL << 26)) return 0;
+    return rtus_pipe_ws_bytes(n_e, n_scan);
+}
+
+extern "C" int rtus_tt_pipe_dev(const rtus_lens* lens, double alpha_lo, double alpha_hi, const rtus_pipe* pipe, double beta_lo,
+                                double beta_hi, int n_scan, const double* d_xe, const double* d_ze, int n_e, const double* d_xf,
+                                const double* d_zf, int n_f, double* d_tt, double* d_alpha_out, double* d_beta_out, void* d_workspace,
+                                size_t workspace_bytes, void* stream)
+{
+    int st = check_pipe(lens, alpha_lo, alpha_hi, pipe, beta_lo, beta_hi, n_scan, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_pipe_ws_bytes(n_e, n_scan)) return RTUS_ERR_WORKSPACE;
+    LAUNCH_TRY(rtus_launch_tt_pipe(*lens, alpha_lo, alpha_hi, *pipe, beta_lo, beta_hi, n_scan, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt,
+                                   d_alpha_out, d_beta_out, d_workspace, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+extern "C" int rtus_tt_pipe(const rtus_lens* lens, double alpha_lo, double alpha_hi, const rtus_pipe* pipe, double beta_lo,
+                            double beta_hi, int n_scan, const double* xe, const double* ze, int n_e, const double* xf, const double* zf,
+                            int n_f, double* tt, double* alpha_out, double* beta_out, int device)
+{
+    int st = check_pipe(lens, alpha_lo, alpha_hi, pipe, beta_lo, beta_hi, n_scan, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_e * n_f, wsb = rtus_pipe_ws_bytes(n_e, n_scan);
+    Session S;
+    if ((st = S.open(device, 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) +
+                                 (1 + (alpha_out ? 1 : 0) + (beta_out ? 1 : 0)) * al256(8 * tot) + al256(wsb))))
+        return st;
+    double *dxe, *dze, *dxf, *dzf;
+    S.upload(dxe, xe, n_e);
+    S.upload(dze, ze, n_e);
+    S.upload(dxf, xf, n_f);
+    S.upload(dzf, zf, n_f);
+    double* dtt = S.take<double>(tot);
+    double* dal = alpha_out ? S.take<double>(tot) : nullptr;
+    double* dbe = beta_out ? S.take<double>(tot) : nullptr;
+    void* ws = S.take<char>(wsb);
+    HIP_TRY(S.flush());
+    LAUNCH_TRY(rtus_launch_tt_pipe(*lens, alpha_lo, alpha_hi, *pipe, beta_lo, beta_hi, n_scan, dxe, dze, n_e, dxf, dzf, n_f, dtt, dal, dbe,
+                                   ws, S.a->stream));
+    S.download(tt, dtt, tot);
+    S.download(alpha_out, dal, tot);
+    S.download(beta_out, dbe, tot);
+    HIP_TRY(S.finish());
+    return RTUS_OK;
+}

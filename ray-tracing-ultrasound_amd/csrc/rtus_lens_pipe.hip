@@ -1,0 +1,379 @@
+// rtus_lens_pipe.hip — element x focal-point Fermat travel times from the elements behind the reference's curved lens, through
+// the water, into the WALL of the pipe: two curved refractions (the lens surface P(alpha), then the pipe's outer circle Q(beta)).
+// NOT IN THE REFERENCE (it defines the wall speed c3 = 5600 and never uses it); checked against tests/pipe_numpy.py, itself checked
+// against a 40-digit joint solve in (alpha, beta) (tests/test_pipe_cpu.py).
+//
+//   T(beta)       = T_lens(E, Q(beta)) + |Q(beta) - F| / c3,   Q(beta) = (x_off + r_outer sin beta, r_outer cos beta)
+//   T_lens(E, Q)  = the least time over alpha in [a_lo, a_hi] of the lens leg (rtus_tt_lens's entry for the target Q)
+//   entry         = the least T over the interior local minima of T on (b_lo, b_hi) whose path qualifies (include/rtus.h)
+//
+//   1. rtus_pipe_setup_kernel: one lane per (element, scan point beta_j = b_lo + j hb): the lens leg to Q_j solved on its own —
+//      rtus_tt_lens's generic step (T, g at PIPE_NS + 1 even samples of alpha, the zero of g in every cell that brackets a
+//      minimum by safeguarded Newton, least T wins, the ends included), never a continuation from a neighbouring lane: the bits
+//      depend on (element, beta_j) alone.  Into the workspace: alpha*, the fp32 time and -(c3 / c2) u . Q' (u the unit water
+//      direction at Q_j: c2 dT_lens / dbeta by the envelope theorem); the scan points (Q_j - Cp, Q'_j) as fp32.
+//   2. rtus_pipe_kernel: rtus_surface_kernel's scan.  Lanes are focal points, a workgroup owns PIPE_EB elements, scan points are
+//      tiled through LDS with the element terms as broadcasts; the lane's term v . Q' (v = (Q - F) / |Q - F|) is shared by the
+//      workgroup's elements.  A sign change - -> + of dT/dbeta is a bracket, ranked by an fp32 estimate of T; PIPE_K are kept.
+//   3. Each kept bracket is refined in fp64: safeguarded Newton in beta (bisection when a step leaves the bracket or T'' <= 0).
+//      Every iterate solves the inner alpha to convergence (lens_time<double, true>), warm-started from the table's alpha at the
+//      bracket's end and then from the previous iterate; a suspect inner minimum (g' < gp_min or pinned at an end: rtus_tt_lens's
+//      own test) takes the whole interval's least time instead (the set-up kernel's step).  T'' by implicit differentiation:
+//      T_lens'' = [(|Q'|^2 - (u.Q')^2) / l + u.Q''] / c2 - (g_aQ . Q')^2 / g' (the last term only at an interior inner minimum).
+//      The refined path qualifies when its water segment arrives from outside the circle and its wall segment keeps off the bore.
+//
+// Determinism: an entry is made from its element, its focal point and the parameters only (the table entries it reads are
+// functions of (element, beta_j)); not of its slot, its lane or whatever else shares the call.
+#include "rtus_lens.h"
+
+#define PIPE_EB 8           // elements per workgroup
+#define PIPE_TILE 64        // scan points per LDS tile
+#define PIPE_K 3            // brackets kept per (element, focal point)
+#define PIPE_NS 32          // even samples of alpha in a whole-interval solve of the lens leg
+
+struct PipeArgs {
+    LensConst<double> k;               // lens constants (lens_time's)
+    double a_lo, a_hi, gp_min;         // alpha interval; g' below gp_min: the inner minimum is suspect
+    double r_out, r_in, x_off, ic3;    // the pipe; 1 / c3
+    double b_lo, hb;                   // scan points beta_j = b_lo + j hb, j < m
+    float k32f, ic3f;                  // c3 / c2, 1 / c3
+    int m, n_e, n_f;
+    const double* __restrict__ xe;
+    const double* __restrict__ ze;
+    const double* __restrict__ xf;
+    const double* __restrict__ zf;
+    double* __restrict__ tt;
+    double* __restrict__ alpha_out;    // nullable
+    double* __restrict__ beta_out;     // nullable
+    float4* __restrict__ pts;          // [m]: (Q - Cp, Q') fp32
+    float2* __restrict__ ent;          // [n_e][m]: (-(c3 / c2) u . Q', T_lens) fp32
+    double* __restrict__ al;           // [n_e][m]: alpha* fp64
+};
+
+// workspace: pts [m] | ent [n_e][m] | al [n_e][m], 256-byte aligned pieces
+static inline size_t al256p(size_t b) { return (b + 255) & ~(size_t)255; }
+size_t rtus_pipe_ws_bytes(int n_e, int m)
+{
+    const size_t nm = (size_t)n_e * (size_t)m;
+    return al256p(16 * (size_t)m) + al256p(8 * nm) + al256p(8 * nm);
+}
+
+// the lens point and its tangent at alpha (lens_time's formulas)
+template <bool POLY>
+__device__ __forceinline__ void lens_point(const LensConst<double>& k, double alpha, double& px, double& pz, double& p1x, double& p1z)
+{
+    double s, c;
+    if (POLY) sincos_poly<double>(alpha, s, c);
+    else sincos_r<double>(alpha, &s, &c);
+    const double B = k.phi_3 * c - k.twoTc, B1 = -k.phi_3 * s;
+    const double disc = B * B - k.C4A;
+    const double rS = rsqrt_r<double>(disc), S = disc * rS;
+    const double h = -(B + S) * k.inv2A, h1 = -B1 * (1.0 + B * rS) * k.inv2A;
+    px = h * s; pz = h * c;
+    p1x = h1 * s + pz; p1z = h1 * c - px;
+}
+
+// The lens leg's least time over the whole interval (rtus_tt_lens's generic step, per lane): T and g at PIPE_NS + 1 even samples
+// (any sample bounds the least time from above: a minimum pinned at an end comes in here), and in every cell whose ends say "a
+// minimum inside" (g < 0 left, g >= 0 right) the zero of g by safeguarded Newton.  Returns alpha; T is its time.
+template <bool POLY>
+__device__ double lens_leg_min(const LensConst<double>& k, double a_lo, double a_hi, double xa, double za, double qx, double qz, double& T)
+{
+    const double dA = (a_hi - a_lo) * (1.0 / PIPE_NS);
+    double bA = a_lo, bT, pg, gp;
+    lens_time<double, false, POLY>(k, a_lo, xa, za, qx, qz, bT, pg, gp);
+    double pa = a_lo;
+    for (int j = 1; j <= PIPE_NS; ++j) {
+        const double ca = j == PIPE_NS ? a_hi : fma((double)j, dA, a_lo);
+        double cT, cg;
+        lens_time<double, false, POLY>(k, ca, xa, za, qx, qz, cT, cg, gp);
+        if (cT < bT) { bT = cT; bA = ca; }
+        if (pg < 0.0 && cg >= 0.0) {
+            // (only the converged point competes: near the focus T is flat enough in alpha for an iterate 1e-8 rad off to be
+            // "earlier" by rounding, and dT/dbeta at the wrong alpha is off by far more than the time is)
+            double lo = pa, hi = ca, x = 0.5 * (pa + ca);
+            for (int it = 0; it < 60; ++it) {
+                double t, g;
+                lens_time<double, true, POLY>(k, x, xa, za, qx, qz, t, g, gp);
+                if (g < 0.0) lo = x; else hi = x;
+                const double step = -g / gp;
+                double xn = x + step;
+                const bool done = (gp > 0.0 && fabs(step) <= 1e-13) || !(hi - lo > 1e-13);
+                if (!(gp > 0.0) || !(xn > lo && xn < hi)) xn = done ? x : 0.5 * (lo + hi);
+                x = xn;
+                if (done) break;
+            }
+            double t, g;
+            lens_time<double, false, POLY>(k, x, xa, za, qx, qz, t, g, gp);
+            if (t < bT) { bT = t; bA = x; }
+        }
+        pa = ca; pg = cg;
+    }
+    T = bT;
+    return bA;
+}
+
+__device__ __forceinline__ void pipe_q(const PipeArgs& a, double beta, double& qx, double& qz, double& q1x, double& q1z)
+{
+    double s, c;
+    sincos(beta, &s, &c);
+    qx = fma(a.r_out, s, a.x_off); qz = a.r_out * c;
+    q1x = a.r_out * c; q1z = -a.r_out * s;
+}
+
+template <bool POLY>
+__global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_setup_kernel(PipeArgs a)
+{
+    const long long t = (long long)blockIdx.x * RTUS_BLOCK + threadIdx.x;
+    if (t >= (long long)a.n_e * a.m) return;
+    const int e = (int)(t / a.m), j = (int)(t - (long long)e * a.m);
+    const double beta = fma((double)j, a.hb, a.b_lo);
+    double qx, qz, q1x, q1z;
+    pipe_q(a, beta, qx, qz, q1x, q1z);
+    if (e == 0) a.pts[j] = make_float4((float)(qx - a.x_off), (float)qz, (float)q1x, (float)q1z);
+    const double xa = a.xe[e], za = a.ze[e];
+    double T = NAN, alpha = NAN;
+    float ng = NAN;
+    if (isfinite(xa) && isfinite(za)) {
+        alpha = lens_leg_min<POLY>(a.k, a.a_lo, a.a_hi, xa, za, qx, qz, T);
+        double px, pz, p1x, p1z;
+        lens_point<POLY>(a.k, alpha, px, pz, p1x, p1z);
+        const double ux = qx - px, uz = qz - pz, r = 1.0 / sqrt(fma(ux, ux, uz * uz));
+        ng = (float)(-(double)a.k32f * (fma(ux, q1x, uz * q1z) * r));
+    }
+    a.ent[t] = make_float2(ng, (float)T);
+    a.al[t] = alpha;
+}
+
+// T(beta) and its first two derivatives for one (element, focal point), with the path's lens point and the inner alpha
+struct PipeT { double t, d1, d2, alpha, px, pz, qx, qz; };
+
+template <bool POLY>
+__device__ PipeT pipe_T(const PipeArgs& a, double xa, double za, double xf, double zf, double beta, double& aw)
+{
+    const LensConst<double>& k = a.k;
+    double qx, qz, q1x, q1z;
+    pipe_q(a, beta, qx, qz, q1x, q1z);
+    // inner: safeguarded Newton on g = dT_lens / dalpha from the warm start, bracket kept by the sign of g
+    double alpha = fmin(fmax(aw, a.a_lo), a.a_hi), lo = a.a_lo, hi = a.a_hi, T = NAN, g = NAN, gp = NAN;
+    for (int it = 0; it < 80; ++it) {
+        lens_time<double, true, POLY>(k, alpha, xa, za, qx, qz, T, g, gp);
+        if (g > 0.0) hi = alpha; else lo = alpha;
+        const double step = -g / gp;
+        double next = alpha + step;
+        const bool done = (gp > 0.0 && fabs(step) <= 1e-13) || !(hi - lo > 1e-13);
+        if (!(gp > 0.0) || !(next >= lo && next <= hi)) next = done ? alpha : 0.5 * (lo + hi);
+        alpha = next;
+        if (done) break;
+    }
+    lens_time<double, true, POLY>(k, alpha, xa, za, qx, qz, T, g, gp);
+    // a minimum beyond an end: the bisections stop within 1e-13 of it, the least time is AT the end (and suspect: below)
+    if (g < 0.0 && a.a_hi - alpha <= 2e-13) alpha = a.a_hi;
+    if (g > 0.0 && alpha - a.a_lo <= 2e-13) alpha = a.a_lo;
+    bool interior = gp > 0.0 && alpha > a.a_lo && alpha < a.a_hi;
+    if (!(interior && gp >= a.gp_min)) {                     // suspect: the whole interval's least time
+        double Tm;
+        const double am = lens_leg_min<POLY>(k, a.a_lo, a.a_hi, xa, za, qx, qz, Tm);
+        if (am != alpha) {
+            alpha = am;
+            lens_time<double, true, POLY>(k, alpha, xa, za, qx, qz, T, g, gp);
+        }
+        interior = gp > 0.0 && alpha > a.a_lo && alpha < a.a_hi;
+    }
+    aw = alpha;
+    double px, pz, p1x, p1z;
+    lens_point<POLY>(k, alpha, px, pz, p1x, p1z);
+    const double inv_c2 = k.c2inv;
+    // lens leg: dT/dQ = u / c2 (envelope theorem)
+    const double ux0 = qx - px, uz0 = qz - pz, l = sqrt(fma(ux0, ux0, uz0 * uz0)), il = 1.0 / l;
+    const double ux = ux0 * il, uz = uz0 * il;
+    const double q2x = -(qx - a.x_off), q2z = -qz;                     // Q''
+    const double QQ = fma(q1x, q1x, q1z * q1z), uQ = fma(ux, q1x, uz * q1z), uP = fma(ux, p1x, uz * p1z);
+    const double gaq = -(fma(p1x, q1x, p1z * q1z) - uP * uQ) * il * inv_c2;     // d g / dQ . Q'
+    double d2l = (fma(-uQ, uQ, QQ) * il + fma(ux, q2x, uz * q2z)) * inv_c2;
+    if (interior) d2l -= gaq * gaq / gp;
+    // wall leg
+    const double vx0 = qx - xf, vz0 = qz - zf, mq = sqrt(fma(vx0, vx0, vz0 * vz0)), im = 1.0 / mq;
+    const double vx = vx0 * im, vz = vz0 * im, vQ = fma(vx, q1x, vz * q1z);
+    PipeT o;
+    o.t = fma(mq, a.ic3, T);
+    o.d1 = fma(uQ, inv_c2, vQ * a.ic3);
+    o.d2 = d2l + (fma(-vQ, vQ, QQ) * im + fma(vx, q2x, vz * q2z)) * a.ic3;
+    o.alpha = alpha; o.px = px; o.pz = pz; o.qx = qx; o.qz = qz;
+    return o;
+}
+
+// insert (t, j) into the sorted triple (t0 <= t1 <= t2)
+#define PIPE_KEEP(t, j, T, J)                                                                               \
+    do {                                                                                                    \
+        const bool c0_ = (t) < T[0], c1_ = (t) < T[1], c2_ = (t) < T[2];                                    \
+        T[2] = c1_ ? T[1] : (c2_ ? (t) : T[2]);  J[2] = c1_ ? J[1] : (c2_ ? (j) : J[2]);                    \
+        T[1] = c0_ ? T[0] : (c1_ ? (t) : T[1]);  J[1] = c0_ ? J[0] : (c1_ ? (j) : J[1]);                    \
+        T[0] = c0_ ? (t) : T[0];                 J[0] = c0_ ? (j) : J[0];                                   \
+    } while (0)
+
+template <bool POLY>
+__global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
+{
+    __shared__ float4 sp[PIPE_TILE];                         // the tile's scan points (Q - Cp, Q')
+    __shared__ float2 sen[PIPE_TILE][PIPE_EB];               // per (point, element): -(c3 / c2) u . Q', T_lens
+    const int tid = threadIdx.x;
+    const int f = blockIdx.x * RTUS_BLOCK + tid;
+    const int e0 = blockIdx.y * PIPE_EB;
+    // the focal point: strictly inside the wall, else no path (NaN coordinates fail every test of the scan)
+    double xf = 0.0, zf = 0.0;
+    bool fok = false;
+    if (f < a.n_f) {
+        xf = a.xf[f];
+        zf = a.zf[f];
+        const double dx = xf - a.x_off, rf = sqrt(fma(dx, dx, zf * zf));
+        fok = rf > a.r_in && rf < a.r_out;
+    }
+    const float xfr = fok ? (float)(xf - a.x_off) : NAN, zfr = fok ? (float)zf : NAN;
+
+    float bt[PIPE_EB][PIPE_K];
+    int bj[PIPE_EB][PIPE_K];
+    bool neg[PIPE_EB];
+#pragma unroll
+    for (int e = 0; e < PIPE_EB; ++e) {
+        neg[e] = false;
+#pragma unroll
+        for (int k = 0; k < PIPE_K; ++k) { bt[e][k] = INFINITY; bj[e][k] = -1; }
+    }
+    for (int base = 0; base < a.m; base += PIPE_TILE) {
+        const int n = a.m - base < PIPE_TILE ? a.m - base : PIPE_TILE;
+        __syncthreads();
+        for (int i = tid; i < PIPE_TILE * PIPE_EB; i += RTUS_BLOCK) {
+            const int j = i / PIPE_EB, e = i % PIPE_EB;
+            const int row = e0 + e < a.n_e ? e0 + e : a.n_e - 1;
+            sen[j][e] = j < n ? a.ent[(size_t)row * a.m + base + j] : make_float2(NAN, NAN);
+            if (e == 0) sp[j] = j < n ? a.pts[base + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        __syncthreads();
+        for (int jj = 0; jj < n; ++jj) {
+            const float4 P = sp[jj];
+            const float vx = P.x - xfr, vz = P.y - zfr;
+            const float q = fmaf(vz, vz, vx * vx);
+            const float r = __builtin_amdgcn_rsqf(q);
+            const float g = fmaf(vz, P.w, vx * P.z) * r;          // c3 dT_wall / dbeta
+            const float tw = q * r * a.ic3f;
+            const int j = base + jj;
+#pragma unroll
+            for (int e = 0; e < PIPE_EB; ++e) {
+                const float2 s = sen[jj][e];
+                const bool pos = g > s.x;                          // dT / dbeta > 0 (NaN: never)
+                if (pos && neg[e]) {                               // - -> + between beta_j-1 and beta_j: a minimum
+                    const float t = s.y + tw;
+                    PIPE_KEEP(t, j - 1, bt[e], bj[e]);
+                }
+                neg[e] = !pos && s.x == s.x;                       // (an element without a lens leg: neither side of a bracket)
+            }
+        }
+    }
+    if (f >= a.n_f) return;
+    const double rin2 = a.r_in * a.r_in;
+#pragma unroll 1
+    for (int e = 0; e < PIPE_EB; ++e) {
+        const int row = e0 + e;
+        if (row >= a.n_e) break;
+        const size_t o = (size_t)row * a.n_f + f;
+        const double xa = a.xe[row], za = a.ze[row];
+        const double* alr = a.al + (size_t)row * a.m;
+        // this element's brackets by selects over constant indices (an index by the loop's e would put the arrays in scratch)
+        float et[PIPE_K];
+        int ej[PIPE_K];
+#pragma unroll
+        for (int kk = 0; kk < PIPE_K; ++kk) {
+            et[kk] = bt[0][kk]; ej[kk] = bj[0][kk];
+#pragma unroll
+            for (int q = 1; q < PIPE_EB; ++q) { et[kk] = q == e ? bt[q][kk] : et[kk]; ej[kk] = q == e ? bj[q][kk] : ej[kk]; }
+        }
+        const float margin = 4e-6f * et[0];
+        double best = NAN, bA = NAN, bB = NAN;
+        for (int kk = 0; kk < PIPE_K; ++kk) {
+            const int j = kk == 0 ? ej[0] : (kk == 1 ? ej[1] : ej[2]);
+            const float tk = kk == 0 ? et[0] : (kk == 1 ? et[1] : et[2]);
+            if (!fok || j < 0 || (kk >= 2 && !(tk <= et[0] + margin))) continue;
+            // the fp32 scan saw dT < 0 at beta_j and > 0 at beta_j+1: the fp64 bracket (beta_j-1 .. beta_j+2 at most)
+            int jl = j, jh = j + 1;
+            double awl = alr[jl], awh = alr[jh];
+            double lo = fma((double)jl, a.hb, a.b_lo), hi = fma((double)jh, a.hb, a.b_lo);
+            const double dlo = pipe_T<POLY>(a, xa, za, xf, zf, lo, awl).d1;
+            const double dhi = pipe_T<POLY>(a, xa, za, xf, zf, hi, awh).d1;
+            if (!(dlo < 0.0)) {                                    // the root is left of beta_j
+                if (!(dhi > 0.0) || j == 0) continue;
+                jh = jl; jl = j - 1;
+                awh = awl; awl = alr[jl];
+                hi = lo; lo = fma((double)jl, a.hb, a.b_lo);
+                if (!(pipe_T<POLY>(a, xa, za, xf, zf, lo, awl).d1 < 0.0)) continue;
+            } else if (!(dhi > 0.0)) {                             // ... or right of beta_j+1
+                if (j + 2 >= a.m) continue;
+                jl = jh; jh = j + 2;
+                awl = awh; awh = alr[jh];
+                lo = hi; hi = fma((double)jh, a.hb, a.b_lo);
+                if (!(pipe_T<POLY>(a, xa, za, xf, zf, hi, awh).d1 > 0.0)) continue;
+            }
+            // safeguarded Newton on dT / dbeta = 0 inside [lo, hi]; the inner alpha starts from the bracket's left end
+            double x = 0.5 * (lo + hi), aw = alr[jl];
+            const double tol = 1e-12;
+            PipeT v = pipe_T<POLY>(a, xa, za, xf, zf, x, aw);
+            for (int it = 0; it < 100; ++it) {
+                if (v.d1 == 0.0) break;
+                if (v.d1 < 0.0) lo = x; else hi = x;
+                const double step = -v.d1 / v.d2;
+                // converged: the last Newton step is taken even when it rounds onto x
+                const bool done = (v.d2 > 0.0 && fabs(step) <= tol) || !(hi - lo > tol);
+                double xn = x + step;
+                if (!(v.d2 > 0.0) || !(xn >= lo && xn <= hi)) xn = done ? x : 0.5 * (lo + hi);
+                x = xn;
+                v = pipe_T<POLY>(a, xa, za, xf, zf, x, aw);
+                if (done) break;
+            }
+            // rule 1: the water segment L -> Q arrives from outside the circle; rule 2: the wall segment Q -> F keeps off the bore
+            const double cx = v.qx - a.x_off, cz = v.qz;
+            const bool outside = fma(v.qx - v.px, cx, (v.qz - v.pz) * cz) < 0.0;
+            const double sx = xf - v.qx, sz = zf - v.qz, ss = fma(sx, sx, sz * sz);
+            const double tc = fmin(fmax(-fma(cx, sx, cz * sz) / ss, 0.0), 1.0);
+            const double nx = fma(tc, sx, cx), nz = fma(tc, sz, cz);
+            const bool clear = fma(nx, nx, nz * nz) >= rin2;
+            if (!(outside && clear && isfinite(v.t))) continue;
+            if (isnan(best) || v.t < best) { best = v.t; bA = v.alpha; bB = x; }
+        }
+        a.tt[o] = best;
+        if (a.alpha_out) a.alpha_out[o] = bA;
+        if (a.beta_out) a.beta_out[o] = bB;
+    }
+}
+
+hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double b_lo, double b_hi, int n_scan,
+                               const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                               double* alpha_out, double* beta_out, void* ws, hipStream_t s)
+{
+    const LensK kk = make_lens_k(L);
+    PipeArgs a;
+    a.k.c1inv = 1.0 / L.c1; a.k.c2inv = 1.0 / L.c2;
+    a.k.phi_3 = kk.phi_3; a.k.twoTc = kk.twoTc; a.k.C4A = kk.C4A; a.k.inv2A = 1.0 / kk.twoA;
+    a.k.poly_trig = (a_lo >= -1.0 && a_hi <= 1.0) ? 1 : 0;
+    a.a_lo = a_lo; a.a_hi = a_hi;
+    a.gp_min = 0.125 * L.h0 / L.c2;                          // rtus_tt_lens's threshold (rtus_lens_fermat.hip: launch_lens)
+    a.r_out = P.r_outer; a.r_in = P.r_inner; a.x_off = P.x_off; a.ic3 = 1.0 / P.c3;
+    a.b_lo = b_lo; a.hb = (b_hi - b_lo) / (double)(n_scan - 1);
+    a.k32f = (float)(P.c3 / L.c2); a.ic3f = (float)(1.0 / P.c3);
+    a.m = n_scan; a.n_e = n_e; a.n_f = n_f;
+    a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.alpha_out = alpha_out; a.beta_out = beta_out;
+    char* p = (char*)ws;
+    a.pts = (float4*)p; p += al256p(16 * (size_t)n_scan);
+    a.ent = (float2*)p; p += al256p(8 * (size_t)n_e * n_scan);
+    a.al = (double*)p;
+    const long long gs = ((long long)n_e * n_scan + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    const long long gy = ((long long)n_e + PIPE_EB - 1) / PIPE_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    if (gy > 65535 || gx > 0x7fffffffLL || gs > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (a.k.poly_trig) {
+        hipLaunchKernelGGL(rtus_pipe_setup_kernel<true>, dim3((unsigned)gs), dim3(RTUS_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(rtus_pipe_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(rtus_pipe_setup_kernel<false>, dim3((unsigned)gs), dim3(RTUS_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(rtus_pipe_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    }
+    return hipGetLastError();
+}

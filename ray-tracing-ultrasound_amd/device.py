@@ -639,3 +639,33 @@ def tfm_weighted_dev(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, t0=0.0, o
                                           _p(tt_tx), _p(tt_rx), _p(w_tx), _p(w_rx), n_f, _p(out), _p(sens), _stream(analytic))
     _lib.check(st, "rtus_tfm_weighted_dev")
     return out if sens is None else (out, sens)
+
+
+def tt_pipe_dev(xe, ze, xf, zf, out=None, alpha_out=None, beta_out=None, *, c3=5600.0, r_inner=0.0, params: Params = None,
+                alpha_lo=None, alpha_hi=None, beta_lo=-_api.np.pi / 2, beta_hi=_api.np.pi / 2, n_scan=None, ws=None):
+    """Lens-to-pipe-wall times on device (rtus_tt_pipe_dev; api.travel_time_pipe's definition and defaults) on float64 CUDA tensors
+    -> out [n_e, n_f] (and alpha_out / beta_out [n_e, n_f] when tensors are given for them).  ``ws``: an optional uint8 tensor of
+    at least rtus_tt_pipe_workspace_bytes(n_e, n_scan) bytes to reuse (a graph capture must not allocate); allocated here
+    otherwise.  Asynchronous on the current stream."""
+    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _api._pipe_args(params, c3, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
+    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
+        _chk(t, n)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    if out is None:
+        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
+    for t, n in ((out, "out"), (alpha_out, "alpha_out"), (beta_out, "beta_out")):
+        if t is not None:
+            _chk(t, n)
+            if t.numel() != n_e * n_f:
+                raise ValueError(f"{n} must hold n_e * n_f values")
+    need = int(_lib.lib().rtus_tt_pipe_workspace_bytes(n_e, n_scan))
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)     # (the caching allocator's blocks are 512-byte aligned)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+        raise ValueError("ws must be a contiguous CUDA uint8 tensor")
+    st = _lib.lib().rtus_tt_pipe_dev(C.byref(lens), a_lo, a_hi, C.byref(pipe), b_lo, b_hi, n_scan, _p(xe), _p(ze), n_e, _p(xf), _p(zf),
+                                     n_f, _p(out), _p(alpha_out), _p(beta_out), _p(ws), ws.numel(), _stream(xe))
+    _lib.check(st, "rtus_tt_pipe_dev")
+    return out
