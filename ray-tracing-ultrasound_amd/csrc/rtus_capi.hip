@@ -124,7 +124,6 @@ struct Arena {
     bool poly_valid = false;
 };
 Arena g_arena[kMaxDevices][kMaxSlots];
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The twins run on `device` and put the caller's current device back when they return.
 struct DeviceGuard {
@@ -132,21 +131,37 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-struct Session {                       // one host-buffer call on one device
-    struct Xfer { void* host; size_t off, bytes; };
+// One host-buffer call on one device.  open() locks the device's arena; the twin then states each buffer once — in() an
+// input, out() a result, scratch() device-only memory — and flush() lays them out, grows the arena to fit, binds the twin's
+// pointers and copies the inputs; finish() copies every result back.  Nothing is placed before flush(): a declared pointer
+// is nullptr until then (and stays nullptr for a count of 0 or an out() the caller does not want).
+struct Session {
+    enum Kind { kIn, kOut, kScratch };
+    struct Buf { void** bind; void* host; size_t bytes, off; Kind kind; bool pinned; };
+    static constexpr int kMaxBufs = 16;
+    // (direct results: at most kPinBytes / 4 of data plus the alignment of each, inside the download half)
+    static_assert(kPinBytes / 4 + kMaxBufs * 256 <= kPinBytes, "direct results must fit the page-locked buffer");
+    static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
     DeviceGuard guard;                 // (declared first: restored last, after the lock is gone)
     std::unique_lock<std::mutex> lock;
     Arena* a = nullptr;
-    size_t off = 0;
-    Xfer up[8], down[8];
-    int n_up = 0, n_down = 0;
+    Buf buf[kMaxBufs];
+    int n_buf = 0;
+    bool overflow = false;             // more than kMaxBufs declared: flush() refuses the call
+    // Small results written by the kernel STRAIGHT into the page-locked buffer (it is device-visible): no device-to-host copy
+    // command behind the kernel (9 of a 32-us call) — the stores cross PCIe while the kernel runs.  (The same for the inputs —
+    // the kernel reading them from the page-locked buffer instead of one small host-to-device copy — was measured: no gain.)
+    // Opt-in per twin, before flush(); taken when all the results the call asks for are small.
+    bool allow_direct = false;
+    bool direct = false;
 
     int dev_index = -1;
     // the session ends with its stream drained whatever happened in between (an early return after flush() must not leave
     // copies in flight while the next call re-uses the page-locked buffer)
-    bool drained = false;              // finish() came back clean: nothing in flight
+    bool drained = false;              // copy_back() came back clean: nothing in flight
     ~Session() { if (a && a->stream && !drained) (void)hipStreamSynchronize(a->stream); }
-    int open(int device, size_t dev_bytes, int slot = 0)
+    int open(int device, int slot = 0)
     {
         int n = 0;
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return RTUS_ERR_NO_DEVICE;
@@ -160,99 +175,113 @@ struct Session {                       // one host-buffer call on one device
         a = ar;
         if (!a->stream) HIP_TRY(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
         if (!a->pin) HIP_TRY(hipHostMalloc((void**)&a->pin, 2 * kPinBytes, hipHostMallocDefault));
+        return RTUS_OK;
+    }
+    void add(void** bind, void* host, size_t bytes, Kind kind)
+    {
+        *bind = nullptr;
+        if (!bytes || (kind == kOut && !host)) return;
+        if (n_buf == kMaxBufs) { overflow = true; return; }
+        buf[n_buf++] = {bind, host, bytes, 0, kind, false};
+    }
+    template <class T> void in(T*& d, const T* h, size_t count) { add((void**)&d, (void*)h, count * sizeof(T), kIn); }
+    template <class T> void out(T*& d, T* h, size_t count) { add((void**)&d, (void*)h, count * sizeof(T), kOut); }
+    template <class T> void scratch(T*& d, size_t count) { add((void**)&d, nullptr, count * sizeof(T), kScratch); }
+    // The inputs first, in declaration order, next to each other at the start of the arena; then the results and the scratch
+    // in declaration order.  All inputs go in one host-to-device copy through the page-locked buffer when they are small (the
+    // reference's calls are: 15 KB in, 58 KB out), one copy each otherwise.
+    int flush()
+    {
+        if (overflow) return RTUS_ERR_UNSUPPORTED;
+        size_t out_bytes = 0;
+        for (int i = 0; i < n_buf; ++i) out_bytes += buf[i].kind == kOut ? buf[i].bytes : 0;
+        direct = allow_direct && out_bytes + 8 * 256 <= kPinBytes / 4;
+        size_t dev_bytes = 0, pin_bytes = 0, in_end = 0;
+        for (bool inputs : {true, false})
+            for (int i = 0; i < n_buf; ++i) {
+                Buf& b = buf[i];
+                if ((b.kind == kIn) != inputs) continue;
+                b.pinned = direct && b.kind == kOut;
+                size_t& end = b.pinned ? pin_bytes : dev_bytes;
+                b.off = end;
+                end += al256(b.bytes);
+                if (inputs) in_end = b.off + b.bytes;
+            }
         if (a->cap < dev_bytes) {                                    // grow-only; the previous call has synchronised
             if (a->dev) { (void)hipFree(a->dev); a->dev = nullptr; a->cap = 0; }
             const size_t want = (dev_bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
             HIP_TRY(hipMalloc(&a->dev, want));
             a->cap = want;
         }
+        for (int i = 0; i < n_buf; ++i) *buf[i].bind = (buf[i].pinned ? a->pin + kPinBytes : (char*)a->dev) + buf[i].off;
+        const bool packed = in_end <= kPinBytes;
+        for (int i = 0; i < n_buf; ++i) {
+            if (buf[i].kind != kIn) continue;
+            if (packed) memcpy(a->pin + buf[i].off, buf[i].host, buf[i].bytes);
+            else HIP_TRY(hipMemcpyAsync((char*)a->dev + buf[i].off, buf[i].host, buf[i].bytes, hipMemcpyHostToDevice, a->stream));
+        }
+        if (packed && in_end) HIP_TRY(hipMemcpyAsync(a->dev, a->pin, in_end, hipMemcpyHostToDevice, a->stream));
         return RTUS_OK;
     }
-    template <class T> T* take(size_t count)                          // nullptr for count == 0
-    {
-        if (!count) return nullptr;
-        T* p = (T*)((char*)a->dev + off);
-        off += al256(count * sizeof(T));
-        return p;
-    }
-    // inputs: carved first, so they sit next to each other at the start of the arena; copied by flush()
-    template <class T> void upload(T*& d, const T* h, size_t count)
-    {
-        up[n_up++] = {(void*)h, off, count * sizeof(T)};
-        d = take<T>(count);
-    }
-    // all inputs in one host-to-device copy through the page-locked buffer when they are small (the reference's calls
-    // are: 15 KB in, 58 KB out), one copy each otherwise
-    hipError_t flush()
-    {
-        if (!n_up) return hipSuccess;
-        const size_t lo = up[0].off, span = up[n_up - 1].off + up[n_up - 1].bytes - lo;
-        if (span <= kPinBytes) {
-            for (int i = 0; i < n_up; ++i) memcpy(a->pin + (up[i].off - lo), up[i].host, up[i].bytes);
-            return hipMemcpyAsync((char*)a->dev + lo, a->pin, span, hipMemcpyHostToDevice, a->stream);
-        }
-        for (int i = 0; i < n_up; ++i) {
-            hipError_t e = hipMemcpyAsync((char*)a->dev + up[i].off, up[i].host, up[i].bytes, hipMemcpyHostToDevice, a->stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
+    // after flush(): one more result, read back from a buffer declared as something else (a twin that works in place)
     template <class T> void download(T* h, const T* d, size_t count)
     {
-        if (h && !((const char*)d >= a->pin && (const char*)d < a->pin + 2 * kPinBytes))      // (direct outputs are already registered)
-            down[n_down++] = {(void*)h, (size_t)((const char*)d - (const char*)a->dev), count * sizeof(T)};
+        if (!h || !count) return;
+        if (n_buf == kMaxBufs) { overflow = true; return; }
+        buf[n_buf++] = {nullptr, (void*)h, count * sizeof(T), (size_t)((const char*)d - (const char*)a->dev), kOut, false};
     }
-    // Small results written by the kernel STRAIGHT into the page-locked buffer (it is device-visible): no device-to-host copy
-    // command behind the kernel (9 of a 32-us call) — the stores cross PCIe while the kernel runs.  (The same for the inputs —
-    // the kernel reading them from the page-locked buffer instead of one small host-to-device copy — was measured: no gain.)
-    // Use: direct_ok(bytes of all results the call will ask for) once, then take_out() per result instead of take() + download().
-    bool direct = false;
-    size_t direct_off = 0;
-    Xfer direct_down[8];
-    int n_direct = 0;
-    void direct_ok(size_t total_result_bytes) { direct = total_result_bytes + 8 * 256 <= kPinBytes / 4; }
-    template <class T> T* take_out(T* host, size_t count)            // nullptr when the caller does not want this result
+    int finish()
     {
-        if (!host || !count) return nullptr;
-        if (!direct) return take<T>(count);
-        T* p = (T*)(a->pin + kPinBytes + direct_off);
-        direct_down[n_direct++] = {(void*)host, direct_off, count * sizeof(T)};
-        direct_off += al256(count * sizeof(T));
-        return p;
+        if (overflow) return RTUS_ERR_UNSUPPORTED;
+        const hipError_t e = copy_back();
+        return e == hipSuccess ? RTUS_OK : hip_fail(e);
     }
-    // results back + synchronise: one device-to-host copy through the page-locked buffer when they are small
-    hipError_t finish()
+    // results back + synchronise: one device-to-host copy through the page-locked buffer when they are small.  (The HIP error
+    // itself: table_multi runs it on a thread per device, and the last error is recorded per thread.)
+    hipError_t copy_back()
     {
-        if (n_direct) {                                              // results are in the page-locked buffer once the stream has drained
+        char* stage = a->pin + kPinBytes;
+        auto back = [](const Buf& b) { return b.kind == kOut && !b.pinned; };   // a result to copy back from the arena
+        int n_back = 0;
+        size_t lo = SIZE_MAX, hi = 0;
+        for (int i = 0; i < n_buf; ++i)
+            if (back(buf[i])) {
+                ++n_back;
+                lo = std::min(lo, buf[i].off);
+                hi = std::max(hi, buf[i].off + buf[i].bytes);
+            }
+        if (direct) {                                                // results are in the page-locked buffer once the stream has drained
             const hipError_t e = hipStreamSynchronize(a->stream);
             if (e != hipSuccess) return e;
             drained = true;
-            for (int i = 0; i < n_direct; ++i) memcpy(direct_down[i].host, a->pin + kPinBytes + direct_down[i].off, direct_down[i].bytes);
-            if (!n_down) return hipSuccess;
+            for (int i = 0; i < n_buf; ++i) if (buf[i].pinned) memcpy(buf[i].host, stage + buf[i].off, buf[i].bytes);
+            if (!n_back) return hipSuccess;
         }
-        if (n_down) {
-            size_t lo = down[0].off, hi = 0;
-            for (int i = 0; i < n_down; ++i) { lo = down[i].off < lo ? down[i].off : lo; hi = down[i].off + down[i].bytes > hi ? down[i].off + down[i].bytes : hi; }
-            if (hi - lo <= kPinBytes) {
-                char* stage = a->pin + kPinBytes;
-                hipError_t e = hipMemcpyAsync(stage, (char*)a->dev + lo, hi - lo, hipMemcpyDeviceToHost, a->stream);
-                if (e != hipSuccess) return e;
-                e = hipStreamSynchronize(a->stream);
-                if (e != hipSuccess) return e;
-                drained = true;
-                for (int i = 0; i < n_down; ++i) memcpy(down[i].host, stage + (down[i].off - lo), down[i].bytes);
-                return hipSuccess;
-            }
-            for (int i = 0; i < n_down; ++i) {
-                hipError_t e = hipMemcpyAsync(down[i].host, (char*)a->dev + down[i].off, down[i].bytes, hipMemcpyDeviceToHost, a->stream);
-                if (e != hipSuccess) return e;
-            }
+        if (n_back && hi - lo <= kPinBytes) {
+            hipError_t e = hipMemcpyAsync(stage, (char*)a->dev + lo, hi - lo, hipMemcpyDeviceToHost, a->stream);
+            if (e != hipSuccess) return e;
+            e = hipStreamSynchronize(a->stream);
+            if (e != hipSuccess) return e;
+            drained = true;
+            for (int i = 0; i < n_buf; ++i) if (back(buf[i])) memcpy(buf[i].host, stage + (buf[i].off - lo), buf[i].bytes);
+            return hipSuccess;
+        }
+        for (int i = 0; i < n_buf; ++i) {
+            if (!back(buf[i])) continue;
+            const hipError_t e = hipMemcpyAsync(buf[i].host, (char*)a->dev + buf[i].off, buf[i].bytes, hipMemcpyDeviceToHost, a->stream);
+            if (e != hipSuccess) return e;
         }
         const hipError_t e = hipStreamSynchronize(a->stream);
         drained = e == hipSuccess;
         return e;
     }
 };
+
+// *_dev entries: the caller's workspace is present, aligned to `align` bytes and large enough
+int check_workspace(const void* ws, size_t bytes, size_t need, uintptr_t align)
+{
+    return ws && !((uintptr_t)ws & (align - 1)) && bytes >= need ? RTUS_OK : RTUS_ERR_WORKSPACE;
+}
 }   // namespace
 
 // curved-lens helpers (C++ linkage: templates)
@@ -274,21 +303,17 @@ static int lens_host(const rtus_lens* lens, double a_lo, double a_hi, const R* x
     if (st) return st;
     const size_t tot = (size_t)n_e * n_f;
     Session S;
-    if ((st = S.open(device, 2 * al256(sizeof(R) * n_e) + 2 * al256(sizeof(R) * n_f) + (alpha_out ? 2 : 1) * al256(sizeof(R) * tot))))
-        return st;
-    R *dxe, *dze, *dxf, *dzf;
-    S.upload(dxe, xe, n_e);
-    S.upload(dze, ze, n_e);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    R* dtt = S.take<R>(tot);
-    R* dal = alpha_out ? S.take<R>(tot) : nullptr;
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    R *dxe, *dze, *dxf, *dzf, *dtt, *dal;
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dal, alpha_out, tot);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(launch(*lens, a_lo, a_hi, dxe, dze, n_e, dxf, dzf, n_f, dtt, dal, 0, n_e, S.a->stream, nullptr));
-    S.download(tt, dtt, tot);
-    S.download(alpha_out, dal, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 extern "C" {
@@ -344,7 +369,7 @@ int rtus_selftest(const rtus_lens* lens, int n_rays, long long n_math, unsigned 
 {
     if (!lens || !counts || n_rays < 8 || n_math < 0 || n_math > (1ll << 36)) return RTUS_ERR_INVALID_ARG;
     Session S;                                       // validates `device`, restores the caller's device, the arena's own stream
-    int st = S.open(device, 0);
+    int st = S.open(device);
     if (st) return st;
     LAUNCH_TRY(rtus_selftest_run(*lens, n_rays, n_math, counts, S.a->stream));
     return RTUS_OK;
@@ -372,7 +397,7 @@ int rtus_shoot_dev(const rtus_lens* lens, const double* d_geoms, int n_geom, con
     int st = check_shoot(lens, d_geoms, n_geom, d_x_a, d_z_a, n_tx, d_alpha, d_z_f, n_rays);
     if (st) return st;
     if (flags & ~RTUS_SHOOT_KNOWN_FLAGS) return RTUS_ERR_INVALID_ARG;
-    if (!d_workspace || ((uintptr_t)d_workspace & 63) || workspace_bytes < rtus_ws_bytes(n_rays)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_ws_bytes(n_rays), 64))) return st;
     LAUNCH_TRY(rtus_launch_shoot(*lens, d_geoms, n_geom, d_x_a, d_z_a, n_tx, d_alpha, d_z_f, n_rays, d_out8,
                               d_tof4, d_tof, d_land_x, d_status, d_workspace, flags, (hipStream_t)stream));
     return RTUS_OK;
@@ -386,11 +411,8 @@ int rtus_shoot(const rtus_lens* lens, const double* geoms, int n_geom, const dou
     if (st) return st;
     if (flags & ~RTUS_SHOOT_KNOWN_FLAGS) return RTUS_ERR_INVALID_ARG;
     const size_t rows = (size_t)n_geom * n_tx, n = (size_t)n_rays, rn = rows * n;
-    const size_t need = al256(16 * (size_t)n_geom) + 2 * al256(8 * (size_t)n_tx) + 2 * al256(8 * n) +
-                        (out8 ? al256(64 * rn) : 0) + (tof4 ? al256(32 * rn) : 0) + (tof ? al256(8 * rn) : 0) +
-                        (land_x ? al256(8 * rn) : 0) + (status ? al256(rn) : 0);
     Session S;
-    if ((st = S.open(device, need))) return st;
+    if ((st = S.open(device))) return st;
     // the polyline of an unchanged (alpha, lens) pair is kept in the arena: no polyline launch, no upload of alpha
     Arena& A = *S.a;
     const size_t pw = rtus_ws_bytes(n_rays);
@@ -404,28 +426,23 @@ int rtus_shoot(const rtus_lens* lens, const double* geoms, int n_geom, const dou
             A.poly_cap = pw;
         }
     }
-    double *g, *xa, *za, *al = nullptr, *zf;
-    S.upload(g, geoms, 2 * (size_t)n_geom);
-    S.upload(xa, x_a, n_tx);
-    S.upload(za, z_a, n_tx);
-    if (!keep) S.upload(al, alpha, n);
-    S.upload(zf, z_f, n);
-    void* ws = A.poly_ws;
-    S.direct_ok((out8 ? 64 * rn : 0) + (tof4 ? 32 * rn : 0) + (tof ? 8 * rn : 0) + (land_x ? 8 * rn : 0) + (status ? rn : 0));
-    double* o8 = S.take_out(out8, 8 * rn);
-    double* t4 = S.take_out(tof4, 4 * rn);
-    double* tt = S.take_out(tof, rn);
-    double* lx = S.take_out(land_x, rn);
-    uint8_t* sb = S.take_out(status, rn);
-    HIP_TRY(S.flush());
-    LAUNCH_TRY(rtus_launch_shoot(*lens, g, n_geom, xa, za, n_tx, al, zf, n_rays, o8, t4, tt, lx, sb, ws,
+    double *g, *xa, *za, *al = nullptr, *zf, *o8, *t4, *tt, *lx;
+    uint8_t* sb;
+    S.in(g, geoms, 2 * (size_t)n_geom);
+    S.in(xa, x_a, n_tx);
+    S.in(za, z_a, n_tx);
+    if (!keep) S.in(al, alpha, n);
+    S.in(zf, z_f, n);
+    S.out(o8, out8, 8 * rn);
+    S.out(t4, tof4, 4 * rn);
+    S.out(tt, tof, rn);
+    S.out(lx, land_x, rn);
+    S.out(sb, status, rn);
+    S.allow_direct = true;
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_shoot(*lens, g, n_geom, xa, za, n_tx, al, zf, n_rays, o8, t4, tt, lx, sb, A.poly_ws,
                                  (flags & ~RTUS_POLYLINE_READY) | (keep ? RTUS_POLYLINE_READY : 0u), S.a->stream));
-    S.download(out8, o8, 8 * rn);
-    S.download(tof4, t4, 4 * rn);
-    S.download(tof, tt, rn);
-    S.download(land_x, lx, rn);
-    S.download(status, sb, rn);
-    HIP_TRY(S.finish());
+    if ((st = S.finish())) return st;
     if (!keep && n <= ((size_t)1 << 22)) {                  // the call came back clean: the polyline in the arena belongs to this (alpha, lens)
         A.poly_alpha.assign(alpha, alpha + n);
         A.poly_lens = *lens;
@@ -460,7 +477,7 @@ int rtus_solve_dev(const rtus_lens* lens, const double* d_geoms, int n_geom, con
 {
     int st = check_solve(lens, d_geoms, n_geom, d_x_a, d_z_a, n_tx, d_alpha, n_rays, d_x_rx, n_rx, z_land, d_tt, flags);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 63) || workspace_bytes < rtus_solve_ws_bytes(n_rays, n_geom, n_tx, n_rx)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_solve_ws_bytes(n_rays, n_geom, n_tx, n_rx), 64))) return st;
     LAUNCH_TRY(rtus_launch_solve(*lens, d_geoms, n_geom, d_x_a, d_z_a, n_tx, d_alpha, n_rays, d_x_rx, n_rx, z_land, d_tt,
                               d_alpha_root, d_tt_all, d_alpha_all, d_n_roots, d_workspace, flags, (hipStream_t)stream));
     return RTUS_OK;
@@ -475,37 +492,27 @@ int rtus_solve(const rtus_lens* lens, const double* geoms, int n_geom, const dou
     for (int i = 0; i + 1 < n_rays; ++i)                    // the brackets are intervals of the grid: strictly ascending (host arrays can be checked)
         if (!(alpha[i] < alpha[i + 1])) return RTUS_ERR_INVALID_ARG;
     const size_t tot = (size_t)n_geom * n_tx * n_rx;
-    const size_t wsb = rtus_solve_ws_bytes(n_rays, n_geom, n_tx, n_rx);
-    const size_t need = al256(16 * (size_t)n_geom) + 2 * al256(8 * (size_t)n_tx) + al256(8 * (size_t)n_rays) + al256(8 * (size_t)n_rx) +
-                        al256(wsb) + al256(8 * tot) + (alpha_root ? al256(8 * tot) : 0) +
-                        (tt_all ? al256(8 * tot * RTUS_MAX_ROOTS) : 0) + (alpha_all ? al256(8 * tot * RTUS_MAX_ROOTS) : 0) +
-                        (n_roots ? al256(tot) : 0);
     Session S;
-    if ((st = S.open(device, need))) return st;
-    double *g, *xa, *za, *al, *rx;
-    S.upload(g, geoms, 2 * (size_t)n_geom);
-    S.upload(xa, x_a, n_tx);
-    S.upload(za, z_a, n_tx);
-    S.upload(al, alpha, n_rays);
-    S.upload(rx, x_rx, n_rx);
-    void* ws = S.take<char>(wsb);
-    S.direct_ok(8 * tot + (alpha_root ? 8 * tot : 0) + (tt_all ? 8 * tot * RTUS_MAX_ROOTS : 0) + (alpha_all ? 8 * tot * RTUS_MAX_ROOTS : 0) +
-                (n_roots ? tot : 0));
-    double* dt = S.take_out(tt, tot);
-    double* da = S.take_out(alpha_root, tot);
-    double* dta = S.take_out(tt_all, tot * RTUS_MAX_ROOTS);
-    double* daa = S.take_out(alpha_all, tot * RTUS_MAX_ROOTS);
-    uint8_t* dn = S.take_out(n_roots, tot);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *g, *xa, *za, *al, *rx, *dt, *da, *dta, *daa;
+    char* ws;
+    uint8_t* dn;
+    S.in(g, geoms, 2 * (size_t)n_geom);
+    S.in(xa, x_a, n_tx);
+    S.in(za, z_a, n_tx);
+    S.in(al, alpha, n_rays);
+    S.in(rx, x_rx, n_rx);
+    S.scratch(ws, rtus_solve_ws_bytes(n_rays, n_geom, n_tx, n_rx));
+    S.out(dt, tt, tot);
+    S.out(da, alpha_root, tot);
+    S.out(dta, tt_all, tot * RTUS_MAX_ROOTS);
+    S.out(daa, alpha_all, tot * RTUS_MAX_ROOTS);
+    S.out(dn, n_roots, tot);
+    S.allow_direct = true;
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_solve(*lens, g, n_geom, xa, za, n_tx, al, n_rays, rx, n_rx, z_land, dt, da, dta, daa, dn, ws,
                               flags & ~RTUS_POLYLINE_READY, S.a->stream));
-    S.download(tt, dt, tot);
-    S.download(alpha_root, da, tot);
-    S.download(tt_all, dta, tot * RTUS_MAX_ROOTS);
-    S.download(alpha_all, daa, tot * RTUS_MAX_ROOTS);
-    S.download(n_roots, dn, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- element matcher
@@ -549,23 +556,20 @@ int rtus_match(const double* land_x, const double* tof, int n_batch, int n_rays,
     if (tof_hit && !tof) return RTUS_ERR_INVALID_ARG;
     const size_t rn = (size_t)n_batch * n_rays, re = (size_t)n_batch * n_rx;
     Session S;
-    if ((st = S.open(device, (tof ? 2 : 1) * al256(8 * rn) + al256(8 * (size_t)n_rx) + al256(4 * re) + (hit ? al256(re) : 0) +
-                                 (tof_hit ? al256(8 * re) : 0))))
-        return st;
-    double *lx, *tf = nullptr, *rx;
-    S.upload(lx, land_x, rn);
-    if (tof) S.upload(tf, tof, rn);
-    S.upload(rx, x_rx, n_rx);
-    int32_t* fr = S.take<int32_t>(re);
-    uint8_t* hb = hit ? S.take<uint8_t>(re) : nullptr;
-    double* th = tof_hit ? S.take<double>(re) : nullptr;
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *lx, *tf = nullptr, *rx, *th;
+    int32_t* fr;
+    uint8_t* hb;
+    S.in(lx, land_x, rn);
+    if (tof) S.in(tf, tof, rn);
+    S.in(rx, x_rx, n_rx);
+    if (first_ray) S.out(fr, first_ray, re);
+    else S.scratch(fr, re);                                   // (the matcher writes it whether or not the caller wants it)
+    S.out(hb, hit, re);
+    S.out(th, tof_hit, re);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_match(lx, tf, n_batch, n_rays, rx, n_rx, atol, rtol, fr, hb, th, nullptr, S.a->stream));
-    S.download(first_ray, fr, re);
-    S.download(hit, hb, re);
-    S.download(tof_hit, th, re);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 int rtus_ray_hits(const double* land_x, int n_batch, int n_rays, const double* x_rx, int n_rx, double atol,
@@ -576,16 +580,15 @@ int rtus_ray_hits(const double* land_x, int n_batch, int n_rays, const double* x
     if (!ray_hit) return RTUS_ERR_INVALID_ARG;
     const size_t rn = (size_t)n_batch * n_rays;
     Session S;
-    if ((st = S.open(device, al256(8 * rn) + al256(8 * (size_t)n_rx) + al256(rn)))) return st;
+    if ((st = S.open(device))) return st;
     double *lx, *rx;
-    S.upload(lx, land_x, rn);
-    S.upload(rx, x_rx, n_rx);
-    uint8_t* rh = S.take<uint8_t>(rn);
-    HIP_TRY(S.flush());
+    uint8_t* rh;
+    S.in(lx, land_x, rn);
+    S.in(rx, x_rx, n_rx);
+    S.out(rh, ray_hit, rn);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_match(lx, nullptr, n_batch, n_rays, rx, n_rx, atol, rtol, nullptr, nullptr, nullptr, rh, S.a->stream));
-    S.download(ray_hit, rh, rn);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- fused sweep (forward trace + matcher)
@@ -614,7 +617,7 @@ int rtus_sweep_dev(const rtus_lens* lens, const double* d_geoms, int n_geom, con
 {
     int st = check_sweep(lens, d_geoms, n_geom, d_x_a, d_z_a, n_tx, d_alpha, d_z_f, n_rays, d_x_rx, n_rx, atol, rtol, d_first_ray, flags);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 63) || workspace_bytes < rtus_sweep_ws_bytes(n_rays, n_geom, n_tx, n_rx)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_sweep_ws_bytes(n_rays, n_geom, n_tx, n_rx), 64))) return st;
     LAUNCH_TRY(rtus_launch_sweep(*lens, d_geoms, n_geom, d_x_a, d_z_a, n_tx, d_alpha, d_z_f, n_rays, d_x_rx, n_rx, atol, rtol, d_first_ray,
                               d_hit, d_tof_hit, d_tof, d_land_x, d_workspace, flags, (hipStream_t)stream));
     return RTUS_OK;
@@ -627,36 +630,29 @@ int rtus_sweep(const rtus_lens* lens, const double* geoms, int n_geom, const dou
     int st = check_sweep(lens, geoms, n_geom, x_a, z_a, n_tx, alpha, z_f, n_rays, x_rx, n_rx, atol, rtol, first_ray, flags);
     if (st) return st;
     const size_t rows = (size_t)n_geom * n_tx, n = (size_t)n_rays, rn = rows * n, re = rows * (size_t)n_rx;
-    const size_t wsb = rtus_sweep_ws_bytes(n_rays, n_geom, n_tx, n_rx);
-    const size_t need = al256(16 * (size_t)n_geom) + 2 * al256(8 * (size_t)n_tx) + 2 * al256(8 * n) + al256(8 * (size_t)n_rx) + al256(wsb) +
-                        al256(4 * re) + (hit ? al256(re) : 0) + (tof_hit ? al256(8 * re) : 0) + (tof ? al256(8 * rn) : 0) +
-                        (land_x ? al256(8 * rn) : 0);
     Session S;
-    if ((st = S.open(device, need))) return st;
-    double *g, *xa, *za, *al, *zf, *rx;
-    S.upload(g, geoms, 2 * (size_t)n_geom);
-    S.upload(xa, x_a, n_tx);
-    S.upload(za, z_a, n_tx);
-    S.upload(al, alpha, n);
-    S.upload(zf, z_f, n);
-    S.upload(rx, x_rx, n_rx);
-    void* ws = S.take<char>(wsb);
-    S.direct_ok(4 * re + (hit ? re : 0) + (tof_hit ? 8 * re : 0) + (tof ? 8 * rn : 0) + (land_x ? 8 * rn : 0));
-    int32_t* fr = S.take_out(first_ray, re);
-    uint8_t* hb = S.take_out(hit, re);
-    double* th = S.take_out(tof_hit, re);
-    double* tt = S.take_out(tof, rn);
-    double* lx = S.take_out(land_x, rn);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *g, *xa, *za, *al, *zf, *rx, *th, *tt, *lx;
+    char* ws;
+    int32_t* fr;
+    uint8_t* hb;
+    S.in(g, geoms, 2 * (size_t)n_geom);
+    S.in(xa, x_a, n_tx);
+    S.in(za, z_a, n_tx);
+    S.in(al, alpha, n);
+    S.in(zf, z_f, n);
+    S.in(rx, x_rx, n_rx);
+    S.scratch(ws, rtus_sweep_ws_bytes(n_rays, n_geom, n_tx, n_rx));
+    S.out(fr, first_ray, re);
+    S.out(hb, hit, re);
+    S.out(th, tof_hit, re);
+    S.out(tt, tof, rn);
+    S.out(lx, land_x, rn);
+    S.allow_direct = true;
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_sweep(*lens, g, n_geom, xa, za, n_tx, al, zf, n_rays, rx, n_rx, atol, rtol, fr, hb, th, tt, lx, ws,
                               flags & ~RTUS_POLYLINE_READY, S.a->stream));
-    S.download(first_ray, fr, re);
-    S.download(hit, hb, re);
-    S.download(tof_hit, th, re);
-    S.download(tof, tt, rn);
-    S.download(land_x, lx, rn);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- planar layers
@@ -734,7 +730,7 @@ int rtus_tt_layers_sorted_dev(const double* z_if, const double* c, int n_if, con
     if (st) return st;
     if (flags & ~RTUS_TT_TAUP_TAIL) return RTUS_ERR_INVALID_ARG;
     if (n_e > RTUS_SORT_MAX_ELEMENTS) return RTUS_ERR_UNSUPPORTED;
-    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_layers_sort_ws_bytes(n_e)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_layers_sort_ws_bytes(n_e), 256))) return st;
     LAUNCH_TRY(rtus_launch_tt_layers_sorted(z_if, c, n_if, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, d_workspace, nullptr, flags,
                                          (hipStream_t)stream));
     return RTUS_OK;
@@ -777,25 +773,21 @@ int rtus_tt_layers_ex(const double* z_if, const double* c, int n_if, const doubl
     if (!iters) aperture_order(xe, ze, n_e, order, sx, sz);     // (the iteration counts are a diagnostic of the elements AS GIVEN)
     const bool perm = !order.empty();
     Session S;
-    if ((st = S.open(device, 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) + al256(8 * tot) + (iters ? al256(tot) : 0) +
-                                 (perm ? al256(4 * (size_t)n_e) : 0))))
-        return st;
-    double *dxe, *dze, *dxf, *dzf;
+    if ((st = S.open(device))) return st;
+    double *dxe, *dze, *dxf, *dzf, *dtt;
     int* drow = nullptr;
-    S.upload(dxe, perm ? sx.data() : xe, n_e);
-    S.upload(dze, perm ? sz.data() : ze, n_e);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    if (perm) S.upload(drow, (const int*)order.data(), n_e);
-    double* dtt = S.take<double>(tot);
-    uint8_t* dit = iters ? S.take<uint8_t>(tot) : nullptr;
-    HIP_TRY(S.flush());
+    uint8_t* dit;
+    S.in(dxe, perm ? sx.data() : xe, n_e);
+    S.in(dze, perm ? sz.data() : ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    if (perm) S.in(drow, (const int*)order.data(), n_e);
+    S.out(dtt, tt, tot);
+    S.out(dit, iters, tot);
+    if ((st = S.flush())) return st;
     if (perm) LAUNCH_TRY(rtus_launch_tt_layers_sorted(z_if, c, n_if, dxe, dze, n_e, dxf, dzf, n_f, dtt, nullptr, drow, flags, S.a->stream));
     else LAUNCH_TRY(rtus_launch_tt_layers(z_if, c, n_if, dxe, dze, n_e, dxf, dzf, n_f, dtt, dit, flags, S.a->stream));
-    S.download(tt, dtt, tot);
-    S.download(iters, dit, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 int rtus_tt_layers(const double* z_if, const double* c, int n_if, const double* xe, const double* ze, int n_e,
@@ -823,7 +815,7 @@ int rtus_tt_surface_dev(double x0, double dx, const double* d_zs, int n_s, doubl
 {
     int st = check_surface(x0, dx, d_zs, n_s, c1, c2, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_surface_ws_bytes(n_s), 256))) return st;
     LAUNCH_TRY(rtus_launch_tt_surface(x0, dx, d_zs, n_s, c1, c2, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, d_x_entry, d_workspace,
                                       (hipStream_t)stream));
     return RTUS_OK;
@@ -834,26 +826,22 @@ int rtus_tt_surface(double x0, double dx, const double* zs, int n_s, double c1, 
 {
     int st = check_surface(x0, dx, zs, n_s, c1, c2, xe, ze, n_e, xf, zf, n_f, tt);
     if (st) return st;
-    const size_t tot = (size_t)n_e * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    const size_t tot = (size_t)n_e * n_f;
     Session S;
-    if ((st = S.open(device, al256(8 * (size_t)n_s) + 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) + (x_entry ? 2 : 1) * al256(8 * tot) +
-                                 al256(wsb))))
-        return st;
-    double *dzs, *dxe, *dze, *dxf, *dzf;
-    S.upload(dzs, zs, n_s);
-    S.upload(dxe, xe, n_e);
-    S.upload(dze, ze, n_e);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    double* dtt = S.take<double>(tot);
-    double* dxn = x_entry ? S.take<double>(tot) : nullptr;
-    void* ws = S.take<char>(wsb);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *dzs, *dxe, *dze, *dxf, *dzf, *dtt, *dxn;
+    char* ws;
+    S.in(dzs, zs, n_s);
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dxn, x_entry, tot);
+    S.scratch(ws, rtus_surface_ws_bytes(n_s));
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tt_surface(x0, dx, dzs, n_s, c1, c2, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, ws, S.a->stream));
-    S.download(tt, dtt, tot);
-    S.download(x_entry, dxn, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // skip legs through the surface: rtus_tt_surface's checks, c_down in c2's place, and the leg's own speed and backwall
@@ -870,7 +858,7 @@ int rtus_tt_surface_skip_dev(double x0, double dx, const double* d_zs, int n_s, 
 {
     int st = check_surface_skip(x0, dx, d_zs, n_s, c1, c_down, c_up, z_back, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_surface_ws_bytes(n_s), 256))) return st;
     LAUNCH_TRY(rtus_launch_tt_surface_skip(x0, dx, d_zs, n_s, c1, c_down, c_up, z_back, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, d_x_entry,
                                            d_x_back, d_workspace, (hipStream_t)stream));
     return RTUS_OK;
@@ -882,29 +870,24 @@ int rtus_tt_surface_skip(double x0, double dx, const double* zs, int n_s, double
 {
     int st = check_surface_skip(x0, dx, zs, n_s, c1, c_down, c_up, z_back, xe, ze, n_e, xf, zf, n_f, tt);
     if (st) return st;
-    const size_t tot = (size_t)n_e * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    const size_t tot = (size_t)n_e * n_f;
     Session S;
-    if ((st = S.open(device, al256(8 * (size_t)n_s) + 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) +
-                                 (1 + (x_entry ? 1 : 0) + (x_back ? 1 : 0)) * al256(8 * tot) + al256(wsb))))
-        return st;
-    double *dzs, *dxe, *dze, *dxf, *dzf;
-    S.upload(dzs, zs, n_s);
-    S.upload(dxe, xe, n_e);
-    S.upload(dze, ze, n_e);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    double* dtt = S.take<double>(tot);
-    double* dxn = x_entry ? S.take<double>(tot) : nullptr;
-    double* dxb = x_back ? S.take<double>(tot) : nullptr;
-    void* ws = S.take<char>(wsb);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *dzs, *dxe, *dze, *dxf, *dzf, *dtt, *dxn, *dxb;
+    char* ws;
+    S.in(dzs, zs, n_s);
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dxn, x_entry, tot);
+    S.out(dxb, x_back, tot);
+    S.scratch(ws, rtus_surface_ws_bytes(n_s));
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tt_surface_skip(x0, dx, dzs, n_s, c1, c_down, c_up, z_back, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, dxb, ws,
                                            S.a->stream));
-    S.download(tt, dtt, tot);
-    S.download(x_entry, dxn, tot);
-    S.download(x_back, dxb, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- consumers: focal laws, TFM
@@ -929,15 +912,14 @@ int rtus_focal_delays(const double* tt, int n_e, int n_f, double* delays, int de
     if (!tt || !delays || n_e <= 0 || n_f <= 0) return RTUS_ERR_INVALID_ARG;
     const size_t tot = (size_t)n_e * n_f;
     Session S;
-    int st = S.open(device, al256(8 * tot));
+    int st = S.open(device);
     if (st) return st;
     double* d;
-    S.upload(d, tt, tot);
-    HIP_TRY(S.flush());
+    S.in(d, tt, tot);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_focal_delays(d, n_e, n_f, d, S.a->stream));     // in place: each entry is read before it is written
     S.download(delays, d, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 int rtus_tfm_dev(const float* d_fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* d_tt_tx,
@@ -957,19 +939,16 @@ int rtus_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0
     const size_t nfmc = (size_t)n_tx * n_rx * n_t;
     const bool same = tt_tx == tt_rx && n_tx == n_rx;
     Session S;
-    if ((st = S.open(device, al256(4 * nfmc) + (same ? 1 : 2) * al256(8 * (size_t)(n_tx > n_rx ? n_tx : n_rx) * n_f) + al256(4 * (size_t)n_f))))
-        return st;
-    float* dfmc;
-    double *dtx, *drx;
-    S.upload(dfmc, fmc, nfmc);
-    S.upload(dtx, tt_tx, (size_t)n_tx * n_f);
-    if (same) drx = dtx; else S.upload(drx, tt_rx, (size_t)n_rx * n_f);
-    float* dimg = S.take<float>(n_f);
-    HIP_TRY(S.flush());
-    LAUNCH_TRY(rtus_launch_tfm(dfmc, n_tx, n_rx, n_t, fs, t0, dtx, drx, n_f, dimg, S.a->stream));
-    S.download(image, dimg, (size_t)n_f);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    if ((st = S.open(device))) return st;
+    float *dfmc, *dimg;
+    double *dtx, *drx = nullptr;
+    S.in(dfmc, fmc, nfmc);
+    S.in(dtx, tt_tx, (size_t)n_tx * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_rx * n_f);
+    S.out(dimg, image, n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tfm(dfmc, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- adaptive TFM: analytic FMC, surface from the couplant image
@@ -1001,15 +980,13 @@ int rtus_fmc_analytic(const float* fmc, int n_tx, int n_rx, int n_t, int n_taps,
     if (st) return st;
     const size_t n = (size_t)n_tx * n_rx * n_t;
     Session S;
-    if ((st = S.open(device, al256(4 * n) + al256(8 * n)))) return st;
-    float* din;
-    S.upload(din, fmc, n);
-    float* dout = S.take<float>(2 * n);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    float *din, *dout;
+    S.in(din, fmc, n);
+    S.out(dout, out, 2 * n);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_fmc_analytic(din, (long long)n_tx * n_rx, n_t, n_taps, (float2*)dout, S.a->stream));
-    S.download(out, dout, 2 * n);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 #define RTUS_SURFACE_FIND_MAX_E 4096
@@ -1042,25 +1019,20 @@ int rtus_surface_find(const float* a, int n_e, int n_t, double fs, double t0, co
 {
     int st = check_surface_find(a, n_e, n_t, fs, t0, xe, ze, c1, x0, dx, n_s, z_lo, dz, n_z, z_peak, amp);
     if (st) return st;
-    const size_t na = (size_t)n_e * n_e * n_t * 2, ni = image ? (size_t)n_s * n_z : 0;
+    const size_t na = (size_t)n_e * n_e * n_t * 2;
     Session S;
-    if ((st = S.open(device, al256(4 * na) + 2 * al256(8 * (size_t)n_e) + al256(8 * (size_t)n_s) + al256(4 * (size_t)n_s) + al256(4 * ni))))
-        return st;
-    float* da;
-    double *dxe, *dze;
-    S.upload(da, a, na);
-    S.upload(dxe, xe, n_e);
-    S.upload(dze, ze, n_e);
-    double* dzp = S.take<double>(n_s);
-    float* damp = S.take<float>(n_s);
-    float* dimg = S.take<float>(ni);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    float *da, *damp, *dimg;
+    double *dxe, *dze, *dzp;
+    S.in(da, a, na);
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.out(dzp, z_peak, n_s);
+    S.out(damp, amp, n_s);
+    S.out(dimg, image, (size_t)n_s * n_z);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_surface_find(da, n_e, n_t, fs, t0, dxe, dze, c1, x0, dx, n_s, z_lo, dz, n_z, dzp, damp, dimg, S.a->stream));
-    S.download(z_peak, dzp, n_s);
-    S.download(amp, damp, n_s);
-    S.download(image, dimg, ni);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- envelope TFM + coherence factor over an analytic FMC
@@ -1090,22 +1062,17 @@ int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     const size_t na = (size_t)n_tx * n_rx * n_t * 2;
     const bool same = tt_tx == tt_rx && n_tx == n_rx;
     Session S;
-    if ((st = S.open(device, al256(4 * na) + (same ? 1 : 2) * al256(8 * (size_t)(n_tx > n_rx ? n_tx : n_rx) * n_f) +
-                                 al256(8 * (size_t)n_f) + (cf ? al256(4 * (size_t)n_f) : 0))))
-        return st;
-    float* da;
-    double *dtx, *drx;
-    S.upload(da, a, na);
-    S.upload(dtx, tt_tx, (size_t)n_tx * n_f);
-    if (same) drx = dtx; else S.upload(drx, tt_rx, (size_t)n_rx * n_f);
-    float* dimg = S.take<float>(2 * (size_t)n_f);
-    float* dcf = cf ? S.take<float>(n_f) : nullptr;
-    HIP_TRY(S.flush());
-    LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, n_f, dimg, dcf, S.a->stream));
-    S.download(image, dimg, 2 * (size_t)n_f);
-    if (cf) S.download(cf, dcf, (size_t)n_f);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    if ((st = S.open(device))) return st;
+    float *da, *dimg, *dcf;
+    double *dtx, *drx = nullptr;
+    S.in(da, a, na);
+    S.in(dtx, tt_tx, (size_t)n_tx * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_rx * n_f);
+    S.out(dimg, image, 2 * (size_t)n_f);
+    S.out(dcf, cf, n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- weighted envelope TFM + sensitivity
@@ -1134,24 +1101,19 @@ int rtus_tfm_weighted(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     if (st) return st;
     const size_t na = (size_t)n_tx * n_rx * n_t * 2, ntx = (size_t)n_tx * n_f, nrx = (size_t)n_rx * n_f;
     Session S;
-    if ((st = S.open(device, al256(4 * na) + al256(8 * ntx) + al256(8 * nrx) + al256(8 * ntx) + al256(8 * nrx) + al256(8 * (size_t)n_f) +
-                                 (sens ? al256(4 * (size_t)n_f) : 0))))
-        return st;
-    float *da, *dwt, *dwr;
+    if ((st = S.open(device))) return st;
+    float *da, *dwt, *dwr, *dimg, *dsens;
     double *dtx, *drx;
-    S.upload(da, a, na);
-    S.upload(dtx, tt_tx, ntx);
-    S.upload(drx, tt_rx, nrx);
-    S.upload(dwt, w_tx, 2 * ntx);
-    S.upload(dwr, w_rx, 2 * nrx);
-    float* dimg = S.take<float>(2 * (size_t)n_f);
-    float* dsens = sens ? S.take<float>(n_f) : nullptr;
-    HIP_TRY(S.flush());
+    S.in(da, a, na);
+    S.in(dtx, tt_tx, ntx);
+    S.in(drx, tt_rx, nrx);
+    S.in(dwt, w_tx, 2 * ntx);
+    S.in(dwr, w_rx, 2 * nrx);
+    S.out(dimg, image, 2 * (size_t)n_f);
+    S.out(dsens, sens, n_f);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tfm_weighted(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, dwt, dwr, n_f, dimg, dsens, S.a->stream));
-    S.download(image, dimg, 2 * (size_t)n_f);
-    if (sens) S.download(sens, dsens, (size_t)n_f);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- ray amplitude tables through a measured surface
@@ -1179,7 +1141,7 @@ int rtus_leg_amp_surface_dev(double x0, double dx, const double* d_zs, int n_s, 
     int st = check_leg_amp(x0, dx, d_zs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, d_xe, d_ze, n_e, d_xf,
                            d_zf, n_f, d_x_entry, d_x_back, d_amp);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_surface_ws_bytes(n_s), 256))) return st;
     LAUNCH_TRY(rtus_launch_leg_amp_surface(x0, dx, d_zs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, d_xe,
                                            d_ze, n_e, d_xf, d_zf, n_f, d_x_entry, leg >= RTUS_LEG_LL ? d_x_back : nullptr, d_amp,
                                            d_workspace, (hipStream_t)stream));
@@ -1195,27 +1157,25 @@ int rtus_leg_amp_surface(double x0, double dx, const double* zs, int n_s, double
                            n_f, x_entry, x_back, amp);
     if (st) return st;
     const bool skip = leg >= RTUS_LEG_LL;
-    const size_t tot = (size_t)n_e * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    const size_t tot = (size_t)n_e * n_f;
     Session S;
-    if ((st = S.open(device, al256(8 * (size_t)n_s) + 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) + (skip ? 2 : 1) * al256(8 * tot) +
-                                 al256(8 * tot) + al256(wsb))))
-        return st;
+    if ((st = S.open(device))) return st;
     double *dzs, *dxe, *dze, *dxf, *dzf, *dxn, *dxb = nullptr;
-    S.upload(dzs, zs, n_s);
-    S.upload(dxe, xe, n_e);
-    S.upload(dze, ze, n_e);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    S.upload(dxn, x_entry, tot);
-    if (skip) S.upload(dxb, x_back, tot);
-    float* damp = S.take<float>(2 * tot);
-    void* ws = S.take<char>(wsb);
-    HIP_TRY(S.flush());
+    float* damp;
+    char* ws;
+    S.in(dzs, zs, n_s);
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.in(dxn, x_entry, tot);
+    if (skip) S.in(dxb, x_back, tot);
+    S.out(damp, amp, 2 * tot);
+    S.scratch(ws, rtus_surface_ws_bytes(n_s));
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_leg_amp_surface(x0, dx, dzs, n_s, c1, rho1, c_l, c_t, rho2, z_back, leg, direction, element_width, f_c, dxe, dze,
                                            n_e, dxf, dzf, n_f, dxn, dxb, damp, ws, S.a->stream));
-    S.download(amp, damp, 2 * tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- plane-wave imaging
@@ -1263,17 +1223,15 @@ int rtus_pw_layers(const double* z_if, const double* c, int n_if, const double* 
     if (st) return st;
     const size_t tot = (size_t)n_a * n_f;
     Session S;
-    if ((st = S.open(device, al256(8 * (size_t)n_a) + 2 * al256(8 * (size_t)n_f) + al256(8 * tot)))) return st;
-    double *dang, *dxf, *dzf;
-    S.upload(dang, angles, n_a);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    double* dtt = S.take<double>(tot);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *dang, *dxf, *dzf, *dtt;
+    S.in(dang, angles, n_a);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_pw_layers(z_if, c, n_if, dang, n_a, x_lo, x_hi, z_a, dxf, dzf, n_f, dtt, S.a->stream));
-    S.download(tt, dtt, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 static int check_pw_surface(double x0, double dx, const void* zs, int n_s, double c1, double c2, const void* ang, int n_a, double x_lo,
@@ -1293,7 +1251,7 @@ int rtus_pw_surface_dev(double x0, double dx, const double* d_zs, int n_s, doubl
 {
     int st = check_pw_surface(x0, dx, d_zs, n_s, c1, c2, d_angles, n_a, x_lo, x_hi, z_a, d_xf, d_zf, n_f, d_tt);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_surface_ws_bytes(n_s)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_surface_ws_bytes(n_s), 256))) return st;
     LAUNCH_TRY(rtus_launch_pw_surface(x0, dx, d_zs, n_s, c1, c2, d_angles, n_a, x_lo, x_hi, z_a, d_xf, d_zf, n_f, d_tt, d_x_entry,
                                       d_workspace, (hipStream_t)stream));
     return RTUS_OK;
@@ -1304,25 +1262,21 @@ int rtus_pw_surface(double x0, double dx, const double* zs, int n_s, double c1, 
 {
     int st = check_pw_surface(x0, dx, zs, n_s, c1, c2, angles, n_a, x_lo, x_hi, z_a, xf, zf, n_f, tt);
     if (st) return st;
-    const size_t tot = (size_t)n_a * n_f, wsb = rtus_surface_ws_bytes(n_s);
+    const size_t tot = (size_t)n_a * n_f;
     Session S;
-    if ((st = S.open(device, al256(8 * (size_t)n_s) + al256(8 * (size_t)n_a) + 2 * al256(8 * (size_t)n_f) + (x_entry ? 2 : 1) * al256(8 * tot) +
-                                 al256(wsb))))
-        return st;
-    double *dzs, *dang, *dxf, *dzf;
-    S.upload(dzs, zs, n_s);
-    S.upload(dang, angles, n_a);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    double* dtt = S.take<double>(tot);
-    double* dxn = x_entry ? S.take<double>(tot) : nullptr;
-    void* ws = S.take<char>(wsb);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *dzs, *dang, *dxf, *dzf, *dtt, *dxn;
+    char* ws;
+    S.in(dzs, zs, n_s);
+    S.in(dang, angles, n_a);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dxn, x_entry, tot);
+    S.scratch(ws, rtus_surface_ws_bytes(n_s));
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_pw_surface(x0, dx, dzs, n_s, c1, c2, dang, n_a, x_lo, x_hi, z_a, dxf, dzf, n_f, dtt, dxn, ws, S.a->stream));
-    S.download(tt, dtt, tot);
-    S.download(x_entry, dxn, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 static int check_synth(const void* fmc, int n_tx, int n_rx, int n_t, double fs, const void* d, int n_v, const void* out)
@@ -1352,17 +1306,15 @@ int rtus_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, 
     if (st) return st;
     const size_t nin = (size_t)n_tx * n_rx * n_t, nout = (size_t)n_v * n_rx * n_t, nd = (size_t)n_v * n_tx;
     Session S;
-    if ((st = S.open(device, al256(4 * nin) + al256(8 * nd) + al256(4 * nout)))) return st;
-    float* din;
+    if ((st = S.open(device))) return st;
+    float *din, *dout;
     double* dd;
-    S.upload(din, fmc, nin);
-    S.upload(dd, delays, nd);
-    float* dout = S.take<float>(nout);
-    HIP_TRY(S.flush());
+    S.in(din, fmc, nin);
+    S.in(dd, delays, nd);
+    S.out(dout, out, nout);
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_fmc_synth_tx(din, n_tx, n_rx, n_t, fs, dd, n_v, dout, S.a->stream));
-    S.download(out, dout, nout);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- curved lens
@@ -1518,17 +1470,17 @@ static int table_multi(const R* xe, const R* ze, int n_e, const R* xf, const R* 
     for (int i : ord) {                                               // uploads + launches: asynchronous on each device's stream
         const long long lo = per * i, hi = lo + per < n_e ? lo + per : n_e;
         const size_t rows = (size_t)(hi - lo), tot = rows * n_f;
-        if ((st = S[i].open(devices[i], 2 * al256(sizeof(R) * rows) + 2 * al256(sizeof(R) * (size_t)n_f) + al256(sizeof(R) * tot), slot[i]))) break;
-        R *dxe, *dze, *dxf, *dzf;
-        S[i].upload(dxe, xe + lo, rows);
-        S[i].upload(dze, ze + lo, rows);
-        S[i].upload(dxf, xf, (size_t)n_f);
-        S[i].upload(dzf, zf, (size_t)n_f);
-        R* dtt = S[i].template take<R>(tot);
-        hipError_t e = S[i].flush();
-        if (e == hipSuccess) { (void)hipGetLastError(); e = launch(dxe, dze, (int)rows, (int)lo, dxf, dzf, dtt, S[i].a->stream); }
+        if ((st = S[i].open(devices[i], slot[i]))) break;
+        R *dxe, *dze, *dxf, *dzf, *dtt;
+        S[i].in(dxe, xe + lo, rows);
+        S[i].in(dze, ze + lo, rows);
+        S[i].in(dxf, xf, (size_t)n_f);
+        S[i].in(dzf, zf, (size_t)n_f);
+        S[i].out(dtt, tt + (size_t)lo * n_f, tot);
+        if ((st = S[i].flush())) break;
+        (void)hipGetLastError();
+        const hipError_t e = launch(dxe, dze, (int)rows, (int)lo, dxf, dzf, dtt, S[i].a->stream);
         if (e != hipSuccess) { st = hip_fail(e); break; }
-        S[i].download(tt + (size_t)lo * n_f, dtt, tot);
         live[i] = 1;
     }
     // results back: one host thread per device (a device-to-pageable-host copy occupies its caller; the links are independent)
@@ -1538,9 +1490,9 @@ static int table_multi(const R* xe, const R* ze, int n_e, const R* xf, const R* 
     for (int i = 0; i < n_dev; ++i) {
         if (!live[i]) continue;
         if (mine < 0) { mine = i; continue; }
-        th.emplace_back([&, i] { (void)hipSetDevice(S[i].dev_index); err[i] = S[i].finish(); });
+        th.emplace_back([&, i] { (void)hipSetDevice(S[i].dev_index); err[i] = S[i].copy_back(); });
     }
-    if (mine >= 0) { (void)hipSetDevice(S[mine].dev_index); err[mine] = S[mine].finish(); }
+    if (mine >= 0) { (void)hipSetDevice(S[mine].dev_index); err[mine] = S[mine].copy_back(); }
     for (auto& t : th) t.join();
     for (int i = 0; i < n_dev; ++i) if (st == RTUS_OK && err[i] != hipSuccess) st = hip_fail(err[i]);
     return st;
@@ -1764,7 +1716,7 @@ extern "C" int rtus_tt_pipe_dev(const rtus_lens* lens, double alpha_lo, double a
 {
     int st = check_pipe(lens, alpha_lo, alpha_hi, pipe, beta_lo, beta_hi, n_scan, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
     if (st) return st;
-    if (!d_workspace || ((uintptr_t)d_workspace & 255) || workspace_bytes < rtus_pipe_ws_bytes(n_e, n_scan)) return RTUS_ERR_WORKSPACE;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_pipe_ws_bytes(n_e, n_scan), 256))) return st;
     LAUNCH_TRY(rtus_launch_tt_pipe(*lens, alpha_lo, alpha_hi, *pipe, beta_lo, beta_hi, n_scan, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt,
                                    d_alpha_out, d_beta_out, d_workspace, (hipStream_t)stream));
     return RTUS_OK;
@@ -1776,26 +1728,21 @@ extern "C" int rtus_tt_pipe(const rtus_lens* lens, double alpha_lo, double alpha
 {
     int st = check_pipe(lens, alpha_lo, alpha_hi, pipe, beta_lo, beta_hi, n_scan, xe, ze, n_e, xf, zf, n_f, tt);
     if (st) return st;
-    const size_t tot = (size_t)n_e * n_f, wsb = rtus_pipe_ws_bytes(n_e, n_scan);
+    const size_t tot = (size_t)n_e * n_f;
     Session S;
-    if ((st = S.open(device, 2 * al256(8 * (size_t)n_e) + 2 * al256(8 * (size_t)n_f) +
-                                 (1 + (alpha_out ? 1 : 0) + (beta_out ? 1 : 0)) * al256(8 * tot) + al256(wsb))))
-        return st;
-    double *dxe, *dze, *dxf, *dzf;
-    S.upload(dxe, xe, n_e);
-    S.upload(dze, ze, n_e);
-    S.upload(dxf, xf, n_f);
-    S.upload(dzf, zf, n_f);
-    double* dtt = S.take<double>(tot);
-    double* dal = alpha_out ? S.take<double>(tot) : nullptr;
-    double* dbe = beta_out ? S.take<double>(tot) : nullptr;
-    void* ws = S.take<char>(wsb);
-    HIP_TRY(S.flush());
+    if ((st = S.open(device))) return st;
+    double *dxe, *dze, *dxf, *dzf, *dtt, *dal, *dbe;
+    char* ws;
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dal, alpha_out, tot);
+    S.out(dbe, beta_out, tot);
+    S.scratch(ws, rtus_pipe_ws_bytes(n_e, n_scan));
+    if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tt_pipe(*lens, alpha_lo, alpha_hi, *pipe, beta_lo, beta_hi, n_scan, dxe, dze, n_e, dxf, dzf, n_f, dtt, dal, dbe,
                                    ws, S.a->stream));
-    S.download(tt, dtt, tot);
-    S.download(alpha_out, dal, tot);
-    S.download(beta_out, dbe, tot);
-    HIP_TRY(S.finish());
-    return RTUS_OK;
+    return S.finish();
 }
