@@ -813,7 +813,9 @@ int rtus_tfm_weighted(const float *a, int n_tx, int n_rx, int n_t, double fs, do
  * pipe entry point's angles.
  * Guarantee: beta_lo .. beta_hi is scanned at n_scan equally spaced points; every interior local minimum whose neighbouring
  * stationary points of T(beta) lie at least one scan step away is found.  A missed minimum can only make an entry later (or NaN),
- * never earlier.
+ * never earlier.  The three earliest minima (by an fp32 estimate of T) are kept; each is refined and put to rules 1-2 in turn, the
+ * third however late it is while the first two were rejected, and otherwise when its estimate is within 4e-6 of the qualifying
+ * one's.  A fourth minimum is never looked at (none of the tested geometries has one: tests/test_gpu_pipe_branches.py).
  * Determinism: an entry depends only on its element, its focal point and the parameters, not on which other elements or points
  * share the call.
  * Rejected: a pipe that touches the lens, r_outer >= min over alpha in [alpha_lo, alpha_hi] of |P(alpha) - Cp| (RTUS_ERR_INVALID_ARG,

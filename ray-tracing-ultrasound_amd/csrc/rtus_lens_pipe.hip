@@ -288,12 +288,14 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
 #pragma unroll
             for (int q = 1; q < PIPE_EB; ++q) { et[kk] = q == e ? bt[q][kk] : et[kk]; ej[kk] = q == e ? bj[q][kk] : ej[kk]; }
         }
-        const float margin = 4e-6f * et[0];
+        // the third bracket is skipped only once an earlier one has given a qualifying time and the fp32 estimate puts the third
+        // clearly (4e-6) after it; while the earlier ones were rejected by a rule it is refined however late it is
+        float tb = INFINITY;                                       // fp32 time of the bracket that gave best
         double best = NAN, bA = NAN, bB = NAN;
         for (int kk = 0; kk < PIPE_K; ++kk) {
             const int j = kk == 0 ? ej[0] : (kk == 1 ? ej[1] : ej[2]);
             const float tk = kk == 0 ? et[0] : (kk == 1 ? et[1] : et[2]);
-            if (!fok || j < 0 || (kk >= 2 && !(tk <= et[0] + margin))) continue;
+            if (!fok || j < 0 || (kk >= 2 && !(tk <= fmaf(4e-6f, tb, tb)))) continue;
             // the fp32 scan saw dT < 0 at beta_j and > 0 at beta_j+1: the fp64 bracket (beta_j-1 .. beta_j+2 at most)
             int jl = j, jh = j + 1;
             double awl = alr[jl], awh = alr[jh];
@@ -337,7 +339,7 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
             const double nx = fma(tc, sx, cx), nz = fma(tc, sz, cz);
             const bool clear = fma(nx, nx, nz * nz) >= rin2;
             if (!(outside && clear && isfinite(v.t))) continue;
-            if (isnan(best) || v.t < best) { best = v.t; bA = v.alpha; bB = x; }
+            if (isnan(best) || v.t < best) { best = v.t; bA = v.alpha; bB = x; tb = tk; }
         }
         a.tt[o] = best;
         if (a.alpha_out) a.alpha_out[o] = bA;

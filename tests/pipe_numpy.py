@@ -114,13 +114,18 @@ def _dT(lens, pipe, xa, za, xf, zf, beta, a_lo, a_hi):
     return d1, Tl + lv / pipe.c3, al, px, pz, qx, qz
 
 
-def qualifies(px, pz, qx, qz, xf, zf, pipe):
-    """rule 1: the water segment L -> Q arrives from outside the circle; rule 2: the wall segment Q -> F keeps r_inner off Cp"""
+def rules(px, pz, qx, qz, xf, zf, pipe):
+    """-> (rule 1: the water segment L -> Q arrives from outside the circle, rule 2: the wall segment Q -> F keeps r_inner off Cp)"""
     cx, cz = qx - pipe.x0, qz
     outside = (qx - px) * cx + (qz - pz) * cz < 0
     sx, sz = xf - qx, zf - qz
     t = np.clip(-(cx * sx + cz * sz) / (sx * sx + sz * sz), 0.0, 1.0)
     clear = np.hypot(cx + t * sx, cz + t * sz) >= pipe.ri
+    return outside, clear
+
+
+def qualifies(px, pz, qx, qz, xf, zf, pipe):
+    outside, clear = rules(px, pz, qx, qz, xf, zf, pipe)
     return outside & clear
 
 
@@ -129,9 +134,11 @@ def default_n_scan(r_outer, b_lo=-np.pi / 2, b_hi=np.pi / 2, arc=0.25e-3):
 
 
 def table(lens, pipe, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, b_lo=-np.pi / 2, b_hi=np.pi / 2, n_scan=None, pairs=None,
-          dense=4, iters=60):
+          dense=4, iters=60, detail=False):
     """-> dict t, alpha, beta [n_e, n_f] (or [n_pairs] for pairs = (ie, jf) index arrays) and flag: an interior minimum of T has a
-    neighbouring stationary point closer than one scan step of the kernel (such entries may be found late by the kernel)"""
+    neighbouring stationary point closer than one scan step of the kernel (such entries may be found late by the kernel).
+    detail: also n_min, the interior minima of T found on the dense grid; rank, how many of them are earlier than the winner (-1
+    without a winner); rej1 / rej2, how many of those earlier ones (of all of them without a winner) fail rule 1 / rule 2"""
     xe, ze, xf, zf = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (xe, ze, xf, zf))
     if pairs is None:
         ie, jf = (a.ravel() for a in np.meshgrid(np.arange(xe.size), np.arange(xf.size), indexing="ij"))
@@ -153,6 +160,7 @@ def table(lens, pipe, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, b_lo=-
     P = ie.size
     out_t, out_a, out_b = np.full(P, np.nan), np.full(P, np.nan), np.full(P, np.nan)
     flag = np.zeros(P, dtype=bool)
+    m_p, m_T, m_1, m_2 = [], [], [], []                                 # every refined minimum: entry, time, rule 1, rule 2
     fx, fz = xf[jf], zf[jf]
     rf = np.hypot(fx - pipe.x0, fz)
     inwall = (rf > pipe.ri) & (rf < pipe.r) & np.isfinite(xe[ie]) & np.isfinite(ze[ie])
@@ -193,11 +201,22 @@ def table(lens, pipe, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, b_lo=-
             if np.all(hi - lo <= 4e-16):
                 break
         _, T, a_, px_, pz_, qx_, qz_ = _dT(lens, pipe, xe[ia], ze[ia], xf[jf[p]], zf[jf[p]], x, a_lo, a_hi)
-        ok = qualifies(px_, pz_, qx_, qz_, xf[jf[p]], zf[jf[p]], pipe) & np.isfinite(T)
+        r1, r2 = rules(px_, pz_, qx_, qz_, xf[jf[p]], zf[jf[p]], pipe)
+        ok = r1 & r2 & np.isfinite(T)
+        m_p.append(p); m_T.append(np.where(np.isfinite(T), T, np.inf)); m_1.append(r1); m_2.append(r2)
         for n in np.nonzero(ok)[0]:
             if not (T[n] >= out_t[p[n]]):
                 out_t[p[n]], out_a[p[n]], out_b[p[n]] = T[n], a_[n], x[n]
-    return {"t": out_t.reshape(shape), "alpha": out_a.reshape(shape), "beta": out_b.reshape(shape), "flag": flag.reshape(shape)}
+    o = {"t": out_t.reshape(shape), "alpha": out_a.reshape(shape), "beta": out_b.reshape(shape), "flag": flag.reshape(shape)}
+    if detail:
+        m_p, m_T = (np.concatenate(v) if v else np.zeros(0, dtype=t) for v, t in ((m_p, np.intp), (m_T, np.float64)))
+        m_1, m_2 = (np.concatenate(v) if v else np.zeros(0, dtype=bool) for v in (m_1, m_2))
+        earlier = ~(m_T >= out_t[m_p])                                  # (no winner: every minimum)
+        count = lambda w: np.bincount(m_p, weights=w, minlength=P).astype(np.int64)      # noqa: E731
+        o["n_min"] = count(np.ones(m_p.size)).reshape(shape)
+        o["rank"] = np.where(np.isfinite(out_t), count(earlier), -1).reshape(shape)
+        o["rej1"], o["rej2"] = count(earlier & ~m_1).reshape(shape), count(earlier & ~m_2).reshape(shape)
+    return o
 
 
 def snell_residuals(lens, pipe, xe, ze, xf, zf, alpha, beta):

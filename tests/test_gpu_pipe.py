@@ -15,6 +15,9 @@ XE64 = (np.arange(64) - 31.5) * 0.6e-3                      # the reference aper
 ZE64 = np.full(64, O.D)
 LENS = O.Lens()
 CORNERS = [(r, off) for r in (0.01, 0.037, 0.06) for off in (-0.01, 0.0038, 0.01)]
+# the share of an input set that the oracle may flag (entries _compare excuses for being late): tests/test_gpu_skip.py's.  The
+# oracle flags nothing on the nine sweep-corner grids and on the production shape's 2000 sampled pairs.
+FLAG_CAP = 2e-3
 
 
 def _params(rtus, r_outer, off):
@@ -53,6 +56,7 @@ def test_against_the_oracle_at_the_sweep_corners(rtus, r_outer, off):
     tt, al, be = rtus.travel_time_pipe(xe, ze, xf, zf, r_inner=ri, params=p, return_path=True)
     pipe = O.Pipe(r_outer, off, ri)
     o = O.table(LENS, pipe, xe, ze, xf, zf)
+    assert o["flag"].mean() <= FLAG_CAP
     both = _compare(tt, o, (r_outer, off))
     assert np.isnan(tt[:, -3:]).all()
     assert both.mean() > 0.5
@@ -199,6 +203,7 @@ def test_production_shape(rtus):
     rng = np.random.default_rng(7)
     ie, jf = rng.integers(0, 64, 2000), rng.integers(0, xf.size, 2000)
     o = O.table(LENS, O.Pipe(0.037, 0.0038, 0.029), XE64, ZE64, xf, zf, pairs=(ie, jf))
+    assert o["flag"].mean() <= FLAG_CAP
     _compare(tt[ie, jf], o, "production")
     assert np.isfinite(tt).mean() > 0.9
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device="cuda")      # noqa: E731

@@ -185,3 +185,116 @@ def test_python_layer_before_any_gpu_call(rtus):
     r = np.hypot(xf - 0.0038, zf).reshape(4, 5)
     th = np.arctan2(xf - 0.0038, zf).reshape(4, 5)
     assert np.allclose(r, np.linspace(0.03, 0.036, 4)[:, None]) and np.allclose(th, np.linspace(-0.5, 0.5, 5)[None, :])
+
+
+def _recount(pipe, xe, ze, xf, zf, n_grid=4033):
+    """every interior minimum of T(beta) of one (element, point) on a grid eight times the oracle's, each refined by plain bisection
+    of T': (T, alpha, beta, rule 1, rule 2, margin of rule 2 [m]) sorted by T — O.table's detail fields, worked out one entry at a
+    time in scalar arithmetic"""
+    a = (-O.ALPHA_MAX, O.ALPHA_MAX)
+    beta = np.linspace(-np.pi / 2, np.pi / 2, n_grid)
+    d1 = O._dT(LENS, pipe, xe, ze, xf, zf, beta, *a)[0]
+    found = []
+    for i in np.nonzero((d1[:-1] < 0) & (d1[1:] >= 0))[0]:
+        lo, hi = beta[i], beta[i + 1]
+        for _ in range(100):
+            mid = 0.5 * (lo + hi)
+            if O._dT(LENS, pipe, xe, ze, xf, zf, mid, *a)[0] < 0:
+                lo = mid
+            else:
+                hi = mid
+        b = 0.5 * (lo + hi)
+        _, T, al, px, pz, qx, qz = (float(v) for v in O._dT(LENS, pipe, xe, ze, xf, zf, b, *a))
+        outside = (qx - px) * (qx - pipe.x0) + (qz - pz) * qz < 0
+        # the wall segment's point nearest to the centre (pipe.x0, 0)
+        sx, sz, cx, cz = xf - qx, zf - qz, qx - pipe.x0, qz
+        t = min(max(-(cx * sx + cz * sz) / (sx * sx + sz * sz), 0.0), 1.0)
+        near = float(np.hypot(cx + t * sx, cz + t * sz))
+        found.append((T, al, b, bool(outside), near >= pipe.ri, near - pipe.ri))
+    return sorted(found)
+
+
+def _thin_wall_case():
+    """the 10 mm pipe 3.8 mm off the axis with a 0.5 mm wall: up to three minima per entry, the earliest often through the bore"""
+    pipe = O.Pipe(0.01, 0.0038, 0.0095)
+    xe, ze = np.array([-0.0189, -0.0081, 0.0189]), np.full(3, O.D)          # (-8.1 mm: element 18 of the reference's 64)
+    rr, th = np.meshgrid([0.0097, 0.00984], np.r_[np.linspace(-1.5, 1.5, 21), -1.1, -1.0875, -1.075], indexing="ij")
+    return pipe, xe, ze, (pipe.x0 + rr * np.sin(th)).ravel(), (rr * np.cos(th)).ravel()
+
+
+def test_oracle_detail_against_a_recount():
+    pipe, xe, ze, xf, zf = _thin_wall_case()
+    o = O.table(LENS, pipe, xe, ze, xf, zf, detail=True)
+    plain = O.table(LENS, pipe, xe, ze, xf, zf)
+    for k in ("t", "alpha", "beta", "flag"):
+        assert np.array_equal(o[k], plain[k], equal_nan=True)
+    assert set(o) == set(plain) | {"n_min", "rank", "rej1", "rej2"}
+    seen = set()
+    for i in range(xe.size):
+        for j in range(xf.size):
+            if o["flag"][i, j]:                               # (stationary points closer than a scan step: the grids may differ)
+                continue
+            m = _recount(pipe, xe[i], ze[i], xf[j], zf[j])
+            ok = [k for k, v in enumerate(m) if v[3] and v[4]]
+            rank = ok[0] if ok else -1
+            early = m[:rank] if ok else m
+            want = (len(m), rank, sum(not v[3] for v in early), sum(not v[4] for v in early))
+            assert (o["n_min"][i, j], o["rank"][i, j], o["rej1"][i, j], o["rej2"][i, j]) == want, (i, j, want)
+            if ok:
+                assert abs(o["t"][i, j] - m[rank][0]) <= 1e-14 * m[rank][0] and abs(o["beta"][i, j] - m[rank][2]) <= 1e-9
+            else:
+                assert np.isnan(o["t"][i, j])
+            seen.add(want[:2])
+    # the case holds what it is for: one, two and three minima, winners of every rank, entries without a winner
+    assert {(1, 0), (2, 0), (2, 1), (3, 2)} <= seen and any(r == -1 and n >= 1 for n, r in seen), sorted(seen)
+    assert (~o["flag"]).mean() > 0.9
+
+
+def _mp_rules(a, b, xf, zf, pipe):
+    """the two validity rules at the path (alpha, beta) in mpmath -> (rule 1, rule 2, margin of rule 2)"""
+    c1, c2, d = mp.mpf(O.C1), mp.mpf(O.C2), mp.mpf(O.L0) + mp.mpf(O.H0)
+    Tl = mp.mpf(O.L0) / c1 + mp.mpf(O.H0) / c2
+    A, Cc = c1 ** 2 / c2 ** 2 - 1, c1 ** 2 * Tl ** 2 - d ** 2
+    B = 2 * d * mp.cos(a) - 2 * Tl * c1 ** 2 / c2
+    h = (-B - mp.sqrt(B ** 2 - 4 * A * Cc)) / (2 * A)
+    px, pz = h * mp.sin(a), h * mp.cos(a)
+    cx, cz = mp.mpf(pipe.r) * mp.sin(b), mp.mpf(pipe.r) * mp.cos(b)
+    qx, qz = mp.mpf(pipe.x0) + cx, cz
+    sx, sz = mp.mpf(float(xf)) - qx, mp.mpf(float(zf)) - qz
+    t = min(max(-(cx * sx + cz * sz) / (sx * sx + sz * sz), mp.mpf(0)), mp.mpf(1))
+    near = mp.sqrt((cx + t * sx) ** 2 + (cz + t * sz) ** 2)
+    return (qx - px) * cx + (qz - pz) * cz < 0, near >= mp.mpf(pipe.ri), near - mp.mpf(pipe.ri)
+
+
+@pytest.mark.parametrize("case", ["third minimum", "second minimum"])
+def test_oracle_selection_against_mpmath(case):
+    """an entry whose earliest minima are rejected by a rule: every minimum of the entry is solved jointly in 40 digits, the rules
+    are applied to the 40-digit paths, and the oracle's entry is the earliest one that qualifies there"""
+    if case == "third minimum":
+        pipe, xe, ze, xf, zf = _thin_wall_case()
+        i, want_rank = 1, 2
+        j = int(np.argmin(np.hypot(xf - (pipe.x0 + 0.00984 * np.sin(-1.0875)), zf - 0.00984 * np.cos(-1.0875))))
+    else:
+        pipe, xe, ze = O.Pipe(0.037, 0.01, 0.0296), XE, ZE
+        xf, zf = pipe.x0 + 0.0335 * np.sin(np.array([-1.2, -0.9, 0.9, 1.2])), 0.0335 * np.cos(np.array([-1.2, -0.9, 0.9, 1.2]))
+        o = O.table(LENS, pipe, xe, ze, xf, zf, detail=True)
+        i, j = (int(v[0]) for v in np.nonzero((o["rank"] == 1) & ~o["flag"]))
+        want_rank = 1
+    o = O.table(LENS, pipe, xe, ze, xf, zf, detail=True)
+    assert o["rank"][i, j] == want_rank and not o["flag"][i, j] and o["n_min"][i, j] == want_rank + 1
+    minima = _recount(pipe, xe[i], ze[i], xf[j], zf[j])
+    assert len(minima) == want_rank + 1
+    solved = []
+    for T, al, be, r1, r2, margin in minima:
+        t, a, b = _mp_solve(xe[i], ze[i], xf[j], zf[j], pipe, al, be)
+        assert abs(float(t) - T) <= 1e-14 * T and abs(float(a) - al) <= 1e-9 and abs(float(b) - be) <= 1e-9
+        m1, m2, mm = _mp_rules(a, b, xf[j], zf[j], pipe)
+        assert (bool(m1), bool(m2)) == (r1, r2) and abs(float(mm)) > 1e-6          # no rule decided by rounding
+        solved.append((t, bool(m1) and bool(m2), a, b))
+    solved.sort(key=lambda v: v[0])
+    assert [v[1] for v in solved] == [False] * want_rank + [True]
+    t, _, a, b = solved[want_rank]
+    assert abs(float(t) - o["t"][i, j]) <= 1e-14 * o["t"][i, j]
+    assert abs(float(a) - o["alpha"][i, j]) <= 1e-9 and abs(float(b) - o["beta"][i, j]) <= 1e-9
+    assert (o["rej1"][i, j], o["rej2"][i, j]) == (0, want_rank)
+    assert float(solved[want_rank][0] / solved[0][0]) - 1 > 1e-3 or want_rank == 1           # far outside any fp32 tie margin
