@@ -11,6 +11,9 @@
 
 #define RTUS_PI_2 1.57079632679489661923
 
+// the pieces of a device workspace are 256-byte aligned
+static inline size_t rtus_al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 // Lens constants hoisted out of the per-ray math (all wave-uniform -> SGPRs).
 // Restates the scalar prologue of h_from_alpha / dh_from_alpha (main_rt.py:181-201).
 struct LensK {

@@ -12,10 +12,10 @@
 //      minimum by safeguarded Newton, least T wins, the ends included), never a continuation from a neighbouring lane: the bits
 //      depend on (element, beta_j) alone.  Into the workspace: alpha*, the fp32 time and -(c3 / c2) u . Q' (u the unit water
 //      direction at Q_j: c2 dT_lens / dbeta by the envelope theorem); the scan points (Q_j - Cp, Q'_j) as fp32.
-//   2. rtus_pipe_kernel: rtus_surface_kernel's scan.  Lanes are focal points, a workgroup owns PIPE_EB elements, scan points are
+//   2. rtus_pipe_kernel: the bracket scan of rtus_bracket.h.  Lanes are focal points, a workgroup owns PIPE_EB elements, scan points are
 //      tiled through LDS with the element terms as broadcasts; the lane's term v . Q' (v = (Q - F) / |Q - F|) is shared by the
 //      workgroup's elements.  A sign change - -> + of dT/dbeta is a bracket, ranked by an fp32 estimate of T; PIPE_K are kept.
-//   3. Each kept bracket is refined in fp64: safeguarded Newton in beta (bisection when a step leaves the bracket or T'' <= 0).
+//   3. Each kept bracket is refined in fp64 (rtus_bracket.h): the fp64 bracket, then safeguarded Newton in beta.
 //      Every iterate solves the inner alpha to convergence (lens_time<double, true>), warm-started from the table's alpha at the
 //      bracket's end and then from the previous iterate; a suspect inner minimum (g' < gp_min or pinned at an end: rtus_tt_lens's
 //      own test) takes the whole interval's least time instead (the set-up kernel's step).  T'' by implicit differentiation:
@@ -25,6 +25,7 @@
 // Determinism: an entry is made from its element, its focal point and the parameters only (the table entries it reads are
 // functions of (element, beta_j)); not of its slot, its lane or whatever else shares the call.
 #include "rtus_lens.h"
+#include "rtus_bracket.h"
 
 #define PIPE_EB 8           // elements per workgroup
 #define PIPE_TILE 64        // scan points per LDS tile
@@ -50,13 +51,19 @@ struct PipeArgs {
     double* __restrict__ al;           // [n_e][m]: alpha* fp64
 };
 
-// workspace: pts [m] | ent [n_e][m] | al [n_e][m], 256-byte aligned pieces
-static inline size_t al256p(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t rtus_pipe_ws_bytes(int n_e, int m)
+// workspace: pts [m] | ent [n_e][m] | al [n_e][m], 256-byte aligned pieces; returns its size (a: the pieces' pointers, nullable)
+static size_t pipe_ws(void* ws, int n_e, int m, PipeArgs* a)
 {
     const size_t nm = (size_t)n_e * (size_t)m;
-    return al256p(16 * (size_t)m) + al256p(8 * nm) + al256p(8 * nm);
+    const size_t o_ent = rtus_al256(16 * (size_t)m), o_al = o_ent + rtus_al256(8 * nm);
+    if (a) {
+        a->pts = (float4*)ws;
+        a->ent = (float2*)((char*)ws + o_ent);
+        a->al = (double*)((char*)ws + o_al);
+    }
+    return o_al + rtus_al256(8 * nm);
 }
+size_t rtus_pipe_ws_bytes(int n_e, int m) { return pipe_ws(nullptr, n_e, m, nullptr); }
 
 // the lens point and its tangent at alpha (lens_time's formulas)
 template <bool POLY>
@@ -203,15 +210,6 @@ __device__ PipeT pipe_T(const PipeArgs& a, double xa, double za, double xf, doub
     return o;
 }
 
-// insert (t, j) into the sorted triple (t0 <= t1 <= t2)
-#define PIPE_KEEP(t, j, T, J)                                                                               \
-    do {                                                                                                    \
-        const bool c0_ = (t) < T[0], c1_ = (t) < T[1], c2_ = (t) < T[2];                                    \
-        T[2] = c1_ ? T[1] : (c2_ ? (t) : T[2]);  J[2] = c1_ ? J[1] : (c2_ ? (j) : J[2]);                    \
-        T[1] = c0_ ? T[0] : (c1_ ? (t) : T[1]);  J[1] = c0_ ? J[0] : (c1_ ? (j) : J[1]);                    \
-        T[0] = c0_ ? (t) : T[0];                 J[0] = c0_ ? (j) : J[0];                                   \
-    } while (0)
-
 template <bool POLY>
 __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
 {
@@ -264,7 +262,7 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
                 const bool pos = g > s.x;                          // dT / dbeta > 0 (NaN: never)
                 if (pos && neg[e]) {                               // - -> + between beta_j-1 and beta_j: a minimum
                     const float t = s.y + tw;
-                    PIPE_KEEP(t, j - 1, bt[e], bj[e]);
+                    RTUS_KEEP3(t, j - 1, bt[e], bj[e]);
                 }
                 neg[e] = !pos && s.x == s.x;                       // (an element without a lens leg: neither side of a bracket)
             }
@@ -296,41 +294,17 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
             const int j = kk == 0 ? ej[0] : (kk == 1 ? ej[1] : ej[2]);
             const float tk = kk == 0 ? et[0] : (kk == 1 ? et[1] : et[2]);
             if (!fok || j < 0 || (kk >= 2 && !(tk <= fmaf(4e-6f, tb, tb)))) continue;
-            // the fp32 scan saw dT < 0 at beta_j and > 0 at beta_j+1: the fp64 bracket (beta_j-1 .. beta_j+2 at most)
-            int jl = j, jh = j + 1;
-            double awl = alr[jl], awh = alr[jh];
-            double lo = fma((double)jl, a.hb, a.b_lo), hi = fma((double)jh, a.hb, a.b_lo);
-            const double dlo = pipe_T<POLY>(a, xa, za, xf, zf, lo, awl).d1;
-            const double dhi = pipe_T<POLY>(a, xa, za, xf, zf, hi, awh).d1;
-            if (!(dlo < 0.0)) {                                    // the root is left of beta_j
-                if (!(dhi > 0.0) || j == 0) continue;
-                jh = jl; jl = j - 1;
-                awh = awl; awl = alr[jl];
-                hi = lo; lo = fma((double)jl, a.hb, a.b_lo);
-                if (!(pipe_T<POLY>(a, xa, za, xf, zf, lo, awl).d1 < 0.0)) continue;
-            } else if (!(dhi > 0.0)) {                             // ... or right of beta_j+1
-                if (j + 2 >= a.m) continue;
-                jl = jh; jh = j + 2;
-                awl = awh; awh = alr[jh];
-                lo = hi; hi = fma((double)jh, a.hb, a.b_lo);
-                if (!(pipe_T<POLY>(a, xa, za, xf, zf, hi, awh).d1 > 0.0)) continue;
-            }
-            // safeguarded Newton on dT / dbeta = 0 inside [lo, hi]; the inner alpha starts from the bracket's left end
-            double x = 0.5 * (lo + hi), aw = alr[jl];
-            const double tol = 1e-12;
-            PipeT v = pipe_T<POLY>(a, xa, za, xf, zf, x, aw);
-            for (int it = 0; it < 100; ++it) {
-                if (v.d1 == 0.0) break;
-                if (v.d1 < 0.0) lo = x; else hi = x;
-                const double step = -v.d1 / v.d2;
-                // converged: the last Newton step is taken even when it rounds onto x
-                const bool done = (v.d2 > 0.0 && fabs(step) <= tol) || !(hi - lo > tol);
-                double xn = x + step;
-                if (!(v.d2 > 0.0) || !(xn >= lo && xn <= hi)) xn = done ? x : 0.5 * (lo + hi);
-                x = xn;
-                v = pipe_T<POLY>(a, xa, za, xf, zf, x, aw);
-                if (done) break;
-            }
+            // the fp64 bracket (beta_j-1 .. beta_j+2 at most); the inner alpha at a scan point starts from the table's alpha there
+            int jl, jh;
+            auto d1_at = [&](int jp) {
+                double aw = alr[jp];
+                return pipe_T<POLY>(a, xa, za, xf, zf, fma((double)jp, a.hb, a.b_lo), aw).d1;
+            };
+            if (!rtus_bracket_fix(j, a.m, d1_at, jl, jh)) continue;
+            // Newton on dT / dbeta = 0 inside it; the inner alpha starts from the bracket's left end, then from the previous iterate
+            double x, aw = alr[jl];
+            const PipeT v = rtus_newton_min([&](double beta) { return pipe_T<POLY>(a, xa, za, xf, zf, beta, aw); },
+                                            fma((double)jl, a.hb, a.b_lo), fma((double)jh, a.hb, a.b_lo), 1e-12, x);
             // rule 1: the water segment L -> Q arrives from outside the circle; rule 2: the wall segment Q -> F keeps off the bore
             const double cx = v.qx - a.x_off, cz = v.qz;
             const bool outside = fma(v.qx - v.px, cx, (v.qz - v.pz) * cz) < 0.0;
@@ -363,10 +337,7 @@ hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, con
     a.k32f = (float)(P.c3 / L.c2); a.ic3f = (float)(1.0 / P.c3);
     a.m = n_scan; a.n_e = n_e; a.n_f = n_f;
     a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.alpha_out = alpha_out; a.beta_out = beta_out;
-    char* p = (char*)ws;
-    a.pts = (float4*)p; p += al256p(16 * (size_t)n_scan);
-    a.ent = (float2*)p; p += al256p(8 * (size_t)n_e * n_scan);
-    a.al = (double*)p;
+    pipe_ws(ws, n_e, n_scan, &a);
     const long long gs = ((long long)n_e * n_scan + RTUS_BLOCK - 1) / RTUS_BLOCK;
     const long long gy = ((long long)n_e + PIPE_EB - 1) / PIPE_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
     if (gy > 65535 || gx > 0x7fffffffLL || gs > 0x7fffffffLL) return hipErrorInvalidValue;

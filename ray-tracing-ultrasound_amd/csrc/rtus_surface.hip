@@ -40,7 +40,10 @@
 // scan point) and tests -(u + a_d s') > ng (T_in' = -(p + q_d s'), envelope theorem); the bracket estimate is T_in + st1.  The
 // refine solves u to convergence in fp64 (skip_inner) inside surf_T_skip.  The set-up kernel also reduces max s (smin[1]) for
 // the rule zb > max s.
+//
+// The kept triple, the fp64 bracket of step 3 and its Newton are rtus_bracket.h's, shared with rtus_lens_pipe.hip.
 #include "rtus_device.h"
+#include "rtus_bracket.h"
 
 // no implicit contraction: the fma()s are written out, so every element slot's inlined copy of the arithmetic rounds alike
 #pragma clang fp contract(off)
@@ -74,11 +77,10 @@ struct SurfArgs {
 };
 
 // workspace layout (256-byte aligned pieces): M [n_s] | Thomas scratch [n_s] | coef [4 (n_s - 1)] | pts [m] | smin, smax
-static inline size_t al256s(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline __host__ __device__ int surf_points(int n_s) { return SURF_SUB * (n_s - 1) + 1; }
 size_t rtus_surface_ws_bytes(int n_s)
 {
-    return 2 * al256s(8 * (size_t)n_s) + al256s(32 * (size_t)(n_s - 1)) + al256s(16 * (size_t)surf_points(n_s)) + 256;
+    return 2 * rtus_al256(8 * (size_t)n_s) + rtus_al256(32 * (size_t)(n_s - 1)) + rtus_al256(16 * (size_t)surf_points(n_s)) + 256;
 }
 
 struct SurfWs {
@@ -89,10 +91,10 @@ static SurfWs surf_ws(void* ws, int n_s)
 {
     char* p = (char*)ws;
     SurfWs w;
-    w.M = (double*)p;  p += al256s(8 * (size_t)n_s);
-    w.cp = (double*)p; p += al256s(8 * (size_t)n_s);
-    w.coef = (double*)p; p += al256s(32 * (size_t)(n_s - 1));
-    w.pts = (float4*)p; p += al256s(16 * (size_t)surf_points(n_s));
+    w.M = (double*)p;  p += rtus_al256(8 * (size_t)n_s);
+    w.cp = (double*)p; p += rtus_al256(8 * (size_t)n_s);
+    w.coef = (double*)p; p += rtus_al256(32 * (size_t)(n_s - 1));
+    w.pts = (float4*)p; p += rtus_al256(16 * (size_t)surf_points(n_s));
     w.smin = (double*)p;
     return w;
 }
@@ -303,37 +305,10 @@ __device__ __forceinline__ double surf_refine(TF T_at, BF band, int m, double x0
         const int j = k == 0 ? j0 : (k == 1 ? j1 : j2);
         const float tk = k == 0 ? t0 : (k == 1 ? t1 : t2);
         if (!ok || j < 0 || (k >= 2 && !(tk <= t0 + margin))) continue;
-        // the fp32 scan saw T' < 0 at P_j and > 0 at P_j+1; find the fp64 bracket (P_j-1 .. P_j+2 at most)
-        double lo = fma((double)j, hq, x0), hi = fma((double)(j + 1), hq, x0);
-        const double dlo = T_at(lo).d1;
-        const double dhi = T_at(hi).d1;
-        if (!(dlo < 0.0)) {                                  // the root is left of P_j
-            if (!(dhi > 0.0) || j == 0) continue;
-            hi = lo;
-            lo = fma((double)(j - 1), hq, x0);
-            if (!(T_at(lo).d1 < 0.0)) continue;
-        } else if (!(dhi > 0.0)) {                           // ... or right of P_j+1
-            if (j + 2 >= m) continue;
-            lo = hi;
-            hi = fma((double)(j + 2), hq, x0);
-            if (!(T_at(hi).d1 > 0.0)) continue;
-        }
-        // safeguarded Newton on T' = 0 inside [lo, hi], T'(lo) < 0 < T'(hi)
-        double x = 0.5 * (lo + hi);
-        const double tol = 1e-10 * hq;
-        Tder v = T_at(x);
-        for (int it = 0; it < 100; ++it) {
-            if (v.d1 == 0.0) break;
-            if (v.d1 < 0.0) lo = x; else hi = x;
-            const double step = -v.d1 / v.d2;
-            // converged: the last Newton step is taken even when it rounds onto x (a bisection there would jump away from the root)
-            const bool done = (v.d2 > 0.0 && fabs(step) <= tol) || !(hi - lo > tol);
-            double xn = x + step;
-            if (!(v.d2 > 0.0) || !(xn >= lo && xn <= hi)) xn = done ? x : 0.5 * (lo + hi);
-            x = xn;
-            v = T_at(x);
-            if (done) break;
-        }
+        int jl, jh;
+        if (!rtus_bracket_fix(j, m, [&](int jp) { return T_at(fma((double)jp, hq, x0)).d1; }, jl, jh)) continue;
+        double x;
+        const Tder v = rtus_newton_min(T_at, fma((double)jl, hq, x0), fma((double)jh, hq, x0), 1e-10 * hq, x);
         if (!band(x)) continue;
         if (isnan(best) || v.t < best) { best = v.t; bx = x; }
     }
@@ -341,15 +316,6 @@ __device__ __forceinline__ double surf_refine(TF T_at, BF band, int m, double x0
     if (xent_out) *xent_out = bx;
     return bx;
 }
-
-// insert (t, j) into the sorted triple (t0 <= t1 <= t2): selects on values (references invite a phi of pointers -> scratch)
-#define SURF_KEEP(t, j, T, J)                                                                               \
-    do {                                                                                                    \
-        const bool c0_ = (t) < T[0], c1_ = (t) < T[1], c2_ = (t) < T[2];                                    \
-        T[2] = c1_ ? T[1] : (c2_ ? (t) : T[2]);  J[2] = c1_ ? J[1] : (c2_ ? (j) : J[2]);                    \
-        T[1] = c0_ ? T[0] : (c1_ ? (t) : T[1]);  J[1] = c0_ ? J[0] : (c1_ ? (j) : J[1]);                    \
-        T[0] = c0_ ? (t) : T[0];                 J[0] = c0_ ? (j) : J[0];                                   \
-    } while (0)
 
 // the kernel's instantiations: element rows, plane-wave rows, element rows of a skip leg
 enum SurfMode { SURF_ELEM = 0, SURF_PW = 1, SURF_SKIP = 2 };
@@ -475,7 +441,7 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
                 const bool pos = g2 > ng[e];
                 if (pos && neg[e]) {                                    // - -> + between P_j-1 and P_j: a minimum
                     const float t = fmaf(tin, a.ic2f, ((const float*)&st1[jj][0])[e]);
-                    SURF_KEEP(t, j - 1, bt[e], bj[e]);
+                    RTUS_KEEP3(t, j - 1, bt[e], bj[e]);
                 }
                 if constexpr (MODE == SURF_PW) neg[e] = !pos && ng[e] == ng[e];       // out of band (NaN): neither side of a bracket
                 else neg[e] = !pos;                                     // (T' = 0 counts as -; NaN: never +)
@@ -490,49 +456,74 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
         const int row = e0 + e;
         if (row < a.n_e) {
             const size_t o = (size_t)row * a.n_f + f;
-            if constexpr (MODE == SURF_PW) {
-                const PwAngle w = pw_angle(a.ang[row], a.xlo, a.xhi);
-                const double za = a.za;
-                auto T_at = [&](double x) {
-                    return surf_T_pw(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, w.sn, w.cs, w.xref, za, xf, zf, x);
-                };
-                auto band = [&](double x) {
+            // the mode's T(x), which roots count and whether the row has paths at all (PW: the aperture's depth in ze's place)
+            const PwAngle w = MODE == SURF_PW ? pw_angle(a.ang[row], a.xlo, a.xhi) : PwAngle{};
+            const double xe = MODE == SURF_PW ? 0.0 : a.xe[row], ze = MODE == SURF_PW ? a.za : a.ze[row], kap2 = a.kap * a.kap;
+            double uw = NAN;                                            // the skip leg's warm start, carried from call to call
+            auto T_at = [&](double x) {
+                if constexpr (MODE == SURF_PW)
+                    return surf_T_pw(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, w.sn, w.cs, w.xref, ze, xf, zf, x);
+                else if constexpr (MODE == SURF_SKIP)
+                    return surf_T_skip(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, kap2, a.umax, a.zb, xe, ze, xf, zf, x, uw);
+                else
+                    return surf_T(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x);
+            };
+            auto band = [&](double x) {
+                if constexpr (MODE == SURF_PW) {
                     double s, s1, s2;
                     spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, x, s, s1, s2);
-                    const double xb = fma(-(s - za), w.tn, x);
+                    const double xb = fma(-(s - ze), w.tn, x);
                     return xb >= a.xlo && xb <= a.xhi;
-                };
-                surf_refine(T_at, band, a.m, a.x0, a.hq, fok && w.ok && za < smin, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1],
-                            bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
-            } else if constexpr (MODE == SURF_ELEM) {
-                const double xe = a.xe[row], ze = a.ze[row];
-                auto T_at = [&](double x) { return surf_T(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_c2, xe, ze, xf, zf, x); };
-                auto band = [](double) { return true; };
-                surf_refine(T_at, band, a.m, a.x0, a.hq, fok && ze < smin, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1], bj[e][2],
-                            a.tt + o, a.xent ? a.xent + o : nullptr);
-            } else {                                                    // SURF_SKIP
-                const double xe = a.xe[row], ze = a.ze[row], inv_cd = inv_c2, kap2 = a.kap * a.kap;
-                double uw = NAN;
-                auto T_at = [&](double x) {
-                    return surf_T_skip(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, inv_c1, inv_cd, kap2, a.umax, a.zb, xe, ze, xf, zf, x, uw);
-                };
-                auto band = [](double) { return true; };
-                const double bx = surf_refine(T_at, band, a.m, a.x0, a.hq, fok && ze < smin && a.zb > smax, bt[e][0], bt[e][1], bt[e][2],
-                                              bj[e][0], bj[e][1], bj[e][2], a.tt + o, a.xent ? a.xent + o : nullptr);
-                if (a.xback) {                                          // the reflection point of the winning root
-                    double xb = NAN;
-                    if (!isnan(bx)) {
-                        double s, s1, s2, fu;
-                        spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, bx, s, s1, s2);
-                        const double h1 = a.zb - s, h2 = a.zb - zf, X = xf - bx;
-                        const double u = skip_inner(h1, h2, X, kap2, a.umax, skip_u0(h1, h2, X, a.umax), fu);
-                        xb = fma(h1, u / sqrt(fma(-u, u, 1.0)), bx);
-                    }
-                    a.xback[o] = xb;
                 }
+                return true;
+            };
+            const bool ok = fok && ze < smin && (MODE != SURF_PW || w.ok) && (MODE != SURF_SKIP || a.zb > smax);
+            const double bx = surf_refine(T_at, band, a.m, a.x0, a.hq, ok, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1], bj[e][2],
+                                          a.tt + o, a.xent ? a.xent + o : nullptr);
+            if (MODE == SURF_SKIP && a.xback) {                         // the reflection point of the winning root
+                double xb = NAN;
+                if (!isnan(bx)) {
+                    double s, s1, s2, fu;
+                    spline_eval(a.coef, a.n_s, a.x0, a.dx, a.inv_dx, bx, s, s1, s2);
+                    const double h1 = a.zb - s, h2 = a.zb - zf, X = xf - bx;
+                    const double u = skip_inner(h1, h2, X, kap2, a.umax, skip_u0(h1, h2, X, a.umax), fu);
+                    xb = fma(h1, u / sqrt(fma(-u, u, 1.0)), bx);
+                }
+                a.xback[o] = xb;
             }
         }
     }
+}
+
+// the origin of the fp32 scan coordinates: the extent's centre; depths stay absolute (zs is device memory, and a few cm of depth
+// is ~4e-9 m in fp32)
+static double surf_xo(double x0, double dx, int n_s) { return x0 + 0.5 * (double)(n_s - 1) * dx; }
+static const double surf_zo = 0.0;
+
+// what every mode's table launch passes: the profile, the speeds (c2: below the surface), the rows' count, the grid, the workspace
+static SurfArgs surf_args(double x0, double dx, int n_s, double c1, double c2, int n_rows, const double* xf, const double* zf, int n_f,
+                          double* tt, double* xent, const SurfWs& w)
+{
+    SurfArgs a = {};
+    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
+    a.c1 = c1; a.c2 = c2;
+    a.xo = surf_xo(x0, dx, n_s); a.zo = surf_zo;
+    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1);
+    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_rows; a.n_f = n_f;
+    a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
+    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
+    return a;
+}
+
+// the set-up kernel, then the table kernel of one mode
+template <int MODE>
+static hipError_t surf_launch(const SurfArgs& a, const double* zs, const SurfWs& w, hipStream_t s)
+{
+    const long long gy = ((long long)a.n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)a.n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, a.n_s, a.x0, a.dx, a.xo, a.zo, w);
+    hipLaunchKernelGGL(rtus_surface_kernel<MODE>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
 }
 
 hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_s, double c1, double c2, const double* xe,
@@ -540,22 +531,9 @@ hipError_t rtus_launch_tt_surface(double x0, double dx, const double* zs, int n_
                                   void* ws, hipStream_t s)
 {
     const SurfWs w = surf_ws(ws, n_s);
-    SurfArgs a;
-    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
-    a.c1 = c1; a.c2 = c2;
-    a.xo = x0 + 0.5 * (double)(n_s - 1) * dx;
-    a.zo = 0.0;                                   // (zs is device memory: depths stay absolute; a few cm of depth is ~4e-9 m in fp32)
-    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1);
-    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_e; a.n_f = n_f;
-    a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
-    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
-    a.ang = nullptr; a.xlo = a.xhi = a.za = 0.0;
-    a.zb = a.kap = a.umax = 0.0; a.zbr = a.kap2f = a.umaxf = 0.0f; a.xback = nullptr;
-    const long long gy = ((long long)n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
-    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
-    hipLaunchKernelGGL(rtus_surface_kernel<SURF_ELEM>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
-    return hipGetLastError();
+    SurfArgs a = surf_args(x0, dx, n_s, c1, c2, n_e, xf, zf, n_f, tt, xent, w);
+    a.xe = xe; a.ze = ze;
+    return surf_launch<SURF_ELEM>(a, zs, w, s);
 }
 
 // plane waves: angles in the elements' place (the set-up kernel and its workspace as above)
@@ -564,22 +542,9 @@ hipError_t rtus_launch_pw_surface(double x0, double dx, const double* zs, int n_
                                   void* ws, hipStream_t s)
 {
     const SurfWs w = surf_ws(ws, n_s);
-    SurfArgs a;
-    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
-    a.c1 = c1; a.c2 = c2;
-    a.xo = x0 + 0.5 * (double)(n_s - 1) * dx;
-    a.zo = 0.0;
-    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1);
-    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_a; a.n_f = n_f;
-    a.xe = nullptr; a.ze = nullptr; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
-    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
+    SurfArgs a = surf_args(x0, dx, n_s, c1, c2, n_a, xf, zf, n_f, tt, xent, w);
     a.ang = ang; a.xlo = xlo; a.xhi = xhi; a.za = za;
-    a.zb = a.kap = a.umax = 0.0; a.zbr = a.kap2f = a.umaxf = 0.0f; a.xback = nullptr;
-    const long long gy = ((long long)n_a + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
-    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
-    hipLaunchKernelGGL(rtus_surface_kernel<SURF_PW>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
-    return hipGetLastError();
+    return surf_launch<SURF_PW>(a, zs, w, s);
 }
 
 // skip legs: elements, the leg below the surface down in c_down to the backwall at z_back and up in c_up to the point
@@ -588,25 +553,13 @@ hipError_t rtus_launch_tt_surface_skip(double x0, double dx, const double* zs, i
                                        double* xent, double* xback, void* ws, hipStream_t s)
 {
     const SurfWs w = surf_ws(ws, n_s);
-    SurfArgs a;
-    a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
-    a.c1 = c1; a.c2 = c_down;
-    a.xo = x0 + 0.5 * (double)(n_s - 1) * dx;
-    a.zo = 0.0;
-    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c_down); a.k21f = (float)(c_down / c1);
-    a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_e; a.n_f = n_f;
-    a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
-    a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
-    a.ang = nullptr; a.xlo = a.xhi = a.za = 0.0;
+    SurfArgs a = surf_args(x0, dx, n_s, c1, c_down, n_e, xf, zf, n_f, tt, xent, w);
+    a.xe = xe; a.ze = ze;
     a.zb = z_back; a.kap = c_down / c_up; a.umax = a.kap < 1.0 ? a.kap : 1.0;
     a.zbr = (float)(z_back - a.zo); a.kap2f = (float)(a.kap * a.kap);
     a.umaxf = (float)a.umax * (1.0f - 1e-6f);                 // (the fp32 scan stays off the ends, where a_d or a_u is 0)
     a.xback = xback;
-    const long long gy = ((long long)n_e + SURF_EB - 1) / SURF_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
-    if (gy > 65535 || gx > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, a.xo, a.zo, w);
-    hipLaunchKernelGGL(rtus_surface_kernel<SURF_SKIP>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
-    return hipGetLastError();
+    return surf_launch<SURF_SKIP>(a, zs, w, s);
 }
 
 // the set-up kernel alone, for the consumers of a surface table in other files (rtus_amp.hip): the spline's coefficients land in
@@ -615,7 +568,6 @@ hipError_t rtus_launch_surface_setup(const double* zs, int n_s, double x0, doubl
 {
     const SurfWs w = surf_ws(ws, n_s);
     *coef = w.coef;
-    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, x0 + 0.5 * (double)(n_s - 1) * dx,
-                       0.0, w);
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, surf_xo(x0, dx, n_s), surf_zo, w);
     return hipGetLastError();
 }

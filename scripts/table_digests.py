@@ -1,0 +1,72 @@
+"""sha256 of every output array of the bracket-and-refine tables (rtus_tt_surface, rtus_pw_surface, rtus_tt_surface_skip, rtus_tt_pipe)
+at the shapes that scripts/surface_throughput.py, pwi_throughput.py, skip_throughput.py and pipe_throughput.py time at their
+defaults, and of rtus_tt_pipe on the thin-wall geometries and the alpha = +-1.05 rad window of tests/test_gpu_pipe_branches.py (the
+general-trigonometry instantiation).  The bytes are hashed, NaNs included.  Run once per library and compare the lines:
+    python scripts/table_digests.py > this.txt;  RTUS_LIB=variants/librtus_prev.so python scripts/table_digests.py > prev.txt
+A change that only moves code gives the same digests; one differing line means arithmetic or evaluation order changed."""
+import hashlib
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from importlib import import_module  # noqa: E402
+
+import rtus  # noqa: E402
+
+dev = import_module("ray-tracing-ultrasound_amd.device")
+f64 = dict(dtype=torch.float64, device="cuda")
+
+
+def show(case, **arrays):
+    for name, v in arrays.items():
+        v = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        print(f"{hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()} {case}:{name} {v.shape} finite {np.isfinite(v).mean():.4f}",
+              flush=True)
+
+
+# the curved-interface tables: 256-sample profile, 256^2 focal points
+x0, dx = -0.032, 0.064 / 255
+zs = 0.02 + 0.0015 * torch.sin(2 * torch.pi * (x0 + dx * torch.arange(256, **f64)) / 0.010)
+gx, gz = torch.meshgrid(torch.linspace(-0.03, 0.03, 256, **f64), torch.linspace(0.025, 0.065, 256, **f64), indexing="xy")
+xf, zf = gx.reshape(-1).contiguous(), gz.reshape(-1).contiguous()
+xe, ze = torch.linspace(-0.0192, 0.0192, 128, **f64), torch.zeros(128, **f64)
+new = lambda rows: torch.empty((rows, xf.numel()), **f64)      # noqa: E731
+tt, xent, xback = new(128), new(128), new(128)
+dev.tt_surface_dev(x0, dx, zs, 1480.0, 5900.0, xe, ze, xf, zf, out=tt, x_entry=xent)
+show("tt_surface", tt=tt, x_entry=xent)
+for mode, (cd, cu) in {"LL": (5900.0, 5900.0), "LT": (5900.0, 3230.0), "TL": (3230.0, 5900.0), "TT": (3230.0, 3230.0)}.items():
+    dev.tt_surface_skip_dev(x0, dx, zs, 1480.0, cd, cu, 0.07, xe, ze, xf, zf, out=tt, x_entry=xent, x_back=xback)
+    show("tt_surface_skip_" + mode, tt=tt, x_entry=xent, x_back=xback)
+xa = (np.arange(64) - 31.5) * 0.6e-3
+ang = torch.as_tensor(np.deg2rad(np.linspace(-15, 15, 31)), **f64)
+tt, xent = new(31), new(31)
+dev.pw_surface_dev(x0, dx, zs, 1480.0, 5900.0, ang, xa.min(), xa.max(), 0.0, xf, zf, out=tt, x_entry=xent)
+show("pw_surface", tt=tt, x_entry=xent)
+
+# the pipe-wall table at the production shape
+p = rtus.Params(r_outer=0.037, pipe_offset=0.0038)
+za = np.full(64, p.d)
+wx, wz = rtus.pipe_wall_grid(0.029 + 3e-5, 0.037 - 3e-5, 128, 256, -np.pi / 6, np.pi / 6, params=p)
+t = lambda v: torch.as_tensor(np.ascontiguousarray(v), **f64)      # noqa: E731
+out = [torch.empty((64, wx.size), **f64) for _ in range(3)]
+dev.tt_pipe_dev(t(xa), t(za), t(wx), t(wz), out=out[0], alpha_out=out[1], beta_out=out[2], r_inner=0.029, params=p)
+show("tt_pipe", tt=out[0], alpha=out[1], beta=out[2])
+
+
+# tests/test_gpu_pipe_branches.py's sets: thin walls and off-axis pipes, then the window past +-1 rad
+def wall_grid(off, ri, ro, n_r, n_th, th_lo=-1.5, th_hi=1.5, margin=1e-4):
+    rr, th = np.meshgrid(np.linspace(ri + margin, ro - margin, n_r), np.linspace(th_lo, th_hi, n_th), indexing="ij")
+    return (off + rr * np.sin(th)).ravel(), (rr * np.cos(th)).ravel()
+
+
+xe8, ze8 = xa[::9], za[::9]
+for name, (ro, off, ri, n_th) in {"thin10": (0.01, 0.0038, 0.0095, 241), "wall10": (0.01, 0.0038, 0.008, 61),
+                                  "off37p": (0.037, 0.01, 0.0296, 61), "off37m": (0.037, -0.01, 0.0296, 61)}.items():
+    wx, wz = wall_grid(off, ri, ro, 6, n_th)
+    tt, al, be = rtus.travel_time_pipe(xe8, ze8, wx, wz, r_inner=ri, params=rtus.Params(r_outer=ro, pipe_offset=off), return_path=True)
+    show("tt_pipe_" + name, tt=tt, alpha=al, beta=be)
+wx, wz = wall_grid(0.0038, 0.029, 0.037, 5, 41, -1.2, 1.2)
+tt, al, be = rtus.travel_time_pipe(xe8, ze8, wx, wz, r_inner=0.029, params=p, alpha_lo=-1.05, alpha_hi=1.05, return_path=True)
+show("tt_pipe_wide", tt=tt, alpha=al, beta=be)
