@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 110 /* 0.1.9: rtus_tt_pipe* (lens to pipe-wall travel times) */
+#define RTUS_VERSION 111 /* 0.1.10: rtus_tt_pipe_skip* (bore-reflected skip legs into the pipe wall) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -843,6 +843,44 @@ int rtus_tt_pipe(const rtus_lens *lens, double alpha_lo, double alpha_hi, const 
                  double beta_lo, double beta_hi, int n_scan,
                  const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
                  double *tt, double *alpha_out, double *beta_out, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * BORE-REFLECTED SKIP LEG into the pipe wall: the half-skip leg of multi-view TFM (LL, LT, TL, TT) for rtus_tt_pipe's geometry.
+ * NOT IN THE REFERENCE; checked against tests/pipe_skip_numpy.py, itself checked against a 40-digit joint solve in (alpha, beta,
+ * gamma) (tests/test_pipe_skip_cpu.py).
+ *
+ * Geometry and symbols are rtus_tt_pipe's; new is the reflection point on the bore, R(gamma) = Cp + r_inner (sin gamma, cos gamma).
+ * A skip path is E -> P(alpha) -> Q(beta) -> R(gamma) -> F:
+ *     T(beta) = T_lens(E, Q(beta)) + W(Q(beta), F)
+ *     W(Q, F) = min over gamma of |Q - R(gamma)| / c_down + |R(gamma) - F| / c_up
+ * c_down = pipe->c3 is the wall speed before the bounce, c_up the speed after it (a different speed: a mode conversion at the bore).
+ * T_lens is rtus_tt_pipe's lens leg.  gamma runs over the arc of the bore that Q and F both see, (Q - R) . (R - Cp) > 0 and
+ * (F - R) . (R - Cp) > 0: both wall segments leave R outwards, touch the convex bore nowhere else and stay inside the outer circle.
+ * W is the time at the interior local minimum on that arc.  On the arc both lengths are convex functions of gamma
+ * (d2|Q - R| / dgamma2 = r_outer r_inner (r_outer cos u - r_inner)(r_outer - r_inner cos u) / |Q - R|^3, u = gamma - beta, which
+ * is positive exactly where Q sees R; likewise for F), so for any pair of speeds there is at most one such minimum.  Where the arc is
+ * empty or the least time sits at an end of it (a grazing bounce; past the critical angle of a T -> L conversion) there is no W: such
+ * a beta is neither side of a bracket, as an element without a lens leg is in rtus_tt_pipe.
+ *     tt[e][f] = the least T over the interior local minima of T on (beta_lo, beta_hi) whose path satisfies rtus_tt_pipe's rule 1.
+ * NaN for an F not strictly inside the wall, for a non-finite element position and where no minimum qualifies.  alpha_out, beta_out,
+ * gamma_out [n_e][n_f] (nullable): the angles of the lens point, the entry point and the bounce (gamma = beta + u, not wrapped).
+ * Guarantee and selection among the three earliest minima: rtus_tt_pipe's; a minimum closer than one scan step to a beta without W
+ * may be missed as one closer than a scan step to another stationary point may.  Determinism: an entry depends only on its element,
+ * its focal point and the parameters.
+ * Rejected with RTUS_ERR_INVALID_ARG: everything rtus_tt_pipe rejects, r_inner <= 0 (no bore, no skip leg) and a c_up that is not
+ * finite and positive.  Limits (-5) and the workspace (-4; rtus_tt_pipe_skip_workspace_bytes, 256-byte aligned) as rtus_tt_pipe's.
+ * The _dev entry allocates nothing and does not synchronise (capturable).  Method and figures: DESIGN.md section 4 (pipe wall).
+ * ---------------------------------------------------------------------------------------- */
+size_t rtus_tt_pipe_skip_workspace_bytes(int n_e, int n_scan);
+int rtus_tt_pipe_skip_dev(const rtus_lens *lens, double alpha_lo, double alpha_hi, const rtus_pipe *pipe, double c_up,
+                          double beta_lo, double beta_hi, int n_scan,
+                          const double *d_xe, const double *d_ze, int n_e, const double *d_xf, const double *d_zf, int n_f,
+                          double *d_tt, double *d_alpha_out, double *d_beta_out, double *d_gamma_out,
+                          void *d_workspace, size_t workspace_bytes, void *stream);
+int rtus_tt_pipe_skip(const rtus_lens *lens, double alpha_lo, double alpha_hi, const rtus_pipe *pipe, double c_up,
+                      double beta_lo, double beta_hi, int n_scan,
+                      const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
+                      double *tt, double *alpha_out, double *beta_out, double *gamma_out, int device);
 
 #ifdef __cplusplus
 }

@@ -218,6 +218,15 @@ def lib():
     except AttributeError:                # a build from before version 110, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        L.rtus_tt_pipe_skip_workspace_bytes.argtypes = [ip, ip]
+        L.rtus_tt_pipe_skip_workspace_bytes.restype = C.c_size_t
+        L.rtus_tt_pipe_skip_dev.argtypes = [LP, dd, dd, PP, dd, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, vp, C.c_size_t, vp]
+        L.rtus_tt_pipe_skip.argtypes = [LP, dd, dd, PP, dd, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, ip]
+        L.rtus_tt_pipe_skip_dev.restype = L.rtus_tt_pipe_skip.restype = ip
+    except AttributeError:                # a build from before version 111, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -247,4 +256,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx",
            "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip",
            "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted",
-           "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe")
+           "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe",
+           "rtus_tt_pipe_skip_workspace_bytes", "rtus_tt_pipe_skip_dev", "rtus_tt_pipe_skip")

@@ -1009,3 +1009,42 @@ def pipe_wall_grid(r_inner, r_outer, n_r, n_theta, theta_lo, theta_hi, *, params
     th = np.linspace(float(theta_lo), float(theta_hi), int(n_theta))
     rr, tt = np.meshgrid(r, th, indexing="ij")
     return (float(p.pipe_offset) + rr * np.sin(tt)).ravel(), (rr * np.cos(tt)).ravel()
+
+
+def skip_travel_time_pipe(xe, ze, xf, zf, *, c_down, c_up=None, r_inner, params: Params = None, alpha_lo=None, alpha_hi=None,
+                          beta_lo=-np.pi / 2, beta_hi=np.pi / 2, n_scan=None, return_path=False, out=None, device=0):
+    """Bore-reflected skip leg into the pipe wall -> tt[n_e, n_f]: element -> lens -> water -> the pipe's outer circle -> the wall
+    at ``c_down`` -> a bounce off the bore (radius ``r_inner`` > 0) -> the wall at ``c_up`` (default ``c_down``; another speed is a
+    mode conversion at the bore) -> the point.  travel_time_pipe's geometry, scan and defaults; NaN for a point outside the wall or
+    without a qualifying path (no bounce that both the entry point and the point see).  ``return_path``: -> (tt, alpha, beta,
+    gamma), the angles of the lens point, the entry point and the bounce.  Definition: include/rtus.h (rtus_tt_pipe_skip).  Not in
+    the reference."""
+    c_up = c_down if c_up is None else c_up
+    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _pipe_args(params, c_down, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    tt = _out(out, (xe.size, xf.size), np.float64)
+    al, be, ga = (np.empty((xe.size, xf.size), dtype=np.float64) if return_path else None for _ in range(3))
+    st = _lib.lib().rtus_tt_pipe_skip(C.byref(lens), a_lo, a_hi, C.byref(pipe), float(c_up), b_lo, b_hi, n_scan, _ptr(xe), _ptr(ze), xe.size,
+                                      _ptr(xf), _ptr(zf), xf.size, _ptr(tt), _ptr(al), _ptr(be), _ptr(ga), int(device))
+    _lib.check(st, "rtus_tt_pipe_skip")
+    return (tt, al, be, ga) if return_path else tt
+
+
+def view_legs_pipe(c_l, c_t, r_inner, xe, ze, xf, zf, *, legs=LEGS, params: Params = None, alpha_lo=None, alpha_hi=None,
+                   beta_lo=-np.pi / 2, beta_hi=np.pi / 2, n_scan=None, device=0):
+    """The leg tables of multi-view TFM of the pipe wall -> {leg: tt [n_e, n_f]} for ``legs`` (default all six: L, T, LL, LT, TL,
+    TT), in the shape tfm_views takes.  The wall has speeds ``c_l`` / ``c_t`` and the bore ``r_inner``; the pipe and the lens are
+    ``params``'.  Direct legs: travel_time_pipe; skip legs (a bounce off the bore): skip_travel_time_pipe."""
+    legs = _legs_wanted(legs)
+    sp = {"L": float(c_l), "T": float(c_t)}
+    kw = dict(r_inner=r_inner, params=params, alpha_lo=alpha_lo, alpha_hi=alpha_hi, beta_lo=beta_lo, beta_hi=beta_hi, n_scan=n_scan,
+              device=device)
+    out = {}
+    for g in legs:
+        if len(g) == 1:
+            out[g] = travel_time_pipe(xe, ze, xf, zf, c3=sp[g], **kw)
+        else:
+            out[g] = skip_travel_time_pipe(xe, ze, xf, zf, c_down=sp[g[0]], c_up=sp[g[1]], **kw)
+    return out

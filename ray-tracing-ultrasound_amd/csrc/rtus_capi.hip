@@ -86,6 +86,9 @@ hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, con
                                const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
                                double* alpha_out, double* beta_out, void* ws, hipStream_t s);
 size_t rtus_pipe_ws_bytes(int n_e, int m);
+hipError_t rtus_launch_tt_pipe_skip(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double c_up, double b_lo, double b_hi,
+                                    int n_scan, const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f,
+                                    double* tt, double* alpha_out, double* beta_out, double* gamma_out, void* ws, hipStream_t s);
 hipError_t rtus_launch_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, const double* d, int n_v, float* out,
                                     hipStream_t s);
 
@@ -1744,5 +1747,57 @@ extern "C" int rtus_tt_pipe(const rtus_lens* lens, double alpha_lo, double alpha
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tt_pipe(*lens, alpha_lo, alpha_hi, *pipe, beta_lo, beta_hi, n_scan, dxe, dze, n_e, dxf, dzf, n_f, dtt, dal, dbe,
                                    ws, S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- lens -> pipe wall, bore-reflected skip leg
+// everything rtus_tt_pipe rejects, a pipe without a bore and a c_up that is not finite and positive
+static int check_pipe_skip(const rtus_lens* lens, double a_lo, double a_hi, const rtus_pipe* pipe, double c_up, double b_lo, double b_hi,
+                           int n_scan, const void* xe, const void* ze, int n_e, const void* xf, const void* zf, int n_f, const void* tt)
+{
+    const int st = check_pipe(lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    if (!(pipe->r_inner > 0) || !isfinite(c_up) || !(c_up > 0)) return RTUS_ERR_INVALID_ARG;
+    return RTUS_OK;
+}
+
+extern "C" size_t rtus_tt_pipe_skip_workspace_bytes(int n_e, int n_scan) { return rtus_tt_pipe_workspace_bytes(n_e, n_scan); }
+
+extern "C" int rtus_tt_pipe_skip_dev(const rtus_lens* lens, double alpha_lo, double alpha_hi, const rtus_pipe* pipe, double c_up,
+                                     double beta_lo, double beta_hi, int n_scan, const double* d_xe, const double* d_ze, int n_e,
+                                     const double* d_xf, const double* d_zf, int n_f, double* d_tt, double* d_alpha_out, double* d_beta_out,
+                                     double* d_gamma_out, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int st = check_pipe_skip(lens, alpha_lo, alpha_hi, pipe, c_up, beta_lo, beta_hi, n_scan, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_pipe_ws_bytes(n_e, n_scan), 256))) return st;
+    LAUNCH_TRY(rtus_launch_tt_pipe_skip(*lens, alpha_lo, alpha_hi, *pipe, c_up, beta_lo, beta_hi, n_scan, d_xe, d_ze, n_e, d_xf, d_zf, n_f,
+                                        d_tt, d_alpha_out, d_beta_out, d_gamma_out, d_workspace, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+extern "C" int rtus_tt_pipe_skip(const rtus_lens* lens, double alpha_lo, double alpha_hi, const rtus_pipe* pipe, double c_up, double beta_lo,
+                                 double beta_hi, int n_scan, const double* xe, const double* ze, int n_e, const double* xf,
+                                 const double* zf, int n_f, double* tt, double* alpha_out, double* beta_out, double* gamma_out, int device)
+{
+    int st = check_pipe_skip(lens, alpha_lo, alpha_hi, pipe, c_up, beta_lo, beta_hi, n_scan, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_e * n_f;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dxe, *dze, *dxf, *dzf, *dtt, *dal, *dbe, *dga;
+    char* ws;
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dal, alpha_out, tot);
+    S.out(dbe, beta_out, tot);
+    S.out(dga, gamma_out, tot);
+    S.scratch(ws, rtus_pipe_ws_bytes(n_e, n_scan));
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tt_pipe_skip(*lens, alpha_lo, alpha_hi, *pipe, c_up, beta_lo, beta_hi, n_scan, dxe, dze, n_e, dxf, dzf, n_f, dtt,
+                                        dal, dbe, dga, ws, S.a->stream));
     return S.finish();
 }

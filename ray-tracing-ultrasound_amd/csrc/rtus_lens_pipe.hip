@@ -24,6 +24,20 @@
 //
 // Determinism: an entry is made from its element, its focal point and the parameters only (the table entries it reads are
 // functions of (element, beta_j)); not of its slot, its lane or whatever else shares the call.
+//
+// The SKIP leg (rtus_tt_pipe_skip: Q -> a bounce off the bore at R(gamma) -> F, c_down before and c_up after it) is the same scan
+// and refine with the wall leg |Q - F| / c3 replaced by W(Q, F) = min over gamma of |Q - R| / c_down + |R - F| / c_up, an inner
+// solve that belongs to (beta, F) alone.  In the angles u = gamma - beta, v = gamma - theta_F (theta_F, r_F: F about the centre):
+//   |Q - R|^2 = (ro - ri)^2 + 4 ro ri sin^2(u / 2),  |R - F|^2 = (r_F - ri)^2 + 4 r_F ri sin^2(v / 2)
+//   h = dW_path / dgamma = A(u) + B(v),  A = ro ri sin u / (|Q - R| c_down),  B = r_F ri sin v / (|R - F| c_up)
+//   A' = ro ri (ro cos u - ri)(ro - ri cos u) / (|Q - R|^3 c_down) > 0 exactly where Q sees R (and B' likewise for F): on the arc
+//   that both see the path's time is convex, so W exists iff h < 0 at the arc's lower end and h > 0 at its upper end, the
+//   minimum is unique, and it lies between beta and theta_F (where the two sines have opposite signs).
+//   dW/dbeta = -A (envelope theorem), d2W/dbeta2 = A' B' / (A' + B') (implicit differentiation of h = 0).
+// The scan solves u in fp32 per (scan point, lane) by safeguarded Newton, warm-started in v from the previous scan point (a
+// function of (F, j) only); a beta without W is neither side of a bracket.  The refine solves it in fp64 at every iterate, beside
+// the inner alpha: two independent inner solves.  Only rule 1 applies (the wall segments keep off the bore by construction).
+#include <type_traits>
 #include "rtus_lens.h"
 #include "rtus_bracket.h"
 
@@ -128,6 +142,95 @@ __device__ __forceinline__ void pipe_q(const PipeArgs& a, double beta, double& q
     q1x = a.r_out * c; q1z = -a.r_out * s;
 }
 
+// ---- the skip leg's inner solve
+struct PipeSkip {
+    double icu, aQ, dQ;                // 1 / c_up; arccos(ri / ro): half the arc of the bore that Q sees; ro - ri
+    float icuf, aQf, dQf;
+    double* __restrict__ gamma_out;    // nullable
+};
+struct BoreW { double w, d1, d2, gamma, v; };    // W, dW/dbeta, d2W/dbeta2, the bounce's angle, v; NaN without W
+struct BoreK { double ro, ri, icd, icu, aQ, dQ, rF, thF, aF, dF; };      // bore_W's constants, passed by value (registers)
+
+#define RTUS_TWO_PI 6.283185307179586476925286766559
+// the arc's ends in u and the root's bracket inside it (lo1, hi1): false when the arc is empty or the root lies outside it
+template <class R>
+__device__ __forceinline__ bool bore_arc(R aQ, R aF, R dl, R& lo0, R& hi0, R& lo1, R& hi1)
+{
+    lo0 = aQ * R(-1) > dl - aF ? aQ * R(-1) : dl - aF;
+    hi0 = aQ < dl + aF ? aQ : dl + aF;
+    const R z0 = dl < R(0) ? dl : R(0), z1 = dl > R(0) ? dl : R(0);
+    lo1 = lo0 > z0 ? lo0 : z0;
+    hi1 = hi0 < z1 ? hi0 : z1;
+    return hi0 > lo0 && hi1 >= lo1;
+}
+
+// h = A icd + B icu and h' at u (Ag, Bg, Ap, Bp: the terms without / with the speeds), W the path's time
+__device__ __forceinline__ void bore_h(const BoreK& c, double u, double dl, double& h, double& Ag, double& Ap, double& Bp, double& W)
+{
+    double s2, c2, t2, e2;
+    sincos(0.5 * u, &s2, &c2);
+    sincos(0.5 * (u - dl), &t2, &e2);
+    const double su = 2.0 * s2 * c2, cu = fma(-2.0 * s2, s2, 1.0), sv = 2.0 * t2 * e2, cv = fma(-2.0 * t2, t2, 1.0);
+    const double rr = c.ro * c.ri, fr = c.rF * c.ri;
+    const double lq2 = fma(4.0 * rr * s2, s2, c.dQ * c.dQ), lf2 = fma(4.0 * fr * t2, t2, c.dF * c.dF);
+    const double lq = sqrt(lq2), lf = sqrt(lf2);
+    Ag = rr * su / lq;
+    Ap = rr * (fma(c.ro, cu, -c.ri) * fma(-c.ri, cu, c.ro)) / (lq2 * lq) * c.icd;
+    Bp = fr * (fma(c.rF, cv, -c.ri) * fma(-c.ri, cv, c.rF)) / (lf2 * lf) * c.icu;
+    h = fma(Ag, c.icd, fr * sv / lf * c.icu);
+    W = fma(lq, c.icd, lf * c.icu);
+}
+
+// W(Q(beta), F) in fp64: safeguarded Newton on h from the warm start vw (v of the previous call; NaN: from the end of the root's
+// bracket nearer to theta_F), bracket kept by the sign of h.  Everything by value (a pointer to a lane's local would put it in
+// scratch) and left to the inliner: marked noinline the call frame costs 104 B of scratch, inlined the kernel has none.
+__device__ BoreW bore_W(BoreK c, double v0, double beta)
+{
+    BoreW o;
+    o.w = o.d1 = o.d2 = o.gamma = o.v = NAN;
+    double dl = c.thF - beta;
+    dl = fma(-RTUS_TWO_PI, rint(dl * (1.0 / RTUS_TWO_PI)), dl);
+    double lo0, hi0, lo, hi, h, Ag, Ap, Bp, W;
+    if (!bore_arc<double>(c.aQ, c.aF, dl, lo0, hi0, lo, hi)) return o;
+    if (lo == lo0) { bore_h(c, lo0, dl, h, Ag, Ap, Bp, W); if (!(h < 0.0)) return o; }
+    if (hi == hi0) { bore_h(c, hi0, dl, h, Ag, Ap, Bp, W); if (!(h > 0.0)) return o; }
+    double u = v0 + dl;
+    if (!(u >= lo && u <= hi)) u = fmin(fmax(dl, lo), hi);
+    for (int it = 0; it < 80; ++it) {
+        bore_h(c, u, dl, h, Ag, Ap, Bp, W);
+        if (h == 0.0) break;
+        if (h < 0.0) lo = u; else hi = u;
+        const double step = -h / (Ap + Bp);
+        double un = u + step;
+        const bool done = fabs(step) <= 1e-14 || !(hi - lo > 1e-14);
+        if (!(un >= lo && un <= hi)) un = done ? u : 0.5 * (lo + hi);
+        u = un;
+        if (done) { bore_h(c, u, dl, h, Ag, Ap, Bp, W); break; }
+    }
+    o.w = W;
+    o.d1 = -Ag * c.icd;
+    o.d2 = Ap * Bp / (Ap + Bp);
+    o.gamma = beta + u;
+    o.v = u - dl;
+    return o;
+}
+
+// the scan's fp32 evaluation: h, h', Ag and W at u
+__device__ __forceinline__ void bore_h32(float rr, float fr, float ro, float ri, float rF, float dQ, float dF, float icd, float icu, float u,
+                                         float dl, float& h, float& hp, float& Ag, float& W)
+{
+    const float hu = 0.5f * u, hv = 0.5f * (u - dl);
+    const float s2 = __sinf(hu), c2 = __cosf(hu), t2 = __sinf(hv), e2 = __cosf(hv);
+    const float su = 2.0f * s2 * c2, cu = fmaf(-2.0f * s2, s2, 1.0f), sv = 2.0f * t2 * e2, cv = fmaf(-2.0f * t2, t2, 1.0f);
+    const float lq2 = fmaf(4.0f * rr * s2, s2, dQ * dQ), lf2 = fmaf(4.0f * fr * t2, t2, dF * dF);
+    const float iq = __builtin_amdgcn_rsqf(lq2), jf = __builtin_amdgcn_rsqf(lf2);
+    Ag = rr * su * iq;
+    h = fmaf(Ag, icd, fr * sv * jf * icu);
+    hp = fmaf(rr * (fmaf(ro, cu, -ri) * fmaf(-ri, cu, ro)) * (iq * iq * iq), icd,
+              fr * (fmaf(rF, cv, -ri) * fmaf(-ri, cv, rF)) * (jf * jf * jf) * icu);
+    W = fmaf(lq2 * iq, icd, lf2 * jf * icu);
+}
+
 template <bool POLY>
 __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_setup_kernel(PipeArgs a)
 {
@@ -154,10 +257,14 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_setup_kernel(PipeArgs a)
 
 // T(beta) and its first two derivatives for one (element, focal point), with the path's lens point and the inner alpha
 struct PipeT { double t, d1, d2, alpha, px, pz, qx, qz; };
+struct PipeTS : PipeT { double gamma, v; };
 
-template <bool POLY>
-__device__ PipeT pipe_T(const PipeArgs& a, double xa, double za, double xf, double zf, double beta, double& aw)
+// S...: nothing for the direct leg; (BoreK, double v0) for the skip leg: bore_W's constants and the inner gamma's warm start, by value
+template <bool POLY, class... S>
+__device__ std::conditional_t<(sizeof...(S) > 0), PipeTS, PipeT> pipe_T(const PipeArgs& a, double xa, double za, double xf, double zf,
+                                                                       double beta, double& aw, S... skip)
 {
+    constexpr bool SKIP = sizeof...(S) > 0;
     const LensConst<double>& k = a.k;
     double qx, qz, q1x, q1z;
     pipe_q(a, beta, qx, qz, q1x, q1z);
@@ -199,19 +306,30 @@ __device__ PipeT pipe_T(const PipeArgs& a, double xa, double za, double xf, doub
     const double gaq = -(fma(p1x, q1x, p1z * q1z) - uP * uQ) * il * inv_c2;     // d g / dQ . Q'
     double d2l = (fma(-uQ, uQ, QQ) * il + fma(ux, q2x, uz * q2z)) * inv_c2;
     if (interior) d2l -= gaq * gaq / gp;
-    // wall leg
-    const double vx0 = qx - xf, vz0 = qz - zf, mq = sqrt(fma(vx0, vx0, vz0 * vz0)), im = 1.0 / mq;
-    const double vx = vx0 * im, vz = vz0 * im, vQ = fma(vx, q1x, vz * q1z);
-    PipeT o;
-    o.t = fma(mq, a.ic3, T);
-    o.d1 = fma(uQ, inv_c2, vQ * a.ic3);
-    o.d2 = d2l + (fma(-vQ, vQ, QQ) * im + fma(vx, q2x, vz * q2z)) * a.ic3;
+    std::conditional_t<SKIP, PipeTS, PipeT> o;
+    if constexpr (SKIP) {
+        // wall legs: down to the bore and up to F
+        const BoreW w = bore_W(skip..., beta);
+        o.t = T + w.w;
+        o.d1 = fma(uQ, inv_c2, w.d1);
+        o.d2 = d2l + w.d2;
+        o.gamma = w.gamma;
+        o.v = w.v;
+    } else {
+        // wall leg
+        const double vx0 = qx - xf, vz0 = qz - zf, mq = sqrt(fma(vx0, vx0, vz0 * vz0)), im = 1.0 / mq;
+        const double vx = vx0 * im, vz = vz0 * im, vQ = fma(vx, q1x, vz * q1z);
+        o.t = fma(mq, a.ic3, T);
+        o.d1 = fma(uQ, inv_c2, vQ * a.ic3);
+        o.d2 = d2l + (fma(-vQ, vQ, QQ) * im + fma(vx, q2x, vz * q2z)) * a.ic3;
+    }
     o.alpha = alpha; o.px = px; o.pz = pz; o.qx = qx; o.qz = qz;
     return o;
 }
 
-template <bool POLY>
-__global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
+// the table kernel's body: the direct leg (SKIP false: k is not read) or the skip leg
+template <bool POLY, bool SKIP>
+__device__ __forceinline__ void pipe_table(const PipeArgs& a, const PipeSkip& k)
 {
     __shared__ float4 sp[PIPE_TILE];                         // the tile's scan points (Q - Cp, Q')
     __shared__ float2 sen[PIPE_TILE][PIPE_EB];               // per (point, element): -(c3 / c2) u . Q', T_lens
@@ -228,6 +346,19 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
         fok = rf > a.r_in && rf < a.r_out;
     }
     const float xfr = fok ? (float)(xf - a.x_off) : NAN, zfr = fok ? (float)zf : NAN;
+    // skip leg: F about the centre, and the scan's fp32 copies
+    BoreK L;                                                 // (rF, thF: F about the centre; aF = arccos(ri / rF); dF = rF - ri)
+    float rrf = 0.f, frf = 0.f, rof = 0.f, rif = 0.f, rFf = 0.f, dFf = 0.f, aFf = 0.f, vwf = NAN;
+    if constexpr (SKIP) {
+        const double dx = xf - a.x_off;
+        L.rF = sqrt(fma(dx, dx, zf * zf));
+        L.thF = atan2(dx, zf);
+        L.aF = acos(a.r_in / L.rF);
+        L.dF = L.rF - a.r_in;
+        L.ro = a.r_out; L.ri = a.r_in; L.icd = a.ic3; L.icu = k.icu; L.aQ = k.aQ; L.dQ = k.dQ;
+        rrf = (float)(a.r_out * a.r_in); frf = (float)(L.rF * a.r_in);
+        rof = (float)a.r_out; rif = (float)a.r_in; rFf = (float)L.rF; dFf = (float)L.dF; aFf = (float)L.aF;
+    }
 
     float bt[PIPE_EB][PIPE_K];
     int bj[PIPE_EB][PIPE_K];
@@ -249,12 +380,44 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
         }
         __syncthreads();
         for (int jj = 0; jj < n; ++jj) {
-            const float4 P = sp[jj];
-            const float vx = P.x - xfr, vz = P.y - zfr;
-            const float q = fmaf(vz, vz, vx * vx);
-            const float r = __builtin_amdgcn_rsqf(q);
-            const float g = fmaf(vz, P.w, vx * P.z) * r;          // c3 dT_wall / dbeta
-            const float tw = q * r * a.ic3f;
+            float g, tw;
+            if constexpr (SKIP) {
+                // the bounce at beta_j: u by safeguarded Newton from the previous scan point's v; NaN without W
+                g = NAN; tw = NAN;
+                double dld = L.thF - fma((double)(base + jj), a.hb, a.b_lo);
+                dld = fma(-RTUS_TWO_PI, rint(dld * (1.0 / RTUS_TWO_PI)), dld);
+                const float dl = (float)dld;
+                float lo0, hi0, lo, hi, h, hp, Ag, W;
+                bool ok = bore_arc<float>(k.aQf, aFf, dl, lo0, hi0, lo, hi) && fok;
+                if (ok && lo == lo0) { bore_h32(rrf, frf, rof, rif, rFf, k.dQf, dFf, a.ic3f, k.icuf, lo0, dl, h, hp, Ag, W); ok = h < 0.f; }
+                if (ok && hi == hi0) { bore_h32(rrf, frf, rof, rif, rFf, k.dQf, dFf, a.ic3f, k.icuf, hi0, dl, h, hp, Ag, W); ok = h > 0.f; }
+                float u = vwf + dl;
+                vwf = NAN;
+                if (ok) {
+                    if (!(u >= lo && u <= hi)) u = fminf(fmaxf(dl, lo), hi);
+                    for (int it = 0; it < 16; ++it) {
+                        bore_h32(rrf, frf, rof, rif, rFf, k.dQf, dFf, a.ic3f, k.icuf, u, dl, h, hp, Ag, W);
+                        if (h < 0.f) lo = u; else hi = u;
+                        const float step = -h / hp;
+                        float un = u + step;
+                        const bool done = fabsf(step) <= 2e-7f || !(hi - lo > 2e-7f);
+                        if (!(un >= lo && un <= hi)) un = done ? u : 0.5f * (lo + hi);
+                        u = un;
+                        if (done) break;
+                    }
+                    bore_h32(rrf, frf, rof, rif, rFf, k.dQf, dFf, a.ic3f, k.icuf, u, dl, h, hp, Ag, W);
+                    g = -Ag;                                       // c_down dW / dbeta
+                    tw = W;
+                    vwf = u - dl;
+                }
+            } else {
+                const float4 P = sp[jj];
+                const float vx = P.x - xfr, vz = P.y - zfr;
+                const float q = fmaf(vz, vz, vx * vx);
+                const float r = __builtin_amdgcn_rsqf(q);
+                g = fmaf(vz, P.w, vx * P.z) * r;                   // c3 dT_wall / dbeta
+                tw = q * r * a.ic3f;
+            }
             const int j = base + jj;
 #pragma unroll
             for (int e = 0; e < PIPE_EB; ++e) {
@@ -265,6 +428,7 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
                     RTUS_KEEP3(t, j - 1, bt[e], bj[e]);
                 }
                 neg[e] = !pos && s.x == s.x;                       // (an element without a lens leg: neither side of a bracket)
+                if constexpr (SKIP) neg[e] = neg[e] && g == g;     // (nor is a beta without a bounce)
             }
         }
     }
@@ -289,41 +453,69 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
         // the third bracket is skipped only once an earlier one has given a qualifying time and the fp32 estimate puts the third
         // clearly (4e-6) after it; while the earlier ones were rejected by a rule it is refined however late it is
         float tb = INFINITY;                                       // fp32 time of the bracket that gave best
-        double best = NAN, bA = NAN, bB = NAN;
+        double best = NAN, bA = NAN, bB = NAN, bG = NAN;
         for (int kk = 0; kk < PIPE_K; ++kk) {
             const int j = kk == 0 ? ej[0] : (kk == 1 ? ej[1] : ej[2]);
             const float tk = kk == 0 ? et[0] : (kk == 1 ? et[1] : et[2]);
             if (!fok || j < 0 || (kk >= 2 && !(tk <= fmaf(4e-6f, tb, tb)))) continue;
             // the fp64 bracket (beta_j-1 .. beta_j+2 at most); the inner alpha at a scan point starts from the table's alpha there
             int jl, jh;
+            double vw = NAN;                                      // (skip leg: the inner gamma's warm start, from iterate to iterate)
             auto d1_at = [&](int jp) {
                 double aw = alr[jp];
-                return pipe_T<POLY>(a, xa, za, xf, zf, fma((double)jp, a.hb, a.b_lo), aw).d1;
+                if constexpr (SKIP)
+                    return pipe_T<POLY>(a, xa, za, xf, zf, fma((double)jp, a.hb, a.b_lo), aw, L, (double)NAN).d1;
+                else
+                    return pipe_T<POLY>(a, xa, za, xf, zf, fma((double)jp, a.hb, a.b_lo), aw).d1;
             };
             if (!rtus_bracket_fix(j, a.m, d1_at, jl, jh)) continue;
             // Newton on dT / dbeta = 0 inside it; the inner alpha starts from the bracket's left end, then from the previous iterate
             double x, aw = alr[jl];
-            const PipeT v = rtus_newton_min([&](double beta) { return pipe_T<POLY>(a, xa, za, xf, zf, beta, aw); },
-                                            fma((double)jl, a.hb, a.b_lo), fma((double)jh, a.hb, a.b_lo), 1e-12, x);
+            const auto v = rtus_newton_min([&](double beta) {
+                                               if constexpr (SKIP) {
+                                                   const PipeTS r = pipe_T<POLY>(a, xa, za, xf, zf, beta, aw, L, vw);
+                                                   vw = r.v;
+                                                   return r;
+                                               } else
+                                                   return pipe_T<POLY>(a, xa, za, xf, zf, beta, aw);
+                                           },
+                                           fma((double)jl, a.hb, a.b_lo), fma((double)jh, a.hb, a.b_lo), 1e-12, x);
             // rule 1: the water segment L -> Q arrives from outside the circle; rule 2: the wall segment Q -> F keeps off the bore
             const double cx = v.qx - a.x_off, cz = v.qz;
             const bool outside = fma(v.qx - v.px, cx, (v.qz - v.pz) * cz) < 0.0;
             const double sx = xf - v.qx, sz = zf - v.qz, ss = fma(sx, sx, sz * sz);
             const double tc = fmin(fmax(-fma(cx, sx, cz * sz) / ss, 0.0), 1.0);
             const double nx = fma(tc, sx, cx), nz = fma(tc, sz, cz);
-            const bool clear = fma(nx, nx, nz * nz) >= rin2;
+            const bool clear = SKIP || fma(nx, nx, nz * nz) >= rin2;      // (the skip leg's segments keep off the bore by construction)
             if (!(outside && clear && isfinite(v.t))) continue;
-            if (isnan(best) || v.t < best) { best = v.t; bA = v.alpha; bB = x; tb = tk; }
+            if (isnan(best) || v.t < best) {
+                best = v.t; bA = v.alpha; bB = x; tb = tk;
+                if constexpr (SKIP) bG = v.gamma;
+            }
         }
         a.tt[o] = best;
         if (a.alpha_out) a.alpha_out[o] = bA;
         if (a.beta_out) a.beta_out[o] = bB;
+        if constexpr (SKIP) { if (k.gamma_out) k.gamma_out[o] = bG; }
     }
 }
 
-hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double b_lo, double b_hi, int n_scan,
-                               const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
-                               double* alpha_out, double* beta_out, void* ws, hipStream_t s)
+template <bool POLY>
+__global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_kernel(PipeArgs a)
+{
+    pipe_table<POLY, false>(a, PipeSkip{});
+}
+
+template <bool POLY>
+__global__ void __launch_bounds__(RTUS_BLOCK) rtus_pipe_skip_kernel(PipeArgs a, PipeSkip k)
+{
+    pipe_table<POLY, true>(a, k);
+}
+
+// c_up > 0: the skip leg (P.c3 is c_down; gamma_out nullable); c_up == 0: the direct leg
+static hipError_t launch_pipe(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double c_up, double b_lo, double b_hi,
+                              int n_scan, const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f,
+                              double* tt, double* alpha_out, double* beta_out, double* gamma_out, void* ws, hipStream_t s)
 {
     const LensK kk = make_lens_k(L);
     PipeArgs a;
@@ -341,6 +533,20 @@ hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, con
     const long long gs = ((long long)n_e * n_scan + RTUS_BLOCK - 1) / RTUS_BLOCK;
     const long long gy = ((long long)n_e + PIPE_EB - 1) / PIPE_EB, gx = ((long long)n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
     if (gy > 65535 || gx > 0x7fffffffLL || gs > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (c_up > 0.0) {
+        PipeSkip k;
+        k.icu = 1.0 / c_up; k.aQ = acos(P.r_inner / P.r_outer); k.dQ = P.r_outer - P.r_inner;
+        k.icuf = (float)k.icu; k.aQf = (float)k.aQ; k.dQf = (float)k.dQ;
+        k.gamma_out = gamma_out;
+        if (a.k.poly_trig) {
+            hipLaunchKernelGGL(rtus_pipe_setup_kernel<true>, dim3((unsigned)gs), dim3(RTUS_BLOCK), 0, s, a);
+            hipLaunchKernelGGL(rtus_pipe_skip_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a, k);
+        } else {
+            hipLaunchKernelGGL(rtus_pipe_setup_kernel<false>, dim3((unsigned)gs), dim3(RTUS_BLOCK), 0, s, a);
+            hipLaunchKernelGGL(rtus_pipe_skip_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a, k);
+        }
+        return hipGetLastError();
+    }
     if (a.k.poly_trig) {
         hipLaunchKernelGGL(rtus_pipe_setup_kernel<true>, dim3((unsigned)gs), dim3(RTUS_BLOCK), 0, s, a);
         hipLaunchKernelGGL(rtus_pipe_kernel<true>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
@@ -349,4 +555,18 @@ hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, con
         hipLaunchKernelGGL(rtus_pipe_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(RTUS_BLOCK), 0, s, a);
     }
     return hipGetLastError();
+}
+
+hipError_t rtus_launch_tt_pipe(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double b_lo, double b_hi, int n_scan,
+                               const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                               double* alpha_out, double* beta_out, void* ws, hipStream_t s)
+{
+    return launch_pipe(L, a_lo, a_hi, P, 0.0, b_lo, b_hi, n_scan, xe, ze, n_e, xf, zf, n_f, tt, alpha_out, beta_out, nullptr, ws, s);
+}
+
+hipError_t rtus_launch_tt_pipe_skip(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double c_up, double b_lo, double b_hi,
+                                    int n_scan, const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f,
+                                    double* tt, double* alpha_out, double* beta_out, double* gamma_out, void* ws, hipStream_t s)
+{
+    return launch_pipe(L, a_lo, a_hi, P, c_up, b_lo, b_hi, n_scan, xe, ze, n_e, xf, zf, n_f, tt, alpha_out, beta_out, gamma_out, ws, s);
 }

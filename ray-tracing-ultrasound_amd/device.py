@@ -669,3 +669,36 @@ def tt_pipe_dev(xe, ze, xf, zf, out=None, alpha_out=None, beta_out=None, *, c3=5
                                      n_f, _p(out), _p(alpha_out), _p(beta_out), _p(ws), ws.numel(), _stream(xe))
     _lib.check(st, "rtus_tt_pipe_dev")
     return out
+
+
+def tt_pipe_skip_dev(xe, ze, xf, zf, out=None, alpha_out=None, beta_out=None, gamma_out=None, *, c_down, c_up=None, r_inner,
+                     params: Params = None, alpha_lo=None, alpha_hi=None, beta_lo=-_api.np.pi / 2, beta_hi=_api.np.pi / 2, n_scan=None,
+                     ws=None):
+    """Bore-reflected skip legs into the pipe wall on device (rtus_tt_pipe_skip_dev; api.skip_travel_time_pipe's definition and
+    defaults) on float64 CUDA tensors -> out [n_e, n_f] (and alpha_out / beta_out / gamma_out [n_e, n_f] when tensors are given for
+    them).  ``ws``: an optional uint8 tensor of at least rtus_tt_pipe_skip_workspace_bytes(n_e, n_scan) bytes to reuse (a graph
+    capture must not allocate); allocated here otherwise.  Asynchronous on the current stream."""
+    c_up = c_down if c_up is None else c_up
+    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _api._pipe_args(params, c_down, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
+    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
+        _chk(t, n)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    if out is None:
+        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
+    for t, n in ((out, "out"), (alpha_out, "alpha_out"), (beta_out, "beta_out"), (gamma_out, "gamma_out")):
+        if t is not None:
+            _chk(t, n)
+            if t.numel() != n_e * n_f:
+                raise ValueError(f"{n} must hold n_e * n_f values")
+    need = int(_lib.lib().rtus_tt_pipe_skip_workspace_bytes(n_e, n_scan))
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)     # (the caching allocator's blocks are 512-byte aligned)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+        raise ValueError("ws must be a contiguous CUDA uint8 tensor")
+    st = _lib.lib().rtus_tt_pipe_skip_dev(C.byref(lens), a_lo, a_hi, C.byref(pipe), float(c_up), b_lo, b_hi, n_scan, _p(xe), _p(ze), n_e,
+                                          _p(xf), _p(zf), n_f, _p(out), _p(alpha_out), _p(beta_out), _p(gamma_out), _p(ws), ws.numel(),
+                                          _stream(xe))
+    _lib.check(st, "rtus_tt_pipe_skip_dev")
+    return out
