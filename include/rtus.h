@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 111 /* 0.1.10: rtus_tt_pipe_skip* (bore-reflected skip legs into the pipe wall) */
+#define RTUS_VERSION 112 /* 0.1.11: rtus_leg_amp_pipe* (ray amplitudes of the legs into the pipe wall) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -881,6 +881,70 @@ int rtus_tt_pipe_skip(const rtus_lens *lens, double alpha_lo, double alpha_hi, c
                       double beta_lo, double beta_hi, int n_scan,
                       const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
                       double *tt, double *alpha_out, double *beta_out, double *gamma_out, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * RAY AMPLITUDES OF THE LEGS INTO THE PIPE WALL: rtus_leg_amp_surface's table for rtus_tt_pipe's / rtus_tt_pipe_skip's geometry, so
+ * that rtus_tfm_weighted images the pipe wall in sensitivity-normalised views.  NOT IN THE REFERENCE; checked against
+ * tests/pipe_amplitude_numpy.py, itself checked against a finite-difference ray tube through the three curved interfaces, a
+ * closed-form point on the axis, reciprocity and mirror symmetry (tests/test_pipe_amplitude_cpu.py).
+ *
+ * Geometry and symbols are rtus_tt_pipe's / rtus_tt_pipe_skip's (z up, elements at ze, normally d, above the lens surface and facing
+ * -z; P(alpha), Q(beta), R(gamma), Cp = (x_off, 0)).  A path is E -> P(alpha) -> Q(beta) -> [R(gamma)] -> F; alpha, beta, gamma are
+ * what rtus_tt_pipe[_skip] return, no solve is made.  Direction and views: the surface section's (DOWN E -> F, UP F -> E).
+ * Media: the lens is an isotropic solid (rho_lens, L speed lens->c1, shear speed ct_lens, 0 < ct_lens < c1; only its L wave is
+ * traced); water (rho_water, lens->c2); the wall (rho_wall, c_l > c_t); the bore is traction-free.
+ *
+ * Amplitude A = conj(D C_lens C_outer [C_bore] G), formed in fp64, stored as complex64, with the surface section's conventions:
+ * component algebra in (x, z) exactly as written there (polarisation L along the propagation direction d, T along (-d_z, d_x); an
+ * interface frame is a unit normal n with the tangent t = (n_z, -n_x), the horizontal slowness p is taken along t; angles grow from
+ * +z towards +x), derivation in e^{i(k.x - wt)}, the conjugate stored.
+ *   D        sinc(w sin(theta_E) f_c / c1), theta_E the angle of P - E to the element's facing direction; w = 0: D = 1.
+ *   C_lens   DOWN solid -> fluid from L, UP fluid -> solid into L, the lens being the solid.  Frame: n into the lens, t = P' / |P'|.
+ *   C_outer  DOWN fluid -> solid into the leg's first mode, UP solid -> fluid from the mode that arrives at Q.  Frame: n into the
+ *            wall, n = -(Q - Cp) / r_outer.
+ *   C_bore   (skip legs) free-surface reflection, incoming -> outgoing mode in propagation order.  Frame: n out of the wall,
+ *            n = -(R - Cp) / r_inner.
+ *            Each coefficient is evaluated at the horizontal slowness of the segment that arrives at the interface.
+ *   G        the surface section's ray tube, sqrt(prod_k (cos theta_out,k / cos theta_in,k) / |J|), through three (direct) or four
+ *            (skip) segments.  Tube normals and their turning rates K = d(angle of n) / d(arc along t), before the tube orients each
+ *            along the incoming ray (which flips K with it): the lens n = (P'_z, -P'_x) / |P'| (towards the water),
+ *            K = (P'_x P''_z - P'_z P''_x) / |P'|^3, the signed curvature of P(alpha); the outer circle n = (Q - Cp) / r_outer,
+ *            K = 1 / r_outer; the bore n = (R - Cp) / r_inner, K = 1 / r_inner.
+ *   Mirror rule: mirroring x_off, the elements and the points in x (alpha, beta, gamma change sign) keeps |A|; A changes sign
+ *   exactly when the mode at F is T (the T polarisation (-d_z, d_x) is a pseudovector).
+ *   Invalid entries: NaN + NaN i exactly where alpha or beta (or, for skip legs, gamma) is NaN — where the time table is NaN.
+ *   0 + 0 i where the path is not a ray: the lens leg is pinned (alpha equal to alpha_lo or alpha_hi, which the time kernels return
+ *   bit-exactly), or a segment does not cross its interface in the propagating sense ((P - E) . n and (Q - P) . n not both positive on
+ *   the lens normal; (Q - P) or the wall segment from Q not pointing into the circle; for skip legs the segment to R not pointing
+ *   into the bore or the segment from R not pointing out of it).  +inf + inf i at a caustic (J = 0; rtus_tfm_weighted drops it).
+ *
+ * rtus_leg_amp_pipe: amp [n_e][n_f] complex64 (interleaved float32 pairs) of one leg in one direction.
+ *   lens, alpha_lo, alpha_hi, pipe (r_outer, r_inner, x_off; c3 is not read), xe, ze, xf, zf: rtus_tt_pipe's; alpha, beta [n_e][n_f] and
+ *   gamma [n_e][n_f] (skip legs; nullable for L and T): the path.  leg: RTUS_LEG_*; direction: RTUS_AMP_*; element_width >= 0 [m]
+ *   and f_c > 0 [Hz] (read only with a width).  Determinism: an entry depends only on its own inputs (subsets give the same bits).
+ *   Argument checks run before any HIP call: -1 for a null pointer, a non-positive size, a bad leg or direction, a non-finite or
+ *   non-positive speed or density, c_t >= c_l, ct_lens >= c1, a non-finite or non-positive r_outer, a non-finite x_off, r_inner
+ *   outside [0, r_outer) or r_inner = 0 with a skip leg, alpha_lo >= alpha_hi, a negative width, f_c <= 0 with a width, a skip leg
+ *   without gamma; -5 past n_e <= 65535.  No workspace.
+ * The _dev entry allocates nothing and does not synchronise (capturable); the host twin stages through the device's arena.
+ * Kernel, resources and measured figures on MI355X: DESIGN.md section 4 (pipe wall, ray amplitudes).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct rtus_pipe_media {
+    double rho_lens;  /* density of the lens [kg/m^3] */
+    double ct_lens;   /* shear speed of the lens [m/s], 0 < ct_lens < lens->c1 */
+    double rho_water; /* density of the water [kg/m^3] */
+    double rho_wall;  /* density of the wall [kg/m^3] */
+    double c_l;       /* L speed of the wall [m/s] */
+    double c_t;       /* T speed of the wall [m/s], c_t < c_l */
+} rtus_pipe_media;
+int rtus_leg_amp_pipe_dev(const rtus_lens *lens, double alpha_lo, double alpha_hi, const rtus_pipe *pipe, const rtus_pipe_media *media,
+                          int leg, int direction, double element_width, double f_c,
+                          const double *d_xe, const double *d_ze, int n_e, const double *d_xf, const double *d_zf, int n_f,
+                          const double *d_alpha, const double *d_beta, const double *d_gamma, float *d_amp, void *stream);
+int rtus_leg_amp_pipe(const rtus_lens *lens, double alpha_lo, double alpha_hi, const rtus_pipe *pipe, const rtus_pipe_media *media,
+                      int leg, int direction, double element_width, double f_c,
+                      const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
+                      const double *alpha, const double *beta, const double *gamma, float *amp, int device);
 
 #ifdef __cplusplus
 }

@@ -4,19 +4,20 @@ edudscrc/ray-tracing-ultrasound: main_rt.py's shoot_rays + element matcher).
 The directory is called ``ray-tracing-ultrasound_amd``; import it as ``import rtus`` (the alias
 module at the repo root) or ``importlib.import_module("ray-tracing-ultrasound_amd")``.
 """
-from ._lib import EXPORTS, LIB_PATH, Lens, Pipe, RtusError, build, lib  # noqa: F401
+from ._lib import EXPORTS, LIB_PATH, Lens, Pipe, PipeMedia, RtusError, build, lib  # noqa: F401
 from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits,  # noqa: F401
                   reference_elements, shoot_batch, shoot_rays, travel_time_layers, travel_time_lens, travel_time_surface,
                   fmc_table_layers, solve_travel_times, focal_delays, tfm_image, sweep_batch, fmc_analytic, measure_surface,
                   adaptive_tfm, tfm_analytic, pw_delays, pw_travel_time_layers, pw_travel_time_surface, fmc_synth_tx, pwi_image,
                   LEGS, VIEWS, reverse_leg, view_tables, skip_travel_time_layers, skip_travel_time_surface, view_legs_layers,
                   view_legs_surface, tfm_views, leg_amplitudes_surface, view_amplitudes_surface, tfm_weighted,
-                  travel_time_pipe, pipe_wall_grid, skip_travel_time_pipe, view_legs_pipe)
+                  travel_time_pipe, pipe_wall_grid, skip_travel_time_pipe, view_legs_pipe,
+                  leg_amplitudes_pipe, view_amplitudes_pipe)
 
 __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "focal_delays", "tfm_image", "fmc_analytic",
            "measure_surface", "adaptive_tfm", "tfm_analytic", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
            "fmc_synth_tx", "pwi_image", "LEGS", "VIEWS", "reverse_leg", "view_tables", "skip_travel_time_layers",
            "skip_travel_time_surface", "view_legs_layers", "view_legs_surface", "tfm_views", "leg_amplitudes_surface",
            "view_amplitudes_surface", "tfm_weighted", "travel_time_pipe", "pipe_wall_grid", "skip_travel_time_pipe",
-           "view_legs_pipe", "Params",
+           "view_legs_pipe", "leg_amplitudes_pipe", "view_amplitudes_pipe", "Params",
            "configure", "reference_elements", "ALPHA_MAX", "KEYS", "build", "lib", "RtusError"]

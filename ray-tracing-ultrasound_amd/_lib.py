@@ -35,6 +35,12 @@ class Pipe(C.Structure):
     _fields_ = [("r_outer", C.c_double), ("r_inner", C.c_double), ("x_off", C.c_double), ("c3", C.c_double)]
 
 
+class PipeMedia(C.Structure):
+    """rtus_pipe_media — densities and the speeds the lens and the pipe structs do not hold (rtus_leg_amp_pipe)."""
+    _fields_ = [("rho_lens", C.c_double), ("ct_lens", C.c_double), ("rho_water", C.c_double), ("rho_wall", C.c_double),
+                ("c_l", C.c_double), ("c_t", C.c_double)]
+
+
 def build(force: bool = False) -> str:
     """Compile librtus.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     args = ["make", "-C", CSRC, "-j4"]
@@ -227,6 +233,14 @@ def lib():
     except AttributeError:                # a build from before version 111, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        MP = C.POINTER(PipeMedia)
+        L.rtus_leg_amp_pipe_dev.argtypes = [LP, dd, dd, PP, MP, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, vp]
+        L.rtus_leg_amp_pipe.argtypes = [LP, dd, dd, PP, MP, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, ip]
+        L.rtus_leg_amp_pipe_dev.restype = L.rtus_leg_amp_pipe.restype = ip
+    except AttributeError:                # a build from before version 112, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -257,4 +271,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip",
            "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted",
            "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe",
-           "rtus_tt_pipe_skip_workspace_bytes", "rtus_tt_pipe_skip_dev", "rtus_tt_pipe_skip")
+           "rtus_tt_pipe_skip_workspace_bytes", "rtus_tt_pipe_skip_dev", "rtus_tt_pipe_skip",
+           "rtus_leg_amp_pipe_dev", "rtus_leg_amp_pipe")

@@ -16,7 +16,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib
-from ._lib import Lens, Pipe
+from ._lib import Lens, Pipe, PipeMedia
 
 KEYS = ("lens_1_x", "lens_1_z", "pipe_x", "pipe_z", "lens_2_x", "lens_2_z", "target_x", "target_z")
 
@@ -1048,3 +1048,76 @@ def view_legs_pipe(c_l, c_t, r_inner, xe, ze, xf, zf, *, legs=LEGS, params: Para
         else:
             out[g] = skip_travel_time_pipe(xe, ze, xf, zf, c_down=sp[g[0]], c_up=sp[g[1]], **kw)
     return out
+
+
+def _pipe_amp_args(params, r_inner, alpha_lo, alpha_hi, c_l, c_t, rho_wall, rho_water, rho_lens, ct_lens):
+    p = _resolve(params)
+    a_lo = -ALPHA_MAX if alpha_lo is None else float(alpha_lo)
+    a_hi = ALPHA_MAX if alpha_hi is None else float(alpha_hi)
+    pipe = Pipe(float(p.r_outer), float(r_inner), float(p.pipe_offset), 0.0)        # (c3 is not read: the media hold the speeds)
+    media = PipeMedia(float(rho_lens), float(ct_lens), float(rho_water), float(rho_wall), float(c_l), float(c_t))
+    return p.lens(), a_lo, a_hi, pipe, media
+
+
+def leg_amplitudes_pipe(leg, xe, ze, xf, zf, alpha, beta, gamma=None, *, c_l, c_t, rho_wall, rho_water, rho_lens, ct_lens, r_inner,
+                        up=False, element_width=0.0, f_c=None, params: Params = None, alpha_lo=None, alpha_hi=None, out=None, device=0):
+    """Ray amplitudes of one multi-view leg into the pipe wall -> complex64 [n_e, n_f]: A = D C_lens C_outer [C_bore] G (element
+    directivity, the displacement coefficients at the lens surface, the pipe's outer circle and the bore, 2-D ray-tube spreading
+    through the three curved interfaces), in the analytic signal's phase convention.  ``alpha``, ``beta`` (and ``gamma`` for skip
+    legs) [n_e, n_f] are the path as travel_time_pipe(return_path=True) / skip_travel_time_pipe(return_path=True) return it.
+    ``up``: the wave travels point -> element along the same path.  The lens is a solid (``rho_lens``, L speed params.c1, shear speed
+    ``ct_lens``), the water has ``rho_water`` and params.c2, the wall ``rho_wall``, ``c_l`` > ``c_t``; the pipe is ``params``' with
+    the bore ``r_inner``.  ``alpha_lo`` / ``alpha_hi``: the lens interval the times were made with (a path pinned at an end of it
+    carries no ray: 0).  ``element_width`` [m] > 0 needs ``f_c`` [Hz].  NaN where the path is NaN.  Definition: include/rtus.h
+    (rtus_leg_amp_pipe).  Not in the reference."""
+    if leg not in LEGS:
+        raise ValueError(f"unknown leg {leg!r}: legs are {LEGS}")
+    skip = len(leg) == 2
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    shape = (xe.size, xf.size)
+    al, be = _f64(alpha, "alpha", 2), _f64(beta, "beta", 2)
+    if al.shape != shape or be.shape != shape:
+        raise ValueError(f"alpha and beta must be [n_e, n_f] = {shape}")
+    ga = None
+    if skip:
+        if gamma is None:
+            raise ValueError(f"the skip leg {leg!r} needs gamma")
+        ga = _f64(gamma, "gamma", 2)
+        if ga.shape != shape:
+            raise ValueError(f"gamma must be [n_e, n_f] = {shape}")
+    if element_width > 0 and f_c is None:
+        raise ValueError("an element width needs the centre frequency f_c")
+    lens, a_lo, a_hi, pipe, media = _pipe_amp_args(params, r_inner, alpha_lo, alpha_hi, c_l, c_t, rho_wall, rho_water, rho_lens, ct_lens)
+    amp = _out(out, shape, np.complex64)
+    st = _lib.lib().rtus_leg_amp_pipe(C.byref(lens), a_lo, a_hi, C.byref(pipe), C.byref(media), LEG_CODES[leg], 1 if up else 0,
+                                      float(element_width), float(f_c or 0.0), _ptr(xe), _ptr(ze), xe.size, _ptr(xf), _ptr(zf), xf.size,
+                                      _ptr(al), _ptr(be), _ptr(ga), _ptr(amp), int(device))
+    _lib.check(st, "rtus_leg_amp_pipe")
+    return amp
+
+
+def view_amplitudes_pipe(xe, ze, xf, zf, *, c_l, c_t, rho_wall, rho_water, rho_lens, ct_lens, r_inner, legs=LEGS, element_width=0.0,
+                         f_c=None, params: Params = None, alpha_lo=None, alpha_hi=None, beta_lo=-np.pi / 2, beta_hi=np.pi / 2,
+                         n_scan=None, device=0):
+    """The leg tables of multi-view TFM of the pipe wall with their ray amplitudes -> (legs_tt, amps): legs_tt = {leg: tt [n_e, n_f]}
+    as view_legs_pipe makes them, amps = {leg: (down, up)} complex64 [n_e, n_f] (leg_amplitudes_pipe in both directions on the
+    tables' own paths).  Feed both to ``tfm_views(..., envelope=True, amplitudes=amps)``."""
+    legs = _legs_wanted(legs)
+    sp = {"L": float(c_l), "T": float(c_t)}
+    kw = dict(r_inner=r_inner, params=params, alpha_lo=alpha_lo, alpha_hi=alpha_hi, beta_lo=beta_lo, beta_hi=beta_hi, n_scan=n_scan,
+              return_path=True, device=device)
+    tts, amps = {}, {}
+    for g in legs:
+        if len(g) == 1:
+            tt, al, be = travel_time_pipe(xe, ze, xf, zf, c3=sp[g], **kw)
+            ga = None
+        else:
+            tt, al, be, ga = skip_travel_time_pipe(xe, ze, xf, zf, c_down=sp[g[0]], c_up=sp[g[1]], **kw)
+        tts[g] = tt
+        amps[g] = tuple(leg_amplitudes_pipe(g, xe, ze, xf, zf, al, be, ga, c_l=c_l, c_t=c_t, rho_wall=rho_wall, rho_water=rho_water,
+                                            rho_lens=rho_lens, ct_lens=ct_lens, r_inner=r_inner, up=u, element_width=element_width,
+                                            f_c=f_c, params=params, alpha_lo=alpha_lo, alpha_hi=alpha_hi, device=device)
+                        for u in (False, True))
+    return tts, amps

@@ -89,6 +89,10 @@ size_t rtus_pipe_ws_bytes(int n_e, int m);
 hipError_t rtus_launch_tt_pipe_skip(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, double c_up, double b_lo, double b_hi,
                                     int n_scan, const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f,
                                     double* tt, double* alpha_out, double* beta_out, double* gamma_out, void* ws, hipStream_t s);
+hipError_t rtus_launch_leg_amp_pipe(const rtus_lens& L, double a_lo, double a_hi, const rtus_pipe& P, const rtus_pipe_media& M, int leg,
+                                    int up, double width, double f_c, const double* xe, const double* ze, int n_e, const double* xf,
+                                    const double* zf, int n_f, const double* alpha, const double* beta, const double* gamma, float* amp,
+                                    hipStream_t s);
 hipError_t rtus_launch_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, const double* d, int n_v, float* out,
                                     hipStream_t s);
 
@@ -1799,5 +1803,69 @@ extern "C" int rtus_tt_pipe_skip(const rtus_lens* lens, double alpha_lo, double 
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tt_pipe_skip(*lens, alpha_lo, alpha_hi, *pipe, c_up, beta_lo, beta_hi, n_scan, dxe, dze, n_e, dxf, dzf, n_f, dtt,
                                         dal, dbe, dga, ws, S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- ray amplitude tables of the legs into the pipe wall
+static int check_leg_amp_pipe(const rtus_lens* lens, double a_lo, double a_hi, const rtus_pipe* pipe, const rtus_pipe_media* m, int leg,
+                              int dir, double width, double f_c, const void* xe, const void* ze, int n_e, const void* xf, const void* zf,
+                              int n_f, const void* alpha, const void* beta, const void* gamma, const void* amp)
+{
+    if (!lens || !pipe || !m || !xe || !ze || !xf || !zf || !alpha || !beta || !amp || n_e <= 0 || n_f <= 0) return RTUS_ERR_INVALID_ARG;
+    if (leg < RTUS_LEG_L || leg > RTUS_LEG_TT || (dir != RTUS_AMP_DOWN && dir != RTUS_AMP_UP)) return RTUS_ERR_INVALID_ARG;
+    const bool skip = leg >= RTUS_LEG_LL;
+    if (skip && !gamma) return RTUS_ERR_INVALID_ARG;
+    const double sp[8] = {lens->c1, lens->c2, m->rho_lens, m->ct_lens, m->rho_water, m->rho_wall, m->c_l, m->c_t};
+    for (double v : sp)
+        if (!isfinite(v) || !(v > 0)) return RTUS_ERR_INVALID_ARG;
+    if (!(m->c_t < m->c_l) || !(m->ct_lens < lens->c1) || lens->c1 == lens->c2) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(lens->l0) || !isfinite(lens->h0) || !isfinite(lens->d)) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(pipe->r_outer) || !(pipe->r_outer > 0) || !isfinite(pipe->x_off)) return RTUS_ERR_INVALID_ARG;
+    if (!(pipe->r_inner >= 0) || !(pipe->r_inner < pipe->r_outer) || (skip && !(pipe->r_inner > 0))) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(a_lo) || !isfinite(a_hi) || !(a_hi > a_lo)) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(width) || width < 0 || (width > 0 && (!isfinite(f_c) || !(f_c > 0)))) return RTUS_ERR_INVALID_ARG;
+    if (n_e > 65535) return RTUS_ERR_UNSUPPORTED;                                         // grid.y: one element per row of workgroups
+    return RTUS_OK;
+}
+
+extern "C" int rtus_leg_amp_pipe_dev(const rtus_lens* lens, double alpha_lo, double alpha_hi, const rtus_pipe* pipe,
+                                     const rtus_pipe_media* media, int leg, int direction, double element_width, double f_c,
+                                     const double* d_xe, const double* d_ze, int n_e, const double* d_xf, const double* d_zf, int n_f,
+                                     const double* d_alpha, const double* d_beta, const double* d_gamma, float* d_amp, void* stream)
+{
+    const int st = check_leg_amp_pipe(lens, alpha_lo, alpha_hi, pipe, media, leg, direction, element_width, f_c, d_xe, d_ze, n_e, d_xf,
+                                      d_zf, n_f, d_alpha, d_beta, d_gamma, d_amp);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_leg_amp_pipe(*lens, alpha_lo, alpha_hi, *pipe, *media, leg, direction, element_width, f_c, d_xe, d_ze, n_e,
+                                        d_xf, d_zf, n_f, d_alpha, d_beta, leg >= RTUS_LEG_LL ? d_gamma : nullptr, d_amp,
+                                        (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+extern "C" int rtus_leg_amp_pipe(const rtus_lens* lens, double alpha_lo, double alpha_hi, const rtus_pipe* pipe,
+                                 const rtus_pipe_media* media, int leg, int direction, double element_width, double f_c, const double* xe,
+                                 const double* ze, int n_e, const double* xf, const double* zf, int n_f, const double* alpha,
+                                 const double* beta, const double* gamma, float* amp, int device)
+{
+    int st = check_leg_amp_pipe(lens, alpha_lo, alpha_hi, pipe, media, leg, direction, element_width, f_c, xe, ze, n_e, xf, zf, n_f, alpha,
+                                beta, gamma, amp);
+    if (st) return st;
+    const bool skip = leg >= RTUS_LEG_LL;
+    const size_t tot = (size_t)n_e * n_f;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dxe, *dze, *dxf, *dzf, *dal, *dbe, *dga = nullptr;
+    float* damp;
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.in(dal, alpha, tot);
+    S.in(dbe, beta, tot);
+    if (skip) S.in(dga, gamma, tot);
+    S.out(damp, amp, 2 * tot);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_leg_amp_pipe(*lens, alpha_lo, alpha_hi, *pipe, *media, leg, direction, element_width, f_c, dxe, dze, n_e, dxf,
+                                        dzf, n_f, dal, dbe, dga, damp, S.a->stream));
     return S.finish();
 }

@@ -702,3 +702,37 @@ def tt_pipe_skip_dev(xe, ze, xf, zf, out=None, alpha_out=None, beta_out=None, ga
                                           _stream(xe))
     _lib.check(st, "rtus_tt_pipe_skip_dev")
     return out
+
+
+def leg_amp_pipe_dev(leg, xe, ze, xf, zf, alpha, beta, gamma=None, *, c_l, c_t, rho_wall, rho_water, rho_lens, ct_lens, r_inner,
+                     up=False, element_width=0.0, f_c=None, params: Params = None, alpha_lo=None, alpha_hi=None, out=None):
+    """Ray amplitudes of one leg into the pipe wall on device (rtus_leg_amp_pipe_dev; api.leg_amplitudes_pipe's definition): float64
+    CUDA tensors in (alpha, beta, gamma: n_e * n_f values each, as tt_pipe_dev / tt_pipe_skip_dev write them), out float32
+    [n_e, n_f, 2] (interleaved complex64).  No workspace; asynchronous on the current stream (capturable with ``out`` given)."""
+    if leg not in _api.LEG_CODES:
+        raise ValueError(f"unknown leg {leg!r}: legs are {_api.LEGS}")
+    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf"), (alpha, "alpha"), (beta, "beta")):
+        _chk(t, n)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f or alpha.numel() != n_e * n_f or beta.numel() != n_e * n_f:
+        raise ValueError("xe/ze and xf/zf must pair up, alpha and beta hold n_e * n_f values")
+    if len(leg) == 2:
+        if gamma is None:
+            raise ValueError(f"the skip leg {leg!r} needs gamma")
+        _chk(gamma, "gamma")
+        if gamma.numel() != n_e * n_f:
+            raise ValueError("gamma must hold n_e * n_f values")
+    if element_width > 0 and f_c is None:
+        raise ValueError("an element width needs the centre frequency f_c")
+    if out is None:
+        out = torch.empty((n_e, n_f, 2), dtype=torch.float32, device=xe.device)
+    _chk(out, "out", torch.float32)
+    if out.numel() != 2 * n_e * n_f:
+        raise ValueError("out must hold 2 * n_e * n_f float32 values")
+    lens, a_lo, a_hi, pipe, media = _api._pipe_amp_args(params, r_inner, alpha_lo, alpha_hi, c_l, c_t, rho_wall, rho_water, rho_lens,
+                                                        ct_lens)
+    st = _lib.lib().rtus_leg_amp_pipe_dev(C.byref(lens), a_lo, a_hi, C.byref(pipe), C.byref(media), _api.LEG_CODES[leg], 1 if up else 0,
+                                          float(element_width), float(f_c or 0.0), _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(alpha),
+                                          _p(beta), _p(gamma if len(leg) == 2 else None), _p(out), _stream(xe))
+    _lib.check(st, "rtus_leg_amp_pipe_dev")
+    return out
