@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 112 /* 0.1.11: rtus_leg_amp_pipe* (ray amplitudes of the legs into the pipe wall) */
+#define RTUS_VERSION 113 /* 0.1.12: rtus_echo_pick*, rtus_geom_misfit*, rtus_pipe_clearance (pipe geometry from measured echo times) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -945,6 +945,60 @@ int rtus_leg_amp_pipe(const rtus_lens *lens, double alpha_lo, double alpha_hi, c
                       int leg, int direction, double element_width, double f_c,
                       const double *xe, const double *ze, int n_e, const double *xf, const double *zf, int n_f,
                       const double *alpha, const double *beta, const double *gamma, float *amp, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Estimating the pipe's geometry (r_outer, pipe_offset) from measured echo times: pick the outer-surface echo of every pair of an
+ * FMC (rtus_echo_pick), then compare the picks with rtus_solve's times for a batch of geometries (rtus_geom_misfit) — the
+ * reference's database search (main_rt.py:464-504 tabulates 210 geometries, main_compare.py:526-553 takes the one of least mean
+ * squared error) on any batch, which the Python layer (api.pipe_misfit, api.fit_pipe) turns into a coarse map and a
+ * Levenberg-Marquardt refinement.  The kernels are NOT IN THE REFERENCE; checked against tests/geomfit_numpy.py.
+ *
+ * rtus_echo_pick: the time of the strongest echo inside a gate, for every pair.
+ *   a        [n_tx][n_rx][n_t][2]  an analytic FMC as rtus_fmc_analytic makes it (8-byte aligned, -1 otherwise); sample i is at
+ *                                  t0 + i / fs
+ *   gate     the samples i with t_lo <= t0 + i / fs <= t_hi, formed as i_lo = ceil((t_lo - t0) fs), i_hi = floor((t_hi - t0) fs) in
+ *            fp64 and cut to the record [0, n_t - 1].  t_lo / t_hi are either the two scalars or, where the pointer is not null,
+ *            the pair's entry of d_t_lo / d_t_hi [n_tx][n_rx] (fp64; DEVICE memory in the _dev entry); each array wins over its
+ *            scalar on its own.  An infinite bound leaves that side open.
+ *   Magnitude: m[i] = sqrt(re * re + im * im) in fp32, each of the four operations correctly rounded on its own (no fused
+ *            multiply-add, no approximate root).
+ *   Pick:    j* = the first index of the maximum of m over the gate.  t_pick = NaN when j* is the first or the last sample of the
+ *            gate, when the maximum is 0 or not finite, when the gate is empty (a NaN bound included) or lies outside the record;
+ *            otherwise t0 + (j* + d) / fs with rtus_surface_find's parabolic step d = (m- - m+) / (2 (m- - 2 m0 + m+)) over
+ *            m[j* - 1 .. j* + 1] in fp64, clamped to [-1/2, 1/2].
+ *   Outputs: t_pick [n_tx][n_rx] fp64; amp [n_tx][n_rx] float32 = m[j*] (NaN when the gate is empty or holds a non-finite
+ *            magnitude).
+ *   Determinism: a pair's bits depend only on its own A-scan and gate, not on the other pairs of the call nor on the block's
+ *            alignment.
+ *   Limits:  n_t >= 3, fs > 0 and finite, t0 finite, a scalar bound that is read not NaN (-1); n_t <= 2^26, n_tx n_rx <= 2^31 - 1
+ *            (-5); checked before any HIP call.  No workspace.
+ *
+ * rtus_geom_misfit: sums of the residuals tt[g] - t_meas for every geometry of a batch.
+ *   tt       [n_geom][n_tx][n_rx]  rtus_solve's least times (NaN: no path)
+ *   t_meas   [n_tx][n_rx]          measured times (NaN: no measurement);  w [n_tx][n_rx] weights, nullable (then 1)
+ *   A pair counts for geometry g where tt[g] and t_meas are both finite and w > 0.  Over those pairs, with r = tt[g] - t_meas:
+ *     n[g] = their number,  sse[g] = sum w r^2,  sum_r[g] = sum w r,  sum_w[g] = sum w (nullable output).
+ *   A common time offset (a wedge delay, a trigger offset) then follows in closed form: delay = -sum_r / sum_w removes it, and the
+ *   sum of squares without it is sse - sum_r^2 / sum_w.  With unit weights and one transmit row, sse / n is the reference's mse.
+ *   Order of the sums (fp64): within a transmit row the receive elements in ascending order, q = fma(w r, r, q) for sse; then the
+ *   row sums in ascending row order.  A geometry's bits do not depend on which other geometries share the call.
+ *   n[g] = 0 and zero sums for a geometry without a counting pair.
+ *   Limits:  n_tx n_rx <= 2^31 - 1 (-5); null pointers and non-positive sizes -1; before any HIP call.  No workspace.
+ *
+ * rtus_pipe_clearance: the least distance from (x_off, 0) to the lens surface over [alpha_lo, alpha_hi] — rtus_tt_pipe rejects a
+ *   pipe whose r_outer is not below it.  Host arithmetic only; NaN for invalid arguments.
+ * The _dev entries allocate nothing and do not synchronise (capturable); the host twins stage through the device's arena.
+ * Kernels, resources and measured figures on MI355X: DESIGN.md section 4 (pipe geometry from echo times).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_echo_pick_dev(const float *d_a, int n_tx, int n_rx, int n_t, double fs, double t0, double t_lo, double t_hi,
+                       const double *d_t_lo, const double *d_t_hi, double *d_t_pick, float *d_amp, void *stream);
+int rtus_echo_pick(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0, double t_lo, double t_hi,
+                   const double *t_lo_pair, const double *t_hi_pair, double *t_pick, float *amp, int device);
+int rtus_geom_misfit_dev(const double *d_tt, int n_geom, int n_tx, int n_rx, const double *d_t_meas, const double *d_w,
+                         int *d_n, double *d_sse, double *d_sum_r, double *d_sum_w, void *stream);
+int rtus_geom_misfit(const double *tt, int n_geom, int n_tx, int n_rx, const double *t_meas, const double *w,
+                     int *n, double *sse, double *sum_r, double *sum_w, int device);
+double rtus_pipe_clearance(const rtus_lens *lens, double alpha_lo, double alpha_hi, double x_off);
 
 #ifdef __cplusplus
 }

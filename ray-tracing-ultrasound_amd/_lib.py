@@ -241,6 +241,18 @@ def lib():
     except AttributeError:                # a build from before version 112, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        L.rtus_echo_pick_dev.argtypes = [dp, ip, ip, ip, dd, dd, dd, dd, dp, dp, dp, dp, vp]
+        L.rtus_echo_pick.argtypes = [dp, ip, ip, ip, dd, dd, dd, dd, dp, dp, dp, dp, ip]
+        L.rtus_geom_misfit_dev.argtypes = [dp, ip, ip, ip, dp, dp, dp, dp, dp, dp, vp]
+        L.rtus_geom_misfit.argtypes = [dp, ip, ip, ip, dp, dp, dp, dp, dp, dp, ip]
+        for name in ("rtus_echo_pick_dev", "rtus_echo_pick", "rtus_geom_misfit_dev", "rtus_geom_misfit"):
+            getattr(L, name).restype = ip
+        L.rtus_pipe_clearance.argtypes = [LP, dd, dd, dd]
+        L.rtus_pipe_clearance.restype = dd
+    except AttributeError:                # a build from before version 113, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -272,4 +284,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted",
            "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe",
            "rtus_tt_pipe_skip_workspace_bytes", "rtus_tt_pipe_skip_dev", "rtus_tt_pipe_skip",
-           "rtus_leg_amp_pipe_dev", "rtus_leg_amp_pipe")
+           "rtus_leg_amp_pipe_dev", "rtus_leg_amp_pipe",
+           "rtus_echo_pick_dev", "rtus_echo_pick", "rtus_geom_misfit_dev", "rtus_geom_misfit", "rtus_pipe_clearance")

@@ -1121,3 +1121,250 @@ def view_amplitudes_pipe(xe, ze, xf, zf, *, c_l, c_t, rho_wall, rho_water, rho_l
                                             f_c=f_c, params=params, alpha_lo=alpha_lo, alpha_hi=alpha_hi, device=device)
                         for u in (False, True))
     return tts, amps
+
+
+# ---------------------------------------------------------------------------------------------- pipe geometry from echo times
+def pick_echo_times(fmc_or_analytic, fs, t_lo, t_hi, *, t0=0.0, n_taps=63, threshold=0.1, device=0):
+    """The arrival time of the strongest echo inside a gate, for every pair of an FMC -> dict(t float64 [n_tx, n_rx], amplitude
+    float32 [n_tx, n_rx], valid bool [n_tx, n_rx]).  ``fmc_or_analytic``: a real FMC [n_tx, n_rx, n_t] (its analytic signal is
+    formed with ``n_taps`` Hilbert taps) or an analytic one (complex64, or float32 [..., 2]); sample i is at t0 + i / fs.  The gate
+    t_lo <= t <= t_hi is two scalars or, either of them, an array [n_tx, n_rx] of per-pair bounds.  A pair's time is that of the
+    first maximum of the envelope over the gate's samples, moved by a parabolic step; NaN when the maximum sits on the gate's first
+    or last sample, is zero or not finite, or the gate holds no sample of the record.  A pair is valid where its time is finite and
+    its amplitude is at least ``threshold`` times the largest.  Definition: include/rtus.h (rtus_echo_pick).  Not in the
+    reference."""
+    a = np.asarray(fmc_or_analytic)
+    if a.ndim == 3 and not np.iscomplexobj(a):
+        a = fmc_analytic(a, n_taps, device=device)
+    a = _complex_fmc(a)
+
+    def bound(v, name):
+        if np.ndim(v) == 0:
+            return float(v), None
+        arr = np.ascontiguousarray(v, dtype=np.float64)
+        if arr.shape != a.shape[:2]:
+            raise ValueError(f"{name} must be a scalar or an array of shape {a.shape[:2]}")
+        return 0.0, arr
+    lo, lo_arr = bound(t_lo, "t_lo")
+    hi, hi_arr = bound(t_hi, "t_hi")
+    t = np.empty(a.shape[:2], dtype=np.float64)
+    amp = np.empty(a.shape[:2], dtype=np.float32)
+    st = _lib.lib().rtus_echo_pick(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), lo, hi, _ptr(lo_arr), _ptr(hi_arr),
+                                   _ptr(t), _ptr(amp), int(device))
+    _lib.check(st, "rtus_echo_pick")
+    fin = np.isfinite(amp)
+    top = amp[fin].max() if fin.any() else np.nan
+    with np.errstate(invalid="ignore"):
+        valid = np.isfinite(t) & fin & (amp >= threshold * top)
+    return dict(t=t, amplitude=amp, valid=valid)
+
+
+def geom_misfit(tt, t_meas, weights=None, *, device=0):
+    """rtus_geom_misfit on host arrays: tt [G, T, E], t_meas [T, E], weights [T, E] or None -> (n int32 [G], sse, sum_r, sum_w
+    float64 [G]) over the pairs where both times are finite and the weight is positive (include/rtus.h)."""
+    tt = np.ascontiguousarray(tt, dtype=np.float64)
+    tm = np.ascontiguousarray(t_meas, dtype=np.float64)
+    if tt.ndim != 3 or tm.shape != tt.shape[1:]:
+        raise ValueError("tt must be [G, T, E] and t_meas [T, E]")
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and w.shape != tm.shape:
+        raise ValueError("weights must have t_meas's shape")
+    G = tt.shape[0]
+    n = np.empty(G, dtype=np.int32)
+    sse, sr, sw = np.empty(G), np.empty(G), np.empty(G)
+    st = _lib.lib().rtus_geom_misfit(_ptr(tt), G, tt.shape[1], tt.shape[2], _ptr(tm), _ptr(w), _ptr(n), _ptr(sse), _ptr(sr), _ptr(sw),
+                                     int(device))
+    _lib.check(st, "rtus_geom_misfit")
+    return n, sse, sr, sw
+
+
+def _misfit_stats(n, sse, sr, sw, fit_delay):
+    """(mse, delay) per geometry from rtus_geom_misfit's sums: delay = the common offset of t_meas over the model, the weighted
+    mean of t_meas - tt (0 unless fitted); mse = the weighted sum of squares left, over n (NaN where n = 0)"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if fit_delay:
+            delay = np.where(n > 0, -sr / sw, np.nan)
+            mse = np.where(n > 0, np.maximum(sse - sr * sr / sw, 0.0) / n, np.nan)
+        else:
+            delay = np.where(n > 0, 0.0, np.nan)
+            mse = np.where(n > 0, sse / n, np.nan)
+    return mse, delay
+
+
+def _meas(t_meas, x_a, x_rx, weights):
+    x_a, x_rx = _f64(x_a, "x_a"), _f64(x_rx, "x_rx")
+    tm = np.ascontiguousarray(t_meas, dtype=np.float64)
+    if tm.shape != (x_a.size, x_rx.size):
+        raise ValueError(f"t_meas must be [n_tx, n_rx] = {(x_a.size, x_rx.size)}, got {tm.shape}")
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and w.shape != tm.shape:
+        raise ValueError("weights must have t_meas's shape")
+    return tm, w
+
+
+def pipe_misfit(t_meas, x_a, z_a, x_rx, alpha, geoms, *, weights=None, fit_delay=False, params: Params = None, device=0, **solve):
+    """The misfit of measured pulse-echo times t_meas [n_tx, n_rx] (NaN: no echo) to the model times of every geometry of
+    ``geoms`` [G, 2] = (r_outer, pipe_offset): one solve_travel_times call (its arguments x_a, z_a, x_rx, alpha and options
+    ``**solve``) and one rtus_geom_misfit launch — the reference's database search (main_compare.py:526-553) on any batch of
+    geometries.  -> dict(mse [G]: the weighted mean squared residual over the n [G] pairs where the model and the measurement are
+    both finite and the weight positive, NaN where there is none; delay [G]: with ``fit_delay`` the common offset of the
+    measurement over the model (t_meas = model + delay, removed from mse in closed form), else 0)."""
+    tm, w = _meas(t_meas, x_a, x_rx, weights)
+    tt = solve_travel_times(x_a, z_a, x_rx, alpha, geoms, params=params, device=device, **solve)[0]
+    n, sse, sr, sw = geom_misfit(tt, tm, w, device=device)
+    mse, delay = _misfit_stats(n, sse, sr, sw, fit_delay)
+    return dict(mse=mse, n=n, delay=delay)
+
+
+FIT_STEP = (2e-5, 2e-5)      # fit_pipe's central-difference half steps in (r_outer, pipe_offset) [m]
+FIT_TOL = 1e-10              # fit_pipe stops when both components of the step are below this [m]
+
+
+def pipe_clearance(pipe_offset, *, params: Params = None, alpha_lo=None, alpha_hi=None):
+    """The radius a pipe centred at (pipe_offset, 0) must stay under for travel_time_pipe to take it: the least distance from its
+    centre to the lens surface (rtus_pipe_clearance)."""
+    p = _resolve(params)
+    lens = p.lens()
+    a_lo = -ALPHA_MAX if alpha_lo is None else float(alpha_lo)
+    a_hi = ALPHA_MAX if alpha_hi is None else float(alpha_hi)
+    return float(_lib.lib().rtus_pipe_clearance(C.byref(lens), a_lo, a_hi, float(pipe_offset)))
+
+
+def fit_pipe(t_meas, x_a, z_a, x_rx, alpha, *, radii=None, offsets=None, min_pairs=8, fit_delay=False, weights=None, max_iter=40,
+             params: Params = None, device=0, **solve):
+    """The pipe's outer radius and offset from measured pulse-echo times t_meas [n_tx, n_rx] of its outer surface (NaN: no echo;
+    pick_echo_times makes them from an FMC), by least squares against solve_travel_times' model.
+
+    1. A coarse map: pipe_misfit over ``radii`` x ``offsets`` (default: the reference's sweep, drivers.sweep_geometries(): 1..10 cm
+       by -10..10 mm).  Nodes with fewer than ``min_pairs`` counting pairs, and nodes travel_time_pipe would reject for touching
+       the lens (pipe_clearance), are out.  ValueError when none is left.
+    2. Levenberg-Marquardt from the best node.  Every iteration is one solve_travel_times call on five geometries — the centre and
+       +-FIT_STEP in r_outer and in pipe_offset — and one rtus_geom_misfit launch: the launch gives the centre's cost (and delay),
+       the five tables give the residuals and their central differences over the pairs that are finite at all five.  A step
+       whose centre costs more than the last accepted one, has fewer than ``min_pairs`` pairs or would touch the lens is taken
+       back and the damping raised tenfold; an accepted one lowers it tenfold.
+    3. It stops when both components of the next step are below FIT_TOL (converged), or after ``max_iter`` iterations.
+
+    -> dict(r_outer, pipe_offset, delay (0 unless ``fit_delay``), mse, n_pairs, cov [2, 2] = s^2 (J^T J)^-1 with s^2 the residual
+    variance (weighted sum of squares over n_pairs - the number of fitted parameters), grid_mse [n_radii, n_offsets] (NaN where
+    a node is out), iterations, converged).  The geometry returned is always one travel_time_pipe takes."""
+    p = _resolve(params)
+    tm, w = _meas(t_meas, x_a, x_rx, weights)
+    if radii is None or offsets is None:
+        from . import drivers                              # (drivers imports this module)
+        ref = drivers.sweep_geometries()                   # radius-major: 10 radii x 21 offsets
+        radii = ref[::21, 0] if radii is None else radii
+        offsets = ref[:21, 1] if offsets is None else offsets
+    radii, offsets = _f64(radii, "radii"), _f64(offsets, "offsets")
+    min_pairs = int(min_pairs)
+    n_par = 3 if fit_delay else 2
+    if min_pairs < n_par + 1:
+        raise ValueError(f"min_pairs must be at least {n_par + 1}: the fit has {n_par} parameters")
+    a_lo, a_hi = float(np.min(alpha)), float(np.max(alpha))
+    dr, dx = FIT_STEP
+
+    def fits(r, x):
+        """the five geometries about (r, x) are pipes below the lens"""
+        return r - dr > 0 and all(r + dr < pipe_clearance(x + s, params=p, alpha_lo=a_lo, alpha_hi=a_hi) for s in (-dx, 0.0, dx))
+
+    geoms = np.asarray([[r, x] for r in radii for x in offsets], dtype=np.float64)
+    grid = pipe_misfit(tm, x_a, z_a, x_rx, alpha, geoms, weights=w, fit_delay=fit_delay, params=p, device=device, **solve)
+    ok = (grid["n"] >= min_pairs) & np.isfinite(grid["mse"]) & np.asarray([fits(r, x) for r, x in geoms])
+    grid_mse = np.where(ok, grid["mse"], np.nan).reshape(radii.size, offsets.size)
+    if not ok.any():
+        raise ValueError(f"no node of the geometry grid has {min_pairs} pairs with both a measured and a model time "
+                         f"(the most: {int(grid['n'].max())})")
+    x = geoms[np.nanargmin(np.where(ok, grid["mse"], np.nan))].copy()
+    sw_all = np.ones_like(tm) if w is None else w
+    lam, last, it, converged = 1e-3, None, 0, False      # last: the accepted state (x, mse, delay, n, JtJ, Jtr, s2)
+    step = None
+    while it < int(max_iter):
+        if last is not None:
+            x = last["x"] + step
+            if not fits(x[0], x[1]):                      # no solve: the step is taken back
+                lam *= 10.0
+                step = _lm_step(last, lam)
+                if lam > 1e12:
+                    break
+                continue
+        it += 1
+        g5 = np.asarray([x, x + [dr, 0], x - [dr, 0], x + [0, dx], x - [0, dx]], dtype=np.float64)
+        tt = solve_travel_times(x_a, z_a, x_rx, alpha, g5, params=p, device=device, **solve)[0]
+        n, sse, sr, sw = geom_misfit(tt, tm, w, device=device)
+        mse, delay = _misfit_stats(n, sse, sr, sw, fit_delay)
+        if n[0] < min_pairs or not np.isfinite(mse[0]) or (last is not None and mse[0] > last["mse"]):
+            if last is None:
+                raise ValueError("the best grid node lost its pairs")       # (cannot happen: the map counted them)
+            lam *= 10.0
+            step = _lm_step(last, lam)
+            if abs(step[0]) <= FIT_TOL and abs(step[1]) <= FIT_TOL:
+                converged = True                          # nothing better within a step of the tolerance
+                break
+            if lam > 1e12:
+                break
+            continue
+        with np.errstate(invalid="ignore"):
+            use = np.isfinite(tt).all(axis=0) & np.isfinite(tm) & (sw_all > 0)
+        res = (tt[0] - tm)[use]
+        J = np.stack([(tt[1] - tt[2])[use] / (2 * dr), (tt[3] - tt[4])[use] / (2 * dx)], axis=1)
+        wt = sw_all[use]
+        if fit_delay and wt.size:                         # the common offset projected out of the residuals and of the Jacobian
+            res = res - np.sum(wt * res) / np.sum(wt)
+            J = J - (wt @ J) / np.sum(wt)
+        JtJ, Jtr = J.T @ (J * wt[:, None]), J.T @ (wt * res)
+        dof = max(int(use.sum()) - n_par, 1)
+        state = dict(x=x.copy(), mse=float(mse[0]), delay=float(delay[0]), n=int(n[0]), JtJ=JtJ, Jtr=Jtr,
+                     s2=float(np.sum(wt * res * res)) / dof, n_use=int(use.sum()))
+        if last is not None:
+            lam = max(lam / 10.0, 1e-12)
+        last = state
+        if state["n_use"] < n_par or not np.all(np.isfinite(JtJ)) or np.linalg.cond(JtJ) > 1e15:
+            break                                         # the pairs left do not determine a step
+        step = _lm_step(last, lam)
+        if abs(step[0]) <= FIT_TOL and abs(step[1]) <= FIT_TOL:
+            converged = True
+            break
+    with np.errstate(all="ignore"):
+        try:
+            cov = last["s2"] * np.linalg.inv(last["JtJ"])
+        except np.linalg.LinAlgError:
+            cov = np.full((2, 2), np.nan)
+    return dict(r_outer=float(last["x"][0]), pipe_offset=float(last["x"][1]), delay=last["delay"], mse=last["mse"], n_pairs=last["n"],
+                cov=cov, grid_mse=grid_mse, iterations=it, converged=converged)
+
+
+def _lm_step(state, lam):
+    """(J^T J + lam diag(J^T J)) step = -J^T r"""
+    A = state["JtJ"] + lam * np.diag(np.diag(state["JtJ"]))
+    return -np.linalg.solve(A, state["Jtr"])
+
+
+def adaptive_tfm_pipe(fmc, fs, xe, ze, xf, zf, *, t_lo, t_hi, c3, r_inner, t0=0.0, alpha=None, n_taps=63, threshold=0.1, envelope=False,
+                      fit_delay=False, min_pairs=8, radii=None, offsets=None, max_iter=40, params: Params = None, device=0, **solve):
+    """Adaptive TFM of a pipe wall: pick the outer-surface echo of every pair of a square FMC inside the gate [t_lo, t_hi]
+    (pick_echo_times), fit the pipe's radius and offset to the valid picks (fit_pipe; the elements (xe, ze) transmit and receive,
+    ``alpha``: the launch-angle grid of the model, default 905 angles over +-ALPHA_MAX as in the reference's sweep), build the
+    wall's travel times for the fitted geometry (travel_time_pipe with speed ``c3`` and bore ``r_inner``) and image the points
+    (xf, zf): tfm_image, or with ``envelope=True`` the envelope np.abs(tfm_analytic(...)).  The analytic FMC is formed once.
+    A fitted delay shifts the record's time origin for the image (an echo the model puts at t is looked up at t + delay).
+    -> (image float32 [n_f], fit dict of fit_pipe plus ``picks``: the dict of pick_echo_times)."""
+    p = _resolve(params)
+    fmc = np.ascontiguousarray(fmc, dtype=np.float32)
+    if fmc.ndim != 3 or fmc.shape[0] != fmc.shape[1]:
+        raise ValueError("fmc must be a square block [n_e, n_e, n_t]")
+    xe, ze = _f64(xe, "xe"), _f64(ze, "ze")
+    if xe.size != fmc.shape[0] or ze.size != fmc.shape[0]:
+        raise ValueError("xe / ze must hold one position per element of the FMC")
+    alpha = np.linspace(-ALPHA_MAX, ALPHA_MAX, 905) if alpha is None else _f64(alpha, "alpha")
+    analytic = fmc_analytic(fmc, n_taps, device=device)
+    picks = pick_echo_times(analytic, fs, t_lo, t_hi, t0=t0, threshold=threshold, device=device)
+    tm = np.where(picks["valid"], picks["t"], np.nan)
+    fit = fit_pipe(tm, xe, ze, xe, alpha, radii=radii, offsets=offsets, min_pairs=min_pairs, fit_delay=fit_delay, max_iter=max_iter,
+                   params=p, device=device, **solve)
+    fitted = replace(p, r_outer=fit["r_outer"], pipe_offset=fit["pipe_offset"])
+    tt = travel_time_pipe(xe, ze, xf, zf, c3=c3, r_inner=r_inner, params=fitted, alpha_lo=float(alpha[0]), alpha_hi=float(alpha[-1]),
+                          device=device)
+    fit["picks"] = picks
+    if envelope:
+        return np.abs(tfm_analytic(analytic, fs, tt, t0=t0 - fit["delay"], device=device)), fit
+    return tfm_image(fmc, fs, tt, t0=t0 - fit["delay"], device=device), fit

@@ -1,12 +1,14 @@
 // rtus_autofocus.hip — measuring the surface profile from the FMC data that is later imaged ("adaptive TFM"): an analytic
 // (complex) FMC by an FIR Hilbert transform, and an envelope image of the couplant above the part, reduced to the depth of the
 // surface echo in every column.  NOT IN THE REFERENCE: checked against tests/autofocus_numpy.py.  Definitions in include/rtus.h
-// (rtus_fmc_analytic, rtus_surface_find).
+// (rtus_fmc_analytic, rtus_surface_find, rtus_echo_pick).
 //
 //   * rtus_analytic_kernel: one workgroup = RTUS_ANA_TILE samples of one A-scan plus the filter's halo in LDS; streams the FMC
 //     (4 B in, 8 B out per sample) -> HBM roofline, a small share of the chain.
 //   * rtus_surface_find_kernel: the rtus_tfm gather loop on complex samples, with straight-ray delays formed in the kernel instead
 //     of read from a table: 16 B of L2 traffic per (pair, pixel).  The roof is the L2 gather rate, as for rtus_tfm.
+//   * rtus_echo_pick_kernel: one wave = one A-scan, lanes over the samples of its gate, 16-byte loads, a cross-lane arg-max that
+//     keeps the first index; streams the gated part of the analytic FMC once -> HBM roofline.
 #include "rtus_device.h"
 
 // ---------------------------------------------------------------------------------------------- analytic FMC
@@ -194,5 +196,130 @@ hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs
     a.n_e = n_e; a.n_t = n_t; a.n_s = n_s; a.n_z = n_z;
     a.c1 = c1; a.fs = fs; a.half_t0s = 0.5 * t0 * fs; a.x0 = x0; a.dx = dx; a.z_lo = z_lo; a.dz = dz;
     hipLaunchKernelGGL(rtus_surface_find_kernel, dim3(n_s), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- echo time of every pair
+// t_pick[pair] = t0 + (j* + d) / fs, j* the first index of the maximum of |a[pair][.]| over the samples of the pair's gate and d
+// rtus_surface_find's parabolic step.  The magnitude is fp32, every operation rounded on its own (no fused multiply-add), so that
+// it can be restated bit for bit: sqrt(re * re + im * im), the root correctly rounded.
+//
+// One wave = one A-scan (RTUS_BLOCK / RTUS_WAVE per workgroup, no barrier).  Lane l takes the sample pairs (2 l, 2 l + 1) of a
+// trip of 128 samples, counted from the 16-byte boundary at or below the gate's first sample; four trips' loads are issued before
+// the first is used.  A 16-byte load is issued only where both of its samples are inside the gate (so nothing outside the caller's
+// block is read); the one or two half-filled loads at the gate's ends are 8-byte loads.
+#define RTUS_PICK_UNROLL 4
+
+struct PickArgs {
+    const float2* __restrict__ a;        // [n_pairs][n_t]
+    const double* __restrict__ g_lo;     // [n_pairs] or null
+    const double* __restrict__ g_hi;     // [n_pairs] or null
+    double* __restrict__ t_pick;         // [n_pairs]
+    float* __restrict__ amp;             // [n_pairs]
+    long long n_pairs;
+    int n_t;
+    double fs, t0, t_lo, t_hi;
+};
+
+__device__ __forceinline__ float pick_mag(float re, float im)
+{
+#pragma clang fp contract(off)                               // re * re + im * im must not become a fused multiply-add
+    const float p = re * re, q = im * im;
+    // v_sqrt_f32 is good to 1 ulp only.  The fp64 root is correctly rounded (rtus_trig.h), and rounding it once more to fp32 is
+    // innocuous for a square root: 53 >= 2 * 24 + 2 bits.
+    return (float)rtus_sqrt((double)(p + q));
+}
+
+// one sample into a lane's running maximum: ascending index within a lane, strict > keeps the first
+__device__ __forceinline__ void pick_take(float m, int i, float& best, int& best_i, bool& bad)
+{
+    bad |= !(m <= 3.402823466e38f);                          // NaN or inf
+    if (m > best) { best = m; best_i = i; }
+}
+
+// the samples i, i + 1 (rec + i 16-byte aligned), each only where it lies inside [i_lo, i_hi]
+__device__ __forceinline__ void pick_guarded(const float2* rec, int i, int i_lo, int i_hi, float& best, int& best_i, bool& bad)
+{
+    const bool in0 = i >= i_lo && i <= i_hi, in1 = i + 1 >= i_lo && i + 1 <= i_hi;
+    if (in0 && in1) {
+        const float4 v = *(const float4*)(rec + i);
+        pick_take(pick_mag(v.x, v.y), i, best, best_i, bad);
+        pick_take(pick_mag(v.z, v.w), i + 1, best, best_i, bad);
+    } else if (in0) {
+        const float2 v = rec[i];
+        pick_take(pick_mag(v.x, v.y), i, best, best_i, bad);
+    } else if (in1) {
+        const float2 v = rec[i + 1];
+        pick_take(pick_mag(v.x, v.y), i + 1, best, best_i, bad);
+    }
+}
+
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_echo_pick_kernel(PickArgs a)
+{
+    const long long pair = (long long)blockIdx.x * (RTUS_BLOCK / RTUS_WAVE) + (threadIdx.x / RTUS_WAVE);
+    if (pair >= a.n_pairs) return;                           // (whole waves: no barrier below)
+    const int lane = threadIdx.x % RTUS_WAVE;
+    // the gate in samples: t_lo <= t0 + i / fs <= t_hi, inside the record
+    double lo = ceil(((a.g_lo ? a.g_lo[pair] : a.t_lo) - a.t0) * a.fs);
+    double hi = floor(((a.g_hi ? a.g_hi[pair] : a.t_hi) - a.t0) * a.fs);
+    const bool ordered = lo <= hi;                           // (false for a NaN bound: fmax / fmin below would drop it)
+    lo = fmax(lo, 0.0);
+    hi = fmin(hi, (double)(a.n_t - 1));
+    const bool open = ordered && lo <= hi;                   // (false for an empty gate and for a gate outside the record)
+    const int i_lo = open ? (int)lo : 0, i_hi = open ? (int)hi : -1;
+    const float2* rec = a.a + pair * (long long)a.n_t;
+    float best = -1.0f;
+    int best_i = a.n_t;
+    bool bad = false;
+    const int s0 = i_lo - (int)(((uintptr_t)(rec + i_lo) >> 3) & 1);      // rec + s0 is 16-byte aligned; s0 >= i_lo - 1
+    const int step = 2 * RTUS_WAVE;
+    int i = s0 + 2 * lane;
+    if (s0 < i_lo) {                                         // the gate starts on an odd boundary: lane 0 holds the sample before it
+        pick_guarded(rec, i, i_lo, i_hi, best, best_i, bad);
+        i += step;
+    }
+    // full trips: every lane's two samples of all RTUS_PICK_UNROLL trips lie inside the gate (a wave-uniform test)
+    for (; (long long)(i - 2 * lane) + RTUS_PICK_UNROLL * step - 1 <= i_hi; i += RTUS_PICK_UNROLL * step) {
+        float4 v[RTUS_PICK_UNROLL];
+#pragma unroll
+        for (int q = 0; q < RTUS_PICK_UNROLL; ++q) v[q] = *(const float4*)(rec + i + q * step);
+#pragma unroll
+        for (int q = 0; q < RTUS_PICK_UNROLL; ++q) {
+            pick_take(pick_mag(v[q].x, v[q].y), i + q * step, best, best_i, bad);
+            pick_take(pick_mag(v[q].z, v[q].w), i + q * step + 1, best, best_i, bad);
+        }
+    }
+    for (; i <= i_hi; i += step) pick_guarded(rec, i, i_lo, i_hi, best, best_i, bad);      // the tail
+    // cross-lane arg-max, the first index among equal maxima; every lane ends with the wave's result
+    int key = bad ? -1 : best_i;                             // -1: a non-finite magnitude inside the gate
+#pragma unroll
+    for (int h = RTUS_WAVE / 2; h > 0; h >>= 1) {
+        const float v2 = __shfl_xor(best, h, RTUS_WAVE);
+        const int k2 = __shfl_xor(key, h, RTUS_WAVE);
+        if (key < 0 || k2 < 0) key = -1;
+        else if (v2 > best || (v2 == best && k2 < key)) { best = v2; key = k2; }
+    }
+    if (lane == 0) {
+        double t = NAN;
+        if (key > i_lo && key < i_hi && best > 0.0f) {       // inside the gate, a finite, non-zero maximum
+            const float2 vm = rec[key - 1], vp = rec[key + 1];
+            const double am = pick_mag(vm.x, vm.y), a0 = best, ap = pick_mag(vp.x, vp.y);
+            double d = (am - ap) / (2.0 * (am - 2.0 * a0 + ap));         // am < a0, ap <= a0: denominator < 0
+            d = fmin(fmax(d, -0.5), 0.5);
+            t = a.t0 + ((double)key + d) / a.fs;
+        }
+        a.t_pick[pair] = t;
+        a.amp[pair] = (key < 0 || !open) ? NAN : best;
+    }
+}
+
+hipError_t rtus_launch_echo_pick(const float* an, long long n_pairs, int n_t, double fs, double t0, double t_lo, double t_hi,
+                                 const double* g_lo, const double* g_hi, double* t_pick, float* amp, hipStream_t s)
+{
+    PickArgs a;
+    a.a = (const float2*)an; a.g_lo = g_lo; a.g_hi = g_hi; a.t_pick = t_pick; a.amp = amp;
+    a.n_pairs = n_pairs; a.n_t = n_t; a.fs = fs; a.t0 = t0; a.t_lo = t_lo; a.t_hi = t_hi;
+    const int per = RTUS_BLOCK / RTUS_WAVE;
+    hipLaunchKernelGGL(rtus_echo_pick_kernel, dim3((unsigned)((n_pairs + per - 1) / per)), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }

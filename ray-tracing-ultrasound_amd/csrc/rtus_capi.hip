@@ -68,6 +68,10 @@ hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t
 hipError_t rtus_launch_surface_find(const float* an, int n_e, int n_t, double fs, double t0, const double* xe, const double* ze,
                                     double c1, double x0, double dx, int n_s, double z_lo, double dz, int n_z, double* z_peak,
                                     float* amp, float* image, hipStream_t s);
+hipError_t rtus_launch_echo_pick(const float* an, long long n_pairs, int n_t, double fs, double t0, double t_lo, double t_hi,
+                                 const double* g_lo, const double* g_hi, double* t_pick, float* amp, hipStream_t s);
+hipError_t rtus_launch_geom_misfit(const double* tt, int n_geom, int n_tx, int n_rx, const double* t_meas, const double* w, int* n,
+                                   double* sse, double* sum_r, double* sum_w, hipStream_t s);
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
@@ -1042,6 +1046,90 @@ int rtus_surface_find(const float* a, int n_e, int n_t, double fs, double t0, co
     return S.finish();
 }
 
+// ---------------------------------------------------------------------------- echo times of every pair of an analytic FMC
+#define RTUS_ECHO_PICK_MAX_PAIRS 0x7fffffffLL
+static int check_echo_pick(const void* a, int n_tx, int n_rx, int n_t, double fs, double t0, double t_lo, double t_hi, const void* g_lo,
+                           const void* g_hi, const void* t_pick, const void* amp)
+{
+    if (!a || !t_pick || !amp || n_tx <= 0 || n_rx <= 0 || n_t < 3) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(fs) || !(fs > 0) || !isfinite(t0)) return RTUS_ERR_INVALID_ARG;
+    if ((!g_lo && isnan(t_lo)) || (!g_hi && isnan(t_hi))) return RTUS_ERR_INVALID_ARG;   // (infinite: open on that side)
+    if ((uintptr_t)a & 7) return RTUS_ERR_INVALID_ARG;                                   // complex samples are read whole
+    if (n_t > RTUS_ANALYTIC_MAX_SAMPLES || (long long)n_tx * n_rx > RTUS_ECHO_PICK_MAX_PAIRS) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+int rtus_echo_pick_dev(const float* d_a, int n_tx, int n_rx, int n_t, double fs, double t0, double t_lo, double t_hi,
+                       const double* d_t_lo, const double* d_t_hi, double* d_t_pick, float* d_amp, void* stream)
+{
+    int st = check_echo_pick(d_a, n_tx, n_rx, n_t, fs, t0, t_lo, t_hi, d_t_lo, d_t_hi, d_t_pick, d_amp);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_echo_pick(d_a, (long long)n_tx * n_rx, n_t, fs, t0, t_lo, t_hi, d_t_lo, d_t_hi, d_t_pick, d_amp,
+                                     (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_echo_pick(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, double t_lo, double t_hi, const double* g_lo,
+                   const double* g_hi, double* t_pick, float* amp, int device)
+{
+    int st = check_echo_pick(a, n_tx, n_rx, n_t, fs, t0, t_lo, t_hi, g_lo, g_hi, t_pick, amp);
+    if (st) return st;
+    const size_t n_pairs = (size_t)n_tx * n_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    float *da, *damp;
+    double *dlo, *dhi, *dt;
+    S.in(da, a, n_pairs * n_t * 2);
+    S.in(dlo, g_lo, g_lo ? n_pairs : 0);
+    S.in(dhi, g_hi, g_hi ? n_pairs : 0);
+    S.out(dt, t_pick, n_pairs);
+    S.out(damp, amp, n_pairs);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_echo_pick(da, (long long)n_pairs, n_t, fs, t0, t_lo, t_hi, dlo, dhi, dt, damp, S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- misfit of a batch of geometries to measured times
+#define RTUS_MISFIT_MAX_GEOMS 0x7fffffff
+static int check_geom_misfit(const void* tt, int n_geom, int n_tx, int n_rx, const void* t_meas, const void* n, const void* sse,
+                             const void* sum_r)
+{
+    if (!tt || !t_meas || !n || !sse || !sum_r || n_geom <= 0 || n_tx <= 0 || n_rx <= 0) return RTUS_ERR_INVALID_ARG;
+    if ((long long)n_tx * n_rx > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;             // n[g] is an int
+    return RTUS_OK;
+}
+
+int rtus_geom_misfit_dev(const double* d_tt, int n_geom, int n_tx, int n_rx, const double* d_t_meas, const double* d_w, int* d_n,
+                         double* d_sse, double* d_sum_r, double* d_sum_w, void* stream)
+{
+    int st = check_geom_misfit(d_tt, n_geom, n_tx, n_rx, d_t_meas, d_n, d_sse, d_sum_r);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_geom_misfit(d_tt, n_geom, n_tx, n_rx, d_t_meas, d_w, d_n, d_sse, d_sum_r, d_sum_w, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_geom_misfit(const double* tt, int n_geom, int n_tx, int n_rx, const double* t_meas, const double* w, int* n, double* sse,
+                     double* sum_r, double* sum_w, int device)
+{
+    int st = check_geom_misfit(tt, n_geom, n_tx, n_rx, t_meas, n, sse, sum_r);
+    if (st) return st;
+    const size_t row = (size_t)n_tx * n_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dtt, *dtm, *dw, *dq, *dr, *dsw;
+    int* dn;
+    S.in(dtt, tt, row * n_geom);
+    S.in(dtm, t_meas, row);
+    S.in(dw, w, w ? row : 0);
+    S.out(dn, n, n_geom);
+    S.out(dq, sse, n_geom);
+    S.out(dr, sum_r, n_geom);
+    S.out(dsw, sum_w, n_geom);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_geom_misfit(dtt, n_geom, n_tx, n_rx, dtm, dw, dn, dq, dr, dsw, S.a->stream));
+    return S.finish();
+}
+
 // ---------------------------------------------------------------------------- envelope TFM + coherence factor over an analytic FMC
 static int check_tfm_analytic(const void* a, int n_tx, int n_rx, int n_t, double fs, double t0, const void* tt_tx, const void* tt_rx,
                               int n_f, const void* image)
@@ -1692,6 +1780,13 @@ static double lens_clearance(const rtus_lens& L, double a_lo, double a_hi, doubl
         if (d1 < d2) hi = x2; else lo = x1;
     }
     return best;
+}
+
+// the radius below which rtus_tt_pipe takes a pipe centred at (x_off, 0): what the geometry fit must stay under
+extern "C" double rtus_pipe_clearance(const rtus_lens* lens, double alpha_lo, double alpha_hi, double x_off)
+{
+    if (!lens || !isfinite(alpha_lo) || !isfinite(alpha_hi) || !(alpha_hi > alpha_lo) || !isfinite(x_off)) return NAN;
+    return lens_clearance(*lens, alpha_lo, alpha_hi, x_off);
 }
 
 #define RTUS_PIPE_MAX_SCAN 65536

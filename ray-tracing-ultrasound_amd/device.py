@@ -736,3 +736,62 @@ def leg_amp_pipe_dev(leg, xe, ze, xf, zf, alpha, beta, gamma=None, *, c_l, c_t, 
                                           _p(beta), _p(gamma if len(leg) == 2 else None), _p(out), _stream(xe))
     _lib.check(st, "rtus_leg_amp_pipe_dev")
     return out
+
+
+def echo_pick_dev(analytic, fs, t_lo, t_hi, t0=0.0, t_pick=None, amp=None):
+    """Echo time of every pair on device (rtus_echo_pick_dev; api.pick_echo_times' definition): analytic float32
+    [n_tx, n_rx, n_t, 2]; t_lo / t_hi: a scalar each, or a float64 tensor [n_tx, n_rx] of per-pair bounds -> (t_pick float64
+    [n_tx, n_rx], amp float32 [n_tx, n_rx]).  Outputs not given are allocated here; asynchronous on the current stream (capturable
+    with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32)
+    if analytic.dim() != 4 or analytic.shape[3] != 2:
+        raise ValueError("analytic must be [n_tx, n_rx, n_t, 2]")
+    n_tx, n_rx, n_t = analytic.shape[:3]
+
+    def bound(v, name):
+        if not isinstance(v, torch.Tensor):
+            return float(v), None
+        _chk(v, name)
+        if v.numel() != n_tx * n_rx or v.device != analytic.device:
+            raise ValueError(f"{name} must hold one bound per pair on the device of analytic")
+        return 0.0, v
+    lo, lo_t = bound(t_lo, "t_lo")
+    hi, hi_t = bound(t_hi, "t_hi")
+    if t_pick is None:
+        t_pick = torch.empty((n_tx, n_rx), dtype=torch.float64, device=analytic.device)
+    if amp is None:
+        amp = torch.empty((n_tx, n_rx), dtype=torch.float32, device=analytic.device)
+    _chk(t_pick, "t_pick"); _chk(amp, "amp", torch.float32)
+    if t_pick.numel() != n_tx * n_rx or amp.numel() != n_tx * n_rx:
+        raise ValueError("t_pick / amp must hold one value per pair")
+    st = _lib.lib().rtus_echo_pick_dev(_p(analytic), n_tx, n_rx, n_t, float(fs), float(t0), lo, hi, _p(lo_t), _p(hi_t), _p(t_pick),
+                                       _p(amp), _stream(analytic))
+    _lib.check(st, "rtus_echo_pick_dev")
+    return t_pick, amp
+
+
+def geom_misfit_dev(tt, t_meas, weights=None, n=None, sse=None, sum_r=None, sum_w=None):
+    """Misfit sums of a batch of geometries on device (rtus_geom_misfit_dev; include/rtus.h): tt float64 [G, T, E] (SolvePlan's
+    ``tt``), t_meas [T, E], weights [T, E] or None -> (n int32 [G], sse, sum_r, sum_w float64 [G]).  Outputs not given are
+    allocated here; asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    _chk(tt, "tt"); _chk(t_meas, "t_meas")
+    if tt.dim() != 3 or tuple(t_meas.shape) != tuple(tt.shape[1:]):
+        raise ValueError("tt must be [G, T, E] and t_meas [T, E]")
+    if weights is not None:
+        _chk(weights, "weights")
+        if tuple(weights.shape) != tuple(t_meas.shape):
+            raise ValueError("weights must have t_meas's shape")
+    G = tt.shape[0]
+    if n is None:
+        n = torch.empty(G, dtype=torch.int32, device=tt.device)
+    outs = []
+    for o in (sse, sum_r, sum_w):
+        outs.append(torch.empty(G, dtype=torch.float64, device=tt.device) if o is None else o)
+    sse, sum_r, sum_w = outs
+    _chk(n, "n", torch.int32); _chk(sse, "sse"); _chk(sum_r, "sum_r"); _chk(sum_w, "sum_w")
+    if any(o.numel() != G for o in (n, sse, sum_r, sum_w)):
+        raise ValueError("n / sse / sum_r / sum_w must hold one value per geometry")
+    st = _lib.lib().rtus_geom_misfit_dev(_p(tt), G, tt.shape[1], tt.shape[2], _p(t_meas), _p(weights), _p(n), _p(sse), _p(sum_r),
+                                         _p(sum_w), _stream(tt))
+    _lib.check(st, "rtus_geom_misfit_dev")
+    return n, sse, sum_r, sum_w
