@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 113 /* 0.1.12: rtus_echo_pick*, rtus_geom_misfit*, rtus_pipe_clearance (pipe geometry from measured echo times) */
+#define RTUS_VERSION 114 /* 0.1.13: rtus_fmc_sim*, rtus_fmc_sim_echo* (ray-model FMC simulator: arrivals to A-scans) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -999,6 +999,73 @@ int rtus_geom_misfit_dev(const double *d_tt, int n_geom, int n_tx, int n_rx, con
 int rtus_geom_misfit(const double *tt, int n_geom, int n_tx, int n_rx, const double *t_meas, const double *w,
                      int *n, double *sse, double *sum_r, double *sum_w, int device);
 double rtus_pipe_clearance(const rtus_lens *lens, double alpha_lo, double alpha_hi, double x_off);
+
+/* ------------------------------------------------------------------------------------------
+ * THE FORWARD MODEL: arrivals to the A-scans of a full-matrix capture (FMC) — the way back from the tables of this library to
+ * data.  rtus_tfm_weighted with w = conj(A) is the matched filter of this model.  NOT IN THE REFERENCE; checked against
+ * tests/fmcsim_numpy.py (the same formulas with fp64 sums).
+ *
+ * Every arrival, a time tau and a complex amplitude a, adds a p(t_j - tau) to the samples t_j = t0 + j / fs, 0 <= j < n_t, of
+ * its A-scan.  Two ways of stating the arrivals, one kernel body:
+ *   rtus_fmc_sim       scatterer s arrives in A-scan (tx, rx) at tau = tt_tx[tx][s] + tt_rx[rx][s] (one fp64 sum) with
+ *                      a = (q[s] w_tx[tx][s]) w_rx[rx][s].
+ *                        tt_tx [n_tx][n_s], tt_rx [n_rx][n_s]  fp64; any table of this library; the two may be one table
+ *                        q [n_s], w_tx [n_tx][n_s], w_rx [n_rx][n_s]  complex64 (interleaved float32 pairs, 8-byte aligned), each
+ *                        nullable: null is the factor 1 (that product is skipped)
+ *   rtus_fmc_sim_echo  arrival k of pair (tx, rx) is given directly: tau = t_pair[tx][rx][k], a = amp[tx][rx][k]
+ *                        t_pair [n_tx][n_rx][n_a] fp64 (n_a >= 1; e.g. rtus_solve's tt, n_a = 1); amp complex64, nullable (1)
+ *   A complex product is (ar br - ai bi, ar bi + ai br) in fp32, every operation rounded on its own.
+ *
+ * The wavelet p is a table: pulse [n_p] complex64 sampled at fs * oversample (oversample an integer >= 1), time zero at index
+ * `centre`.  The table continues with p[-1] = p[n_p] = 0 and is zero beyond; between samples it is interpolated linearly, the real
+ * and the imaginary part separately, each as fmaf(w, p[i + 1] - p[i], p[i]) with the difference rounded to fp32 (rtus_tfm_analytic's
+ * rule).  The values of the table are expected to be finite.
+ * Position (PINNED; fp64, every operation rounded on its own, no fused multiply-add):
+ *     d  = ((tau - t0) * fs) * oversample          the arrival in table steps after the record's start
+ *     x0 = centre - d                              the table position of sample 0
+ *     i0 = floor(x0),  w = (float)(x0 - i0)        (the difference is exact; w is rounded once)
+ *   sample j reads the table at i = i0 + j * oversample with the weight w — the same w for every sample of the arrival; it is
+ *   touched iff -1 <= i <= n_p - 1.  An arrival contributes NOTHING when its time is not finite or |d| >= 2^30, or when q, w_tx,
+ *   w_rx / amp or their product has a non-finite part: it never poisons the A-scan.  Samples before 0 or at / past n_t are dropped,
+ *   the rest of the pulse is still written.
+ * Sample update, with (pr, pi) the interpolated wavelet and (ar, ai) the amplitude:
+ *     re = fmaf(-ai, pi, fmaf(ar, pr, re)),   im = fmaf(ai, pr, fmaf(ar, pi, im))
+ *
+ * out  [n_tx][n_rx][n_t] float32: the real part; with RTUS_SIM_ANALYTIC complex64 [n_tx][n_rx][n_t][2] (the real parts of the two
+ *      are the same bits).  Without RTUS_SIM_ACCUMULATE the call zeroes out itself (what out held is never read); with it, the
+ *      arrivals are added onto what out holds.
+ * ACCUMULATION CONTRACT (tested by bits):
+ *   - a sample's real and imaginary sums are fp32; its arrivals are added strictly in ascending s (or k), starting from the
+ *     sample's initial value (0, or what out held);
+ *   - the bits of an A-scan depend only on its own rows of the inputs and the scalars: any subset of tx or rx rows reproduces them;
+ *   - one call over n_s scatterers equals, bit for bit, a call over the first m followed by a RTUS_SIM_ACCUMULATE call over the rest:
+ *     reflector sets of any size can be streamed in chunks.  A multi-view FMC is such a chain, one call per view in the order the
+ *     caller states (api.simulate_views: the views in the order given, "A-B" before its reciprocal "B-A");
+ *   - host twin, _dev twin and a captured-graph replay give the same bits.
+ * Argument checks run before any HIP call: -1 for a null required pointer (the time tables, pulse, out), a non-positive size,
+ *   fs not finite and positive, t0 not finite, oversample < 1, centre outside [0, n_p), an unknown flag bit, a complex64 array that
+ *   is not 8-byte aligned or an out that is not 4-byte aligned; -5 past n_t <= 2^26, n_p + oversample <= 2048 (the wavelet's 16-byte
+ *   entries take half of a workgroup's 64 KB of LDS), n_tx n_rx ceil(n_t / 1024) <= 2^31 - 1.  No workspace.
+ * The _dev entries allocate nothing and do not synchronise (capturable); the host twins stage through the device's arena (one
+ * table uploaded when tt_tx == tt_rx, out uploaded only with RTUS_SIM_ACCUMULATE).
+ * Kernel, resources and measured figures on MI355X: DESIGN.md section 4 (FMC simulator).
+ * ---------------------------------------------------------------------------------------- */
+#define RTUS_SIM_ANALYTIC 0x1u
+#define RTUS_SIM_ACCUMULATE 0x2u
+int rtus_fmc_sim_dev(const double *d_tt_tx, const double *d_tt_rx, int n_tx, int n_rx, int n_s,
+                     const float *d_q, const float *d_w_tx, const float *d_w_rx,
+                     const float *d_pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t,
+                     float *d_out, unsigned flags, void *stream);
+int rtus_fmc_sim(const double *tt_tx, const double *tt_rx, int n_tx, int n_rx, int n_s,
+                 const float *q, const float *w_tx, const float *w_rx,
+                 const float *pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t,
+                 float *out, unsigned flags, int device);
+int rtus_fmc_sim_echo_dev(const double *d_t_pair, const float *d_amp, int n_tx, int n_rx, int n_a,
+                          const float *d_pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t,
+                          float *d_out, unsigned flags, void *stream);
+int rtus_fmc_sim_echo(const double *t_pair, const float *amp, int n_tx, int n_rx, int n_a,
+                      const float *pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t,
+                      float *out, unsigned flags, int device);
 
 #ifdef __cplusplus
 }

@@ -253,6 +253,16 @@ def lib():
     except AttributeError:                # a build from before version 113, loaded through RTUS_LIB for an A/B run
         if not os.environ.get("RTUS_LIB"):
             raise
+    try:
+        L.rtus_fmc_sim_dev.argtypes = [dp, dp, ip, ip, ip, dp, dp, dp, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, vp]
+        L.rtus_fmc_sim.argtypes = [dp, dp, ip, ip, ip, dp, dp, dp, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, ip]
+        L.rtus_fmc_sim_echo_dev.argtypes = [dp, dp, ip, ip, ip, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, vp]
+        L.rtus_fmc_sim_echo.argtypes = [dp, dp, ip, ip, ip, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, ip]
+        for name in ("rtus_fmc_sim_dev", "rtus_fmc_sim", "rtus_fmc_sim_echo_dev", "rtus_fmc_sim_echo"):
+            getattr(L, name).restype = ip
+    except AttributeError:                # a build from before version 114, loaded through RTUS_LIB for an A/B run
+        if not os.environ.get("RTUS_LIB"):
+            raise
     for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
                  "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
         getattr(L, name).restype = ip
@@ -285,4 +295,5 @@ EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_
            "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe",
            "rtus_tt_pipe_skip_workspace_bytes", "rtus_tt_pipe_skip_dev", "rtus_tt_pipe_skip",
            "rtus_leg_amp_pipe_dev", "rtus_leg_amp_pipe",
-           "rtus_echo_pick_dev", "rtus_echo_pick", "rtus_geom_misfit_dev", "rtus_geom_misfit", "rtus_pipe_clearance")
+           "rtus_echo_pick_dev", "rtus_echo_pick", "rtus_geom_misfit_dev", "rtus_geom_misfit", "rtus_pipe_clearance",
+           "rtus_fmc_sim_dev", "rtus_fmc_sim", "rtus_fmc_sim_echo_dev", "rtus_fmc_sim_echo")

@@ -1368,3 +1368,150 @@ def adaptive_tfm_pipe(fmc, fs, xe, ze, xf, zf, *, t_lo, t_hi, c3, r_inner, t0=0.
     if envelope:
         return np.abs(tfm_analytic(analytic, fs, tt, t0=t0 - fit["delay"], device=device)), fit
     return tfm_image(fmc, fs, tt, t0=t0 - fit["delay"], device=device), fit
+
+
+# ---------------------------------------------------------------------------------------------- the forward model: FMC simulator
+SIM_ANALYTIC = 0x1          # RTUS_SIM_ANALYTIC (include/rtus.h)
+SIM_ACCUMULATE = 0x2        # RTUS_SIM_ACCUMULATE
+SIM_MAX_TABLE = 2048        # n_p + oversample (rtus_fmc_sim's limit)
+
+
+def gaussian_pulse(f0, cycles, fs, oversample=8, *, analytic=True):
+    """A Gaussian tone burst as simulate_fmc's wavelet table -> (pulse complex64 [n_p], centre): exp(-u^2 / (2 sigma^2))
+    exp(2 pi i f0 u) with sigma = cycles / f0 / 2.355, sampled at u = (k - centre) / (fs oversample) for |u| <= 6 sigma (the dropped
+    tail is below 1.6e-8 of the peak, under half an fp32 ulp).  ``analytic=False``: the imaginary part is zero (an RF pulse,
+    exp(.) cos(2 pi f0 u))."""
+    f0, cycles, fs = float(f0), float(cycles), float(fs)
+    if not (f0 > 0 and cycles > 0 and fs > 0 and np.isfinite(f0 * cycles * fs)):
+        raise ValueError("f0, cycles and fs must be finite and positive")
+    if int(oversample) != oversample or oversample < 1:
+        raise ValueError("oversample must be an integer >= 1")
+    sig = cycles / f0 / 2.355
+    step = 1.0 / (fs * int(oversample))
+    half = int(np.floor(6.0 * sig / step))
+    u = np.arange(-half, half + 1, dtype=np.float64) * step
+    p = np.exp(-0.5 * (u / sig) ** 2) * np.exp(2j * np.pi * f0 * u)
+    if not analytic:
+        p = p.real + 0j
+    return p.astype(np.complex64), half
+
+
+def _sim_common(n_tx, n_rx, fs, n_t, pulse, centre, oversample, analytic, accumulate, out):
+    """the checks and buffers the three simulate_* calls share -> (pulse, out, flags)"""
+    if pulse is None or centre is None or oversample is None:
+        raise ValueError("pulse, centre and oversample are needed (gaussian_pulse makes them)")
+    pulse = np.ascontiguousarray(pulse, dtype=np.complex64)
+    if pulse.ndim != 1 or pulse.size < 1:
+        raise ValueError("pulse must be a 1-D complex64 table")
+    if int(oversample) != oversample or oversample < 1:
+        raise ValueError("oversample must be an integer >= 1")
+    if int(centre) != centre or not 0 <= centre < pulse.size:
+        raise ValueError("centre must be an index into pulse")
+    if pulse.size + int(oversample) > SIM_MAX_TABLE:
+        raise ValueError(f"len(pulse) + oversample must not exceed {SIM_MAX_TABLE}")
+    if int(n_t) != n_t or n_t < 1:
+        raise ValueError("n_t must be a positive integer")
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("fs must be finite and positive")
+    shape = (n_tx, n_rx, int(n_t))
+    dtype = np.complex64 if analytic else np.float32
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the FMC to add onto in ``out``")
+    return pulse, _out(out, shape, dtype), (SIM_ANALYTIC if analytic else 0) | (SIM_ACCUMULATE if accumulate else 0)
+
+
+def _sim_factor(w, shape, name):
+    if w is None:
+        return None
+    w = np.ascontiguousarray(w, dtype=np.complex64)
+    if w.shape != shape:
+        raise ValueError(f"{name} must be complex64 of shape {shape}")
+    return w
+
+
+def simulate_fmc(tt_tx, tt_rx=None, *, fs, n_t, pulse, centre, oversample, t0=0.0, strength=None, w_tx=None, w_rx=None,
+                 analytic=False, accumulate=False, out=None, device=0):
+    """The forward model of tfm_weighted: point scatterers to an FMC.  Scatterer s arrives in A-scan (tx, rx) at
+    tt_tx[tx, s] + tt_rx[rx, s] with the complex amplitude strength[s] w_tx[tx, s] w_rx[rx, s] and adds amplitude x
+    pulse(t - arrival) to the samples t = t0 + j / fs.  ``tt_tx`` [n_tx, n_s] / ``tt_rx`` [n_rx, n_s] float64: any travel-time
+    table of this library over the scatterers as focal points (tt_rx defaults to tt_tx, and then w_rx to w_tx); ``strength``: a
+    scalar or [n_s]; ``w_tx`` / ``w_rx``: complex64 leg amplitudes (None: 1).  ``pulse``, ``centre``, ``oversample``: the wavelet
+    table (gaussian_pulse), sampled at fs oversample with time zero at index centre, interpolated linearly.  A NaN time or a
+    non-finite factor drops that arrival only.  -> float32 [n_tx, n_rx, n_t] (the real part) or, with ``analytic=True``,
+    complex64.  ``accumulate=True`` adds onto ``out`` (bit-identical to one call over all scatterers when the chunks are added in
+    order).  Definition and the accumulation contract: include/rtus.h (rtus_fmc_sim).  Not in the reference."""
+    tt_tx = np.ascontiguousarray(tt_tx, dtype=np.float64)
+    if tt_rx is None:
+        tt_rx = tt_tx
+        w_rx = w_tx if w_rx is None else w_rx
+    tt_rx = np.ascontiguousarray(tt_rx, dtype=np.float64)
+    if tt_tx.ndim != 2 or tt_rx.ndim != 2 or tt_tx.shape[1] != tt_rx.shape[1] or tt_tx.size == 0 or tt_rx.size == 0:
+        raise ValueError("tt_tx / tt_rx must be [n_tx, n_s] / [n_rx, n_s]")
+    n_tx, n_rx, n_s = tt_tx.shape[0], tt_rx.shape[0], tt_tx.shape[1]
+    q = None
+    if strength is not None:
+        q = np.ascontiguousarray(np.broadcast_to(np.asarray(strength, dtype=np.complex64), (n_s,)) if np.ndim(strength) == 0
+                                 else strength, dtype=np.complex64)
+        if q.shape != (n_s,):
+            raise ValueError(f"strength must be a scalar or hold one value per scatterer ({n_s})")
+    w_tx, w_rx = _sim_factor(w_tx, (n_tx, n_s), "w_tx"), _sim_factor(w_rx, (n_rx, n_s), "w_rx")
+    pulse, out, flags = _sim_common(n_tx, n_rx, fs, n_t, pulse, centre, oversample, analytic, accumulate, out)
+    st = _lib.lib().rtus_fmc_sim(_ptr(tt_tx), _ptr(tt_rx), n_tx, n_rx, n_s, _ptr(q), _ptr(w_tx), _ptr(w_rx), _ptr(pulse), pulse.size,
+                                 int(centre), int(oversample), float(fs), float(t0), int(n_t), _ptr(out), flags, int(device))
+    _lib.check(st, "rtus_fmc_sim")
+    return out
+
+
+def simulate_echoes(t_pair, amp=None, *, fs, n_t, pulse, centre, oversample, t0=0.0, analytic=False, accumulate=False, out=None,
+                    device=0):
+    """Echoes given per pair to an FMC: arrival k of pair (tx, rx) at ``t_pair[tx, rx, k]`` (float64 [n_tx, n_rx] or
+    [n_tx, n_rx, n_a]; e.g. solve_travel_times' outer-surface echo) with the complex amplitude ``amp`` (same shape; None: 1).
+    Wavelet, output, ``accumulate`` and the rules for NaN times: simulate_fmc's.  Definition: include/rtus.h (rtus_fmc_sim_echo)."""
+    t_pair = np.ascontiguousarray(t_pair, dtype=np.float64)
+    if t_pair.ndim == 2:
+        t_pair = t_pair[:, :, None]
+    if t_pair.ndim != 3 or t_pair.size == 0:
+        raise ValueError("t_pair must be [n_tx, n_rx] or [n_tx, n_rx, n_a]")
+    if amp is not None:
+        amp = np.ascontiguousarray(amp, dtype=np.complex64)
+        amp = _sim_factor(amp[:, :, None] if amp.ndim == 2 else amp, t_pair.shape, "amp")
+    n_tx, n_rx, n_a = t_pair.shape
+    pulse, out, flags = _sim_common(n_tx, n_rx, fs, n_t, pulse, centre, oversample, analytic, accumulate, out)
+    st = _lib.lib().rtus_fmc_sim_echo(_ptr(t_pair), _ptr(amp), n_tx, n_rx, n_a, _ptr(pulse), pulse.size, int(centre), int(oversample),
+                                      float(fs), float(t0), int(n_t), _ptr(out), flags, int(device))
+    _lib.check(st, "rtus_fmc_sim_echo")
+    return out
+
+
+def simulate_views(legs, views=VIEWS, *, amplitudes=None, reciprocal=True, fs, n_t, pulse, centre, oversample, t0=0.0, strength=None,
+                   analytic=False, accumulate=False, out=None, device=0):
+    """The FMC of point scatterers seen through several views — the model tfm_views inverts.  ``legs``: {leg: tt [n_e, n_s]} over the
+    scatterers (view_legs_*); a view "A-B" is simulated with tt_tx = legs[A], tt_rx = legs[reverse_leg(B)] and, with ``amplitudes``
+    ({leg: (down, up)}, view_amplitudes_*), w_tx = amplitudes[A][0], w_rx = amplitudes[reverse_leg(B)][1] — not conjugated: this is
+    the model, not its matched filter.  ``reciprocal=True``: a view with A != B also adds "B-A" (real data holds both).  The views
+    are accumulated in the order given ("A-B" before its "B-A"), each one simulate_fmc call with accumulate=True after the first:
+    the result is that chain's, bit for bit.  An unknown view or a leg missing from ``legs`` (or ``amplitudes``) raises ValueError
+    before any GPU call."""
+    views = (views,) if isinstance(views, str) else tuple(views)
+    if not views:
+        raise ValueError("at least one view is needed")
+    chain = []
+    for v in views:
+        a, b = view_tables(v)
+        chain.append((a, b))
+        if reciprocal and a != reverse_leg(b):
+            chain.append(view_tables("-".join(v.split("-")[::-1])))
+    missing = sorted({g for p in chain for g in p if g not in legs})
+    if missing:
+        raise ValueError(f"legs {missing} are needed by the views and missing from ``legs``")
+    if amplitudes is not None:
+        missing = sorted({g for p in chain for g in p if g not in amplitudes})
+        if missing:
+            raise ValueError(f"legs {missing} are needed by the views and missing from ``amplitudes``")
+    for i, (a, b) in enumerate(chain):
+        w_tx = None if amplitudes is None else amplitudes[a][0]
+        w_rx = None if amplitudes is None else amplitudes[b][1]
+        out = simulate_fmc(legs[a], legs[b], fs=fs, n_t=n_t, pulse=pulse, centre=centre, oversample=oversample, t0=t0,
+                           strength=strength, w_tx=w_tx, w_rx=w_rx, analytic=analytic, accumulate=accumulate or i > 0, out=out,
+                           device=device)
+    return out

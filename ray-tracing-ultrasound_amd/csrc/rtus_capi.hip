@@ -99,6 +99,9 @@ hipError_t rtus_launch_leg_amp_pipe(const rtus_lens& L, double a_lo, double a_hi
                                     hipStream_t s);
 hipError_t rtus_launch_fmc_synth_tx(const float* fmc, int n_tx, int n_rx, int n_t, double fs, const double* d, int n_v, float* out,
                                     hipStream_t s);
+hipError_t rtus_launch_fmc_sim(const double* t1, const double* t2, const float* q, const float* a1, const float* a2, int n_tx, int n_rx,
+                               int n, int echo, const float* pulse, int n_p, int centre, int os, double fs, double t0, int n_t, float* out,
+                               int analytic, int accumulate, hipStream_t s);
 
 static thread_local int g_last_hip = 0;
 static int hip_fail(hipError_t e) { g_last_hip = (int)e; return RTUS_ERR_HIP; }
@@ -1128,6 +1131,90 @@ int rtus_geom_misfit(const double* tt, int n_geom, int n_tx, int n_rx, const dou
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_geom_misfit(dtt, n_geom, n_tx, n_rx, dtm, dw, dn, dq, dr, dsw, S.a->stream));
     return S.finish();
+}
+
+// ---------------------------------------------------------------------------- FMC simulator: arrivals to A-scans
+#define RTUS_SIM_MAX_TABLE 2048                 // n_p + oversample: 16-byte LDS entries, half of a workgroup's 64 KB
+#define RTUS_SIM_TILE_SAMPLES 1024              // (rtus_fmcsim.hip: RTUS_SIM_TILE)
+static int check_sim(const void* t1, const void* t2, int n_tx, int n_rx, int n, const void* c0, const void* c1, const void* c2,
+                     const void* pulse, int n_p, int centre, int os, double fs, double t0, int n_t, const void* out, unsigned flags)
+{
+    if (!t1 || !t2 || !pulse || !out || n_tx <= 0 || n_rx <= 0 || n <= 0 || n_p <= 0 || n_t <= 0) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(fs) || !(fs > 0) || !isfinite(t0) || os < 1 || centre < 0 || centre >= n_p) return RTUS_ERR_INVALID_ARG;
+    if (flags & ~(RTUS_SIM_ANALYTIC | RTUS_SIM_ACCUMULATE)) return RTUS_ERR_INVALID_ARG;
+    if ((((uintptr_t)c0 | (uintptr_t)c1 | (uintptr_t)c2 | (uintptr_t)pulse) & 7) || ((uintptr_t)out & 3)) return RTUS_ERR_INVALID_ARG;
+    if (n_t > RTUS_ANALYTIC_MAX_SAMPLES || (long long)n_p + os > RTUS_SIM_MAX_TABLE) return RTUS_ERR_UNSUPPORTED;
+    const long long n_tiles = (n_t + RTUS_SIM_TILE_SAMPLES - 1) / RTUS_SIM_TILE_SAMPLES;
+    if ((long long)n_tx * n_rx * n_tiles > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;   // one wave per (pair, 1024 samples)
+    return RTUS_OK;
+}
+
+int rtus_fmc_sim_dev(const double* d_tt_tx, const double* d_tt_rx, int n_tx, int n_rx, int n_s, const float* d_q, const float* d_w_tx,
+                     const float* d_w_rx, const float* d_pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t,
+                     float* d_out, unsigned flags, void* stream)
+{
+    int st = check_sim(d_tt_tx, d_tt_rx, n_tx, n_rx, n_s, d_q, d_w_tx, d_w_rx, d_pulse, n_p, centre, oversample, fs, t0, n_t, d_out, flags);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_fmc_sim(d_tt_tx, d_tt_rx, d_q, d_w_tx, d_w_rx, n_tx, n_rx, n_s, 0, d_pulse, n_p, centre, oversample, fs, t0, n_t,
+                                   d_out, !!(flags & RTUS_SIM_ANALYTIC), !!(flags & RTUS_SIM_ACCUMULATE), (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_fmc_sim_echo_dev(const double* d_t_pair, const float* d_amp, int n_tx, int n_rx, int n_a, const float* d_pulse, int n_p,
+                          int centre, int oversample, double fs, double t0, int n_t, float* d_out, unsigned flags, void* stream)
+{
+    int st = check_sim(d_t_pair, d_t_pair, n_tx, n_rx, n_a, d_amp, nullptr, nullptr, d_pulse, n_p, centre, oversample, fs, t0, n_t, d_out,
+                       flags);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_fmc_sim(d_t_pair, nullptr, nullptr, d_amp, nullptr, n_tx, n_rx, n_a, 1, d_pulse, n_p, centre, oversample, fs, t0,
+                                   n_t, d_out, !!(flags & RTUS_SIM_ANALYTIC), !!(flags & RTUS_SIM_ACCUMULATE), (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+// the two host twins: `echo` selects which arrays t1 / a1 are (SimArgs in rtus_fmcsim.hip)
+static int sim_host(const double* t1, const double* t2, const float* q, const float* a1, const float* a2, int n_tx, int n_rx, int n,
+                    int echo, const float* pulse, int n_p, int centre, int os, double fs, double t0, int n_t, float* out, unsigned flags,
+                    int device)
+{
+    const size_t pairs = (size_t)n_tx * n_rx, rows1 = echo ? pairs : (size_t)n_tx;
+    const size_t n_out = pairs * n_t * ((flags & RTUS_SIM_ANALYTIC) ? 2 : 1);
+    const bool same = !echo && t1 == t2 && n_tx == n_rx, acc = flags & RTUS_SIM_ACCUMULATE;
+    Session S;
+    int st = S.open(device);
+    if (st) return st;
+    double *dt1, *dt2 = nullptr;
+    float *dq, *da1, *da2, *dp, *dout;
+    S.in(dt1, t1, rows1 * n);
+    if (!echo && !same) S.in(dt2, t2, (size_t)n_rx * n);
+    S.in(dq, q, q ? 2 * (size_t)n : 0);
+    S.in(da1, a1, a1 ? 2 * rows1 * n : 0);
+    S.in(da2, a2, a2 ? 2 * (size_t)n_rx * n : 0);
+    S.in(dp, pulse, 2 * (size_t)n_p);
+    if (acc) S.in(dout, (const float*)out, n_out);           // in place: uploaded, added onto, read back
+    else S.out(dout, out, n_out);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_fmc_sim(dt1, echo ? nullptr : (same ? dt1 : dt2), dq, da1, da2, n_tx, n_rx, n, echo, dp, n_p, centre, os, fs, t0,
+                                   n_t, dout, !!(flags & RTUS_SIM_ANALYTIC), acc, S.a->stream));
+    if (acc) S.download(out, dout, n_out);
+    return S.finish();
+}
+
+int rtus_fmc_sim(const double* tt_tx, const double* tt_rx, int n_tx, int n_rx, int n_s, const float* q, const float* w_tx,
+                 const float* w_rx, const float* pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t, float* out,
+                 unsigned flags, int device)
+{
+    int st = check_sim(tt_tx, tt_rx, n_tx, n_rx, n_s, q, w_tx, w_rx, pulse, n_p, centre, oversample, fs, t0, n_t, out, flags);
+    if (st) return st;
+    return sim_host(tt_tx, tt_rx, q, w_tx, w_rx, n_tx, n_rx, n_s, 0, pulse, n_p, centre, oversample, fs, t0, n_t, out, flags, device);
+}
+
+int rtus_fmc_sim_echo(const double* t_pair, const float* amp, int n_tx, int n_rx, int n_a, const float* pulse, int n_p, int centre,
+                      int oversample, double fs, double t0, int n_t, float* out, unsigned flags, int device)
+{
+    int st = check_sim(t_pair, t_pair, n_tx, n_rx, n_a, amp, nullptr, nullptr, pulse, n_p, centre, oversample, fs, t0, n_t, out, flags);
+    if (st) return st;
+    return sim_host(t_pair, nullptr, nullptr, amp, nullptr, n_tx, n_rx, n_a, 1, pulse, n_p, centre, oversample, fs, t0, n_t, out, flags,
+                    device);
 }
 
 // ---------------------------------------------------------------------------- envelope TFM + coherence factor over an analytic FMC

@@ -795,3 +795,69 @@ def geom_misfit_dev(tt, t_meas, weights=None, n=None, sse=None, sum_r=None, sum_
                                          _p(sum_w), _stream(tt))
     _lib.check(st, "rtus_geom_misfit_dev")
     return n, sse, sum_r, sum_w
+
+
+def _sim_out(n_tx, n_rx, n_t, pulse, out, analytic, ref):
+    """the wavelet and result checks fmc_sim_dev and fmc_sim_echo_dev share -> out"""
+    _chk(pulse, "pulse", torch.float32)
+    if pulse.dim() != 2 or pulse.shape[1] != 2:
+        raise ValueError("pulse must be float32 [n_p, 2] (complex)")
+    c = 2 if analytic else 1
+    if out is None:
+        out = torch.empty((n_tx, n_rx, n_t, 2) if analytic else (n_tx, n_rx, n_t), dtype=torch.float32, device=ref.device)
+    _chk(out, "out", torch.float32)
+    if out.numel() != n_tx * n_rx * n_t * c:
+        raise ValueError(f"out must hold n_tx * n_rx * n_t * {c} float32 values")
+    if out.device != ref.device or pulse.device != ref.device:
+        raise ValueError("the tables, pulse and out must be on one device")
+    return out
+
+
+def fmc_sim_dev(tt_tx, tt_rx=None, *, fs, n_t, pulse, centre, oversample, t0=0.0, strength=None, w_tx=None, w_rx=None, analytic=False,
+                accumulate=False, out=None):
+    """FMC simulator on device (rtus_fmc_sim_dev; api.simulate_fmc's definition): tt_tx [n_tx, n_s] / tt_rx [n_rx, n_s] float64
+    (tt_rx, w_rx default to tt_tx, w_tx); strength float32 [n_s, 2], w_tx / w_rx float32 [n, n_s, 2] (complex), each optional;
+    pulse float32 [n_p, 2] -> out float32 [n_tx, n_rx, n_t] or, with ``analytic``, [n_tx, n_rx, n_t, 2].  ``accumulate`` adds onto
+    ``out``.  Asynchronous on the current stream (capturable with a pre-allocated ``out``)."""
+    _chk(tt_tx, "tt_tx")
+    if tt_rx is None:
+        tt_rx = tt_tx
+        w_rx = w_tx if w_rx is None else w_rx
+    _chk(tt_rx, "tt_rx")
+    if tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] or tt_tx.device != tt_rx.device:
+        raise ValueError("need tt_tx [n_tx, n_s], tt_rx [n_rx, n_s] on one device")
+    n_tx, n_rx, n_s = tt_tx.shape[0], tt_rx.shape[0], tt_tx.shape[1]
+    for t, name, n in ((strength, "strength", n_s), (w_tx, "w_tx", n_tx * n_s), (w_rx, "w_rx", n_rx * n_s)):
+        if t is not None:
+            _chk(t, name, torch.float32)
+            if t.numel() != 2 * n or t.device != tt_tx.device:
+                raise ValueError(f"{name} must hold {n} complex values (float32 pairs) on the tables' device")
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the FMC to add onto in ``out``")
+    out = _sim_out(n_tx, n_rx, int(n_t), pulse, out, analytic, tt_tx)
+    flags = (_api.SIM_ANALYTIC if analytic else 0) | (_api.SIM_ACCUMULATE if accumulate else 0)
+    st = _lib.lib().rtus_fmc_sim_dev(_p(tt_tx), _p(tt_rx), n_tx, n_rx, n_s, _p(strength), _p(w_tx), _p(w_rx), _p(pulse), pulse.shape[0],
+                                     int(centre), int(oversample), float(fs), float(t0), int(n_t), _p(out), flags, _stream(tt_tx))
+    _lib.check(st, "rtus_fmc_sim_dev")
+    return out
+
+
+def fmc_sim_echo_dev(t_pair, amp=None, *, fs, n_t, pulse, centre, oversample, t0=0.0, analytic=False, accumulate=False, out=None):
+    """Per-pair echoes to an FMC on device (rtus_fmc_sim_echo_dev; api.simulate_echoes' definition): t_pair float64
+    [n_tx, n_rx, n_a], amp float32 [n_tx, n_rx, n_a, 2] or None; the rest as fmc_sim_dev."""
+    _chk(t_pair, "t_pair")
+    if t_pair.dim() != 3:
+        raise ValueError("t_pair must be [n_tx, n_rx, n_a]")
+    n_tx, n_rx, n_a = t_pair.shape
+    if amp is not None:
+        _chk(amp, "amp", torch.float32)
+        if amp.numel() != 2 * t_pair.numel() or amp.device != t_pair.device:
+            raise ValueError("amp must hold one complex value (a float32 pair) per arrival on t_pair's device")
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the FMC to add onto in ``out``")
+    out = _sim_out(n_tx, n_rx, int(n_t), pulse, out, analytic, t_pair)
+    flags = (_api.SIM_ANALYTIC if analytic else 0) | (_api.SIM_ACCUMULATE if accumulate else 0)
+    st = _lib.lib().rtus_fmc_sim_echo_dev(_p(t_pair), _p(amp), n_tx, n_rx, n_a, _p(pulse), pulse.shape[0], int(centre), int(oversample),
+                                          float(fs), float(t0), int(n_t), _p(out), flags, _stream(t_pair))
+    _lib.check(st, "rtus_fmc_sim_echo_dev")
+    return out
