@@ -57,8 +57,126 @@ def _strerror(status):
         return "?"
 
 
+# Every function of include/rtus.h, once, in the header's order: (name, return type, argument types, since).  `since` is the
+# RTUS_VERSION that introduced the entry: 100 stands for every build the loader has met, 101 for "round 4" (older than 107; those
+# builds did not yet count a version per feature).  tests/test_abi_and_host.py holds this table to the header, type by type.
+# Data pointers are void* (callers pass addresses: numpy's .ctypes.data, torch's .data_ptr()); a typed pointer only where a
+# caller hands over a ctypes object.
+i, u, ll, sz, dd, vp = C.c_int, C.c_uint, C.c_longlong, C.c_size_t, C.c_double, C.c_void_p
+LP, PP, MP = C.POINTER(Lens), C.POINTER(Pipe), C.POINTER(PipeMedia)
+i_p, ull_p, vp_p = C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_void_p)
+PROTOTYPES = (
+    ("rtus_strerror", C.c_char_p, [i], 100),
+    ("rtus_version", i, [], 100),
+    ("rtus_last_hip_error", i, [], 100),
+    ("rtus_device_count", i, [i_p], 100),
+    ("rtus_release", i, [i], 100),
+    ("rtus_selftest", i, [LP, i, ll, ull_p, i], 100),
+    # forward trace
+    ("rtus_shoot_workspace_bytes", sz, [i], 100),
+    ("rtus_shoot_dev", i, [LP, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, vp, sz, u, vp], 100),
+    ("rtus_shoot", i, [LP, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, u, i], 100),
+    # pulse-echo travel times by root-finding
+    ("rtus_solve_workspace_bytes", sz, [i, i, i, i], 100),
+    ("rtus_solve_dev", i, [LP, vp, i, vp, vp, i, vp, i, vp, i, dd, vp, vp, vp, vp, vp, vp, sz, u, vp], 100),
+    ("rtus_solve", i, [LP, vp, i, vp, vp, i, vp, i, vp, i, dd, vp, vp, vp, vp, vp, u, i], 100),
+    # element matcher
+    ("rtus_match_dev", i, [vp, vp, i, i, vp, i, dd, dd, vp, vp, vp, vp], 100),
+    ("rtus_match", i, [vp, vp, i, i, vp, i, dd, dd, vp, vp, vp, i], 100),
+    ("rtus_ray_hits_dev", i, [vp, i, i, vp, i, dd, dd, vp, vp], 100),
+    ("rtus_ray_hits", i, [vp, i, i, vp, i, dd, dd, vp, i], 100),
+    # fused sweep
+    ("rtus_sweep_workspace_bytes", sz, [i, i, i, i], 100),
+    ("rtus_sweep_dev", i, [LP, vp, i, vp, vp, i, vp, vp, i, vp, i, dd, dd, vp, vp, vp, vp, vp, vp, sz, u, vp], 100),
+    ("rtus_sweep", i, [LP, vp, i, vp, vp, i, vp, vp, i, vp, i, dd, dd, vp, vp, vp, vp, vp, u, i], 100),
+    # travel times through horizontal layers
+    ("rtus_tt_layers_dev", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp], 100),
+    ("rtus_tt_layers_batch_dev", i, [vp, vp, i, vp, vp, i, ll, vp, vp, i, ll, vp, ll, i, vp], 100),
+    ("rtus_tt_layers", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, i], 100),
+    ("rtus_tt_layers_ex_dev", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, u, vp], 101),
+    ("rtus_tt_layers_batch_ex_dev", i, [vp, vp, i, vp, vp, i, ll, vp, vp, i, ll, vp, ll, i, u, vp], 101),
+    ("rtus_tt_layers_ex", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, u, i], 101),
+    ("rtus_tt_layers_sort_workspace_bytes", sz, [i], 100),
+    ("rtus_tt_layers_sorted_dev", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, sz, u, vp], 100),
+    # travel times through the curved lens surface
+    ("rtus_tt_lens_dev", i, [LP, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp], 100),
+    ("rtus_tt_lens", i, [LP, dd, dd, vp, vp, i, vp, vp, i, vp, vp, i], 100),
+    ("rtus_tt_lens_f32_dev", i, [LP, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp], 100),
+    ("rtus_tt_lens_f32", i, [LP, dd, dd, vp, vp, i, vp, vp, i, vp, vp, i], 100),
+    # row shards of a table, several GPUs
+    ("rtus_table_rows_per_block", i, [ll, i, i], 100),
+    ("rtus_shard_rows", ll, [ll, i, i, i], 100),
+    ("rtus_tt_layers_rows_dev", i, [vp, vp, i, vp, vp, i, ll, ll, vp, vp, i, vp, u, vp], 100),
+    ("rtus_tt_lens_rows_dev", i, [LP, dd, dd, vp, vp, i, ll, ll, vp, vp, i, vp, vp, vp], 100),
+    ("rtus_tt_lens_f32_rows_dev", i, [LP, dd, dd, vp, vp, i, ll, ll, vp, vp, i, vp, vp, vp], 100),
+    ("rtus_tt_lens_stats_dev", i, [LP, dd, dd, vp, vp, i, ll, ll, vp, vp, i, vp, vp, vp], 101),
+    ("rtus_tt_lens_f32_stats_dev", i, [LP, dd, dd, vp, vp, i, ll, ll, vp, vp, i, vp, vp, vp], 101),
+    ("rtus_tt_layers_multi", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, i_p, i], 100),
+    ("rtus_tt_lens_f32_multi", i, [LP, dd, dd, vp, vp, i, vp, vp, i, vp, i_p, i], 100),
+    ("rtus_tt_layers_multi_ex", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, i_p, i, u], 101),
+    ("rtus_tt_layers_multi_ex_dev", i, [vp, vp, i, vp_p, vp_p, i, vp_p, vp_p, i, vp_p, i_p, i, vp_p, i, u], 101),
+    ("rtus_tt_layers_multi_dev", i, [vp, vp, i, vp_p, vp_p, i, vp_p, vp_p, i, vp_p, i_p, i, vp_p, i], 100),
+    ("rtus_tt_lens_f32_multi_dev", i, [LP, dd, dd, vp_p, vp_p, i, vp_p, vp_p, i, vp_p, i_p, i, vp_p, i], 100),
+    # travel times through one measured surface profile
+    ("rtus_tt_surface_workspace_bytes", sz, [i], 100),
+    ("rtus_tt_surface_dev", i, [dd, dd, vp, i, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, sz, vp], 100),
+    ("rtus_tt_surface", i, [dd, dd, vp, i, dd, dd, vp, vp, i, vp, vp, i, vp, vp, i], 100),
+    # consumers of a travel-time table
+    ("rtus_focal_delays_dev", i, [vp, i, i, vp, vp], 100),
+    ("rtus_focal_delays", i, [vp, i, i, vp, i], 100),
+    ("rtus_tfm_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp], 100),
+    ("rtus_tfm", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, i], 100),
+    # the surface profile from the FMC (adaptive TFM)
+    ("rtus_fmc_analytic_dev", i, [vp, i, i, i, i, vp, vp], 100),
+    ("rtus_fmc_analytic", i, [vp, i, i, i, i, vp, i], 100),
+    ("rtus_surface_find_dev", i, [vp, i, i, dd, dd, vp, vp, dd, dd, dd, i, dd, dd, i, vp, vp, vp, vp], 100),
+    ("rtus_surface_find", i, [vp, i, i, dd, dd, vp, vp, dd, dd, dd, i, dd, dd, i, vp, vp, vp, i], 100),
+    ("rtus_tfm_analytic_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, vp], 100),
+    ("rtus_tfm_analytic", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, i], 100),
+    # plane-wave imaging
+    ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
+    ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),
+    ("rtus_pw_surface_dev", i, [dd, dd, vp, i, dd, dd, vp, i, dd, dd, dd, vp, vp, i, vp, vp, vp, sz, vp], 107),
+    ("rtus_pw_surface", i, [dd, dd, vp, i, dd, dd, vp, i, dd, dd, dd, vp, vp, i, vp, vp, i], 107),
+    ("rtus_fmc_synth_tx_dev", i, [vp, i, i, i, dd, vp, i, vp, vp], 107),
+    ("rtus_fmc_synth_tx", i, [vp, i, i, i, dd, vp, i, vp, i], 107),
+    # backwall skip legs
+    ("rtus_tt_surface_skip_dev", i, [dd, dd, vp, i, dd, dd, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, vp, sz, vp], 108),
+    ("rtus_tt_surface_skip", i, [dd, dd, vp, i, dd, dd, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, i], 108),
+    # ray amplitudes, weighted TFM
+    ("rtus_leg_amp_surface_dev", i, [dd, dd, vp, i, dd, dd, dd, dd, dd, dd, i, i, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, vp, sz, vp],
+     109),
+    ("rtus_leg_amp_surface", i, [dd, dd, vp, i, dd, dd, dd, dd, dd, dd, i, i, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, i], 109),
+    ("rtus_tfm_weighted_dev", i, [vp, i, i, i, dd, dd, vp, vp, vp, vp, i, vp, vp, vp], 109),
+    ("rtus_tfm_weighted", i, [vp, i, i, i, dd, dd, vp, vp, vp, vp, i, vp, vp, i], 109),
+    # lens to pipe wall
+    ("rtus_tt_pipe_workspace_bytes", sz, [i, i], 110),
+    ("rtus_tt_pipe_dev", i, [LP, dd, dd, PP, dd, dd, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, sz, vp], 110),
+    ("rtus_tt_pipe", i, [LP, dd, dd, PP, dd, dd, i, vp, vp, i, vp, vp, i, vp, vp, vp, i], 110),
+    # bore-reflected skip legs
+    ("rtus_tt_pipe_skip_workspace_bytes", sz, [i, i], 111),
+    ("rtus_tt_pipe_skip_dev", i, [LP, dd, dd, PP, dd, dd, dd, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, sz, vp], 111),
+    ("rtus_tt_pipe_skip", i, [LP, dd, dd, PP, dd, dd, dd, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, i], 111),
+    # ray amplitudes into the pipe wall
+    ("rtus_leg_amp_pipe_dev", i, [LP, dd, dd, PP, MP, i, i, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp], 112),
+    ("rtus_leg_amp_pipe", i, [LP, dd, dd, PP, MP, i, i, dd, dd, vp, vp, i, vp, vp, i, vp, vp, vp, vp, i], 112),
+    # the pipe's geometry from measured echo times
+    ("rtus_echo_pick_dev", i, [vp, i, i, i, dd, dd, dd, dd, vp, vp, vp, vp, vp], 113),
+    ("rtus_echo_pick", i, [vp, i, i, i, dd, dd, dd, dd, vp, vp, vp, vp, i], 113),
+    ("rtus_geom_misfit_dev", i, [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp], 113),
+    ("rtus_geom_misfit", i, [vp, i, i, i, vp, vp, vp, vp, vp, vp, i], 113),
+    ("rtus_pipe_clearance", dd, [LP, dd, dd, dd], 113),
+    # ray-model FMC simulator
+    ("rtus_fmc_sim_dev", i, [vp, vp, i, i, i, vp, vp, vp, vp, i, i, i, dd, dd, i, vp, u, vp], 114),
+    ("rtus_fmc_sim", i, [vp, vp, i, i, i, vp, vp, vp, vp, i, i, i, dd, dd, i, vp, u, i], 114),
+    ("rtus_fmc_sim_echo_dev", i, [vp, vp, i, i, i, vp, i, i, i, dd, dd, i, vp, u, vp], 114),
+    ("rtus_fmc_sim_echo", i, [vp, vp, i, i, i, vp, i, i, i, dd, dd, i, vp, u, i], 114),
+)
+EXPORTS = tuple(p[0] for p in PROTOTYPES)
+
+
 def lib():
-    """Load librtus.so once; declare every prototype of include/rtus.h."""
+    """Load librtus.so once; bind every entry of PROTOTYPES."""
     global _lib
     if _lib is not None:
         return _lib
@@ -81,191 +199,12 @@ def lib():
             if os.path.exists(hip):
                 C.CDLL(hip, mode=C.RTLD_GLOBAL)
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    vp, dp, ip = C.c_void_p, C.c_void_p, C.c_int
-    L.rtus_strerror.argtypes = [ip]
-    L.rtus_strerror.restype = C.c_char_p
-    L.rtus_version.restype = ip
-    L.rtus_last_hip_error.restype = ip
-    L.rtus_device_count.argtypes = [C.POINTER(C.c_int)]
-    L.rtus_release.argtypes = [ip]
-    L.rtus_release.restype = ip
-    L.rtus_selftest.argtypes = [C.POINTER(Lens), ip, C.c_longlong, C.POINTER(C.c_ulonglong), ip]
-    L.rtus_selftest.restype = ip
-    L.rtus_shoot_workspace_bytes.argtypes = [ip]
-    L.rtus_shoot_workspace_bytes.restype = C.c_size_t
-    LP = C.POINTER(Lens)
-    L.rtus_shoot_dev.argtypes = [LP, dp, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, vp, vp, C.c_size_t, C.c_uint, vp]
-    L.rtus_shoot.argtypes = [LP, dp, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, vp, C.c_uint, ip]
-    L.rtus_match_dev.argtypes = [dp, dp, ip, ip, dp, ip, C.c_double, C.c_double, vp, vp, dp, vp]
-    L.rtus_match.argtypes = [dp, dp, ip, ip, dp, ip, C.c_double, C.c_double, vp, vp, dp, ip]
-    L.rtus_sweep_workspace_bytes.argtypes = [ip, ip, ip, ip]
-    L.rtus_sweep_workspace_bytes.restype = C.c_size_t
-    L.rtus_sweep_dev.argtypes = [LP, dp, ip, dp, dp, ip, dp, dp, ip, dp, ip, C.c_double, C.c_double, vp, vp, dp, dp, dp, vp, C.c_size_t,
-                                 C.c_uint, vp]
-    L.rtus_sweep.argtypes = [LP, dp, ip, dp, dp, ip, dp, dp, ip, dp, ip, C.c_double, C.c_double, vp, vp, dp, dp, dp, C.c_uint, ip]
-    L.rtus_sweep_dev.restype = L.rtus_sweep.restype = ip
-    L.rtus_ray_hits_dev.argtypes = [dp, ip, ip, dp, ip, C.c_double, C.c_double, vp, vp]
-    L.rtus_ray_hits.argtypes = [dp, ip, ip, dp, ip, C.c_double, C.c_double, vp, ip]
-    L.rtus_tt_layers_dev.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, vp, vp]
-    L.rtus_tt_layers.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, vp, ip]
-    L.rtus_tt_layers_batch_dev.argtypes = [dp, dp, ip, dp, dp, ip, C.c_longlong, dp, dp, ip, C.c_longlong, dp,
-                                           C.c_longlong, ip, vp]
-    L.rtus_tt_layers_batch_dev.restype = ip
-    L.rtus_tt_lens_dev.argtypes = [LP, C.c_double, C.c_double, dp, dp, ip, dp, dp, ip, dp, dp, vp]
-    L.rtus_tt_lens.argtypes = [LP, C.c_double, C.c_double, dp, dp, ip, dp, dp, ip, dp, dp, ip]
-    L.rtus_tt_lens_f32_dev.argtypes = L.rtus_tt_lens_dev.argtypes
-    L.rtus_tt_lens_f32.argtypes = L.rtus_tt_lens.argtypes
-    L.rtus_focal_delays_dev.argtypes = [dp, ip, ip, dp, vp]
-    L.rtus_focal_delays.argtypes = [dp, ip, ip, dp, ip]
-    L.rtus_tfm_dev.argtypes = [dp, ip, ip, ip, C.c_double, C.c_double, dp, dp, ip, dp, vp]
-    L.rtus_tfm.argtypes = [dp, ip, ip, ip, C.c_double, C.c_double, dp, dp, ip, dp, ip]
-    for name in ("rtus_focal_delays_dev", "rtus_focal_delays", "rtus_tfm_dev", "rtus_tfm"):
-        getattr(L, name).restype = ip
-    L.rtus_solve_workspace_bytes.argtypes = [ip, ip, ip, ip]
-    L.rtus_solve_workspace_bytes.restype = C.c_size_t
-    L.rtus_solve_dev.argtypes = [LP, dp, ip, dp, dp, ip, dp, ip, dp, ip, C.c_double, dp, dp, dp, dp, vp, vp, C.c_size_t,
-                                 C.c_uint, vp]
-    L.rtus_solve.argtypes = [LP, dp, ip, dp, dp, ip, dp, ip, dp, ip, C.c_double, dp, dp, dp, dp, vp, C.c_uint, ip]
-    L.rtus_solve_dev.restype = ip
-    L.rtus_solve.restype = ip
-    for name in ("rtus_tt_lens_dev", "rtus_tt_lens", "rtus_tt_lens_f32_dev", "rtus_tt_lens_f32"):
-        getattr(L, name).restype = ip
-    ll = C.c_longlong
-    L.rtus_tt_layers_sort_workspace_bytes.argtypes = [ip]
-    L.rtus_tt_layers_sort_workspace_bytes.restype = C.c_size_t
-    L.rtus_tt_layers_sorted_dev.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, vp, C.c_size_t, C.c_uint, vp]
-    L.rtus_tt_layers_sorted_dev.restype = ip
-    L.rtus_table_rows_per_block.argtypes = [ll, ip, ip]
-    L.rtus_table_rows_per_block.restype = ip
-    L.rtus_shard_rows.argtypes = [ll, ip, ip, ip]
-    L.rtus_shard_rows.restype = ll
-    L.rtus_tt_layers_rows_dev.argtypes = [dp, dp, ip, dp, dp, ip, ll, ll, dp, dp, ip, dp, C.c_uint, vp]
-    L.rtus_tt_lens_rows_dev.argtypes = [LP, C.c_double, C.c_double, dp, dp, ip, ll, ll, dp, dp, ip, dp, dp, vp]
-    L.rtus_tt_lens_f32_rows_dev.argtypes = L.rtus_tt_lens_rows_dev.argtypes
-    L.rtus_tt_layers_multi.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, C.POINTER(C.c_int), ip]
-    L.rtus_tt_lens_f32_multi.argtypes = [LP, C.c_double, C.c_double, dp, dp, ip, dp, dp, ip, dp, C.POINTER(C.c_int), ip]
-    pp = C.POINTER(C.c_void_p)
-    L.rtus_tt_layers_multi_dev.argtypes = [dp, dp, ip, pp, pp, ip, pp, pp, ip, pp, C.POINTER(C.c_int), ip, pp, ip]
-    L.rtus_tt_lens_f32_multi_dev.argtypes = [LP, C.c_double, C.c_double, pp, pp, ip, pp, pp, ip, pp, C.POINTER(C.c_int), ip, pp, ip]
-    try:
-        L.rtus_tt_lens_stats_dev.argtypes = [LP, C.c_double, C.c_double, dp, dp, ip, ll, ll, dp, dp, ip, dp, vp, vp]
-        L.rtus_tt_lens_f32_stats_dev.argtypes = L.rtus_tt_lens_stats_dev.argtypes
-        L.rtus_tt_lens_stats_dev.restype = ip
-        L.rtus_tt_lens_f32_stats_dev.restype = ip
-        # the planar entries with the accuracy tier as an argument (flags: RTUS_TT_TAUP_TAIL or 0)
-        up = C.c_uint
-        L.rtus_tt_layers_ex_dev.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, vp, up, vp]
-        L.rtus_tt_layers_ex.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, vp, up, ip]
-        L.rtus_tt_layers_batch_ex_dev.argtypes = [dp, dp, ip, dp, dp, ip, ll, dp, dp, ip, ll, dp, ll, ip, up, vp]
-        L.rtus_tt_layers_multi_ex.argtypes = [dp, dp, ip, dp, dp, ip, dp, dp, ip, dp, C.POINTER(C.c_int), ip, up]
-        L.rtus_tt_layers_multi_ex_dev.argtypes = [dp, dp, ip, pp, pp, ip, pp, pp, ip, pp, C.POINTER(C.c_int), ip, pp, ip, up]
-        for name in ("rtus_tt_layers_ex_dev", "rtus_tt_layers_ex", "rtus_tt_layers_batch_ex_dev", "rtus_tt_layers_multi_ex",
-                     "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev"):
-            getattr(L, name).restype = ip
-    except AttributeError:                # a build from before round 4, loaded through RTUS_LIB for an A/B run: it lacks these entries
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    for name in ("rtus_tt_layers_rows_dev", "rtus_tt_lens_rows_dev", "rtus_tt_lens_f32_rows_dev", "rtus_tt_layers_multi",
-                 "rtus_tt_lens_f32_multi", "rtus_tt_layers_multi_dev", "rtus_tt_lens_f32_multi_dev"):
-        getattr(L, name).restype = ip
-    dd = C.c_double
-    L.rtus_tt_surface_workspace_bytes.argtypes = [ip]
-    L.rtus_tt_surface_workspace_bytes.restype = C.c_size_t
-    L.rtus_tt_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, vp, C.c_size_t, vp]
-    L.rtus_tt_surface.argtypes = [dd, dd, dp, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, ip]
-    L.rtus_tt_surface_dev.restype = L.rtus_tt_surface.restype = ip
-    L.rtus_fmc_analytic_dev.argtypes = [dp, ip, ip, ip, ip, dp, vp]
-    L.rtus_fmc_analytic.argtypes = [dp, ip, ip, ip, ip, dp, ip]
-    L.rtus_surface_find_dev.argtypes = [dp, ip, ip, dd, dd, dp, dp, dd, dd, dd, ip, dd, dd, ip, dp, dp, dp, vp]
-    L.rtus_surface_find.argtypes = [dp, ip, ip, dd, dd, dp, dp, dd, dd, dd, ip, dd, dd, ip, dp, dp, dp, ip]
-    L.rtus_tfm_analytic_dev.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, ip, dp, dp, vp]
-    L.rtus_tfm_analytic.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip]
-    for name in ("rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find", "rtus_tfm_analytic_dev",
-                 "rtus_tfm_analytic"):
-        getattr(L, name).restype = ip
-    try:
-        L.rtus_pw_layers_dev.argtypes = [dp, dp, ip, dp, ip, dd, dd, dd, dp, dp, ip, dp, vp]
-        L.rtus_pw_layers.argtypes = [dp, dp, ip, dp, ip, dd, dd, dd, dp, dp, ip, dp, ip]
-        L.rtus_pw_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dp, ip, dd, dd, dd, dp, dp, ip, dp, dp, vp, C.c_size_t, vp]
-        L.rtus_pw_surface.argtypes = [dd, dd, dp, ip, dd, dd, dp, ip, dd, dd, dd, dp, dp, ip, dp, dp, ip]
-        L.rtus_fmc_synth_tx_dev.argtypes = [dp, ip, ip, ip, dd, dp, ip, dp, vp]
-        L.rtus_fmc_synth_tx.argtypes = [dp, ip, ip, ip, dd, dp, ip, dp, ip]
-        for name in ("rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev",
-                     "rtus_fmc_synth_tx"):
-            getattr(L, name).restype = ip
-    except AttributeError:                # a build from before version 107, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        L.rtus_tt_surface_skip_dev.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, vp, C.c_size_t, vp]
-        L.rtus_tt_surface_skip.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, ip]
-        L.rtus_tt_surface_skip_dev.restype = L.rtus_tt_surface_skip.restype = ip
-    except AttributeError:                # a build from before version 108, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        L.rtus_leg_amp_surface_dev.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dd, dd, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, vp,
-                                               C.c_size_t, vp]
-        L.rtus_leg_amp_surface.argtypes = [dd, dd, dp, ip, dd, dd, dd, dd, dd, dd, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, ip]
-        L.rtus_tfm_weighted_dev.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, dp, dp, ip, dp, dp, vp]
-        L.rtus_tfm_weighted.argtypes = [dp, ip, ip, ip, dd, dd, dp, dp, dp, dp, ip, dp, dp, ip]
-        for name in ("rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted"):
-            getattr(L, name).restype = ip
-    except AttributeError:                # a build from before version 109, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        PP = C.POINTER(Pipe)
-        L.rtus_tt_pipe_workspace_bytes.argtypes = [ip, ip]
-        L.rtus_tt_pipe_workspace_bytes.restype = C.c_size_t
-        L.rtus_tt_pipe_dev.argtypes = [LP, dd, dd, PP, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, vp, C.c_size_t, vp]
-        L.rtus_tt_pipe.argtypes = [LP, dd, dd, PP, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, ip]
-        L.rtus_tt_pipe_dev.restype = L.rtus_tt_pipe.restype = ip
-    except AttributeError:                # a build from before version 110, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        L.rtus_tt_pipe_skip_workspace_bytes.argtypes = [ip, ip]
-        L.rtus_tt_pipe_skip_workspace_bytes.restype = C.c_size_t
-        L.rtus_tt_pipe_skip_dev.argtypes = [LP, dd, dd, PP, dd, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, vp, C.c_size_t, vp]
-        L.rtus_tt_pipe_skip.argtypes = [LP, dd, dd, PP, dd, dd, dd, ip, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, ip]
-        L.rtus_tt_pipe_skip_dev.restype = L.rtus_tt_pipe_skip.restype = ip
-    except AttributeError:                # a build from before version 111, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        MP = C.POINTER(PipeMedia)
-        L.rtus_leg_amp_pipe_dev.argtypes = [LP, dd, dd, PP, MP, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, vp]
-        L.rtus_leg_amp_pipe.argtypes = [LP, dd, dd, PP, MP, ip, ip, dd, dd, dp, dp, ip, dp, dp, ip, dp, dp, dp, dp, ip]
-        L.rtus_leg_amp_pipe_dev.restype = L.rtus_leg_amp_pipe.restype = ip
-    except AttributeError:                # a build from before version 112, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        L.rtus_echo_pick_dev.argtypes = [dp, ip, ip, ip, dd, dd, dd, dd, dp, dp, dp, dp, vp]
-        L.rtus_echo_pick.argtypes = [dp, ip, ip, ip, dd, dd, dd, dd, dp, dp, dp, dp, ip]
-        L.rtus_geom_misfit_dev.argtypes = [dp, ip, ip, ip, dp, dp, dp, dp, dp, dp, vp]
-        L.rtus_geom_misfit.argtypes = [dp, ip, ip, ip, dp, dp, dp, dp, dp, dp, ip]
-        for name in ("rtus_echo_pick_dev", "rtus_echo_pick", "rtus_geom_misfit_dev", "rtus_geom_misfit"):
-            getattr(L, name).restype = ip
-        L.rtus_pipe_clearance.argtypes = [LP, dd, dd, dd]
-        L.rtus_pipe_clearance.restype = dd
-    except AttributeError:                # a build from before version 113, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    try:
-        L.rtus_fmc_sim_dev.argtypes = [dp, dp, ip, ip, ip, dp, dp, dp, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, vp]
-        L.rtus_fmc_sim.argtypes = [dp, dp, ip, ip, ip, dp, dp, dp, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, ip]
-        L.rtus_fmc_sim_echo_dev.argtypes = [dp, dp, ip, ip, ip, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, vp]
-        L.rtus_fmc_sim_echo.argtypes = [dp, dp, ip, ip, ip, dp, ip, ip, ip, dd, dd, ip, dp, C.c_uint, ip]
-        for name in ("rtus_fmc_sim_dev", "rtus_fmc_sim", "rtus_fmc_sim_echo_dev", "rtus_fmc_sim_echo"):
-            getattr(L, name).restype = ip
-    except AttributeError:                # a build from before version 114, loaded through RTUS_LIB for an A/B run
-        if not os.environ.get("RTUS_LIB"):
-            raise
-    for name in ("rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match", "rtus_ray_hits_dev",
-                 "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_device_count"):
-        getattr(L, name).restype = ip
+    for name, restype, argtypes, since in PROTOTYPES:
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        elif not os.environ.get("RTUS_LIB"):  # an older build loaded through RTUS_LIB for an A/B run keeps this ONE symbol unbound
+            raise AttributeError(f"{LIB_PATH} does not export {name} (include/rtus.h, since version {since})")
     _lib = L
     return L
 
@@ -273,27 +212,3 @@ def lib():
 def check(status, what):
     if status != 0:
         raise RtusError(status, what)
-
-
-EXPORTS = ("rtus_strerror", "rtus_version", "rtus_last_hip_error", "rtus_device_count", "rtus_release", "rtus_selftest",
-           "rtus_shoot_workspace_bytes", "rtus_shoot_dev", "rtus_shoot", "rtus_match_dev", "rtus_match",
-           "rtus_ray_hits_dev", "rtus_ray_hits", "rtus_tt_layers_dev", "rtus_tt_layers", "rtus_tt_layers_batch_dev",
-           "rtus_tt_lens_dev", "rtus_tt_lens", "rtus_tt_lens_f32_dev", "rtus_tt_lens_f32",
-           "rtus_solve_workspace_bytes", "rtus_solve_dev", "rtus_solve",
-           "rtus_focal_delays_dev", "rtus_focal_delays", "rtus_tfm_dev", "rtus_tfm",
-           "rtus_tt_layers_sort_workspace_bytes", "rtus_tt_layers_sorted_dev", "rtus_table_rows_per_block", "rtus_shard_rows", "rtus_tt_layers_rows_dev", "rtus_tt_lens_rows_dev",
-           "rtus_tt_lens_f32_rows_dev", "rtus_tt_layers_multi", "rtus_tt_lens_f32_multi", "rtus_tt_layers_multi_dev",
-           "rtus_tt_lens_f32_multi_dev", "rtus_sweep_workspace_bytes", "rtus_sweep_dev", "rtus_sweep",
-           "rtus_tt_layers_ex_dev", "rtus_tt_layers_ex", "rtus_tt_layers_batch_ex_dev", "rtus_tt_layers_multi_ex",
-           "rtus_tt_layers_multi_ex_dev", "rtus_tt_lens_stats_dev", "rtus_tt_lens_f32_stats_dev",
-           "rtus_tt_surface_workspace_bytes", "rtus_tt_surface_dev", "rtus_tt_surface",
-           "rtus_fmc_analytic_dev", "rtus_fmc_analytic", "rtus_surface_find_dev", "rtus_surface_find",
-           "rtus_tfm_analytic_dev", "rtus_tfm_analytic",
-           "rtus_pw_layers_dev", "rtus_pw_layers", "rtus_pw_surface_dev", "rtus_pw_surface", "rtus_fmc_synth_tx_dev", "rtus_fmc_synth_tx",
-           "rtus_tt_surface_skip_dev", "rtus_tt_surface_skip",
-           "rtus_leg_amp_surface_dev", "rtus_leg_amp_surface", "rtus_tfm_weighted_dev", "rtus_tfm_weighted",
-           "rtus_tt_pipe_workspace_bytes", "rtus_tt_pipe_dev", "rtus_tt_pipe",
-           "rtus_tt_pipe_skip_workspace_bytes", "rtus_tt_pipe_skip_dev", "rtus_tt_pipe_skip",
-           "rtus_leg_amp_pipe_dev", "rtus_leg_amp_pipe",
-           "rtus_echo_pick_dev", "rtus_echo_pick", "rtus_geom_misfit_dev", "rtus_geom_misfit", "rtus_pipe_clearance",
-           "rtus_fmc_sim_dev", "rtus_fmc_sim", "rtus_fmc_sim_echo_dev", "rtus_fmc_sim_echo")

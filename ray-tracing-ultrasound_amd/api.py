@@ -87,6 +87,26 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def _medium(z_if, c, flat=False):
+    """The host medium of the planar entries -> (z_if, c) as float64 vectors with len(c) == len(z_if) + 1 (the C layer reads
+    c[0 .. n_if] from the host pointer)."""
+    if flat:      # device.py's wrappers and fmc_table_layers have always flattened whatever shape comes; the others insist on 1-D
+        z_if, c = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (z_if, c))
+    else:
+        z_if, c = _f64(z_if, "z_if") if np.size(z_if) else np.zeros(0), _f64(c, "c")
+    if c.size != z_if.size + 1:
+        raise ValueError("need len(c) == len(z_if) + 1")
+    return z_if, c
+
+
+def _points(xe, ze, xf, zf):
+    """Elements and focal points as float64 vectors, xe/ze and xf/zf of one length each."""
+    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
+    if xe.shape != ze.shape or xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    return xe, ze, xf, zf
+
+
 def _out(out, shape, dtype, name="out"):
     """The caller's result buffer (checked) or a fresh pageable one."""
     if out is None:
@@ -100,6 +120,7 @@ def _out(out, shape, dtype, name="out"):
 SHOOT_FAST_MATH = 0x1       # RTUS_SHOOT_FAST_MATH
 TRUE_PIPE_TANGENT = 0x2     # RTUS_TRUE_PIPE_TANGENT  (physically correct; not the reference)
 ANALYTIC_LENS = 0x4         # RTUS_ANALYTIC_LENS      (physically correct; not the reference)
+POLYLINE_READY = 0x8        # RTUS_POLYLINE_READY     (device entry points: the workspace holds this alpha grid's lens polyline)
 MAX_ROOTS = 4               # RTUS_MAX_ROOTS
 
 
@@ -277,13 +298,8 @@ def travel_time_layers(z_if, c, xe, ze, xf, zf, *, return_iters=False, out=None,
 
     NOT in the reference (no planar interfaces there): parity unpinned, see DESIGN.md.
     """
-    z_if = _f64(z_if, "z_if") if np.size(z_if) else np.zeros(0)
-    c = _f64(c, "c")
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    z_if, c = _medium(z_if, c)
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     if taup and return_iters:
         raise ValueError("return_iters is a diagnostic of the default tier")
     flags = TAUP_TAIL if taup else 0
@@ -345,10 +361,7 @@ def fmc_table_layers(z_if, c, x_tx, x_rx, z_reflector, *, z_array=0.0, device=0,
     under horizontal layers (BASELINE config 5).  The down-and-up path through the layers is unfolded
     about the reflector plane into a one-way path through the mirrored stack, so the table is one
     travel_time_layers call: tt[n_tx, n_rx].  Not in the reference (parity unpinned)."""
-    z_if = np.asarray(z_if, dtype=np.float64).reshape(-1)
-    c = np.asarray(c, dtype=np.float64).reshape(-1)
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
+    z_if, c = _medium(z_if, c, flat=True)
     above = z_if < z_reflector
     zi, cc = z_if[above], c[:above.sum() + 1]
     z_m = np.concatenate([zi, (2.0 * z_reflector - zi)[::-1]])          # mirrored interfaces
@@ -413,9 +426,7 @@ def travel_time_surface(x0, dx, zs, c1, c2, xe, ze, xf, zf, *, return_entry=Fals
     NOT in the reference (no measured profiles there): parity unpinned, see DESIGN.md.
     """
     zs = _f64(zs, "zs")
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     tt = _out(out, (xe.size, xf.size), np.float64)
     xn = np.empty((xe.size, xf.size), dtype=np.float64) if return_entry else None
     st = _lib.lib().rtus_tt_surface(float(x0), float(dx), _ptr(zs), zs.size, float(c1), float(c2), _ptr(xe), _ptr(ze), xe.size,
@@ -630,10 +641,7 @@ def pw_travel_time_layers(z_if, c, angles, xe, ze, xf, zf, *, out=None, device=0
     the wave is evanescent in a crossed layer, the focal point is not below the array, the angle is not finite or |angle| >= pi/2,
     or the focal point is not insonified (its ray traced back misses the aperture).  The table is ``tt_tx`` of tfm_image /
     tfm_analytic / pwi_image with element tables as ``tt_rx``.  Definition: include/rtus.h (rtus_pw_layers).  Not in the reference."""
-    z_if = _f64(z_if, "z_if") if np.size(z_if) else np.zeros(0)
-    c = _f64(c, "c")
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
+    z_if, c = _medium(z_if, c)
     x_lo, x_hi, z_a = _aperture(xe, ze)
     ang = _f64(angles, "angles")
     xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
@@ -733,10 +741,7 @@ def skip_travel_time_layers(z_if, c, z_back, xe, ze, xf, zf, *, c_up=None, taup=
     travel_time_layers(z_if + [z_back], c + [c_up], ..., 2 z_back - zf) — the direct time to the mirrored point — and NaN outside
     z_if[-1] < zf < z_back.  ``taup``, ``out``, ``device``, ``devices``: travel_time_layers's.  Conventions: include/rtus.h
     (multi-view TFM)."""
-    z_if = _f64(z_if, "z_if") if np.size(z_if) else np.zeros(0)
-    c = _f64(c, "c")
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
+    z_if, c = _medium(z_if, c)
     z_back = float(z_back)
     c_up = float(c[-1]) if c_up is None else float(c_up)
     front = float(z_if[-1]) if z_if.size else -np.inf
@@ -762,9 +767,7 @@ def skip_travel_time_surface(x0, dx, zs, c1, c2, z_back, xe, ze, xf, zf, *, c_up
     backwall is not strictly below the whole profile.  ``return_entry``: -> (tt, x_entry, x_back), the winning entry point and
     backwall reflection point.  Definition and guarantee: include/rtus.h (rtus_tt_surface_skip).  Not in the reference."""
     zs = _f64(zs, "zs")
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     c_up = float(c2) if c_up is None else float(c_up)
     tt = _out(out, (xe.size, xf.size), np.float64)
     xn = np.empty((xe.size, xf.size), dtype=np.float64) if return_entry else None
@@ -877,9 +880,7 @@ def leg_amplitudes_surface(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, leg, xe
         raise ValueError(f"unknown leg {leg!r}: legs are {LEGS}")
     skip = len(leg) == 2
     zs = _f64(zs, "zs")
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     shape = (xe.size, xf.size)
     xn = _f64(x_entry, "x_entry", 2)
     if xn.shape != shape:
@@ -985,9 +986,7 @@ def travel_time_pipe(xe, ze, xf, zf, *, c3=5600.0, r_inner=0.0, params: Params =
     wall or without a qualifying path.  ``return_path``: -> (tt, alpha, beta), the lens refraction point's and the pipe entry
     point's angles.  Definition, rules and guarantee: include/rtus.h (rtus_tt_pipe).  Not in the reference."""
     lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _pipe_args(params, c3, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     tt = _out(out, (xe.size, xf.size), np.float64)
     al = np.empty((xe.size, xf.size), dtype=np.float64) if return_path else None
     be = np.empty((xe.size, xf.size), dtype=np.float64) if return_path else None
@@ -1021,9 +1020,7 @@ def skip_travel_time_pipe(xe, ze, xf, zf, *, c_down, c_up=None, r_inner, params:
     the reference."""
     c_up = c_down if c_up is None else c_up
     lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _pipe_args(params, c_down, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     tt = _out(out, (xe.size, xf.size), np.float64)
     al, be, ga = (np.empty((xe.size, xf.size), dtype=np.float64) if return_path else None for _ in range(3))
     st = _lib.lib().rtus_tt_pipe_skip(C.byref(lens), a_lo, a_hi, C.byref(pipe), float(c_up), b_lo, b_hi, n_scan, _ptr(xe), _ptr(ze), xe.size,
@@ -1073,9 +1070,7 @@ def leg_amplitudes_pipe(leg, xe, ze, xf, zf, alpha, beta, gamma=None, *, c_l, c_
     if leg not in LEGS:
         raise ValueError(f"unknown leg {leg!r}: legs are {LEGS}")
     skip = len(leg) == 2
-    xe, ze, xf, zf = _f64(xe, "xe"), _f64(ze, "ze"), _f64(xf, "xf"), _f64(zf, "zf")
-    if xe.shape != ze.shape or xf.shape != zf.shape:
-        raise ValueError("xe/ze and xf/zf must pair up")
+    xe, ze, xf, zf = _points(xe, ze, xf, zf)
     shape = (xe.size, xf.size)
     al, be = _f64(alpha, "alpha", 2), _f64(beta, "beta", 2)
     if al.shape != shape or be.shape != shape:

@@ -7,9 +7,11 @@ import ctypes as C
 
 import torch
 
+import numpy as np
+
 from . import _lib
 from . import api as _api
-from .api import Params, _resolve
+from .api import POLYLINE_READY, TAUP_TAIL, Params, _resolve
 
 
 def _chk(t, name, dtype=torch.float64):
@@ -20,6 +22,51 @@ def _chk(t, name, dtype=torch.float64):
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def _pair(xe, ze, xf, zf, dtype=torch.float64):
+    """xe/ze [n_e] and xf/zf [n_f], checked -> (n_e, n_f)"""
+    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
+        _chk(t, n, dtype)
+    n_e, n_f = xe.numel(), xf.numel()
+    if ze.numel() != n_e or zf.numel() != n_f:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    return n_e, n_f
+
+
+def _result(out, shape, ref, dtype=torch.float64, name="out"):
+    """the caller's result tensor (checked: kind and number of values) or a fresh one of ``shape`` on ref's device"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=ref.device)
+    if _chk(out, name, dtype).numel() != int(np.prod(shape)):
+        raise ValueError(f"{name} must hold {' * '.join(str(n) for n in shape)} values")
+    return out
+
+
+def _optional(n, dtype=torch.float64, **tensors):
+    """outputs (or inputs) that may be None: each one given is checked for kind and for holding n values"""
+    for name, t in tensors.items():
+        if t is not None and _chk(t, name, dtype).numel() != n:
+            raise ValueError(f"{name} must hold {n} values")
+
+
+def _workspace(ws, need, ref):
+    """the caller's uint8 workspace (its kind checked; its size is the C layer's to refuse) or a fresh one of ``need`` bytes"""
+    if ws is None:
+        return torch.empty(max(need, 1), dtype=torch.uint8, device=ref.device)   # (the caching allocator's blocks are 512-byte aligned)
+    return _chk(ws, "ws", torch.uint8)
+
+
+def _tables(tt_tx, tt_rx, data=None, analytic=False):
+    """tt_tx [n_tx, n] and tt_rx [n_rx, n], with ``data`` also its [n_tx, n_rx, n_t] (analytic: [.., 2]) against them -> n"""
+    ok = tt_tx.dim() == 2 and tt_rx.dim() == 2 and tt_tx.shape[1] == tt_rx.shape[1]
+    if ok and data is not None:
+        ok = data.dim() == (4 if analytic else 3) and (not analytic or data.shape[3] == 2) \
+            and data.shape[0] == tt_tx.shape[0] and data.shape[1] == tt_rx.shape[0]
+    if not ok:
+        what = "" if data is None else ("analytic [n_tx, n_rx, n_t, 2], " if analytic else "fmc [n_tx, n_rx, n_t], ")
+        raise ValueError(f"need {what}tt_tx [n_tx, n], tt_rx [n_rx, n]")
+    return tt_tx.shape[1]
 
 
 def _stream(t=None):
@@ -41,7 +88,7 @@ class ShootPlan:
         self.out = {w: torch.empty(shapes[w], dtype=torch.uint8 if w == "status" else torch.float64, device=device)
                     for w in want}
         self.lens = self.p.lens()
-        self.flags = 1 if fast else 0
+        self.flags = _api._flags(fast)
 
     def run(self, geoms, x_a, z_a, alpha, z_f, polyline_ready=False):
         """polyline_ready: the previous ``run`` of this plan used the same ``alpha`` (RTUS_POLYLINE_READY)."""
@@ -53,7 +100,7 @@ class ShootPlan:
         st = _lib.lib().rtus_shoot_dev(C.byref(self.lens), _p(geoms), self.G, _p(x_a), _p(z_a), self.T, _p(alpha),
                                        _p(z_f), self.N, _p(o.get("out8")), _p(o.get("tof4")), _p(o.get("tof")),
                                        _p(o.get("land_x")), _p(o.get("status")), _p(self.ws), self.ws_bytes,
-                                       self.flags | (8 if polyline_ready else 0), _stream())
+                                       self.flags | (POLYLINE_READY if polyline_ready else 0), _stream())
         _lib.check(st, "rtus_shoot_dev")
         return o
 
@@ -77,7 +124,7 @@ class SweepPlan:
                 raise ValueError(f"unknown output {w!r}")
             self.out[w] = torch.empty((G, T, N), dtype=torch.float64, device=device)
         self.lens = self.p.lens()
-        self.flags = 1 if fast else 0
+        self.flags = _api._flags(fast)
         self.atol, self.rtol = float(atol), float(rtol)
 
     def run(self, geoms, x_a, z_a, alpha, z_f, x_rx, polyline_ready=False):
@@ -90,7 +137,7 @@ class SweepPlan:
         st = _lib.lib().rtus_sweep_dev(C.byref(self.lens), _p(geoms), self.G, _p(x_a), _p(z_a), self.T, _p(alpha), _p(z_f), self.N,
                                        _p(x_rx), self.E, self.atol, self.rtol, _p(o["first_ray"]), _p(o["hit"]), _p(o["tof_hit"]),
                                        _p(o.get("tof")), _p(o.get("land_x")), _p(self.ws), self.ws_bytes,
-                                       self.flags | (8 if polyline_ready else 0), _stream())
+                                       self.flags | (POLYLINE_READY if polyline_ready else 0), _stream())
         _lib.check(st, "rtus_sweep_dev")
         return o
 
@@ -113,7 +160,8 @@ class SolvePlan:
             self.out.update(tt_all=torch.empty((G, T, E, 4), **f64), alpha_all=torch.empty((G, T, E, 4), **f64),
                             n_roots=torch.empty((G, T, E), dtype=torch.uint8, device=device))
         self.lens = self.p.lens()
-        self.flags = (1 if fast else 0) | (2 if true_tangent else 0) | (4 if analytic_lens else 0) | (0x10 if one_lane else 0) | (0x20 if three_launches else 0)
+        self.flags = _api._flags(fast, true_tangent, analytic_lens) | (_api.SOLVE_ONE_LANE if one_lane else 0) | \
+            (_api.SOLVE_THREE_LAUNCHES if three_launches else 0)
 
     def run(self, geoms, x_a, z_a, alpha, x_rx, z_land=None, polyline_ready=False):
         """polyline_ready: the previous ``run`` of this plan used the same ``alpha`` tensor contents (RTUS_POLYLINE_READY: the
@@ -126,7 +174,7 @@ class SolvePlan:
         st = _lib.lib().rtus_solve_dev(C.byref(self.lens), _p(geoms), self.G, _p(x_a), _p(z_a), self.T, _p(alpha), self.N,
                                        _p(x_rx), self.E, float(self.p.d if z_land is None else z_land), _p(o["tt"]),
                                        _p(o["alpha_root"]), _p(o.get("tt_all")), _p(o.get("alpha_all")), _p(o.get("n_roots")),
-                                       _p(self.ws), self.ws_bytes, self.flags | (8 if polyline_ready else 0), _stream())
+                                       _p(self.ws), self.ws_bytes, self.flags | (POLYLINE_READY if polyline_ready else 0), _stream())
         _lib.check(st, "rtus_solve_dev")
         return o
 
@@ -146,28 +194,14 @@ def match_dev(land_x, tof, x_rx, atol=1e-6, rtol=1e-5, out=None):
     return out
 
 
-TAUP_TAIL = 0x1             # RTUS_TT_TAUP_TAIL: the faster accuracy tier of the planar solver (include/rtus.h)
-
-
 def tt_layers_dev(z_if, c, xe, ze, xf, zf, out=None, iters=None, row0=0, n_rows_total=None, taup=False):
     """Fermat travel times through horizontal layers; z_if/c are small HOST sequences.
 
     row0 / n_rows_total: xe, ze are rows [row0, row0 + len(xe)) of a table of n_rows_total rows (rtus_tt_layers_rows_dev): with
     row0 a multiple of ``rows_per_block(n_rows_total, n_f)`` the block comes out with the bits the whole table's launch gives it."""
-    import numpy as np
-    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
-    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-    if c.size != z_if.size + 1:               # the C layer reads c[0 .. n_if] from this host pointer
-        raise ValueError("need len(c) == len(z_if) + 1")
-    _chk(xe, "xe"); _chk(ze, "ze"); _chk(xf, "xf"); _chk(zf, "zf")
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f:
-        raise ValueError("xe/ze and xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
-    _chk(out, "out")
-    if out.numel() != n_e * n_f:
-        raise ValueError("out has the wrong size")
+    z_if, c = _api._medium(z_if, c, flat=True)
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
     if iters is not None and (n_rows_total is not None or taup):
         raise ValueError("iters is a whole-table diagnostic of the accurate tier")
     if n_rows_total is not None:
@@ -185,23 +219,14 @@ def tt_layers_dev(z_if, c, xe, ze, xf, zf, out=None, iters=None, row0=0, n_rows_
 def tt_layers_sorted_dev(z_if, c, xe, ze, xf, zf, out=None, ws=None, taup=False):
     """The planar table for an aperture handed over in ANY order (rtus_tt_layers_sorted_dev): sorted by (depth, position) on the
     device, every row stored where it belongs.  ``ws``: optional uint8 workspace tensor to reuse between calls."""
-    import numpy as np
-    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
-    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
-    _chk(xe, "xe"); _chk(ze, "ze"); _chk(xf, "xf"); _chk(zf, "zf")
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f:
-        raise ValueError("xe/ze and xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
-    _chk(out, "out")
+    z_if, c = _api._medium(z_if, c, flat=True)
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
     need = int(_lib.lib().rtus_tt_layers_sort_workspace_bytes(n_e))
-    if ws is None:
+    if ws is None:                            # not _workspace: this entry has always taken ``ws`` as it comes and checked its size here
         ws = torch.empty(need, dtype=torch.uint8, device=xe.device)
-    if ws.numel() < need or out.numel() != n_e * n_f:
-        raise ValueError("workspace or out too small")
+    if ws.numel() < need:
+        raise ValueError("ws is too small")
     st = _lib.lib().rtus_tt_layers_sorted_dev(z_if.ctypes.data if z_if.size else None, c.ctypes.data, z_if.size, _p(xe), _p(ze), n_e,
                                               _p(xf), _p(zf), n_f, _p(out), _p(ws), ws.numel(), TAUP_TAIL if taup else 0, _stream(xe))
     _lib.check(st, "rtus_tt_layers_sorted_dev")
@@ -217,42 +242,32 @@ def rows_per_block(n_rows_total, n_f, dtype=torch.float64):
     return int(r)
 
 
-def tt_lens_rows_dev(xe, ze, xf, zf, out, *, params: Params = None, alpha_lo=None, alpha_hi=None, row0=0, n_rows_total=None):
-    """Curved-lens table rows [row0, row0 + len(xe)) of an n_rows_total-row table, fp64 or fp32 by the tensors' dtype."""
-    from .api import ALPHA_MAX
+def _lens_rows(kind, last, xe, ze, xf, zf, out, params, alpha_lo, alpha_hi, row0, n_rows_total):
+    """rtus_tt_lens[_f32]_{rows,stats}_dev: one argument list, ``last`` being alpha_out (rows) or the counters (stats) -> n_e, n_f"""
     p = _resolve(params)
     f64 = xe.dtype == torch.float64
-    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf"), (out, "out")):
-        _chk(t, n, xe.dtype)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f or out.numel() != n_e * n_f:
-        raise ValueError("xe/ze, xf/zf and out must pair up")
-    fn = _lib.lib().rtus_tt_lens_rows_dev if f64 else _lib.lib().rtus_tt_lens_f32_rows_dev
+    n_e, n_f = _pair(xe, ze, xf, zf, xe.dtype)
+    if _chk(out, "out", xe.dtype).numel() != n_e * n_f:
+        raise ValueError("out must hold n_e * n_f values")
+    fn = getattr(_lib.lib(), f"rtus_tt_lens{'' if f64 else '_f32'}_{kind}_dev")
     lens = p.lens()
-    st = fn(C.byref(lens), -ALPHA_MAX if alpha_lo is None else float(alpha_lo), ALPHA_MAX if alpha_hi is None else float(alpha_hi),
-            _p(xe), _p(ze), n_e, int(row0), int(n_e if n_rows_total is None else n_rows_total), _p(xf), _p(zf), n_f, _p(out), None,
+    st = fn(C.byref(lens), -_api.ALPHA_MAX if alpha_lo is None else float(alpha_lo), _api.ALPHA_MAX if alpha_hi is None else float(alpha_hi),
+            _p(xe), _p(ze), n_e, int(row0), int(n_e if n_rows_total is None else n_rows_total), _p(xf), _p(zf), n_f, _p(out), _p(last),
             _stream())
-    _lib.check(st, "rtus_tt_lens_rows_dev")
+    _lib.check(st, f"rtus_tt_lens_{kind}_dev")
+    return n_e, n_f
+
+
+def tt_lens_rows_dev(xe, ze, xf, zf, out, *, params: Params = None, alpha_lo=None, alpha_hi=None, row0=0, n_rows_total=None):
+    """Curved-lens table rows [row0, row0 + len(xe)) of an n_rows_total-row table, fp64 or fp32 by the tensors' dtype."""
+    _lens_rows("rows", None, xe, ze, xf, zf, out, params, alpha_lo, alpha_hi, row0, n_rows_total)
     return out
 
 
 def tt_lens_stats_dev(xe, ze, xf, zf, out, *, params: Params = None, alpha_lo=None, alpha_hi=None, row0=0, n_rows_total=None):
     """tt_lens_rows_dev + how the rows were solved (rtus_tt_lens[_f32]_stats_dev) -> (out, dict of wave-element counts)."""
-    from .api import ALPHA_MAX
-    p = _resolve(params)
-    f64 = xe.dtype == torch.float64
-    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf"), (out, "out")):
-        _chk(t, n, xe.dtype)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f or out.numel() != n_e * n_f:
-        raise ValueError("xe/ze, xf/zf and out must pair up")
     stats = torch.zeros(5, dtype=torch.int64, device=xe.device)
-    fn = _lib.lib().rtus_tt_lens_stats_dev if f64 else _lib.lib().rtus_tt_lens_f32_stats_dev
-    lens = p.lens()
-    st = fn(C.byref(lens), -ALPHA_MAX if alpha_lo is None else float(alpha_lo), ALPHA_MAX if alpha_hi is None else float(alpha_hi),
-            _p(xe), _p(ze), n_e, int(row0), int(n_e if n_rows_total is None else n_rows_total), _p(xf), _p(zf), n_f, _p(out), _p(stats),
-            _stream())
-    _lib.check(st, "rtus_tt_lens_stats_dev")
+    n_e, n_f = _lens_rows("stats", stats, xe, ze, xf, zf, out, params, alpha_lo, alpha_hi, row0, n_rows_total)
     v = [int(x) for x in stats.cpu()]
     return out, dict(t_only=v[0], one_evaluation=v[1], iterated=v[2], scanned=v[3], iteration_evaluations=v[4],
                      wave_elements=n_e * 4 * ((n_f + 255) // 256))     # waves launched per row: whole workgroups of 256 targets
@@ -263,11 +278,7 @@ def tt_layers_batch_dev(z_if, c, xe, ze, xf, zf, out=None, taup=False):
 
     xe/ze: [B, n_e] or [n_e] (one aperture shared by all problems); xf/zf: [B, n_f] or [n_f] (shared) -> tt [B, n_e, n_f].
     At least one of the two must carry the batch dimension."""
-    import numpy as np
-    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
-    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
+    z_if, c = _api._medium(z_if, c, flat=True)
     for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
         _chk(t, n)
     if xe.shape != ze.shape or xf.shape != zf.shape or xe.dim() not in (1, 2) or xf.dim() not in (1, 2):
@@ -276,11 +287,7 @@ def tt_layers_batch_dev(z_if, c, xe, ze, xf, zf, out=None, taup=False):
     if B is None or (xe.dim() == 2 and xf.dim() == 2 and xe.shape[0] != xf.shape[0]):
         raise ValueError("need a batch dimension on xe/ze and / or xf/zf (equal when on both)")
     n_e, n_f = xe.shape[-1], xf.shape[-1]
-    if out is None:
-        out = torch.empty((B, n_e, n_f), dtype=torch.float64, device=xe.device)
-    _chk(out, "out")
-    if out.numel() != B * n_e * n_f:
-        raise ValueError("out has the wrong size")
+    out = _result(out, (B, n_e, n_f), xe)
     st = _lib.lib().rtus_tt_layers_batch_ex_dev(z_if.ctypes.data if z_if.size else None, c.ctypes.data, z_if.size, _p(xe), _p(ze),
                                                 n_e, n_e if xe.dim() == 2 else 0, _p(xf), _p(zf), n_f,
                                                 n_f if xf.dim() == 2 else 0, _p(out), n_e * n_f, B, TAUP_TAIL if taup else 0, _stream())
@@ -292,20 +299,12 @@ def tt_surface_dev(x0, dx, zs, c1, c2, xe, ze, xf, zf, out=None, x_entry=None):
     """Travel times through one curved interface (rtus_tt_surface_dev; api.travel_time_surface's definition) on float64 CUDA
     tensors -> out [n_e, n_f] (and x_entry [n_e, n_f] when a tensor is given for it).  The spline's workspace is allocated here;
     asynchronous on the current stream."""
-    for t, n in ((zs, "zs"), (xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
-        _chk(t, n)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f:
-        raise ValueError("xe/ze and xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
-    _chk(out, "out")
-    if x_entry is not None:
-        _chk(x_entry, "x_entry")
-    if out.numel() != n_e * n_f or (x_entry is not None and x_entry.numel() != n_e * n_f):
-        raise ValueError("out / x_entry must hold n_e * n_f values")
+    _chk(zs, "zs")
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
+    _optional(n_e * n_f, x_entry=x_entry)
     need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)      # (the caching allocator's blocks are 512-byte aligned)
+    ws = _workspace(None, need, xe)
     st = _lib.lib().rtus_tt_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c2), _p(xe), _p(ze), n_e, _p(xf),
                                         _p(zf), n_f, _p(out), _p(x_entry), _p(ws), need, _stream(xe))
     _lib.check(st, "rtus_tt_surface_dev")
@@ -332,15 +331,10 @@ def tfm_dev(fmc, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
     -> image float32 [n_f].  tt_* may be row blocks / column slices of a larger table as long as they are contiguous."""
     _chk(fmc, "fmc", torch.float32); _chk(tt_tx, "tt_tx")
     tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
-    if fmc.dim() != 3 or tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] \
-            or fmc.shape[0] != tt_tx.shape[0] or fmc.shape[1] != tt_rx.shape[0]:
-        raise ValueError("need fmc [n_tx, n_rx, n_t], tt_tx [n_tx, n_f], tt_rx [n_rx, n_f]")
-    n_f = tt_tx.shape[1]
-    if out is None:
-        out = torch.empty(n_f, dtype=torch.float32, device=fmc.device)
-    _chk(out, "out", torch.float32)
-    if out.numel() != n_f or not (out.device == fmc.device == tt_tx.device == tt_rx.device):
-        raise ValueError("out must hold n_focal float32 values on the device of fmc / tt_tx / tt_rx")
+    n_f = _tables(tt_tx, tt_rx, fmc)
+    out = _result(out, (n_f,), fmc, torch.float32)
+    if not (out.device == fmc.device == tt_tx.device == tt_rx.device):
+        raise ValueError("out must be on the device of fmc / tt_tx / tt_rx")
     st = _lib.lib().rtus_tfm_dev(_p(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], float(fs), float(t0), _p(tt_tx), _p(tt_rx), n_f,
                                  _p(out), _stream(fmc))
     _lib.check(st, "rtus_tfm_dev")
@@ -353,11 +347,9 @@ def fmc_analytic_dev(fmc, n_taps=63, out=None):
     _chk(fmc, "fmc", torch.float32)
     if fmc.dim() != 3:
         raise ValueError("fmc must be [n_tx, n_rx, n_t]")
-    if out is None:
-        out = torch.empty((*fmc.shape, 2), dtype=torch.float32, device=fmc.device)
-    _chk(out, "out", torch.float32)
-    if out.numel() != 2 * fmc.numel() or out.device != fmc.device:
-        raise ValueError("out must hold 2 * fmc.numel() float32 values on the device of fmc")
+    out = _result(out, (*fmc.shape, 2), fmc, torch.float32)
+    if out.device != fmc.device:
+        raise ValueError("out must be on the device of fmc")
     st = _lib.lib().rtus_fmc_analytic_dev(_p(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], int(n_taps), _p(out), _stream(fmc))
     _lib.check(st, "rtus_fmc_analytic_dev")
     return out
@@ -374,15 +366,9 @@ def surface_find_dev(analytic, fs, xe, ze, c1, x0, dx, n_s, z_lo, dz, n_z, t0=0.
     n_e, n_t, n_s, n_z = analytic.shape[0], analytic.shape[2], int(n_s), int(n_z)
     if xe.numel() != n_e or ze.numel() != n_e:
         raise ValueError("xe / ze must hold one position per element")
-    if z_peak is None:
-        z_peak = torch.empty(n_s, dtype=torch.float64, device=analytic.device)
-    if amp is None:
-        amp = torch.empty(n_s, dtype=torch.float32, device=analytic.device)
-    _chk(z_peak, "z_peak"); _chk(amp, "amp", torch.float32)
-    if image is not None:
-        _chk(image, "image", torch.float32)
-    if z_peak.numel() != n_s or amp.numel() != n_s or (image is not None and image.numel() != n_s * n_z):
-        raise ValueError("z_peak / amp must hold n_s values, image n_s * n_z")
+    z_peak = _result(z_peak, (n_s,), analytic, name="z_peak")
+    amp = _result(amp, (n_s,), analytic, torch.float32, "amp")
+    _optional(n_s * n_z, torch.float32, image=image)
     st = _lib.lib().rtus_surface_find_dev(_p(analytic), n_e, n_t, float(fs), float(t0), _p(xe), _p(ze), float(c1), float(x0), float(dx),
                                           n_s, float(z_lo), float(dz), n_z, _p(z_peak), _p(amp), _p(image), _stream(analytic))
     _lib.check(st, "rtus_surface_find_dev")
@@ -396,17 +382,9 @@ def tfm_analytic_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None)
     stream (capturable with pre-allocated outputs)."""
     _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
     tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
-    if analytic.dim() != 4 or analytic.shape[3] != 2 or tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] \
-            or analytic.shape[0] != tt_tx.shape[0] or analytic.shape[1] != tt_rx.shape[0]:
-        raise ValueError("need analytic [n_tx, n_rx, n_t, 2], tt_tx [n_tx, n_f], tt_rx [n_rx, n_f]")
-    n_f = tt_tx.shape[1]
-    if out is None:
-        out = torch.empty((n_f, 2), dtype=torch.float32, device=analytic.device)
-    _chk(out, "out", torch.float32)
-    if cf is not None:
-        _chk(cf, "cf", torch.float32)
-    if out.numel() != 2 * n_f or (cf is not None and cf.numel() != n_f):
-        raise ValueError("out must hold 2 * n_focal float32 values, cf n_focal")
+    n_f = _tables(tt_tx, tt_rx, analytic, analytic=True)
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, cf=cf)
     if not (out.device == analytic.device == tt_tx.device == tt_rx.device and (cf is None or cf.device == analytic.device)):
         raise ValueError("analytic, tt_tx, tt_rx, out and cf must be on one device")
     st = _lib.lib().rtus_tfm_analytic_dev(_p(analytic), analytic.shape[0], analytic.shape[1], analytic.shape[2], float(fs), float(t0),
@@ -420,20 +398,9 @@ class LayersPlan:
     ctypes call (no argument checking, no allocation, no sync) — capturable in a hipGraph."""
 
     def __init__(self, z_if, c, xe, ze, xf, zf, out=None, iters=None, row0=0, n_rows_total=None, taup=False):
-        import numpy as np
-        self.z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
-        self.c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-        if self.c.size != self.z_if.size + 1:
-            raise ValueError("need len(c) == len(z_if) + 1")
-        for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
-            _chk(t, n)
-        self.n_e, self.n_f = xe.numel(), xf.numel()
-        if ze.numel() != self.n_e or zf.numel() != self.n_f:
-            raise ValueError("xe/ze and xf/zf must pair up")
-        self.out = out if out is not None else torch.empty((self.n_e, self.n_f), dtype=torch.float64, device=xe.device)
-        _chk(self.out, "out")
-        if self.out.numel() != self.n_e * self.n_f:
-            raise ValueError("out has the wrong size")
+        self.z_if, self.c = _api._medium(z_if, c, flat=True)
+        self.n_e, self.n_f = _pair(xe, ze, xf, zf)
+        self.out = _result(out, (self.n_e, self.n_f), xe)
         self._keep = (xe, ze, xf, zf, self.out, iters)
         self._fn = _lib.lib().rtus_tt_layers_dev
         self._args = [self.z_if.ctypes.data if self.z_if.size else None, self.c.ctypes.data, self.z_if.size,
@@ -454,20 +421,12 @@ def pw_layers_dev(z_if, c, angles, x_lo, x_hi, z_a, xf, zf, out=None):
     """Plane-wave transmit times through horizontal layers on device (rtus_pw_layers_dev; api.pw_travel_time_layers's definition):
     z_if / c small HOST sequences, angles / xf / zf float64 CUDA tensors, the aperture [x_lo, x_hi] at depth z_a -> out [n_a, n_f].
     Asynchronous on the current stream."""
-    import numpy as np
-    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
-    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-    if c.size != z_if.size + 1:               # the C layer reads c[0 .. n_if] from this host pointer
-        raise ValueError("need len(c) == len(z_if) + 1")
+    z_if, c = _api._medium(z_if, c, flat=True)
     _chk(angles, "angles"); _chk(xf, "xf"); _chk(zf, "zf")
     n_a, n_f = angles.numel(), xf.numel()
     if zf.numel() != n_f:
         raise ValueError("xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_a, n_f), dtype=torch.float64, device=xf.device)
-    _chk(out, "out")
-    if out.numel() != n_a * n_f:
-        raise ValueError("out must hold n_a * n_f values")
+    out = _result(out, (n_a, n_f), xf)
     st = _lib.lib().rtus_pw_layers_dev(z_if.ctypes.data if z_if.size else None, c.ctypes.data, z_if.size, _p(angles), n_a, float(x_lo),
                                        float(x_hi), float(z_a), _p(xf), _p(zf), n_f, _p(out), _stream(xf))
     _lib.check(st, "rtus_pw_layers_dev")
@@ -483,15 +442,10 @@ def pw_surface_dev(x0, dx, zs, c1, c2, angles, x_lo, x_hi, z_a, xf, zf, out=None
     n_a, n_f = angles.numel(), xf.numel()
     if zf.numel() != n_f:
         raise ValueError("xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_a, n_f), dtype=torch.float64, device=xf.device)
-    _chk(out, "out")
-    if x_entry is not None:
-        _chk(x_entry, "x_entry")
-    if out.numel() != n_a * n_f or (x_entry is not None and x_entry.numel() != n_a * n_f):
-        raise ValueError("out / x_entry must hold n_a * n_f values")
+    out = _result(out, (n_a, n_f), xf)
+    _optional(n_a * n_f, x_entry=x_entry)
     need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xf.device)      # (the caching allocator's blocks are 512-byte aligned)
+    ws = _workspace(None, need, xf)
     st = _lib.lib().rtus_pw_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c2), _p(angles), n_a, float(x_lo),
                                         float(x_hi), float(z_a), _p(xf), _p(zf), n_f, _p(out), _p(x_entry), _p(ws), need, _stream(xf))
     _lib.check(st, "rtus_pw_surface_dev")
@@ -502,11 +456,7 @@ def skip_layers_dev(z_if, c, z_back, xe, ze, xf, zf, c_up=None, out=None, taup=F
     """Skip-leg times through horizontal layers on device (api.skip_travel_time_layers's definition): tt_layers_dev on the stack
     z_if + [z_back], c + [c_up] at the mirrored depth 2 z_back - zf, then NaN outside z_if[-1] < zf < z_back.  z_if / c are small
     HOST sequences; asynchronous on the current stream (no host synchronisation)."""
-    import numpy as np
-    z_if = np.ascontiguousarray(z_if, dtype=np.float64).reshape(-1)
-    c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-    if c.size != z_if.size + 1:
-        raise ValueError("need len(c) == len(z_if) + 1")
+    z_if, c = _api._medium(z_if, c, flat=True)
     z_back = float(z_back)
     front = float(z_if[-1]) if z_if.size else -float("inf")
     if not (z_back > front):
@@ -526,23 +476,12 @@ def tt_surface_skip_dev(x0, dx, zs, c1, c_down, c_up, z_back, xe, ze, xf, zf, ou
     """Skip-leg times through one curved interface on device (rtus_tt_surface_skip_dev; api.skip_travel_time_surface's definition)
     on float64 CUDA tensors -> out [n_e, n_f] (and x_entry / x_back [n_e, n_f] when tensors are given for them).  The spline's
     workspace is allocated here; asynchronous on the current stream."""
-    for t, n in ((zs, "zs"), (xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
-        _chk(t, n)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f:
-        raise ValueError("xe/ze and xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
-    _chk(out, "out")
-    for t, n in ((x_entry, "x_entry"), (x_back, "x_back")):
-        if t is not None:
-            _chk(t, n)
-            if t.numel() != n_e * n_f:
-                raise ValueError(f"{n} must hold n_e * n_f values")
-    if out.numel() != n_e * n_f:
-        raise ValueError("out must hold n_e * n_f values")
+    _chk(zs, "zs")
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
+    _optional(n_e * n_f, x_entry=x_entry, x_back=x_back)
     need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)      # (the caching allocator's blocks are 512-byte aligned)
+    ws = _workspace(None, need, xe)
     st = _lib.lib().rtus_tt_surface_skip_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(c_down), float(c_up),
                                              float(z_back), _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(out), _p(x_entry), _p(x_back),
                                              _p(ws), need, _stream(xe))
@@ -558,11 +497,9 @@ def fmc_synth_tx_dev(fmc, fs, delays, out=None):
     if fmc.dim() != 3 or delays.dim() != 2 or delays.shape[1] != fmc.shape[0]:
         raise ValueError("need fmc [n_tx, n_rx, n_t] and delays [n_v, n_tx]")
     n_v = delays.shape[0]
-    if out is None:
-        out = torch.empty((n_v, fmc.shape[1], fmc.shape[2]), dtype=torch.float32, device=fmc.device)
-    _chk(out, "out", torch.float32)
-    if out.numel() != n_v * fmc.shape[1] * fmc.shape[2] or not (out.device == fmc.device == delays.device):
-        raise ValueError("out must hold n_v * n_rx * n_t float32 values on the device of fmc / delays")
+    out = _result(out, (n_v, fmc.shape[1], fmc.shape[2]), fmc, torch.float32)
+    if not (out.device == fmc.device == delays.device):
+        raise ValueError("out must be on the device of fmc / delays")
     st = _lib.lib().rtus_fmc_synth_tx_dev(_p(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], float(fs), _p(delays), n_v, _p(out),
                                           _stream(fmc))
     _lib.check(st, "rtus_fmc_synth_tx_dev")
@@ -576,28 +513,15 @@ def leg_amp_surface_dev(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, leg, xe, z
     bytes (allocated here otherwise; pass one to capture the call in a graph).  Asynchronous on the current stream."""
     if leg not in _api.LEG_CODES:
         raise ValueError(f"unknown leg {leg!r}: legs are {_api.LEGS}")
-    for t, n in ((zs, "zs"), (xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf"), (x_entry, "x_entry")):
-        _chk(t, n)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f or x_entry.numel() != n_e * n_f:
-        raise ValueError("xe/ze and xf/zf must pair up, x_entry hold n_e * n_f values")
-    if len(leg) == 2:
-        if x_back is None:
-            raise ValueError(f"the skip leg {leg!r} needs x_back")
-        _chk(x_back, "x_back")
-        if x_back.numel() != n_e * n_f:
-            raise ValueError("x_back must hold n_e * n_f values")
+    _chk(zs, "zs"); _chk(x_entry, "x_entry")
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    if len(leg) == 2 and x_back is None:
+        raise ValueError(f"the skip leg {leg!r} needs x_back")
+    _optional(n_e * n_f, x_entry=x_entry, x_back=x_back if len(leg) == 2 else None)
     if element_width > 0 and f_c is None:
         raise ValueError("an element width needs the centre frequency f_c")
-    if out is None:
-        out = torch.empty((n_e, n_f, 2), dtype=torch.float32, device=xe.device)
-    _chk(out, "out", torch.float32)
-    if out.numel() != 2 * n_e * n_f:
-        raise ValueError("out must hold 2 * n_e * n_f float32 values")
-    need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
-    if ws is None:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)
-    _chk(ws, "ws", torch.uint8)
+    out = _result(out, (n_e, n_f, 2), xe, torch.float32)
+    ws = _workspace(ws, int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel())), xe)
     st = _lib.lib().rtus_leg_amp_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), float(rho1), float(c_l), float(c_t),
                                              float(rho2), float(z_back), _api.LEG_CODES[leg], 1 if up else 0, float(element_width),
                                              float(f_c or 0.0), _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(x_entry),
@@ -619,19 +543,11 @@ def tfm_weighted_dev(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, t0=0.0, o
     if w_rx is None:
         raise ValueError("w_rx is needed with tt_rx")
     _chk(w_rx, "w_rx", torch.float32)
-    if analytic.dim() != 4 or analytic.shape[3] != 2 or tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] \
-            or analytic.shape[0] != tt_tx.shape[0] or analytic.shape[1] != tt_rx.shape[0]:
-        raise ValueError("need analytic [n_tx, n_rx, n_t, 2], tt_tx [n_tx, n_f], tt_rx [n_rx, n_f]")
-    n_f = tt_tx.shape[1]
+    n_f = _tables(tt_tx, tt_rx, analytic, analytic=True)
     if w_tx.numel() != 2 * tt_tx.numel() or w_rx.numel() != 2 * tt_rx.numel():
         raise ValueError("w_tx / w_rx must hold 2 * n_tx * n_f / 2 * n_rx * n_f float32 values")
-    if out is None:
-        out = torch.empty((n_f, 2), dtype=torch.float32, device=analytic.device)
-    _chk(out, "out", torch.float32)
-    if sens is not None:
-        _chk(sens, "sens", torch.float32)
-    if out.numel() != 2 * n_f or (sens is not None and sens.numel() != n_f):
-        raise ValueError("out must hold 2 * n_focal float32 values, sens n_focal")
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, sens=sens)
     devs = {t.device for t in (analytic, tt_tx, tt_rx, w_tx, w_rx, out) + ((sens,) if sens is not None else ())}
     if len(devs) != 1:
         raise ValueError("analytic, the tables, the weights, out and sens must be on one device")
@@ -641,67 +557,42 @@ def tfm_weighted_dev(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, t0=0.0, o
     return out if sens is None else (out, sens)
 
 
+def _pipe_table(entry, pipe_args, c_up, xe, ze, xf, zf, out, angles, ws):
+    """the body of tt_pipe_dev and tt_pipe_skip_dev: rtus_<entry>_dev with rtus_<entry>_workspace_bytes; ``c_up`` is the skip entry's
+    one more argument (empty for the direct entry), ``angles`` the optional [n_e, n_f] outputs by name, in the entry's order"""
+    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = pipe_args
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
+    _optional(n_e * n_f, **angles)
+    L = _lib.lib()
+    ws = _workspace(ws, int(getattr(L, f"rtus_{entry}_workspace_bytes")(n_e, n_scan)), xe)
+    st = getattr(L, f"rtus_{entry}_dev")(C.byref(lens), a_lo, a_hi, C.byref(pipe), *c_up, b_lo, b_hi, n_scan, _p(xe), _p(ze), n_e, _p(xf),
+                                         _p(zf), n_f, _p(out), *map(_p, angles.values()), _p(ws), ws.numel(), _stream(xe))
+    _lib.check(st, f"rtus_{entry}_dev")
+    return out
+
+
 def tt_pipe_dev(xe, ze, xf, zf, out=None, alpha_out=None, beta_out=None, *, c3=5600.0, r_inner=0.0, params: Params = None,
-                alpha_lo=None, alpha_hi=None, beta_lo=-_api.np.pi / 2, beta_hi=_api.np.pi / 2, n_scan=None, ws=None):
+                alpha_lo=None, alpha_hi=None, beta_lo=-np.pi / 2, beta_hi=np.pi / 2, n_scan=None, ws=None):
     """Lens-to-pipe-wall times on device (rtus_tt_pipe_dev; api.travel_time_pipe's definition and defaults) on float64 CUDA tensors
     -> out [n_e, n_f] (and alpha_out / beta_out [n_e, n_f] when tensors are given for them).  ``ws``: an optional uint8 tensor of
     at least rtus_tt_pipe_workspace_bytes(n_e, n_scan) bytes to reuse (a graph capture must not allocate); allocated here
     otherwise.  Asynchronous on the current stream."""
-    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _api._pipe_args(params, c3, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
-    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
-        _chk(t, n)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f:
-        raise ValueError("xe/ze and xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
-    for t, n in ((out, "out"), (alpha_out, "alpha_out"), (beta_out, "beta_out")):
-        if t is not None:
-            _chk(t, n)
-            if t.numel() != n_e * n_f:
-                raise ValueError(f"{n} must hold n_e * n_f values")
-    need = int(_lib.lib().rtus_tt_pipe_workspace_bytes(n_e, n_scan))
-    if ws is None:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)     # (the caching allocator's blocks are 512-byte aligned)
-    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
-        raise ValueError("ws must be a contiguous CUDA uint8 tensor")
-    st = _lib.lib().rtus_tt_pipe_dev(C.byref(lens), a_lo, a_hi, C.byref(pipe), b_lo, b_hi, n_scan, _p(xe), _p(ze), n_e, _p(xf), _p(zf),
-                                     n_f, _p(out), _p(alpha_out), _p(beta_out), _p(ws), ws.numel(), _stream(xe))
-    _lib.check(st, "rtus_tt_pipe_dev")
-    return out
+    args = _api._pipe_args(params, c3, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
+    return _pipe_table("tt_pipe", args, (), xe, ze, xf, zf, out, dict(alpha_out=alpha_out, beta_out=beta_out), ws)
 
 
 def tt_pipe_skip_dev(xe, ze, xf, zf, out=None, alpha_out=None, beta_out=None, gamma_out=None, *, c_down, c_up=None, r_inner,
-                     params: Params = None, alpha_lo=None, alpha_hi=None, beta_lo=-_api.np.pi / 2, beta_hi=_api.np.pi / 2, n_scan=None,
+                     params: Params = None, alpha_lo=None, alpha_hi=None, beta_lo=-np.pi / 2, beta_hi=np.pi / 2, n_scan=None,
                      ws=None):
     """Bore-reflected skip legs into the pipe wall on device (rtus_tt_pipe_skip_dev; api.skip_travel_time_pipe's definition and
     defaults) on float64 CUDA tensors -> out [n_e, n_f] (and alpha_out / beta_out / gamma_out [n_e, n_f] when tensors are given for
     them).  ``ws``: an optional uint8 tensor of at least rtus_tt_pipe_skip_workspace_bytes(n_e, n_scan) bytes to reuse (a graph
     capture must not allocate); allocated here otherwise.  Asynchronous on the current stream."""
     c_up = c_down if c_up is None else c_up
-    lens, a_lo, a_hi, pipe, b_lo, b_hi, n_scan = _api._pipe_args(params, c_down, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
-    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf")):
-        _chk(t, n)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f:
-        raise ValueError("xe/ze and xf/zf must pair up")
-    if out is None:
-        out = torch.empty((n_e, n_f), dtype=torch.float64, device=xe.device)
-    for t, n in ((out, "out"), (alpha_out, "alpha_out"), (beta_out, "beta_out"), (gamma_out, "gamma_out")):
-        if t is not None:
-            _chk(t, n)
-            if t.numel() != n_e * n_f:
-                raise ValueError(f"{n} must hold n_e * n_f values")
-    need = int(_lib.lib().rtus_tt_pipe_skip_workspace_bytes(n_e, n_scan))
-    if ws is None:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=xe.device)     # (the caching allocator's blocks are 512-byte aligned)
-    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
-        raise ValueError("ws must be a contiguous CUDA uint8 tensor")
-    st = _lib.lib().rtus_tt_pipe_skip_dev(C.byref(lens), a_lo, a_hi, C.byref(pipe), float(c_up), b_lo, b_hi, n_scan, _p(xe), _p(ze), n_e,
-                                          _p(xf), _p(zf), n_f, _p(out), _p(alpha_out), _p(beta_out), _p(gamma_out), _p(ws), ws.numel(),
-                                          _stream(xe))
-    _lib.check(st, "rtus_tt_pipe_skip_dev")
-    return out
+    args = _api._pipe_args(params, c_down, r_inner, alpha_lo, alpha_hi, beta_lo, beta_hi, n_scan)
+    return _pipe_table("tt_pipe_skip", args, (float(c_up),), xe, ze, xf, zf, out,
+                       dict(alpha_out=alpha_out, beta_out=beta_out, gamma_out=gamma_out), ws)
 
 
 def leg_amp_pipe_dev(leg, xe, ze, xf, zf, alpha, beta, gamma=None, *, c_l, c_t, rho_wall, rho_water, rho_lens, ct_lens, r_inner,
@@ -711,24 +602,14 @@ def leg_amp_pipe_dev(leg, xe, ze, xf, zf, alpha, beta, gamma=None, *, c_l, c_t, 
     [n_e, n_f, 2] (interleaved complex64).  No workspace; asynchronous on the current stream (capturable with ``out`` given)."""
     if leg not in _api.LEG_CODES:
         raise ValueError(f"unknown leg {leg!r}: legs are {_api.LEGS}")
-    for t, n in ((xe, "xe"), (ze, "ze"), (xf, "xf"), (zf, "zf"), (alpha, "alpha"), (beta, "beta")):
-        _chk(t, n)
-    n_e, n_f = xe.numel(), xf.numel()
-    if ze.numel() != n_e or zf.numel() != n_f or alpha.numel() != n_e * n_f or beta.numel() != n_e * n_f:
-        raise ValueError("xe/ze and xf/zf must pair up, alpha and beta hold n_e * n_f values")
-    if len(leg) == 2:
-        if gamma is None:
-            raise ValueError(f"the skip leg {leg!r} needs gamma")
-        _chk(gamma, "gamma")
-        if gamma.numel() != n_e * n_f:
-            raise ValueError("gamma must hold n_e * n_f values")
+    _chk(alpha, "alpha"); _chk(beta, "beta")
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    if len(leg) == 2 and gamma is None:
+        raise ValueError(f"the skip leg {leg!r} needs gamma")
+    _optional(n_e * n_f, alpha=alpha, beta=beta, gamma=gamma if len(leg) == 2 else None)
     if element_width > 0 and f_c is None:
         raise ValueError("an element width needs the centre frequency f_c")
-    if out is None:
-        out = torch.empty((n_e, n_f, 2), dtype=torch.float32, device=xe.device)
-    _chk(out, "out", torch.float32)
-    if out.numel() != 2 * n_e * n_f:
-        raise ValueError("out must hold 2 * n_e * n_f float32 values")
+    out = _result(out, (n_e, n_f, 2), xe, torch.float32)
     lens, a_lo, a_hi, pipe, media = _api._pipe_amp_args(params, r_inner, alpha_lo, alpha_hi, c_l, c_t, rho_wall, rho_water, rho_lens,
                                                         ct_lens)
     st = _lib.lib().rtus_leg_amp_pipe_dev(C.byref(lens), a_lo, a_hi, C.byref(pipe), C.byref(media), _api.LEG_CODES[leg], 1 if up else 0,
@@ -757,13 +638,8 @@ def echo_pick_dev(analytic, fs, t_lo, t_hi, t0=0.0, t_pick=None, amp=None):
         return 0.0, v
     lo, lo_t = bound(t_lo, "t_lo")
     hi, hi_t = bound(t_hi, "t_hi")
-    if t_pick is None:
-        t_pick = torch.empty((n_tx, n_rx), dtype=torch.float64, device=analytic.device)
-    if amp is None:
-        amp = torch.empty((n_tx, n_rx), dtype=torch.float32, device=analytic.device)
-    _chk(t_pick, "t_pick"); _chk(amp, "amp", torch.float32)
-    if t_pick.numel() != n_tx * n_rx or amp.numel() != n_tx * n_rx:
-        raise ValueError("t_pick / amp must hold one value per pair")
+    t_pick = _result(t_pick, (n_tx, n_rx), analytic, name="t_pick")
+    amp = _result(amp, (n_tx, n_rx), analytic, torch.float32, "amp")
     st = _lib.lib().rtus_echo_pick_dev(_p(analytic), n_tx, n_rx, n_t, float(fs), float(t0), lo, hi, _p(lo_t), _p(hi_t), _p(t_pick),
                                        _p(amp), _stream(analytic))
     _lib.check(st, "rtus_echo_pick_dev")
@@ -782,15 +658,8 @@ def geom_misfit_dev(tt, t_meas, weights=None, n=None, sse=None, sum_r=None, sum_
         if tuple(weights.shape) != tuple(t_meas.shape):
             raise ValueError("weights must have t_meas's shape")
     G = tt.shape[0]
-    if n is None:
-        n = torch.empty(G, dtype=torch.int32, device=tt.device)
-    outs = []
-    for o in (sse, sum_r, sum_w):
-        outs.append(torch.empty(G, dtype=torch.float64, device=tt.device) if o is None else o)
-    sse, sum_r, sum_w = outs
-    _chk(n, "n", torch.int32); _chk(sse, "sse"); _chk(sum_r, "sum_r"); _chk(sum_w, "sum_w")
-    if any(o.numel() != G for o in (n, sse, sum_r, sum_w)):
-        raise ValueError("n / sse / sum_r / sum_w must hold one value per geometry")
+    n = _result(n, (G,), tt, torch.int32, "n")
+    sse, sum_r, sum_w = (_result(o, (G,), tt, name=name) for o, name in ((sse, "sse"), (sum_r, "sum_r"), (sum_w, "sum_w")))
     st = _lib.lib().rtus_geom_misfit_dev(_p(tt), G, tt.shape[1], tt.shape[2], _p(t_meas), _p(weights), _p(n), _p(sse), _p(sum_r),
                                          _p(sum_w), _stream(tt))
     _lib.check(st, "rtus_geom_misfit_dev")
@@ -802,12 +671,7 @@ def _sim_out(n_tx, n_rx, n_t, pulse, out, analytic, ref):
     _chk(pulse, "pulse", torch.float32)
     if pulse.dim() != 2 or pulse.shape[1] != 2:
         raise ValueError("pulse must be float32 [n_p, 2] (complex)")
-    c = 2 if analytic else 1
-    if out is None:
-        out = torch.empty((n_tx, n_rx, n_t, 2) if analytic else (n_tx, n_rx, n_t), dtype=torch.float32, device=ref.device)
-    _chk(out, "out", torch.float32)
-    if out.numel() != n_tx * n_rx * n_t * c:
-        raise ValueError(f"out must hold n_tx * n_rx * n_t * {c} float32 values")
+    out = _result(out, (n_tx, n_rx, n_t, 2) if analytic else (n_tx, n_rx, n_t), ref, torch.float32)
     if out.device != ref.device or pulse.device != ref.device:
         raise ValueError("the tables, pulse and out must be on one device")
     return out
@@ -824,9 +688,9 @@ def fmc_sim_dev(tt_tx, tt_rx=None, *, fs, n_t, pulse, centre, oversample, t0=0.0
         tt_rx = tt_tx
         w_rx = w_tx if w_rx is None else w_rx
     _chk(tt_rx, "tt_rx")
-    if tt_tx.dim() != 2 or tt_rx.dim() != 2 or tt_tx.shape[1] != tt_rx.shape[1] or tt_tx.device != tt_rx.device:
-        raise ValueError("need tt_tx [n_tx, n_s], tt_rx [n_rx, n_s] on one device")
-    n_tx, n_rx, n_s = tt_tx.shape[0], tt_rx.shape[0], tt_tx.shape[1]
+    n_tx, n_rx, n_s = tt_tx.shape[0], tt_rx.shape[0], _tables(tt_tx, tt_rx)
+    if tt_tx.device != tt_rx.device:
+        raise ValueError("tt_tx and tt_rx must be on one device")
     for t, name, n in ((strength, "strength", n_s), (w_tx, "w_tx", n_tx * n_s), (w_rx, "w_rx", n_rx * n_s)):
         if t is not None:
             _chk(t, name, torch.float32)
