@@ -6,7 +6,12 @@ fs * oversample with time zero at index ``centre``, continued with p[-1] = p[n_p
     d  = ((tau - t0) * fs) * oversample      x0 = centre - d      i0 = floor(x0)      w = float32(x0 - i0)
 sample j reads the table at i = i0 + j * oversample with the weight w.  What differs from the kernel: the amplitude products,
 the interpolation and the sums are fp64 here (the kernel's are fp32), so the two agree to the fp32 summation bound and not by bits.
+
+scan() is the fast oracle and shares the kernel's index arithmetic (first and last sample of an arrival, a padded table);
+scan_by_definition() is the header's sentence per sample and shares none of it: tests/test_fmcsim_cpu.py holds the two together.
 """
+import math
+
 import numpy as np
 
 
@@ -68,6 +73,82 @@ def scan(tau, a, pulse, centre, oversample, fs, t0, n_t, init=None):
         np.add.at(out, jv, a[v] * (lo + w[v] * (hi - lo)))
         touched[jv] = True
     return out, touched, float(np.abs(a[ok]).sum())
+
+
+def scan_by_definition(tau, a, pulse, centre, oversample, fs, t0, n_t, edges=None):
+    """scan() from the text of include/rtus.h, sample by sample: for every arrival d = ((tau - t0) fs) oversample, x0 = centre - d,
+    i0 = floor(x0), w = (float)(x0 - i0); sample j reads the table at i = i0 + j oversample and is touched iff -1 <= i <= n_p - 1;
+    it receives a (P(i) + w (P(i + 1) - P(i))) with P zero outside [0, n_p).  Plain loops over the arrivals and over every sample of
+    the record, Python floats (fp64, each operation rounded on its own).  -> what scan() returns.
+    ``edges``: a list that receives, per arrival that counts, (k, first sample, last sample, |its own term at the first|, |at the
+    last|)."""
+    table = [complex(v) for v in np.asarray(pulse, dtype=np.complex64).ravel()]
+    n_p, os_ = len(table), int(oversample)
+
+    def P(i):
+        return table[i] if 0 <= i < n_p else 0j
+
+    tau = [float(t) for t in np.atleast_1d(np.asarray(tau, dtype=np.float64))]
+    with np.errstate(over="ignore", invalid="ignore"):
+        amp = [1 + 0j] * len(tau) if a is None else [complex(v) for v in np.atleast_1d(np.asarray(a)).astype(np.complex64)]
+    out, touched, sum_abs = [0j] * n_t, [False] * n_t, 0.0
+    for k, (t, ak) in enumerate(zip(tau, amp)):
+        if not (math.isfinite(ak.real) and math.isfinite(ak.imag)):
+            continue
+        d = ((t - float(t0)) * float(fs)) * float(os_)
+        if not abs(d) < 2.0 ** 30:                                              # NaN fails
+            continue
+        x0 = float(centre) - d
+        i0 = math.floor(x0)
+        w = float(np.float32(x0 - i0))
+        first = last = None
+        for j in range(n_t):
+            i = i0 + j * os_
+            if -1 <= i <= n_p - 1:
+                term = ak * (P(i) + w * (P(i + 1) - P(i)))
+                out[j] += term
+                touched[j] = True
+                if first is None:
+                    first = (j, abs(term))
+                last = (j, abs(term))
+        if first is not None:
+            sum_abs += abs(ak)
+            if edges is not None:
+                edges.append((k, first[0], last[0], first[1], last[1]))
+    return np.array(out, dtype=np.complex128), np.array(touched, dtype=bool), sum_abs
+
+
+# ------------------------------------------------------------------------------- inputs that are not small anywhere
+def random_complex(rng, shape):
+    """complex64 m exp(2 pi i phi), m uniform in [0.5, 1.5], phi uniform in [0, 1): as a wavelet no entry is small next to the
+    peak, so a table entry or a sample off by one shows at full size"""
+    m, phi = rng.uniform(0.5, 1.5, shape), rng.uniform(0.0, 1.0, shape)
+    return (m * np.exp(2j * np.pi * phi)).astype(np.complex64)
+
+
+def times_at(k, rng, fs, oversample, t0):
+    """arrival times t0 + (k + f) / (fs oversample), k integers (any shape), f uniform in [0.1, 0.9]: sample 0 reads the table at
+    i0 = centre - k - 1 with the weight 1 - f, away from 0 and 1, and no placement sits within a rounding of a table node"""
+    k = np.asarray(k, dtype=np.int64)
+    return float(t0) + (k + rng.uniform(0.1, 0.9, k.shape)) / (float(fs) * int(oversample))
+
+
+def edge_steps(n_p, centre, oversample, n_t):
+    """the table steps k (times_at) of seven arrivals around the two ends of a record, each the start of a run: an arrival at
+    k + m, m = 0, 1, 2, ..., moves through the table one entry at a time.  With J = n_t - 1, an arrival at k is touched in samples
+    j with k - centre <= j oversample <= k - centre + n_p.
+        0, 1  sample 0 cuts the pulse: it reads i0 = oversample .. -1 (run of 6 each, 12 together: every phase of the first
+              oversample + 1 entries, then pulses that start inside)
+        2, 3  sample J cuts the pulse: it reads i = n_p .. n_p - 11 (n_p: sample J is just missed)
+        4     wholly inside, about the middle of the record
+        5     before the record: k = centre - n_p - 1 is the last that writes nothing, centre - n_p reads p[n_p - 1] at sample 0
+        6     after the record: k = centre + J oversample reads p[-1] at sample J, one more writes nothing"""
+    J = n_t - 1
+    return np.array([centre - oversample - 1, centre - oversample + 5,
+                     centre - n_p + J * oversample - 1, centre - n_p + J * oversample + 5,
+                     centre + oversample * (n_t // 2) - n_p // 2,
+                     centre - n_p - 3,
+                     centre + J * oversample - 3], dtype=np.int64)
 
 
 def simulate(tt_tx, tt_rx, pulse, centre, oversample, fs, t0, n_t, q=None, w_tx=None, w_rx=None, init=None, pairs=None):

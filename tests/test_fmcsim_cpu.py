@@ -1,5 +1,5 @@
-"""CPU: the FMC simulator's NumPy oracle (tests/fmcsim_numpy.py) against oracle/tfm_numpy.synth_fmc, the oracle's accumulate
-property, gaussian_pulse, the status codes of rtus_fmc_sim* (argument checks run before any HIP call: no device needed), the
+"""CPU: the FMC simulator's NumPy oracle (tests/fmcsim_numpy.py) against oracle/tfm_numpy.synth_fmc and against the per-sample
+definition of include/rtus.h (scan_by_definition), the oracle's accumulate property, gaussian_pulse, the status codes of rtus_fmc_sim* (argument checks run before any HIP call: no device needed), the
 ValueErrors of the Python layer and the exports."""
 import numpy as np
 import pytest
@@ -38,6 +38,38 @@ def test_oracle_against_synth_fmc(rtus, oversample, n_scat):
     tol = float(sa.max()) * (_interp_bound(oversample) + 2 * TAIL + 2 * F32)
     print(f"oversample {oversample}, {n_scat} scatterers: max |oracle - synth_fmc| {err:.3e}, bound {tol:.3e}")
     assert np.abs(ref).max() > 0.5 and err <= tol
+
+
+@pytest.mark.parametrize("oversample", [1, 2, 3, 5, 7, 8])
+def test_oracle_against_the_definition_per_sample(oversample):
+    """scan() (first and last sample of an arrival, a padded table, integer division by the oversampling) against
+    scan_by_definition() (none of these) with a wavelet that is not small anywhere and seven arrivals about the record's ends
+    (fmcsim_numpy.edge_steps, each moved on by 0..5 table steps): the same samples touched, the values within 1e-14 max|p| sum|a|
+    (fp64 sums of at most 7 terms in two groupings: some 1e-15).  And the teeth the GPU tests rely on: every arrival's own term at
+    its first and at its last sample is at least 100 times the GPU tests' bound (7 + 16) 2^-23 max|p| sum|a|."""
+    os_ = oversample
+    rng = np.random.default_rng(400 + os_)
+    worst, least, cases = 0.0, np.inf, 0
+    for n_p in sorted({1, 2, os_, os_ + 1, 3 * os_ - 1, 37, 200, 2048 - os_}):
+        pulse = S.random_complex(rng, n_p)
+        for centre in sorted({0, n_p // 2, n_p - 1}):
+            for n_t in (5, 1025, 2049, 2500):
+                k = S.edge_steps(n_p, centre, os_, n_t) + rng.integers(0, 6, 7)
+                if n_p + 1 < os_:                                               # a pulse shorter than a sample step: put one on a sample
+                    k[4] = centre + os_ * (n_t // 2) - rng.integers(0, n_p + 1)
+                tau, a = S.times_at(k, rng, FS, os_, 0.3e-6), S.random_complex(rng, 7)
+                edges = []
+                want, t_want, sa_want = S.scan_by_definition(tau, a, pulse, centre, os_, FS, 0.3e-6, n_t, edges=edges)
+                got, t_got, sa = S.scan(tau, a, pulse, centre, os_, FS, 0.3e-6, n_t)
+                label = (os_, n_p, centre, n_t)
+                assert np.array_equal(t_got, t_want), label
+                assert len(edges) >= 1 and abs(sa - sa_want) <= 1e-14 * sa, label
+                scale = float(np.abs(pulse).max()) * sa
+                worst = max(worst, float(np.abs(got - want).max()) / scale)
+                least = min([least] + [min(e[3], e[4]) / (23 * 2.0 ** -23 * scale) for e in edges])
+                cases += 1
+    print(f"oversample {os_}: {cases} cases, max |scan - definition| / (max|p| sum|a|) {worst:.2e}, least edge term / GPU bound {least:.0f}")
+    assert worst <= 1e-14 and least >= 100.0
 
 
 def test_oracle_accumulate_equals_one_call(rtus):
@@ -123,7 +155,7 @@ def test_status_codes_before_any_hip_call(rtus):
     invalid = [dict(tt_tx=None), dict(pulse=None), dict(out=None), dict(n_tx=0), dict(n_rx=-1), dict(n_s=0), dict(n_p=0), dict(n_t=0),
                dict(fs=0.0), dict(fs=-1.0), dict(fs=np.inf), dict(fs=np.nan), dict(t0=np.nan), dict(t0=np.inf), dict(os=0),
                dict(centre=-1), dict(centre=n_p), dict(flags=4), dict(flags=0x80000001), dict(q=P(q) + 4), dict(out=P(out) + 2)]
-    unsupported = [dict(n_t=(1 << 26) + 1), dict(n_p=2045, os=4, centre=0), dict(n_p=33, os=2016), dict(n_tx=1 << 15, n_rx=1 << 15, n_t=2048)]
+    unsupported = [dict(n_t=(1 << 26) + 1), dict(n_p=2045, os=4, centre=0), dict(n_p=2048, os=1, centre=0), dict(n_p=33, os=2016), dict(n_tx=1 << 15, n_rx=1 << 15, n_t=2048)]
     for dev in (True, False):
         for call in (sim, echo):
             for kw in invalid:

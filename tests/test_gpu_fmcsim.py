@@ -1,6 +1,8 @@
 """GPU: the FMC simulator (rtus_fmc_sim, rtus_fmc_sim_echo) against its fp64 oracle (tests/fmcsim_numpy.py) under the fp32
 summation bound, the accumulation contract of include/rtus.h by bits, and the model closing the loop with the imaging side:
-simulate_views -> tfm_views reads a unit scatterer as 1, simulate_echoes -> pick_echo_times -> fit_pipe recovers the geometry."""
+simulate_views -> tfm_views reads a unit scatterer as 1, simulate_echoes -> pick_echo_times -> fit_pipe recovers the geometry.
+The tests under "a wavelet that is not small anywhere" use a random table (|p| in [0.5, 1.5]) and arrivals about the ends of the
+record, of the table and of the 1024-sample tiles, where a Gaussian pulse's 1e-8 tails would hide a sample or an entry off by one."""
 from importlib import import_module
 
 import numpy as np
@@ -126,6 +128,178 @@ def test_echo_form_against_the_oracle(rtus, n_a, with_amp):
         ref, touched, sa = S.simulate_echo(t_pair, amp, pulse, centre, 8, FS, -0.2e-6, n_t)
         assert not touched[2, 3].any()
         _compare(got, ref, touched, sa, n_a, pulse, f"echo form n_a {n_a} amp {with_amp} analytic {analytic}")
+
+
+# ---------------------------------------------------------------------------------------------- a wavelet that is not small anywhere
+T0 = 0.3e-6
+SWEEP = 3 * np.arange(2)[:, None] + np.arange(3)[None, :]                       # 2 x 3 pairs: six table steps in a row
+
+
+def _teeth(t_pair, amp, touched, sa, n, pulse, centre, oversample, n_t, label, t0=T0):
+    """on the reference alone: every arrival that counts marks its first and its last sample in ``touched``, and its own term at
+    each of the two is at least 100 times the bound _compare grants that A-scan, so that a sample left out or a table entry off by
+    one cannot pass.  The first and last samples come from scan_by_definition, whose touched samples must be the oracle's.
+    -> {(tx, rx, k): (first, last)}"""
+    unit = (n + 16) * 2.0 ** -23 * float(np.abs(pulse).max())
+    least, ends = np.inf, {}
+    for i, j in np.ndindex(t_pair.shape[:2]):
+        edges = []
+        _, by_def, sa_def = S.scan_by_definition(t_pair[i, j], None if amp is None else amp[i, j], pulse, centre, oversample, FS, t0, n_t,
+                                                 edges=edges)
+        assert np.array_equal(by_def, touched[i, j]) and abs(sa_def - sa[i, j]) <= 1e-12 * sa_def, (label, i, j)
+        for k, first, last, c_first, c_last in edges:
+            assert touched[i, j, first] and touched[i, j, last], (label, i, j, k)
+            least = min(least, min(c_first, c_last) / (unit * sa[i, j]))
+            ends[i, j, k] = (first, last)
+    print(f"{label}: {len(ends)} arrivals count, least edge term / bound {least:.0f}")
+    assert ends and least >= 100.0, label
+    return ends
+
+
+def _as_echoes(tt_tx, tt_rx, q, w_tx, w_rx):
+    """the scatterer form's arrivals, stated per pair (the oracle's own sum and product)"""
+    t_pair = tt_tx[:, None, :] + tt_rx[None, :, :]
+    amp = np.array([[S._product([q, w_tx[i], w_rx[j]], q.size) for j in range(tt_rx.shape[0])] for i in range(tt_tx.shape[0])])
+    return t_pair, amp
+
+
+def _edge_run(rtus, n_p, centre, oversample, n_t, analytic, scatterers, rng, label):
+    """2 x 3 pairs, seven arrivals each (fmcsim_numpy.edge_steps), pair (tx, rx) 3 tx + rx table steps after pair (0, 0): against
+    the oracle, with teeth -> the arrivals' first and last samples"""
+    pulse = S.random_complex(rng, n_p)
+    k = S.edge_steps(n_p, centre, oversample, n_t)
+    kw = dict(fs=FS, n_t=n_t, pulse=pulse, centre=centre, oversample=oversample, t0=T0, analytic=analytic)
+    if scatterers:                                                              # tau = tt_tx + tt_rx, a = (q w_tx) w_rx
+        step = 1.0 / (FS * oversample)
+        tt_tx = S.times_at(k[None, :] + 3 * np.arange(2)[:, None], rng, FS, oversample, T0) - 1.0e-6
+        tt_rx = 1.0e-6 + np.arange(3)[:, None] * step + np.zeros((1, 7))
+        q, w_tx, w_rx = S.random_complex(rng, 7), S.random_complex(rng, (2, 7)), S.random_complex(rng, (3, 7))
+        got = rtus.simulate_fmc(tt_tx, tt_rx, strength=q, w_tx=w_tx, w_rx=w_rx, **kw)
+        ref, touched, sa = S.simulate(tt_tx, tt_rx, pulse, centre, oversample, FS, T0, n_t, q=q, w_tx=w_tx, w_rx=w_rx)
+        t_pair, amp = _as_echoes(tt_tx, tt_rx, q, w_tx, w_rx)
+    else:
+        t_pair = S.times_at(k[None, None, :] + SWEEP[:, :, None], rng, FS, oversample, T0)
+        amp = S.random_complex(rng, t_pair.shape)
+        got = rtus.simulate_echoes(t_pair, amp, **kw)
+        ref, touched, sa = S.simulate_echo(t_pair, amp, pulse, centre, oversample, FS, T0, n_t)
+    ends = _teeth(t_pair, amp, touched, sa, 7, pulse, centre, oversample, n_t, label)
+    _compare(got, ref, touched, sa, 7, pulse, label)
+    return ends
+
+
+@pytest.mark.parametrize("analytic", [False, True])
+@pytest.mark.parametrize("oversample", [2, 3, 5, 7])
+def test_wavelet_edges_and_odd_oversampling(rtus, oversample, analytic):
+    """oversamplings that are no power of two, table lengths os + 1, 3 os - 1 (no multiple of os, nor one more) and 37, time zero at
+    either end of the table and in the middle.  Across the six A-scans sample 0 reads the table at every i0 from os down to -1 and
+    on into pulses that start inside; sample n_t - 1 reads every i from n_p (just missed) down to n_p - 11; one pulse is wholly
+    inside; before and after the record the arrivals move from writing nothing to writing one sample."""
+    os_, n_t = oversample, 300
+    rng = np.random.default_rng(500 + 10 * os_ + analytic)
+    for form, n_p in enumerate((os_ + 1, 3 * os_ - 1, 37)):
+        for centre in (0, n_p // 2, n_p - 1):
+            ends = _edge_run(rtus, n_p, centre, os_, n_t, analytic, form != 1, rng,
+                             f"edges os {os_} n_p {n_p} centre {centre} {'echo' if form == 1 else 'scatterer'} form analytic {analytic}")
+            # what the placement promises, on the reference: per run the six A-scans' arrivals are one table step apart
+            cut0 = [ends[i, j, k] for i in range(2) for j in range(3) for k in (0, 1) if (i, j, k) in ends]
+            cut1 = [ends[i, j, k] for i in range(2) for j in range(3) for k in (2, 3) if (i, j, k) in ends]
+            assert sum(f == 0 for f, _ in cut0) >= os_ + 1 and sum(la == n_t - 1 for _, la in cut1) >= os_ + 1
+            assert all(0 < ends[i, j, 4][0] and ends[i, j, 4][1] < n_t - 1 for i in range(2) for j in range(3))
+            before = [(i, j, 5) in ends for i in range(2) for j in range(3)]     # pair (0, 0) first: three silent, then sample 0
+            after = [(i, j, 6) in ends for i in range(2) for j in range(3)]      # up to sample n_t - 1, then two silent
+            assert before == [False] * 3 + [True] * 3 and ends[1, 0, 5] == (0, 0)
+            assert after == [True] * 4 + [False] * 2 and ends[1, 0, 6] == (n_t - 1, n_t - 1)
+
+
+@pytest.mark.parametrize("n_p,oversample", [(1, 1), (2, 1), (1, 3), (2, 3)])
+def test_shortest_wavelets(rtus, n_p, oversample):
+    """one or two table entries, time zero at the first: an arrival spans n_p + 1 table steps, so it touches n_p + 1 samples at
+    oversample 1 and one at most at oversample 3, and but for the middle one of three every sample reads a padded entry,
+    p[-1] = 0 or p[n_p] = 0"""
+    rng = np.random.default_rng(600 + 10 * n_p + oversample)
+    for analytic in (False, True):
+        for scatterers in (False, True):
+            ends = _edge_run(rtus, n_p, 0, oversample, 300, analytic, scatterers, rng,
+                             f"shortest n_p {n_p} os {oversample} analytic {analytic} scatterer form {scatterers}")
+            assert max(la - f for f, la in ends.values()) == n_p // oversample   # (n_p + 1 table steps hold n_p // os + 1 samples)
+
+
+def _seam_case(n_t, rng, n_p=200, centre=100, os_=8):
+    """3 x 3 pairs, seven arrivals each, pair (tx, rx) p = 3 tx + rx table steps after pair (0, 0); an arrival at table step k is
+    touched in the samples j with k - centre <= 8 j <= k - centre + n_p, about 25 of them around k / 8"""
+    p = 3 * np.arange(3)[:, None] + np.arange(3)[None, :]
+    k = np.stack([8187 + p,                                                     # 0: centred at sample 1023.4 .. 1024.5
+                  8189 + p,                                                     # 1: about 1024.0
+                  16377 + p,                                                    # 2: centred at 2047.6 (1 and 2: not at all n_t)
+                  8084 + p % 8,                                                 # 3: 8184 <= k + 100 <= 8191: its last sample is 1023
+                  8285 + p % 8,                                                 # 4: 8185 <= k - 100 <= 8192: its first sample is 1024
+                  8 * (n_t - 1) - 4 + p,                                        # 5: centred about the last sample: cut by the record's end
+                  centre - n_p - 1 - p], axis=-1)                               # 6: before the record (p = 0: just)
+    return S.random_complex(rng, n_p), S.times_at(k, rng, FS, os_, T0), S.random_complex(rng, k.shape)
+
+
+@pytest.mark.parametrize("analytic", [False, True])
+@pytest.mark.parametrize("n_t", [1024, 1025, 2047, 2049, 2500])
+def test_tile_seams(rtus, n_t, analytic):
+    """one wave owns 1024 samples: pulses astride the seams at 1024 and 2048, one whose last sample is 1023 and one whose first is
+    1024, last tiles of 1, 452, 1023 and 1024 samples, and with 3 x 3 pairs and an odd n_t the real A-scans at every 16-byte phase.
+    Then the accumulate contract by bits where the last tile is one sample."""
+    n_p, centre, os_ = 200, 100, 8
+    pulse, t_pair, amp = _seam_case(n_t, np.random.default_rng(700 + n_t))
+    kw = dict(fs=FS, n_t=n_t, pulse=pulse, centre=centre, oversample=os_, t0=T0, analytic=analytic)
+    label = f"seams n_t {n_t} analytic {analytic}"
+    got = rtus.simulate_echoes(t_pair, amp, **kw)
+    ref, touched, sa = S.simulate_echo(t_pair, amp, pulse, centre, os_, FS, T0, n_t)
+    ends = _teeth(t_pair, amp, touched, sa, 7, pulse, centre, os_, n_t, label)
+    for i, j in np.ndindex(3, 3):
+        assert ends[i, j, 0][0] < 1023 and ends[i, j, 3][1] == 1023 and (i, j, 6) not in ends
+        assert ends[i, j, 5][1] == n_t - 1 and ends[i, j, 5][0] < n_t - 1
+        if n_t > 1024:
+            assert ends[i, j, 0][1] >= 1024 and ends[i, j, 1][0] < 1024 <= ends[i, j, 1][1] and ends[i, j, 4][0] == 1024
+        if n_t > 2048:
+            assert ends[i, j, 2][0] < 2047 and ends[i, j, 2][1] >= 2048
+    _compare(got, ref, touched, sa, 7, pulse, label)
+    if n_t in (1025, 2049):                                                     # sim_copy<false> on a one-sample last tile
+        part = rtus.simulate_echoes(t_pair[:, :, :3], amp[:, :, :3], **kw)
+        both = rtus.simulate_echoes(t_pair[:, :, 3:], amp[:, :, 3:], accumulate=True, out=part, **kw)
+        assert both is part and np.array_equal(_bits(both), _bits(got))
+
+
+@pytest.mark.parametrize("oversample", [1, 8])
+def test_largest_wavelet(rtus, oversample):
+    """n_p + oversample = 2048, the most the header admits: 32 KB of table and four 8 KB analytic tiles, 64 KB of LDS.  2 x 2 pairs,
+    four arrivals each: cut by the record's start, by its end, one more (inside at oversample 8; at oversample 1, where the pulse is
+    longer than the record, cut by both ends), and one that ends in the first few samples.  One entry more is refused before any launch."""
+    os_, n_t = oversample, 1500
+    n_p = 2048 - os_
+    centre = n_p // 2
+    rng = np.random.default_rng(800 + os_)
+    pulse = S.random_complex(rng, n_p)
+    p = 2 * np.arange(2)[:, None] + np.arange(2)[None, :]
+    starts = [-600, 700, -200, 3 - n_p] if os_ == 1 else [-100, 1400, 500, 3 - n_p // 8]      # first sample of the pulse
+    k = np.stack([centre + os_ * s + p for s in starts], axis=-1)
+    t_pair, amp = S.times_at(k, rng, FS, os_, T0), S.random_complex(rng, k.shape)
+    kw = dict(fs=FS, n_t=n_t, pulse=pulse, centre=centre, oversample=os_, t0=T0, analytic=True)
+    got = rtus.simulate_echoes(t_pair, amp, **kw)
+    ref, touched, sa = S.simulate_echo(t_pair, amp, pulse, centre, os_, FS, T0, n_t)
+    label = f"largest wavelet n_p {n_p} os {os_}"
+    ends = _teeth(t_pair, amp, touched, sa, 4, pulse, centre, os_, n_t, label)
+    for i, j in np.ndindex(2, 2):
+        assert ends[i, j, 0][0] == 0 and ends[i, j, 0][1] < n_t - 1 and ends[i, j, 1][0] > 0 and ends[i, j, 1][1] == n_t - 1
+        assert ends[i, j, 3][0] == 0 and ends[i, j, 3][1] < 8
+    _compare(got, ref, touched, sa, 4, pulse, label)
+    if os_ == 1:
+        import torch
+        dev = import_module("ray-tracing-ultrasound_amd.device")
+        longer = np.concatenate([pulse, pulse[:1]])                             # n_p = 2048
+        with pytest.raises(ValueError):
+            rtus.simulate_echoes(t_pair, amp, **dict(kw, pulse=longer))
+        d_pulse = torch.view_as_real(torch.from_numpy(longer)).contiguous().cuda()
+        out = torch.full((2, 2, n_t, 2), float("nan"), dtype=torch.float32, device="cuda")
+        with pytest.raises(rtus.RtusError) as ei:
+            dev.fmc_sim_echo_dev(torch.from_numpy(t_pair).cuda(), None, out=out, **dict(kw, pulse=d_pulse))
+        torch.cuda.synchronize()
+        assert ei.value.status == -5 and bool(torch.isnan(out).all())           # refused, and nothing was launched
 
 
 # ---------------------------------------------------------------------------------------------- the contract, by bits
@@ -329,3 +503,25 @@ def test_production_shape(rtus):
     i, j = np.array(pairs).T
     assert touched[i, j].any()
     _compare(got[i, j], ref[i, j], touched[i, j], sa[i, j], 4096, pulse, "production shape, 200 A-scans")
+    # The bound above, n = 4096, is about twice one arrival's |a|: it cannot see one arrival dropped.  So the 8 scatterers that
+    # arrive nearest to sample 1024 of pair (0, 0), alone, under the n = 8 bound: first with the same t0, then at the seam of the
+    # two tiles.  With this t0 every arrival of the FMC lies in samples 75 .. 440 (measured on MI355X; pair (0, 0): 245 .. 313),
+    # so the first comparison has silence at the seam; in the second t0 is moved by whole samples until the median arrival of the
+    # 200 A-scans is sample 1024, and the reference itself says that the seam is loud there.
+    near = np.sort(np.argsort(np.abs((2 * tt[0] - t0) * FS - 1024.0), kind="stable")[:8])
+    tt8, q8 = np.ascontiguousarray(tt[:, near]), q[near]
+    at_sample = (tt8[i] + tt8[j] - t0) * FS                                     # [200, 8]
+    t0_seam = t0 + (int(round(float(np.median(at_sample)))) - 1024) / FS
+    for t0_8, label in ((t0, "the same t0"), (t0_seam, "t0 moved: the median arrival at sample 1024")):
+        got8 = rtus.simulate_fmc(tt8, strength=q8, analytic=True, fs=FS, n_t=n_t, t0=t0_8, pulse=pulse, centre=centre, oversample=8)
+        ref8, touched8, sa8 = S.simulate(tt8, tt8, pulse, centre, 8, FS, t0_8, n_t, q=q8, pairs=pairs)
+        assert got8.shape == (64, 64, n_t) and touched8[i, j].any(axis=-1).all()
+        _compare(got8[i, j], ref8[i, j], touched8[i, j], sa8[i, j], 8, pulse, f"production shape, 8 scatterers, {label}, whole A-scans")
+        _compare(got8[i, j, 1000:1051], ref8[i, j, 1000:1051], touched8[i, j, 1000:1051], sa8[i, j], 8, pulse,
+                 f"production shape, 8 scatterers, {label}, samples 1000..1050")
+    tol8 = 24 * 2.0 ** -23 * float(np.abs(pulse).max()) * sa8[i, j]
+    loud = np.minimum(np.abs(ref8[i, j, 1023]), np.abs(ref8[i, j, 1024])) >= 100.0 * tol8
+    print(f"A-scans whose samples 1023 and 1024 are both at least 100 times the bound: {int(loud.sum())} of {len(pairs)}")
+    # (the arrival sample of an A-scan is about a sum of two terms, one per element, each spread evenly over some 64 samples: within
+    # 37 samples of the median, where a pulse of sigma 10.6 samples is still above 2e-3 of its peak, lie some 80 % of the A-scans)
+    assert loud.sum() >= 50
