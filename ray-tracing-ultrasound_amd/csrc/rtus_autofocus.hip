@@ -5,11 +5,12 @@
 //
 //   * rtus_analytic_kernel: one workgroup = RTUS_ANA_TILE samples of one A-scan plus the filter's halo in LDS; streams the FMC
 //     (4 B in, 8 B out per sample) -> HBM roofline, a small share of the chain.
-//   * rtus_surface_find_kernel: the rtus_tfm gather loop on complex samples, with straight-ray delays formed in the kernel instead
-//     of read from a table: 16 B of L2 traffic per (pair, pixel).  The roof is the L2 gather rate, as for rtus_tfm.
+//   * rtus_surface_find_kernel: the delay-and-sum core of rtus_das.h on complex samples, with straight-ray delays formed in the
+//     kernel instead of read from a table: 16 B of L2 traffic per (pair, pixel).  The roof is the L2 gather rate, as for rtus_tfm
+//     (DESIGN §4).
 //   * rtus_echo_pick_kernel: one wave = one A-scan, lanes over the samples of its gate, 16-byte loads, a cross-lane arg-max that
 //     keeps the first index; streams the gated part of the analytic FMC once -> HBM roofline.
-#include "rtus_device.h"
+#include "rtus_das.h"
 
 // ---------------------------------------------------------------------------------------------- analytic FMC
 // out[pair][n] = (x[n], sum_m h[m] x[n - m]).  h is odd-symmetric and zero at even m, so the sum is
@@ -69,10 +70,8 @@ hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t
 //
 // One workgroup = one column, lanes over depths (n_z > 256: the workgroup walks the column in chunks of 256).  Each element's
 // half of the sample position (fp64, rounded once to fp32, as rtus_tfm's tfm_tau) sits in LDS for a tile of RTUS_SF_TILE
-// elements; sixteen receive elements per trip, all sixteen 16-byte gathers issued before the first is used (rtus_tfm's reasoning:
-// a 256-column image is one wave per SIMD, and only the wave's own loads hide the gather latency).
+// elements; the workgroup order (here: of the columns), the 16-byte loads and the gather loop are rtus_das.h's.
 #define RTUS_SF_TILE 64
-#define RTUS_SF_GROUP 16
 #define RTUS_SF_MAX_Z 1024
 
 struct SfArgs {
@@ -89,15 +88,7 @@ struct SfArgs {
 __device__ __forceinline__ float sf_tau(double xe, double ze, double px, double pz, double c1, double fs, double half_t0s)
 {
     const double ux = xe - px, uz = ze - pz;
-    const float v = (float)(sqrt(ux * ux + uz * uz) / c1 * fs - half_t0s);
-    return fabsf(v) < 1.0e8f ? v : -1.0e8f;                  // (positions are finite; absurd ones read nothing)
-}
-
-__device__ __forceinline__ void sf_accum(sf_u32x4 v, float w, float& re, float& im)
-{
-    const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
-    re += fmaf(w, r1 - r0, r0);
-    im += fmaf(w, i1 - i0, i0);
+    return das_clamp((float)(sqrt(ux * ux + uz * uz) / c1 * fs - half_t0s));   // (positions are finite; absurd ones read nothing)
 }
 
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_surface_find_kernel(SfArgs a)
@@ -106,10 +97,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_surface_find_kernel(SfArgs a)
     __shared__ float col[RTUS_SF_MAX_Z];                     // the column's amplitudes, for the parabolic step
     __shared__ float red_v[RTUS_BLOCK];
     __shared__ int red_i[RTUS_BLOCK];
-    // XCD k takes a contiguous share of the columns: neighbouring columns read the same sample windows (rtus_tfm_kernel)
-    const int nblk = gridDim.x, per = (nblk + 7) >> 3;
-    int k = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (nblk & 7) k = blockIdx.x;
+    const int k = das_workgroup();                           // neighbouring columns read the same sample windows
     const int t = threadIdx.x;
     const double px = a.x0 + k * a.dx;
     const size_t pair_len = (size_t)a.n_t * 2;               // floats per analytic A-scan
@@ -130,26 +118,12 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_surface_find_kernel(SfArgs a)
             __syncthreads();
             for (int tx = 0; tx < a.n_e; ++tx) {
                 const float tt = tx_in_tile ? tau[tx][t] : sf_tau(a.xe[tx], a.ze[tx], px, pz, a.c1, a.fs, a.half_t0s);
-                const float* rec = a.a + ((size_t)tx * a.n_e + r0) * pair_len;   // wave-uniform
-                int r = 0;
-                for (; r + RTUS_SF_GROUP <= nr; r += RTUS_SF_GROUP) {
-                    sf_u32x4 v[RTUS_SF_GROUP];
-                    float w[RTUS_SF_GROUP];
-#pragma unroll
-                    for (int q = 0; q < RTUS_SF_GROUP; ++q) {
-                        const float s = tt + tau[r + q][t];
-                        const float fl = floorf(s);
-                        w[q] = s - fl;
-                        v[q] = sf_load2(rec + (size_t)(r + q) * pair_len, a.n_t, (int)fl);
-                    }
-#pragma unroll
-                    for (int q = 0; q < RTUS_SF_GROUP; ++q) sf_accum(v[q], w[q], re, im);
-                }
-                for (; r < nr; ++r) {                        // receive elements past the last full group
-                    const float s = tt + tau[r][t];
-                    const float fl = floorf(s);
-                    sf_accum(sf_load2(rec + (size_t)r * pair_len, a.n_t, (int)fl), s - fl, re, im);
-                }
+                das_gather<2>(a.a + ((size_t)tx * a.n_e + r0) * pair_len, pair_len, a.n_t, tt, tau, t, nr,
+                              [&](int, das_u32x4 v, float w) {
+                                  const float2 p = das_lerp(v, w);
+                                  re += p.x;
+                                  im += p.y;
+                              });
             }
         }
         const float A = sqrtf(re * re + im * im);

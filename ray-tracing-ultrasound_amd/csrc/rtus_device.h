@@ -93,17 +93,6 @@ __device__ __forceinline__ double dist2d(double x1, double z1, double x2, double
     return rtus_sqrt(dx * dx + dz * dz);
 }
 
-// Two neighbouring complex samples i, i + 1 of one analytic A-scan (wave-uniform base) in one 16-byte load; the descriptor's range
-// check zeroes what lies outside the record.  Negative indices are clamped to one that is out of range with all four dwords (as
-// unsigned they are >= 2^31; times 8 they would wrap): |i| < 2^28 (each leg is clamped to +-1e8 samples), n_t <= 2^26.
-// Shared by rtus_surface_find_kernel and rtus_tfm_analytic_kernel.
-typedef unsigned int sf_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ sf_u32x4 sf_load2(const float* rec, int n_t, int i)
-{
-    const __amdgpu_buffer_rsrc_t q = __builtin_amdgcn_make_buffer_rsrc((void*)rec, 0, (unsigned)n_t * 8u, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b128(q, min((unsigned)i, 0x1ffffff0u) * 8u, 0, 0);
-}
-
 // np.isclose(a, b, rtol, atol) for scalars, equal_nan=False.
 __device__ __forceinline__ bool np_isclose(double a, double b, double rtol, double atol)
 {

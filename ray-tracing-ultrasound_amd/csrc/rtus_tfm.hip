@@ -10,7 +10,7 @@
 //     8 B of L2 traffic per pair and focal point.  The FMC block (n_tx n_rx n_t 4 B: 34 MB at 64 x 64 x 2048) is read
 //     from HBM about once per launch and then lives in L2 / Infinity Cache, so the bound is the L2 gather rate
 //     (MI355X_MICROARCH.md "Indexed rows": 17-19 TB/s chip-wide for rows shared by every workgroup), not HBM.
-#include "rtus_device.h"
+#include "rtus_das.h"
 
 // ---------------------------------------------------------------------------------------------- focal laws
 // delays[e][f] = max_e' tt[e'][f] - tt[e][f]: what element e must wait so that all wavefronts reach f together.
@@ -93,13 +93,10 @@ hipError_t rtus_launch_focal_delays(const double* tt, int n_e, int n_f, double* 
 // (tt_tx[tx][f] + tt_rx[rx][f] - t0) fs.  Samples outside the record count as zero; pairs without a ray path (NaN
 // travel time) contribute nothing.
 //
-// One workgroup = 256 focal points.  The receive delays (in samples, fp32) of a tile of RX_TILE elements sit in LDS,
-// lane-major (lane l reads tau[rx][l]: conflict-free); the transmit delay of the current tx is a register.  The
-// A-scan of a pair is addressed through a buffer descriptor whose base is wave-uniform (SGPRs) and whose extent is
-// the record: the hardware's range check returns 0 for a sample index outside [0, n_t) — no compare / select in the
-// inner loop — and the two neighbouring samples come in one 8-byte load.
+// One workgroup = 256 focal points, a receive tile of RTUS_TFM_RX_TILE elements' delays in LDS, 8 bytes gathered per pair and
+// focal point: the delay-and-sum core of rtus_das.h, where the workgroup order, the loads' edge rules and the gather loop are
+// described.
 #define RTUS_TFM_RX_TILE 64
-typedef unsigned int tfm_u32x2 __attribute__((ext_vector_type(2)));
 
 struct TfmArgs {
     const float* __restrict__ fmc;       // [n_tx][n_rx][n_t]
@@ -111,41 +108,28 @@ struct TfmArgs {
     double half_t0s;                     // t0 * fs / 2: each of the pair's two delays carries half of the time origin
 };
 
-__device__ __forceinline__ float tfm_tau(double t, double fs, double half_t0s)
+// what TfmArgs, TfmaArgs and TfmwArgs have in common (the fields above but image), filled once
+template <class Args>
+static Args tfm_args(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f)
 {
-    // travel time -> half of the pair's sample position (formed in fp64, rounded once: 1e-4 of a sample at 4096
-    // samples); no path -> far outside every record (finite: the sum of two of them must not become NaN or wrap an
-    // integer conversion)
-    // (... and so does every non-finite or absurd time: +inf would pass a NaN test and poison the pixel through floor(inf))
-    const float v = (float)(t * fs - half_t0s);
-    return fabsf(v) < 1.0e8f ? v : -1.0e8f;                  // NaN fails the compare
+    Args a;
+    a.fmc = fmc; a.tt_tx = tt_tx; a.tt_rx = tt_rx;
+    a.n_tx = n_tx; a.n_rx = n_rx; a.n_t = n_t; a.n_f = n_f;
+    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    return a;
 }
 
-// Two neighbouring samples i, i + 1 of one A-scan (wave-uniform base) in one 8-byte load; an index outside the record
-// (negative, huge, the no-path sentinel) is dropped by the descriptor's range check and reads as zeros.
-#define RTUS_TFM_GROUP 16
-// Edges, as oracle/tfm_numpy.py defines them: a position in [n_t - 1, n_t) interpolates towards a zero sample n_t (the second
-// dword of the load is out of range by itself); a NEGATIVE position contributes nothing — index -1 must not wrap: its second
-// dword would sit at byte offset 2^32, which the range check sees as 0 — so negative indices (as unsigned: >= 2^31) are
-// clamped to one that is out of range with both dwords.  |i| stays below 2^30 (tfm_tau clamps to +-1e8 samples).
-__device__ __forceinline__ tfm_u32x2 tfm_load2(const float* rec, int n_t, int i)
-{
-    const __amdgpu_buffer_rsrc_t q = __builtin_amdgcn_make_buffer_rsrc((void*)rec, 0, (unsigned)n_t * 4u, 0x00020000);
-    return __builtin_amdgcn_raw_buffer_load_b64(q, min((unsigned)i, 0x3ffffff0u) * 4u, 0, 0);
-}
+// travel time -> half of the pair's sample position (formed in fp64, rounded once); no path, a non-finite or an absurd time ->
+// RTUS_DAS_NO_PATH
+__device__ __forceinline__ float tfm_tau(double t, double fs, double half_t0s) { return das_clamp((float)(t * fs - half_t0s)); }
+
+__device__ __forceinline__ int tfm_has_path(float tau) { return tau > RTUS_DAS_NO_PATH; }   // a path's |tau| < 1e8
 
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_kernel(TfmArgs a)
 {
     __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB: 2 workgroups per CU; a 64-element receive
                                                                       // aperture is ONE tile: the transmit delays are read once
-    // Workgroups go to the 8 XCDs round-robin, and each XCD has its own 4 MiB L2: with workgroup b on focal points
-    // [256 b, 256 b + 256) every XCD sees focal points from all over the image and pulls (its window of) the WHOLE FMC block
-    // through its L2.  XCD k takes a contiguous eighth of the focal points instead — neighbouring focal points share their
-    // sample windows — so the FMC block is fetched about once, not once per XCD (measured: profiles/traffic_r03.json).
-    const int nblk = gridDim.x, per = (nblk + 7) >> 3;
-    int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (nblk & 7) blk = blockIdx.x;                                   // (ragged grids keep the plain order)
-    const int f_raw = blk * RTUS_BLOCK + threadIdx.x;
+    const int f_raw = das_workgroup() * RTUS_BLOCK + threadIdx.x;
     const bool live = f_raw < a.n_f;
     const int f = live ? f_raw : a.n_f - 1;
     const size_t nf = (size_t)a.n_f;
@@ -155,40 +139,12 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_kernel(TfmArgs a)
         __syncthreads();                                              // the previous tile is no longer read
         for (int r = 0; r < nr; ++r) tau_rx[r][threadIdx.x] = tfm_tau(a.tt_rx[(size_t)(r0 + r) * nf + f], a.fs, a.half_t0s);
         __syncthreads();
-        // Sixteen receive elements per trip: 16 independent gathers in flight per lane, ALL issued before the first is
-        // consumed (two explicit phases: left to itself the scheduler pairs each load with its use).  An image of
-        // 256 x 256 focal points is 1024 waves — one per SIMD — so nothing but the wave's own loads hides the ~1 us a
-        // gather takes: 4 in flight 441 us, 8: 282 us, 16: 214 us (192 us with the whole receive aperture in one tile), 32 (two
-        // transmit elements at once): 218 us — from 16 on
-        // the vector-memory address path binds (64 scattered 8-byte requests per wave-instruction, ~27 cycles each per CU).
         // one table for both legs and the whole receive aperture in this tile: the transmit delay IS a row of the tile
         const bool tx_in_tile = a.tt_tx == a.tt_rx && a.n_tx == a.n_rx && a.n_rx <= RTUS_TFM_RX_TILE;
         for (int tx = 0; tx < a.n_tx; ++tx) {
             const float tt = tx_in_tile ? tau_rx[tx][threadIdx.x] : tfm_tau(a.tt_tx[(size_t)tx * nf + f], a.fs, a.half_t0s);
-            const float* rec = a.fmc + ((size_t)tx * a.n_rx + r0) * (size_t)a.n_t;   // wave-uniform
-            int r = 0;
-            for (; r + RTUS_TFM_GROUP <= nr; r += RTUS_TFM_GROUP) {
-                tfm_u32x2 v[RTUS_TFM_GROUP];
-                float w[RTUS_TFM_GROUP];
-#pragma unroll
-                for (int k = 0; k < RTUS_TFM_GROUP; ++k) {
-                    const float s = tt + tau_rx[r + k][threadIdx.x];
-                    const float fl = floorf(s);
-                    w[k] = s - fl;
-                    v[k] = tfm_load2(rec + (size_t)(r + k) * a.n_t, a.n_t, (int)fl);
-                }
-#pragma unroll
-                for (int k = 0; k < RTUS_TFM_GROUP; ++k) {
-                    const float v0 = __uint_as_float(v[k].x), v1 = __uint_as_float(v[k].y);
-                    acc += fmaf(w[k], v1 - v0, v0);
-                }
-            }
-            for (; r < nr; ++r) {                                     // receive elements past the last full group
-                const float s = tt + tau_rx[r][threadIdx.x];
-                const float fl = floorf(s);
-                const tfm_u32x2 v = tfm_load2(rec + (size_t)r * a.n_t, a.n_t, (int)fl);
-                acc += fmaf(s - fl, __uint_as_float(v.y) - __uint_as_float(v.x), __uint_as_float(v.x));
-            }
+            das_gather<1>(a.fmc + ((size_t)tx * a.n_rx + r0) * (size_t)a.n_t, (size_t)a.n_t, a.n_t, tt, tau_rx, threadIdx.x, nr,
+                          [&](int, das_u32x2 v, float w) { acc += das_lerp(v, w); });
         }
     }
     if (live) a.image[f] = acc;
@@ -197,26 +153,20 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_kernel(TfmArgs a)
 hipError_t rtus_launch_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                            const double* tt_rx, int n_f, float* image, hipStream_t s)
 {
-    TfmArgs a;
-    a.fmc = fmc; a.tt_tx = tt_tx; a.tt_rx = tt_rx; a.image = image;
-    a.n_tx = n_tx; a.n_rx = n_rx; a.n_t = n_t; a.n_f = n_f;
-    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    TfmArgs a = tfm_args<TfmArgs>(fmc, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f);
+    a.image = image;
     hipLaunchKernelGGL(rtus_tfm_kernel, dim3((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), dim3(RTUS_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------- envelope TFM + coherence factor
 // The same delay-and-sum over an analytic (complex) FMC: S[f] = sum over (tx, rx) of a[tx][rx] at rtus_tfm's sample position, real
-// and imaginary parts interpolated separately with rtus_tfm's arithmetic, edge rules and order — so S.re is rtus_tfm on the real
-// parts and S.im rtus_tfm on the imaginary parts, bit for bit.  With CF, also E[f] = sum over the pairs of |a(s)|^2 and
-// N[f] = T[f] R[f], the legs with a path counted while the delays are formed (none of it in the gather loop but two FMAs);
-// cf = |S|^2 / (N E) in fp64.  Definition: include/rtus.h (rtus_tfm_analytic).
-//
-// rtus_tfm_kernel's structure (256 focal points per workgroup, the XCD-contiguous order, the 64-element receive tile in LDS,
-// sixteen gathers in flight per lane) with rtus_surface_find_kernel's 16-byte gathers: two neighbouring complex samples in one
-// range-checked buffer load, 16 B of L2 traffic per (pair, focal point).
+// and imaginary parts interpolated separately with rtus_tfm's arithmetic, edge rules and order — so S.re is
+// rtus_tfm on the real parts and S.im rtus_tfm on the imaginary parts, bit for bit.  With CF, also E[f] = sum over the pairs of
+// |a(s)|^2 and N[f] = T[f] R[f], the legs with a path counted while the delays are formed (none of it in the gather loop but two
+// FMAs); cf = |S|^2 / (N E) in fp64.  Definition: include/rtus.h (rtus_tfm_analytic).  16 B of L2 traffic per (pair, focal point).
 struct TfmaArgs {
-    const float* __restrict__ a;         // [n_tx][n_rx][n_t][2]
+    const float* __restrict__ fmc;       // [n_tx][n_rx][n_t][2]
     const double* __restrict__ tt_tx;    // [n_tx][n_f]
     const double* __restrict__ tt_rx;    // [n_rx][n_f]
     float2* __restrict__ image;          // [n_f]
@@ -225,26 +175,11 @@ struct TfmaArgs {
     double fs, half_t0s;
 };
 
-__device__ __forceinline__ int tfm_has_path(float tau) { return tau > -1.0e8f; }   // tfm_tau's no-path value is -1e8, a path's |tau| < 1e8
-
-template <bool CF>
-__device__ __forceinline__ void tfma_accum(sf_u32x4 v, float w, float& re, float& im, float& en)
-{
-    const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
-    const float pr = fmaf(w, r1 - r0, r0), pi = fmaf(w, i1 - i0, i0);
-    re += pr;
-    im += pi;
-    if (CF) en = fmaf(pi, pi, fmaf(pr, pr, en));
-}
-
 template <bool CF>
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs a)
 {
     __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB, as rtus_tfm_kernel
-    const int nblk = gridDim.x, per = (nblk + 7) >> 3;                // XCD k takes a contiguous share (rtus_tfm_kernel)
-    int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (nblk & 7) blk = blockIdx.x;
-    const int f_raw = blk * RTUS_BLOCK + threadIdx.x;
+    const int f_raw = das_workgroup() * RTUS_BLOCK + threadIdx.x;
     const bool live = f_raw < a.n_f;
     const int f = live ? f_raw : a.n_f - 1;
     const size_t nf = (size_t)a.n_f;
@@ -264,26 +199,13 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs 
         for (int tx = 0; tx < a.n_tx; ++tx) {
             const float tt = tx_in_tile ? tau_rx[tx][threadIdx.x] : tfm_tau(a.tt_tx[(size_t)tx * nf + f], a.fs, a.half_t0s);
             if (CF && r0 == 0) n_tx_ok += tfm_has_path(tt);
-            const float* rec = a.a + ((size_t)tx * a.n_rx + r0) * pair_len;   // wave-uniform
-            int r = 0;
-            for (; r + RTUS_TFM_GROUP <= nr; r += RTUS_TFM_GROUP) {
-                sf_u32x4 v[RTUS_TFM_GROUP];
-                float w[RTUS_TFM_GROUP];
-#pragma unroll
-                for (int k = 0; k < RTUS_TFM_GROUP; ++k) {           // all sixteen gathers issued before the first is used
-                    const float s = tt + tau_rx[r + k][threadIdx.x];
-                    const float fl = floorf(s);
-                    w[k] = s - fl;
-                    v[k] = sf_load2(rec + (size_t)(r + k) * pair_len, a.n_t, (int)fl);
-                }
-#pragma unroll
-                for (int k = 0; k < RTUS_TFM_GROUP; ++k) tfma_accum<CF>(v[k], w[k], re, im, en);
-            }
-            for (; r < nr; ++r) {                                     // receive elements past the last full group
-                const float s = tt + tau_rx[r][threadIdx.x];
-                const float fl = floorf(s);
-                tfma_accum<CF>(sf_load2(rec + (size_t)r * pair_len, a.n_t, (int)fl), s - fl, re, im, en);
-            }
+            das_gather<2>(a.fmc + ((size_t)tx * a.n_rx + r0) * pair_len, pair_len, a.n_t, tt, tau_rx, threadIdx.x, nr,
+                          [&](int, das_u32x4 v, float w) {
+                              const float2 p = das_lerp(v, w);
+                              re += p.x;
+                              im += p.y;
+                              if (CF) en = fmaf(p.y, p.y, fmaf(p.x, p.x, en));
+                          });
         }
     }
     if (!live) return;
@@ -305,10 +227,8 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs 
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s)
 {
-    TfmaArgs a;
-    a.a = an; a.tt_tx = tt_tx; a.tt_rx = tt_rx; a.image = (float2*)image; a.cf = cf;
-    a.n_tx = n_tx; a.n_rx = n_rx; a.n_t = n_t; a.n_f = n_f;
-    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    TfmaArgs a = tfm_args<TfmaArgs>(an, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f);
+    a.image = (float2*)image; a.cf = cf;
     const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
     if (cf) hipLaunchKernelGGL(rtus_tfm_analytic_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(rtus_tfm_analytic_kernel<false>, grid, block, 0, s, a);
@@ -325,10 +245,10 @@ hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t
 // tile is one group of sixteen gathers in flight per lane; per transmit element the tile's weighted sum goes into a partial that is
 // multiplied by the transmit weight once (4 FMAs per tx and tile, not per pair).  The transmit delay and weight are re-read per tile
 // (16 B per tx and focal point, against 16 x 16 B of gathers).
-#define RTUS_TFMW_RX_TILE 16
+#define RTUS_TFMW_RX_TILE RTUS_DAS_GROUP
 
 struct TfmwArgs {
-    const float* __restrict__ a;         // [n_tx][n_rx][n_t][2]
+    const float* __restrict__ fmc;       // [n_tx][n_rx][n_t][2]
     const double* __restrict__ tt_tx;    // [n_tx][n_f]
     const double* __restrict__ tt_rx;    // [n_rx][n_f]
     const float2* __restrict__ w_tx;     // [n_tx][n_f]
@@ -341,27 +261,16 @@ struct TfmwArgs {
 
 __device__ __forceinline__ bool tfmw_finite(float2 w) { return fabsf(w.x) <= 3.4e38f && fabsf(w.y) <= 3.4e38f; }   // NaN fails
 
-__device__ __forceinline__ void tfmw_accum(sf_u32x4 v, float w, float2 g, float& pr, float& pi)
-{
-    const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
-    const float sr = fmaf(w, r1 - r0, r0), si = fmaf(w, i1 - i0, i0);
-    pr = fmaf(g.x, sr, fmaf(-g.y, si, pr));
-    pi = fmaf(g.x, si, fmaf(g.y, sr, pi));
-}
-
 template <bool SENS>
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_weighted_kernel(TfmwArgs a)
 {
     __shared__ float tau_rx[RTUS_TFMW_RX_TILE][RTUS_BLOCK];           // 16 KiB
     __shared__ float2 wr[RTUS_TFMW_RX_TILE][RTUS_BLOCK];              // 32 KiB
-    const int nblk = gridDim.x, per = (nblk + 7) >> 3;                // XCD k takes a contiguous share (rtus_tfm_kernel)
-    int blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (nblk & 7) blk = blockIdx.x;
-    const int f_raw = blk * RTUS_BLOCK + threadIdx.x;
+    const int f_raw = das_workgroup() * RTUS_BLOCK + threadIdx.x;
     const bool live = f_raw < a.n_f;
     const int f = live ? f_raw : a.n_f - 1;
     const size_t nf = (size_t)a.n_f;
-    const size_t pair_len = (size_t)a.n_t * 2;
+    const size_t pair_len = (size_t)a.n_t * 2;                        // floats per analytic A-scan
     float re = 0.0f, im = 0.0f, ptx = 0.0f, prx = 0.0f;
     for (int r0 = 0; r0 < a.n_rx; r0 += RTUS_TFMW_RX_TILE) {
         const int nr = min(RTUS_TFMW_RX_TILE, a.n_rx - r0);
@@ -371,7 +280,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_weighted_kernel(TfmwArgs 
             const float v = tfm_tau(a.tt_rx[o], a.fs, a.half_t0s);
             const float2 g = a.w_rx[o];
             const bool ok = tfm_has_path(v) && tfmw_finite(g);
-            tau_rx[r][threadIdx.x] = ok ? v : -1.0e8f;                // no path: every position of the pair is negative
+            tau_rx[r][threadIdx.x] = ok ? v : RTUS_DAS_NO_PATH;       // every position of the pair is negative
             wr[r][threadIdx.x] = ok ? g : make_float2(0.0f, 0.0f);
             if (SENS && ok) prx = fmaf(g.y, g.y, fmaf(g.x, g.x, prx));
         }
@@ -381,29 +290,15 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_weighted_kernel(TfmwArgs 
             float tt = tfm_tau(a.tt_tx[o], a.fs, a.half_t0s);
             float2 gt = a.w_tx[o];
             const bool ok = tfm_has_path(tt) && tfmw_finite(gt);
-            if (!ok) { tt = -1.0e8f; gt = make_float2(0.0f, 0.0f); }
+            if (!ok) { tt = RTUS_DAS_NO_PATH; gt = make_float2(0.0f, 0.0f); }
             if (SENS && r0 == 0 && ok) ptx = fmaf(gt.y, gt.y, fmaf(gt.x, gt.x, ptx));
-            const float* rec = a.a + ((size_t)tx * a.n_rx + r0) * pair_len;   // wave-uniform
-            float pr = 0.0f, pi = 0.0f;
-            int r = 0;
-            for (; r + RTUS_TFM_GROUP <= nr; r += RTUS_TFM_GROUP) {
-                sf_u32x4 v[RTUS_TFM_GROUP];
-                float w[RTUS_TFM_GROUP];
-#pragma unroll
-                for (int k = 0; k < RTUS_TFM_GROUP; ++k) {           // all sixteen gathers issued before the first is used
-                    const float s = tt + tau_rx[r + k][threadIdx.x];
-                    const float fl = floorf(s);
-                    w[k] = s - fl;
-                    v[k] = sf_load2(rec + (size_t)(r + k) * pair_len, a.n_t, (int)fl);
-                }
-#pragma unroll
-                for (int k = 0; k < RTUS_TFM_GROUP; ++k) tfmw_accum(v[k], w[k], wr[r + k][threadIdx.x], pr, pi);
-            }
-            for (; r < nr; ++r) {                                     // a ragged last tile
-                const float s = tt + tau_rx[r][threadIdx.x];
-                const float fl = floorf(s);
-                tfmw_accum(sf_load2(rec + (size_t)r * pair_len, a.n_t, (int)fl), s - fl, wr[r][threadIdx.x], pr, pi);
-            }
+            float pr = 0.0f, pi = 0.0f;                               // the tile's sum of w_rx a(s)
+            das_gather<2>(a.fmc + ((size_t)tx * a.n_rx + r0) * pair_len, pair_len, a.n_t, tt, tau_rx, threadIdx.x, nr,
+                          [&](int r, das_u32x4 v, float w) {
+                              const float2 g = wr[r][threadIdx.x], p = das_lerp(v, w);
+                              pr = fmaf(g.x, p.x, fmaf(-g.y, p.y, pr));
+                              pi = fmaf(g.x, p.y, fmaf(g.y, p.x, pi));
+                          });
             re = fmaf(gt.x, pr, fmaf(-gt.y, pi, re));
             im = fmaf(gt.x, pi, fmaf(gt.y, pr, im));
         }
@@ -417,11 +312,8 @@ hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s)
 {
-    TfmwArgs a;
-    a.a = an; a.tt_tx = tt_tx; a.tt_rx = tt_rx; a.w_tx = (const float2*)w_tx; a.w_rx = (const float2*)w_rx;
-    a.image = (float2*)image; a.sens = sens;
-    a.n_tx = n_tx; a.n_rx = n_rx; a.n_t = n_t; a.n_f = n_f;
-    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    TfmwArgs a = tfm_args<TfmwArgs>(an, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f);
+    a.w_tx = (const float2*)w_tx; a.w_rx = (const float2*)w_rx; a.image = (float2*)image; a.sens = sens;
     const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
     if (sens) hipLaunchKernelGGL(rtus_tfm_weighted_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(rtus_tfm_weighted_kernel<false>, grid, block, 0, s, a);

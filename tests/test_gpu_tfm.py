@@ -135,3 +135,42 @@ def test_tfm_record_edges_and_non_finite_times(rtus):
     ref_bad = T.tfm(fmc[keep], fs, t0, tt_tx[keep], tt_rx)
     assert np.isfinite(img_bad).all()
     assert np.max(np.abs(img_bad - ref_bad)) <= 1e-4 * max(1.0, np.max(np.abs(ref_bad)))
+
+
+def test_workgroup_order_does_not_change_the_bits(rtus):
+    """The RF, analytic (+ cf) and weighted (+ sensitivity) kernels share one workgroup order, one load and one gather loop
+    (csrc/rtus_das.h).  2048 focal points are 8 workgroups (the XCD-contiguous order), each half of 1024 is 4 (the plain order):
+    a lane's sum depends on its focal point only, so the full call is the two halves, bit for bit.  Twenty receive elements = one
+    full group of sixteen gathers plus a tail of four.  Tables drawn as test_gpu_tfm_analytic.py's _case draws them: positions
+    crossing both record ends, NaN, absurd (1e3 s) and infinite legs, the last three focal points without any path."""
+    rng = np.random.default_rng(11)
+    n_e, n_t, n_f, fs, t0 = 20, 300, 2048, 40e6, 1.5e-6
+    a = (rng.standard_normal((n_e, n_e, n_t)) + 1j * rng.standard_normal((n_e, n_e, n_t))).astype(np.complex64)
+    lo, hi = (-12 + 0.5 * t0 * fs) / fs, (n_t / 2 + 12 + 0.5 * t0 * fs) / fs
+    tt_tx, tt_rx = rng.uniform(lo, hi, (n_e, n_f)), rng.uniform(lo, hi, (n_e, n_f))
+    for t in (tt_tx, tt_rx):
+        m = rng.random(t.shape)
+        t[m < 0.03] = np.nan
+        t[(m >= 0.03) & (m < 0.035)] = 1e3
+        t[(m >= 0.035) & (m < 0.037)] = -np.inf
+        t[(m >= 0.037) & (m < 0.039)] = np.inf
+    tt_tx[:, -3:] = np.nan
+    w_tx, w_rx = ((rng.standard_normal((n_e, n_f)) + 1j * rng.standard_normal((n_e, n_f))).astype(np.complex64) for _ in range(2))
+    re = np.ascontiguousarray(a.real)
+    half = [slice(0, n_f // 2), slice(n_f // 2, n_f)]
+    cut = lambda x, h: np.ascontiguousarray(x[:, h])
+
+    rf = rtus.tfm_image(re, fs, tt_tx, tt_rx, t0=t0)
+    assert np.array_equal(rf, np.concatenate([rtus.tfm_image(re, fs, cut(tt_tx, h), cut(tt_rx, h), t0=t0) for h in half]))
+
+    img, cf = rtus.tfm_analytic(a, fs, tt_tx, tt_rx, t0=t0, coherence=True)
+    parts = [rtus.tfm_analytic(a, fs, cut(tt_tx, h), cut(tt_rx, h), t0=t0, coherence=True) for h in half]
+    assert np.array_equal(img, np.concatenate([p[0] for p in parts]))
+    assert np.array_equal(cf, np.concatenate([p[1] for p in parts]), equal_nan=True)
+    assert np.array_equal(rf, img.real)
+
+    wimg, sens = rtus.tfm_weighted(a, fs, tt_tx, w_tx, tt_rx, w_rx, t0=t0, sensitivity=True)
+    parts = [rtus.tfm_weighted(a, fs, cut(tt_tx, h), cut(w_tx, h), cut(tt_rx, h), cut(w_rx, h), t0=t0, sensitivity=True) for h in half]
+    assert np.array_equal(wimg, np.concatenate([p[0] for p in parts]))
+    assert np.array_equal(sens, np.concatenate([p[1] for p in parts]))
+    assert np.isfinite(wimg).all() and np.abs(rf).max() > 0 and np.abs(wimg).max() > 0
