@@ -26,6 +26,14 @@
 //     T = T(q) + p dXr + (1/2)(dp/dX) dXr^2,  p = dT/dX = sin(theta)/c  — error O(dXr^3): measured max 3.4e-18 s
 //     (median 3e-20 s) against the long-double oracle on BASELINE config 3.
 //
+// Row table (tau-p tier).  Through horizontal layers T depends on a pair only through the two depths and X = |xf - xe|: a workgroup
+// whose 256 targets share one depth (a line of an image grid) and whose elements share another (a linear array) samples ONE
+// function T(X).  Such a workgroup, if its block has 32 rows or more, builds a quintic Hermite table of T on the lattice X_j = j h
+// (h a power of two chosen from zf - ze alone) from fp64 nodes (T, p, p'), checks every interval against a solved point at
+// s = 0.3 to 1e-11 relative, and serves its rows from LDS: ~10 VALU instructions and 48 B of LDS per solve instead of 62 and a
+// root-find.  Anything else — mixed depths, a non-finite x, a span beyond 351 intervals, an interval that fails — runs the solver
+// exactly as before, the whole workgroup.  A served solve's bits are a function of (X, depths, medium) alone: see the kernel.
+//
 // Layout: tt[e][f], f fastest — each wave stores 512 contiguous bytes; xf/zf loads are coalesced; the
 // per-element data of a workgroup (coordinates, extrapolation weights) sits in LDS and is broadcast to the lanes.
 #include "rtus_device.h"
@@ -51,6 +59,8 @@ struct LayerArgs {
     // batched entry (rtus_tt_layers_batch): problem b = blockIdx.z uses elements / targets / output shifted by these
     long long e_stride, f_stride, t_stride;   // in elements of the respective arrays (0: shared by all problems)
     int gx, gy, n_items;               // work items: gx columns of 256 targets x gy blocks of rows (x n_batch problems) = n_items
+    long long n_rows;                  // rows of the WHOLE table (a shard's launch: more than its n_e) — the row table's threshold, see the kernel
+    int rowtab;                        // the launch carries the row table's LDS: tau-p tier and eb >= RTUS_ROWTAB_MIN_ROWS (else no block qualifies)
 };
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -359,6 +369,93 @@ __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL
     return FAST ? qroot : __builtin_copysignf(qroot, __int_as_float(__double2hiint(dxs)));    // one v_bfi_b32
 }
 
+// ---- Row table (tau-p tier) ------------------------------------------------------------------------------------------------
+// Through horizontal layers T depends on an (element, target) pair only through the two depths and X = |xf - xe|.  On an image
+// grid the 256 targets of a workgroup share one depth, on a linear array its elements share another: the workgroup's solves are
+// samples of ONE smooth function T(X).  Such a workgroup tabulates it — a quintic Hermite interpolant on a lattice, from fp64
+// nodes, every interval verified against a solved point — and serves its rows from the table: a subtract, an exact index, 48 B
+// from LDS and five FMAs per solve instead of a root-find.  scripts/study_planar_rowtable.py is the CPU emulation that settled
+// the divisor, the capacity and the bound; DESIGN.md section 4 "Row table" has the error budget and the measurements.
+#define RTUS_ROWTAB_SLOTS 352          // 48-byte intervals per workgroup: 16.5 KB + the records = 19 KB, eight workgroups per CU in 160 KB
+#define RTUS_ROWTAB_MIN_ROWS 32        // rows of the block below which the table does not pay: building it costs each lane two fp64 solves,
+                                       // the coefficients and the reductions (~800 instructions), a served row saves ~48 of the solver's 62
+                                       // -> even at ~17 rows; twice that, so that a block which qualifies wins clearly
+#define RTUS_ROWTAB_DIV (1.4142135623730951 / 128.0)   // h = the power of two nearest (in ratio) to (zf - ze) / 128
+#define RTUS_ROWTAB_CHECK_S 0.3        // where an interval is checked: OFF centre (at s = 1/2 an error common to both nodes' p cancels)
+#define RTUS_ROWTAB_BOUND 1e-11        // relative bound of that check: with the error shape s^3 (1 - s)^3 (0.59 of its maximum at s = 0.3)
+                                       // a passing interval is within 1.7e-11 everywhere, + 1e-13 of node error: under the tier's 6e-11
+#define RTUS_ROWTAB_RESID 1e-13        // fp64 residual |X - X(q)| / X at which a node's Newton iteration stops
+
+struct __attribute__((aligned(16))) RowTabSlot { double c[6]; };   // T on [X_j, X_j + h] = sum c_k s^k, s = (X - X_j) / h
+struct RowTabHdr {
+    double flo[4], fhi[4];             // per wave: range of its targets' x
+    double elo, ehi, ze;               // range of the block's element x, their depth
+    int fok[4];                        // per wave: every target at the workgroup's first target's depth, every xf finite
+    int eok;                           // every element at the first one's depth, every xe finite
+    int bad[4];                        // per wave: a node that did not converge or an interval that failed its check
+};
+
+__device__ __forceinline__ double wave_min_f64(double v) { for (int m = 32; m; m >>= 1) v = fmin(v, __shfl_xor(v, m)); return v; }
+__device__ __forceinline__ double wave_max_f64(double v) { for (int m = 32; m; m >>= 1) v = fmax(v, __shfl_xor(v, m)); return v; }
+
+// T, p = dT/dX and p' = dp/dX at reach X, to fp64: the solver's fp32 Newton iteration from the lower bound of the root, then Newton
+// steps in fp64 until |X - X(q)| <= 1e-13 X (seeds from the fp32 pipe, refined twice: no IEEE sqrt or divide).  A function of
+// (X, L) alone — a lane that is done keeps its q while the wave goes on, so its result does not depend on its neighbours'.
+// Returns false when the residual was not reached (the caller gives the table up).
+template <int NL>
+__device__ __forceinline__ bool rowtab_point(const Lane<NL>& L, double X, double& T, double& p, double& pp)
+{
+    const float Xf = (float)X;
+    const float lb = fmaxf(fmaxf(Xf * L.rs0f, (Xf - L.asymf) * L.rhmf), 0.0f);
+    float q = lb;
+    for (int trip = 0; trip < 64; ++trip) {                 // wave-uniform trip count, ballot exit
+        const float q2 = q * q;
+        float S1 = L.hr0f, S3 = L.hr0f;
+#pragma unroll
+        for (int i = 1; i < NL; ++i) {
+            const float y = __builtin_amdgcn_rsqf(fmaf(L.kkf[i], q2, 1.0f));
+            const float hw = L.hrf[i] * y;
+            S1 += hw;
+            S3 = fmaf(hw, y * y, S3);
+        }
+        const float dq = fmaf(-S1, q, Xf) * __builtin_amdgcn_rcpf(S3);
+        const bool big = fabsf(dq) > RTUS_PLANAR_TAU * q;
+        if (!__builtin_amdgcn_ballot_w64(big)) break;
+        q = big ? fmaxf(q + dq, lb) : q;
+    }
+    double qd = (double)q, S1 = 0.0, S3 = 0.0, ST = 0.0, q2 = 0.0;   // ST: sum (h_i / c_i) cos(theta_i) / u, formed with the sums (no w[] kept)
+    bool ok = false;
+    for (int trip = 0; trip < 8; ++trip) {
+        q2 = qd * qd;
+        S1 = S3 = L.hr0;
+        ST = L.hc0;
+#pragma unroll
+        for (int i = 1; i < NL; ++i) {
+            const double d = fma(L.kk[i], q2, 1.0);
+            const double w = rsqrt_refine(d, rsqrt_refine(d, (double)__builtin_amdgcn_rsqf((float)d)));
+            const double hw = L.hr[i] * w;
+            S1 += hw;
+            S3 = fma(hw, w * w, S3);
+            ST = fma(L.hc[i] * d, w, ST);
+        }
+        const double dX = fma(-S1, qd, X);
+        ok = fabs(dX) <= RTUS_ROWTAB_RESID * X;              // (NaN: never)
+        if (!__builtin_amdgcn_ballot_w64(!ok)) break;
+        double r = (double)__builtin_amdgcn_rcpf((float)S3);
+        r = fma(fma(-S3, r, 1.0), r, r);
+        qd = ok ? qd : fma(dX, r, qd);                      // (a lane that is done stays where it is: the sums remain those of its q)
+    }
+    double r = (double)__builtin_amdgcn_rcpf((float)S3);
+    r = fma(fma(-S3, r, 1.0), r, r);
+    r = fma(fma(-S3, r, 1.0), r, r);
+    const double a1 = 1.0 + q2;
+    const double u = rsqrt_refine(a1, rsqrt_refine(a1, (double)__builtin_amdgcn_rsqf((float)a1)));
+    p = qd * u * L.inv_cm;
+    T = fma(p, X, u * ST);                                  // the tau-p form: stationary in q, the residual enters squared
+    pp = (u * u) * (u * L.inv_cm) * r;
+    return ok;
+}
+
 // A workgroup = 256 focal points x `eb` consecutive elements (loop).  Besides re-using the layer
 // set-up while ze repeats, the loop gives each lane a CONTINUATION PREDICTOR: the signed solution
 // qs = sign(xf - xe) q is a smooth function of the element position, so the four previous
@@ -373,6 +470,15 @@ template <int NL, bool ITERS, bool TAUP = false, bool PERM = false>
 __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_tt_layers_kernel(LayerArgs a)
 {
     __shared__ ElemRec rec[64];
+#if defined(RTUS_EXP_PERSIST) || defined(RTUS_EXP_NO_ROWTAB)   // experiment builds only: the solver path everywhere
+    constexpr bool ROWTAB = false;
+#else
+    constexpr bool ROWTAB = TAUP && !ITERS;                  // the row table is a path of the tau-p tier (see rowtab_point)
+#endif
+    // the table itself is DYNAMIC LDS, asked for by launch_layers only where a block can qualify (a.rowtab): a table of short blocks
+    // — configs[1], configs[4] — launches with the 2 KB of records it always had
+    extern __shared__ __attribute__((aligned(16))) RowTabSlot tab[];
+    __shared__ RowTabHdr hdr;
     // Work items = (column of 256 targets, block of rows, problem of a batch): one per workgroup.  -DRTUS_EXP_PERSIST (experiment
     // builds only, scripts/gpu_planar_r04.sh) runs them as a PERSISTENT grid instead — 8 workgroups per CU, workgroup w takes items
     // w, w + gridDim.x, ... — to find out whether the half-empty wave slots between the two rounds of a configs[2] launch cost time:
@@ -396,11 +502,24 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
     const int f_raw = bx * RTUS_BLOCK + threadIdx.x;
     const bool live = f_raw < a.n_f;
     const int f = live ? f_raw : a.n_f - 1;
-    const double xf = xf_p[f];
+    double xf = xf_p[f];
     const unsigned f8 = (unsigned)f * 8u;                   // the target's byte offset in a row of the table (n_f x 8 < 2^32: the launcher checks)
     const int gb = a.row0 / a.eb + by;                      // the workgroup's block of the whole table
     const int e0 = max(gb * a.eb - a.row0, 0);              // ... in this launch's rows (a shard that starts inside a block keeps its tail)
     const int ne = min((gb + 1) * a.eb - a.row0, a.n_e) - e0;   // elements of this workgroup (<= 64)
+    // Row table: tried where the block OF THE WHOLE TABLE has enough rows for it to pay (a scalar test on the launch's arguments:
+    // a table of short blocks, configs[1] for one, pays nothing further).  Each wave leaves the range of its targets' x and whether
+    // they share the first target's depth; the first wave does the same for the elements below.
+    const bool try_tab = ROWTAB && a.rowtab && min((long long)(gb + 1) * a.eb, a.n_rows) - (long long)gb * a.eb >= RTUS_ROWTAB_MIN_ROWS;
+    double zfv = 0.0;
+    if (try_tab) {
+        zfv = zf_p[f];
+        const bool okl = zfv == zf_p[bx * RTUS_BLOCK] && isfinite(xf);
+        const bool okw = !__builtin_amdgcn_ballot_w64(!okl);
+        double lo = 0.0, hi = 0.0;
+        if (okw) { lo = wave_min_f64(xf); hi = wave_max_f64(xf); }       // (wave-uniform: random targets pay the load and the ballot only)
+        if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; hdr.flo[w] = lo; hdr.fhi[w] = hi; hdr.fok[w] = okw; }
+    }
 
     // ---- per-element records: the first wave works them out, one element per lane ----------------------
     if (threadIdx.x < 64) {
@@ -410,6 +529,13 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
         const double x0 = xe_p[el], z0 = ze_p[el];
         const double x1 = xe_p[b1], x2 = xe_p[b2], x3 = xe_p[b3], x4 = xe_p[b4];
         const double z1 = ze_p[b1], z2 = ze_p[b2], z3 = ze_p[b3], z4 = ze_p[b4];     // all loads issued together
+        if (try_tab) {
+            const bool in = lane < ne;
+            const double zfirst = __shfl(z0, 0);
+            const bool oke = !__builtin_amdgcn_ballot_w64(in && !(z0 == zfirst && isfinite(x0)));
+            const double lo = wave_min_f64(in ? x0 : (double)INFINITY), hi = wave_max_f64(in ? x0 : -(double)INFINITY);
+            if (lane == 0) { hdr.elo = lo; hdr.ehi = hi; hdr.ze = zfirst; hdr.eok = oke; }
+        }
         // how many predecessors inside this workgroup share the element's depth (the history restarts when ze changes)
         // (a predecessor at a non-finite position is no history either — its solution is NaN, and 0 x NaN in the predictor's unused
         // terms would carry it into up to four rows behind it: scripts/exp_nan_rows.py, tests/test_gpu_edge_sizes.py)
@@ -468,11 +594,6 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
     __syncthreads();
 
     const RecPtr rec3 = (RecPtr)rec;
-    Lane<NL> L;
-    L.tau = INFINITY; L.rS3 = 0.0f; L.G = L.dG = 0.0f; L.hic = 0.0f; L.inv_cm = 0.0; L.hr0 = L.hc0 = 0.0; L.hr0f = L.rs0f = L.rhmf = L.asymf = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) { L.hr[i] = L.kk[i] = L.hc[i] = 0.0; L.hrf[i] = L.kkf[i] = 0.0f; }
-    float qa = 0.0f, qb = 0.0f, qc = 0.0f, qd = 0.0f;       // signed solutions of the four previous elements, qa the latest
     const size_t nf = (size_t)a.n_f;
     size_t o = (size_t)e0 * nf;                              // output row of element e0 + li (wave-uniform; ITERS only)
     const unsigned row_bytes = (unsigned)a.n_f * 8u;
@@ -487,6 +608,92 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
         return __builtin_amdgcn_make_buffer_rsrc(tt_p + dest_o(idx, off), 0, row_bytes, 0x00020000);
     };
     auto dest_so = [&](unsigned off) { return PERM ? 0u : off; };
+    // ---- row table ---------------------------------------------------------------------------------------------------------
+    // ELIGIBLE: every target of the workgroup at one depth zf, every element of the block at one depth ze < zf, every x finite, the
+    // block long enough (try_tab).  LATTICE: nodes X_j = j h anchored at X = 0, h the power of two nearest (zf - ze) / 128: a
+    // function of the two depths alone.  The workgroup builds the intervals [tlo, thi] that its |xf - xe| can touch — from the
+    // extreme pairs: fl(xf - xe) is monotone in both, so every solve's index floor(X / h) lies between theirs and no lane needs a
+    // range check — one node per lane (T, h p, h^2 p' / 2: the first three coefficients of the interval that starts there), then
+    // one interval per lane: the upper three coefficients from the two nodes, and a solved point at s = 0.3 against the
+    // interpolant.  A node that did not reach its residual, an interval beyond 1e-11, more intervals than the table holds: the
+    // WHOLE workgroup takes the solver path below, before a row is stored (its history needs every row).
+    // BITS.  A served solve is a function of (X, j, h, the depths, the medium): X / h, X / h - tlo and the fraction are exact, a
+    // node is solved cold from X_j, an interval's coefficients come from its own two nodes — no trace of tlo, of the lane that
+    // built it, of the launch.  So a row served here has the same bits from one launch, from row shards, from the batched entry
+    // and from the sorted entry in any order of the aperture, and the row of an element at +x mirrors that of one at -x.  What is
+    // left is the DECISION, which must not depend on the launch either.  It is a function of the block's rows: of their number
+    // IN THE WHOLE TABLE (gb, eb, n_rows: not the rows this launch holds), and of conditions that are all MONOTONE in the set of
+    // elements — one depth, finite x, [tlo, thi] inside the capacity, every interval of [tlo, thi] good (an interval's verdict is
+    // a function of j).  A launch that holds the whole block (any shard cut at multiples of eb, the batched and the sorted
+    // entries) decides on the same elements as the whole table's launch.  One that holds PART of a block sees a subset: where the
+    // whole block qualifies so does every part of it, and the rows agree bit for bit wherever the shard is cut; where the whole
+    // block does not, the whole table's launch ran the solver — whose bits in a block cut apart were never those of the whole
+    // (its history starts at the cut: rtus_launch_tt_layers_rows promises equal bits for cuts at multiples of eb only).
+    if (try_tab && __builtin_amdgcn_readfirstlane(hdr.fok[0] & hdr.fok[1] & hdr.fok[2] & hdr.fok[3] & hdr.eok)) {
+        const double zE = hdr.ze, D = zfv - zE, elo = hdr.elo, ehi = hdr.ehi;
+        const double flo = fmin(fmin(hdr.flo[0], hdr.flo[1]), fmin(hdr.flo[2], hdr.flo[3]));
+        const double fhi = fmax(fmax(hdr.fhi[0], hdr.fhi[1]), fmax(hdr.fhi[2], hdr.fhi[3]));
+        const double gap = fmax(fmax(flo - ehi, elo - fhi), 0.0), far = fmax(fhi - elo, ehi - flo);
+        const double h = __longlong_as_double(__double_as_longlong(D * RTUS_ROWTAB_DIV) & 0x7ff0000000000000ll);
+        const double inv_h = __longlong_as_double(0x7fe0000000000000ll - __double_as_longlong(h));      // exact: h is a power of two
+        const double tlo = floor(gap * inv_h), thi = floor(far * inv_h);
+        // (D > 0 is zf > ze; the limits keep h and 1 / h normal and the indices in an int; NaN fails every comparison)
+        const bool fits = D > 1e-290 && D < 1e290 && thi < 1073741824.0 && thi - tlo < (double)(RTUS_ROWTAB_SLOTS - 1);
+        if (__builtin_amdgcn_readfirstlane((int)fits)) {
+            const int n_int = __builtin_amdgcn_readfirstlane((int)(thi - tlo)) + 1;      // intervals; nodes 0 .. n_int (<= the slots)
+            const int tid = threadIdx.x, w0 = __builtin_amdgcn_readfirstlane(tid) & ~63;
+            Lane<NL> LT;
+            layer_setup<NL>(a, zE, zf_p, f8, LT);
+            bool bad = false;
+            for (int base = w0; base <= n_int; base += RTUS_BLOCK) {                     // (wave-uniform: a wave without a node skips)
+                const int k = min(base + (tid & 63), n_int);
+                double T, p, pp;
+                bad |= !rowtab_point<NL>(LT, (tlo + (double)k) * h, T, p, pp);
+                tab[k].c[0] = T; tab[k].c[1] = p * h; tab[k].c[2] = pp * (0.5 * h * h);   // (lanes past the last node redo it: same values)
+            }
+            __syncthreads();
+            for (int base = w0; base < n_int; base += RTUS_BLOCK) {
+                const int j = min(base + (tid & 63), n_int - 1);
+                double Tc, pc, ppc;                                                      // (the solve first: the coefficients are not live across it)
+                const bool okc = rowtab_point<NL>(LT, ((tlo + (double)j) + RTUS_ROWTAB_CHECK_S) * h, Tc, pc, ppc);
+                const double c0 = tab[j].c[0], c1 = tab[j].c[1], c2 = tab[j].c[2];
+                const double d = ((tab[j + 1].c[0] - c0) - c1) - c2, e = (tab[j + 1].c[1] - c1) - 2.0 * c2, g = 2.0 * (tab[j + 1].c[2] - c2);
+                const double c3 = fma(10.0, d, fma(-4.0, e, 0.5 * g)), c4 = fma(-15.0, d, fma(7.0, e, -g)), c5 = fma(6.0, d, fma(-3.0, e, 0.5 * g));
+                // (the upper three: words no node pass wrote and no other lane reads now — no barrier between the reads and these)
+                tab[j].c[3] = c3; tab[j].c[4] = c4; tab[j].c[5] = c5;
+                const double sc = RTUS_ROWTAB_CHECK_S;
+                const double Ti = fma(sc, fma(sc, fma(sc, fma(sc, fma(sc, c5, c4), c3), c2), c1), c0);
+                bad |= !(okc && fabs(Ti - Tc) <= RTUS_ROWTAB_BOUND * Tc);
+            }
+            // (the target's x is LOADED again here — an L2 hit, through an offset the compiler cannot see through, as layer_setup
+            // does with zf — instead of being held across the build, which has no register to spare for it: two went to scratch)
+            unsigned f8r = f8;
+            asm volatile("" : "+v"(f8r));
+            xf = *(const double*)((const char*)xf_p + f8r);
+            const bool badw = __builtin_amdgcn_ballot_w64(bad) != 0;
+            if ((tid & 63) == 0) hdr.bad[tid >> 6] = badw;
+            __syncthreads();
+            if (!__builtin_amdgcn_readfirstlane(hdr.bad[0] | hdr.bad[1] | hdr.bad[2] | hdr.bad[3])) {
+                size_t ot = o;
+                unsigned sot = 0;
+                for (int l = 0; l < ne; ++l) {                                           // a row per trip: wave-uniform
+                    const double tq = fma(fabs(xf - rec3[l].xe), inv_h, -tlo);          // X / h - tlo, exact
+                    const double sq = __builtin_amdgcn_fract(tq);
+                    const RowTabSlot* __restrict__ sl = &tab[(int)tq];
+                    const double T = fma(sq, fma(sq, fma(sq, fma(sq, fma(sq, sl->c[5], sl->c[4]), sl->c[3]), sl->c[2]), sl->c[1]), sl->c[0]);
+                    const u32x2 bits = {(unsigned)__double2loint(T), (unsigned)__double2hiint(T)};
+                    __builtin_amdgcn_raw_buffer_store_b64(bits, dest_rs(l, ot), f8, dest_so(sot), 0);
+                    ot += nf; sot += row_bytes;
+                }
+                return;
+            }
+        }
+    }
+    Lane<NL> L;
+    L.tau = INFINITY; L.rS3 = 0.0f; L.G = L.dG = 0.0f; L.hic = 0.0f; L.inv_cm = 0.0; L.hr0 = L.hc0 = 0.0; L.hr0f = L.rs0f = L.rhmf = L.asymf = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) { L.hr[i] = L.kk[i] = L.hc[i] = 0.0; L.hrf[i] = L.kkf[i] = 0.0f; }
+    float qa = 0.0f, qb = 0.0f, qc = 0.0f, qd = 0.0f;       // signed solutions of the four previous elements, qa the latest
     while (li < ne) {                                        // wave-uniform loop
         const int info = __builtin_amdgcn_readfirstlane(rec[li].info);
         if (info & 8) {                                      // depth changed: redo the layer set-up, forget the history
@@ -628,6 +835,8 @@ static hipError_t launch_layers(const double* z_if, const double* c, int n_if, c
     if (eb < 1 || (n_rows_total + eb - 1) / eb > 65535) return hipErrorInvalidValue;
     a.row0 = row0;
     a.eb = eb;
+    a.n_rows = n_rows_total;
+    a.rowtab = (flags & RTUS_TT_TAUP_TAIL) != 0 && !iters && eb >= RTUS_ROWTAB_MIN_ROWS;
     a.gx = (n_f + RTUS_BLOCK - 1) / RTUS_BLOCK; a.gy = (row0 + n_e - 1) / eb - row0 / eb + 1;
     const long long items = (long long)a.gx * a.gy * n_batch;
     if (items > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -647,7 +856,8 @@ static hipError_t launch_layers(const double* z_if, const double* c, int n_if, c
     // LDS the kernel never touches (-DRTUS_PLANAR_SHAPE_LDS=bytes, experiment builds) was worth -3.5 % at six per CU while the kernel
     // still parked set-up values in scratch and loaded extra header words (start-up that nothing overlapped when every wave of a SIMD
     // began at once); on the kernel as it is now six per CU is 0.5 - 1.6 % SLOWER than eight and seven is even: no shaping.
-    const unsigned lds = (n_if + 1 <= 3 && !iters && items >= 4096) ? RTUS_PLANAR_SHAPE_LDS : 0u;
+    const unsigned lds = ((n_if + 1 <= 3 && !iters && items >= 4096) ? RTUS_PLANAR_SHAPE_LDS : 0u) +
+                         (a.rowtab ? (unsigned)(RTUS_ROWTAB_SLOTS * sizeof(RowTabSlot)) : 0u);
     switch (n_if + 1) {
 #define RTUS_CASE(NL) case NL: if (iters) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, true, false, false>), grid, block, lds, s, a); \
                                else if (row_of && taup) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, true, true>), grid, block, lds, s, a); \
