@@ -1,6 +1,7 @@
 // rtus_amp.h — the arithmetic shared by the ray amplitude kernels (rtus_amp.hip: through a measured surface; rtus_amp_pipe.hip: through
 // the lens into the pipe wall): complex helpers, the plane-wave table of one wave, the three displacement coefficients by Cramer's rule
-// on the boundary conditions, one interface of the ray tube.  Definitions: include/rtus.h; oracle: tests/amplitude_numpy.py.
+// on the boundary conditions, one interface of the ray tube, and the walk of a whole leg along its path in either direction (AmpPath,
+// amp_walk: the one place where the up leg is the down leg reversed).  Definitions: include/rtus.h; oracle: tests/amplitude_numpy.py.
 #pragma once
 #include "rtus_device.h"
 
@@ -117,4 +118,67 @@ __device__ __forceinline__ void amp_tube_step(double dx, double dz, double c, do
     W = (refl ? -ds : ds) * cout;
     Th = refl ? K * ds - dtout : K * ds + dtout;
     prod = prod * cout / cin;
+}
+
+// ---- one leg as a path, element towards point: n unit segments, an interface between each two.  The kernels fill it from their own
+// geometry (units and lengths are theirs: the walker never recomputes them) and amp_walk carries the tube and the coefficients along
+// it in either direction: the up leg IS the down leg walked from its other end with negated directions.
+#define AMP_MAX_SEG 4
+enum AmpKind { AMP_INTO_SOLID, AMP_INTO_FLUID, AMP_FREE };   // what the path, element towards point, does at an interface
+struct AmpSeg { double ux, uz, l, c, ic; bool L; };          // unit direction, length, speed, 1 / speed; in a solid: the mode is L
+struct AmpIface {
+    double nx, nz, curv;       // the normal and its rate of turn (amp_tube_step's convention)
+    double tx, tz;             // the tangent of the coefficient frame
+    AmpKind kind;
+    const AmpMedia* m;         // the fluid-solid pair that meets here
+};
+struct AmpPath { int n; AmpSeg s[AMP_MAX_SEG]; AmpIface f[AMP_MAX_SEG - 1]; };
+
+// leg 0..5 = L, T, LL, LT, TL, TT: a skip leg reflects once; the modes before (LX) and after it (LY)
+__device__ __forceinline__ void amp_leg_modes(int leg, bool& skip, bool& LX, bool& LY)
+{
+    skip = leg >= 2;
+    LX = leg == 0 || leg == 2 || leg == 3;
+    LY = skip ? (leg == 2 || leg == 4) : LX;
+}
+
+// the ray crosses f from segment a into segment b (back: against the path, both directions negated): the tube's step, and the
+// displacement coefficient at the tangential slowness of the arriving ray
+__device__ __forceinline__ cd amp_cross(const AmpIface& f, const AmpSeg& a, const AmpSeg& b, bool back, double& W, double& Th, double& prod)
+{
+    const double ax = back ? -a.ux : a.ux, az = back ? -a.uz : a.uz, bx = back ? -b.ux : b.ux, bz = back ? -b.uz : b.uz;
+    amp_tube_step(ax, az, a.c, bx, bz, b.c, f.nx, f.nz, f.curv, f.kind == AMP_FREE, W, Th, prod);
+    const double p = (ax * f.tx + az * f.tz) * a.ic;
+    if (f.kind == AMP_FREE) return amp_free(a.L, b.L, p, *f.m);
+    return (f.kind == AMP_INTO_SOLID) != back ? amp_fluid_solid(b.L, p, *f.m) : amp_solid_fluid(a.L, p, *f.m);
+}
+
+// A = conj(D C_0 C_1 [C_2] G) of the path, down (element -> point) or up (point -> element); width, fc: the element's directivity
+__device__ __forceinline__ float2 amp_walk(const AmpPath& p, bool up, double width, double fc)
+{
+    double W = 0.0, Th = 1.0, prod = 1.0;
+    cd c[AMP_MAX_SEG - 1];
+    if (!up) {
+        W += p.s[0].l * Th;
+#pragma unroll
+        for (int i = 0; i < AMP_MAX_SEG - 1; ++i)
+            if (i + 1 < p.n) { c[i] = amp_cross(p.f[i], p.s[i], p.s[i + 1], false, W, Th, prod); W += p.s[i + 1].l * Th; }
+    } else {
+#pragma unroll
+        for (int i = AMP_MAX_SEG - 2; i >= 0; --i)
+            if (i + 1 < p.n) { W += p.s[i + 1].l * Th; c[i] = amp_cross(p.f[i], p.s[i + 1], p.s[i], true, W, Th, prod); }
+        W += p.s[0].l * Th;
+    }
+    cd C = c[0];
+#pragma unroll
+    for (int i = 1; i < AMP_MAX_SEG - 1; ++i)
+        if (i + 1 < p.n) C = cmul(C, c[i]);
+    double D = 1.0;
+    if (width > 0.0) {
+        const double u = width * p.s[0].ux * fc * p.s[0].ic;     // w sin(theta_E) / lambda_1
+        D = u == 0.0 ? 1.0 : sinpi(u) / (M_PI * u);
+    }
+    if (W == 0.0) return make_float2(INFINITY, INFINITY);        // a caustic: ray theory fails (include/rtus.h)
+    const double G = sqrt(prod / fabs(W));
+    return make_float2((float)(D * G * C.re), (float)(-(D * G * C.im)));    // the conjugate: the analytic signal's convention
 }

@@ -1,5 +1,5 @@
 // rtus_lens.h — the curved lens's arithmetic shared by the kernels that solve a leg through it (rtus_lens_fermat.hip: element to
-// a point in the water; rtus_lens_pipe.hip: element to a point of the pipe's outer surface).  Interface P(alpha) = h(alpha)
+// a point in the water; rtus_lens_pipe.hip: element to a point of the pipe's outer surface) or walk one (rtus_amp_pipe.hip).  Interface P(alpha) = h(alpha)
 // (sin alpha, cos alpha) with the aplanatic h(alpha) of main_rt.py:180-189 and its derivatives main_rt.py:192-214.
 #pragma once
 #include "rtus_device.h"
@@ -73,6 +73,47 @@ template <typename R> struct LensConst {
     R c1inv, c2inv, phi_3, twoTc, C4A, inv2A;
     int poly_trig;
 };
+
+// The constants of lens L for the alpha interval [a_lo, a_hi] (host): sin / cos by polynomial where the interval allows it
+template <typename R> static inline LensConst<R> make_lens_const(const rtus_lens& L, double a_lo, double a_hi)
+{
+    const LensK kk = make_lens_k(L);
+    LensConst<R> k;
+    k.c1inv = (R)(1.0 / L.c1); k.c2inv = (R)(1.0 / L.c2);
+    k.phi_3 = (R)kk.phi_3; k.twoTc = (R)kk.twoTc; k.C4A = (R)kk.C4A; k.inv2A = (R)(1.0 / kk.twoA);
+    k.poly_trig = (a_lo >= -1.0 && a_hi <= 1.0) ? 1 : 0;
+    return k;
+}
+// g' below this at a minimum of the lens leg's time: suspect, a second minimum may exist (rtus_tt_lens and, for its inner solve,
+// rtus_tt_pipe).  The lens's own time scales the constant measured on the reference lens: 7.5e-6 s/rad^2, twice the largest g' seen at
+// an interior minimum of a pair with two minima (h0 / c2 = 5.96e-5 s; scripts/study_lens_minima.py)
+static inline double lens_gp_min(const rtus_lens& L) { return 0.125 * L.h0 / L.c2; }
+
+// the lens point P, its tangent P' and (WITH_P2) P'' at alpha (lens_time's formulas)
+template <bool POLY, bool WITH_P2>
+__device__ __forceinline__ void lens_point(const LensConst<double>& k, double alpha, double& px, double& pz, double& p1x, double& p1z,
+                                           double& p2x, double& p2z)
+{
+    double s, c;
+    if (POLY) sincos_poly<double>(alpha, s, c);
+    else sincos_r<double>(alpha, &s, &c);
+    const double B = k.phi_3 * c - k.twoTc, B1 = -k.phi_3 * s, B2 = -k.phi_3 * c;
+    const double disc = B * B - k.C4A;
+    const double rS = rsqrt_r<double>(disc), S = disc * rS, BrS = B * rS;
+    const double h = -(B + S) * k.inv2A, h1 = -B1 * (1.0 + BrS) * k.inv2A;
+    px = h * s; pz = h * c;
+    p1x = h1 * s + pz; p1z = h1 * c - px;
+    if (WITH_P2) {
+        const double h2 = -(B2 * (1.0 + BrS) + B1 * B1 * rS * (1.0 - BrS * BrS)) * k.inv2A;
+        p2x = h2 * s + 2.0 * h1 * c - px; p2z = h2 * c - 2.0 * h1 * s - pz;
+    }
+}
+template <bool POLY>
+__device__ __forceinline__ void lens_point(const LensConst<double>& k, double alpha, double& px, double& pz, double& p1x, double& p1z)
+{
+    double p2x, p2z;
+    lens_point<POLY, false>(k, alpha, px, pz, p1x, p1z, p2x, p2z);
+}
 
 // T(alpha), g = dT/dalpha and (WITH_GP) g' for one (A, F).  Without g' the second derivatives h'', P'' are skipped:
 // about a quarter of the arithmetic.

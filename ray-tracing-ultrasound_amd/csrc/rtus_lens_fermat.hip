@@ -472,18 +472,16 @@ template <typename R>
 static hipError_t launch_lens(const rtus_lens& L, double a_lo, double a_hi, const R* xe, const R* ze, int n_e,
                               const R* xf, const R* zf, int n_f, R* tt, R* alpha_out, int row0, long long n_rows_total, unsigned long long* stats, hipStream_t s)
 {
-    const LensK kk = make_lens_k(L);
+    const LensConst<R> c = make_lens_const<R>(L, a_lo, a_hi);
     LensFermatArgs<R> k;
-    k.c1inv = (R)(1.0 / L.c1); k.c2inv = (R)(1.0 / L.c2);
-    k.phi_3 = (R)kk.phi_3; k.twoTc = (R)kk.twoTc; k.C4A = (R)kk.C4A; k.inv2A = (R)(1.0 / kk.twoA);
+    k.c1inv = c.c1inv; k.c2inv = c.c2inv; k.phi_3 = c.phi_3; k.twoTc = c.twoTc; k.C4A = c.C4A; k.inv2A = c.inv2A; k.poly_trig = c.poly_trig;
     k.a_lo = (R)a_lo; k.a_hi = (R)a_hi;
     k.xe = xe; k.ze = ze; k.xf = xf; k.zf = zf; k.tt = tt; k.alpha_out = alpha_out;
     k.n_e = n_e; k.n_f = n_f; k.stats = stats;
-    k.poly_trig = (a_lo >= -1.0 && a_hi <= 1.0) ? 1 : 0;
-    // the lens's own time and speed scale the two constants measured on the reference lens: 7.5e-6 s/rad^2 (twice the largest g' seen
-    // at an interior minimum of a pair with two minima; h0 / c2 = 5.96e-5 s) and 3.9e-4 s/rad^2 per metre (g' at the followed minimum
-    // moves by 1.5 ... 2.6e-4 per metre of element position wherever it is above that — 1 / c1 = 1.56e-4 —, faster only next to the focus)
-    k.gp_min = (R)(0.125 * L.h0 / L.c2); k.gp_dx = (R)(2.5 / L.c1);
+    // the lens's own speed scales the constant measured on the reference lens, as lens_gp_min's: 3.9e-4 s/rad^2 per metre (g' at the
+    // followed minimum moves by 1.5 ... 2.6e-4 per metre of element position wherever it is above that — 1 / c1 = 1.56e-4 —, faster only
+    // next to the focus)
+    k.gp_min = (R)lens_gp_min(L); k.gp_dx = (R)(2.5 / L.c1);
     k.eb = rtus_rows_per_block(n_rows_total, n_f, 1, (int)sizeof(R));   // of the WHOLE table: row shards reproduce its bits
     if (k.eb < 1 || (n_rows_total + k.eb - 1) / k.eb > 65535) return hipErrorInvalidValue;
     k.row0 = row0;

@@ -79,21 +79,6 @@ static size_t pipe_ws(void* ws, int n_e, int m, PipeArgs* a)
 }
 size_t rtus_pipe_ws_bytes(int n_e, int m) { return pipe_ws(nullptr, n_e, m, nullptr); }
 
-// the lens point and its tangent at alpha (lens_time's formulas)
-template <bool POLY>
-__device__ __forceinline__ void lens_point(const LensConst<double>& k, double alpha, double& px, double& pz, double& p1x, double& p1z)
-{
-    double s, c;
-    if (POLY) sincos_poly<double>(alpha, s, c);
-    else sincos_r<double>(alpha, &s, &c);
-    const double B = k.phi_3 * c - k.twoTc, B1 = -k.phi_3 * s;
-    const double disc = B * B - k.C4A;
-    const double rS = rsqrt_r<double>(disc), S = disc * rS;
-    const double h = -(B + S) * k.inv2A, h1 = -B1 * (1.0 + B * rS) * k.inv2A;
-    px = h * s; pz = h * c;
-    p1x = h1 * s + pz; p1z = h1 * c - px;
-}
-
 // The lens leg's least time over the whole interval (rtus_tt_lens's generic step, per lane): T and g at PIPE_NS + 1 even samples
 // (any sample bounds the least time from above: a minimum pinned at an end comes in here), and in every cell whose ends say "a
 // minimum inside" (g < 0 left, g >= 0 right) the zero of g by safeguarded Newton.  Returns alpha; T is its time.
@@ -517,13 +502,10 @@ static hipError_t launch_pipe(const rtus_lens& L, double a_lo, double a_hi, cons
                               int n_scan, const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f,
                               double* tt, double* alpha_out, double* beta_out, double* gamma_out, void* ws, hipStream_t s)
 {
-    const LensK kk = make_lens_k(L);
     PipeArgs a;
-    a.k.c1inv = 1.0 / L.c1; a.k.c2inv = 1.0 / L.c2;
-    a.k.phi_3 = kk.phi_3; a.k.twoTc = kk.twoTc; a.k.C4A = kk.C4A; a.k.inv2A = 1.0 / kk.twoA;
-    a.k.poly_trig = (a_lo >= -1.0 && a_hi <= 1.0) ? 1 : 0;
+    a.k = make_lens_const<double>(L, a_lo, a_hi);
     a.a_lo = a_lo; a.a_hi = a_hi;
-    a.gp_min = 0.125 * L.h0 / L.c2;                          // rtus_tt_lens's threshold (rtus_lens_fermat.hip: launch_lens)
+    a.gp_min = lens_gp_min(L);
     a.r_out = P.r_outer; a.r_in = P.r_inner; a.x_off = P.x_off; a.ic3 = 1.0 / P.c3;
     a.b_lo = b_lo; a.hb = (b_hi - b_lo) / (double)(n_scan - 1);
     a.k32f = (float)(P.c3 / L.c2); a.ic3f = (float)(1.0 / P.c3);

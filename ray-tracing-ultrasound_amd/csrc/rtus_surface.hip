@@ -44,6 +44,7 @@
 // The kept triple, the fp64 bracket of step 3 and its Newton are rtus_bracket.h's, shared with rtus_lens_pipe.hip.
 #include "rtus_device.h"
 #include "rtus_bracket.h"
+#include "rtus_spline.h"    // spline_eval; rtus_surface_ws_bytes and rtus_launch_surface_setup, defined here
 
 // no implicit contraction: the fma()s are written out, so every element slot's inlined copy of the arithmetic rounds alike
 #pragma clang fp contract(off)
@@ -97,20 +98,6 @@ static SurfWs surf_ws(void* ws, int n_s)
     w.pts = (float4*)p; p += rtus_al256(16 * (size_t)surf_points(n_s));
     w.smin = (double*)p;
     return w;
-}
-
-// s, s', s'' at x (x clamped to the extent's segments: outside it the end segments' cubics continue)
-__device__ __forceinline__ void spline_eval(const double* __restrict__ coef, int n_s, double x0, double dx, double inv_dx, double x,
-                                            double& s, double& s1, double& s2)
-{
-    double kf = floor((x - x0) * inv_dx);
-    kf = !(kf >= 0.0) ? 0.0 : (kf > (double)(n_s - 2) ? (double)(n_s - 2) : kf);       // (NaN -> segment 0: never out of bounds)
-    const int k = (int)kf;
-    const double t = x - fma(kf, dx, x0);
-    const double a = coef[4 * k], b = coef[4 * k + 1], c = coef[4 * k + 2], d = coef[4 * k + 3];
-    s = fma(fma(fma(d, t, c), t, b), t, a);
-    s1 = fma(fma(3.0 * d, t, 2.0 * c), t, b);
-    s2 = fma(6.0 * d, t, 2.0 * c);
 }
 
 __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_setup_kernel(const double* __restrict__ zs, int n_s, double x0, double dx,
@@ -562,8 +549,7 @@ hipError_t rtus_launch_tt_surface_skip(double x0, double dx, const double* zs, i
     return surf_launch<SURF_SKIP>(a, zs, w, s);
 }
 
-// the set-up kernel alone, for the consumers of a surface table in other files (rtus_amp.hip): the spline's coefficients land in
-// the workspace at *coef (the scan points are written too, as for a table launch)
+// the set-up kernel alone (rtus_spline.h)
 hipError_t rtus_launch_surface_setup(const double* zs, int n_s, double x0, double dx, void* ws, const double** coef, hipStream_t s)
 {
     const SurfWs w = surf_ws(ws, n_s);
