@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 114 /* 0.1.13: rtus_fmc_sim*, rtus_fmc_sim_echo* (ray-model FMC simulator: arrivals to A-scans) */
+#define RTUS_VERSION 115 /* 0.1.14: rtus_tfm_phase* (phase-coherence imaging: vector and sign coherence factors) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -1066,6 +1066,48 @@ int rtus_fmc_sim_echo_dev(const double *d_t_pair, const float *d_amp, int n_tx, 
 int rtus_fmc_sim_echo(const double *t_pair, const float *amp, int n_tx, int n_rx, int n_a,
                       const float *pulse, int n_p, int centre, int oversample, double fs, double t0, int n_t,
                       float *out, unsigned flags, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_phase: phase-coherence imaging (Camacho, Parrilla & Fritsch 2009, "PCI") — rtus_tfm_analytic's delay-and-sum and, per
+ * focal point, two factors that read only the PHASE of the aperture data: the vector coherence factor vcf and the sign coherence
+ * factor scf.  Both ignore amplitude (saturated echoes, gain differences between elements, the dynamic range of multi-view
+ * images), which rtus_tfm_analytic's cf does not.  NOT IN THE REFERENCE; checked against tests/tfm_phase_numpy.py.
+ *   a, fs, t0, tt_tx, tt_rx, n_f: exactly as in rtus_tfm_analytic — the same sample positions (fp32 legs, s = tau_tx + tau_rx,
+ *           i = floor(s), w = s - i), edge rules and accumulation order (receive tiles of 64 elements, then tx ascending, then rx
+ *           ascending inside the tile).  For focal point f let p_k be the interpolated complex sample of pair k, each part
+ *           fmaf(w, x[i + 1] - x[i], x[i]); p_k = 0 for a pair without a path or with a position outside the record.
+ *   image   [n_f][2]  S = sum p_k: BIT-IDENTICAL to rtus_tfm_analytic's image, whichever of the other outputs are asked for.
+ *   N = T R, rtus_tfm_analytic's count (T, R: the tx and rx legs with a path at f).  A pair with a path whose position falls
+ *           outside the record counts in N with a zero phasor and a zero sign (cf's convention).
+ *   U = sum u_k, the sum of unit phasors: u_k = p_k / |p_k|, and u_k = 0 exactly when both parts of p_k are zero.  u_k is a unit
+ *           phasor to a few fp32 ulp for EVERY non-zero finite fp32 p_k, also where |p_k|^2 would under- or overflow in fp32
+ *           (|p| ~ 1e-30, 1e30): both parts are scaled by the power of two 2^-e, e the exponent of max(|re|, |im|) (exact), then
+ *           multiplied by one reciprocal square root of the scaled squared modulus.  U is accumulated in fp32 in the fixed order.
+ *   B = sum sign(Re p_k), sign in {-1, 0, +1}: an int32, exact.
+ *   vcf     [n_f] float32, nullable.  vcf = |U| / N, formed in fp64 from the fp32 sums, clamped to [0, 1], rounded once to fp32;
+ *           NaN when N = 0.  The circular coherence factor of the same paper is 1 - sqrt(1 - vcf^2) when every pair has a non-zero
+ *           sample (the circular variance of the phases is then 1 - vcf^2).
+ *   scf     [n_f] float32, nullable.  scf = 1 - sqrt(1 - (B / N)^2), formed in fp64, rounded once to fp32; NaN when N = 0.
+ *   counts  [n_f][2] int32, nullable: (B, N).
+ *           A weighted image is |S| vcf^p or |S| scf^p, the exponent the caller's choice.  An output that is not asked for costs
+ *           nothing in the gather loop.  Non-finite samples in a are the caller's error.
+ *   Determinism: as rtus_tfm_analytic — the bits of a focal point depend only on its own columns of the tables; no output's bits
+ *           depend on which other outputs are asked for.
+ *   Limits: rtus_tfm_analytic's (image required; vcf, scf, counts nullable) and n_tx n_rx <= 2^30 (the sign sum is an int32): -1
+ *           for invalid arguments, -5 past a limit, before any HIP call.  The _dev entry allocates nothing and does not
+ *           synchronise (capturable).  The host twin stages through the arena as rtus_tfm_analytic does (one table uploaded when
+ *           tt_tx == tt_rx, only the outputs asked for downloaded).
+ * Measured on MI355X (CUDA-event timing, rtus_tfm_analytic_dev without cf in the same run = 1): 64 elements x 2048
+ * samples, 256^2 focal points: image alone 269 us (1.00x of 268 us), vcf 287 us (1.07x), scf 268 us (1.00x), counts 269 us (1.00x),
+ * vcf + scf 305 us (1.14x), all outputs 303 us (1.13x); 1024^2: image alone 1.91 ms (1.00x of 1.91 ms), vcf 2.70 ms (1.42x), scf
+ * 2.03 ms (1.07x), counts 2.03 ms (1.06x), vcf + scf 3.01 ms (1.58x), all outputs 3.01 ms (1.58x).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tfm_phase_dev(const float *d_a, int n_tx, int n_rx, int n_t, double fs, double t0,
+                       const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                       float *d_image, float *d_vcf, float *d_scf, int *d_counts, void *stream);
+int rtus_tfm_phase(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
+                   const double *tt_tx, const double *tt_rx, int n_f,
+                   float *image, float *vcf, float *scf, int *counts, int device);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ from ._lib import EXPORTS, LIB_PATH, Lens, Pipe, PipeMedia, RtusError, build, li
 from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits,  # noqa: F401
                   reference_elements, shoot_batch, shoot_rays, travel_time_layers, travel_time_lens, travel_time_surface,
                   fmc_table_layers, solve_travel_times, focal_delays, tfm_image, sweep_batch, fmc_analytic, measure_surface,
-                  adaptive_tfm, tfm_analytic, pw_delays, pw_travel_time_layers, pw_travel_time_surface, fmc_synth_tx, pwi_image,
+                  adaptive_tfm, tfm_analytic, tfm_phase, pw_delays, pw_travel_time_layers, pw_travel_time_surface, fmc_synth_tx, pwi_image,
                   LEGS, VIEWS, reverse_leg, view_tables, skip_travel_time_layers, skip_travel_time_surface, view_legs_layers,
                   view_legs_surface, tfm_views, leg_amplitudes_surface, view_amplitudes_surface, tfm_weighted,
                   travel_time_pipe, pipe_wall_grid, skip_travel_time_pipe, view_legs_pipe,
@@ -16,7 +16,7 @@ from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits, 
                   adaptive_tfm_pipe, gaussian_pulse, simulate_fmc, simulate_echoes, simulate_views)
 
 __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "focal_delays", "tfm_image", "fmc_analytic",
-           "measure_surface", "adaptive_tfm", "tfm_analytic", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
+           "measure_surface", "adaptive_tfm", "tfm_analytic", "tfm_phase", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
            "fmc_synth_tx", "pwi_image", "LEGS", "VIEWS", "reverse_leg", "view_tables", "skip_travel_time_layers",
            "skip_travel_time_surface", "view_legs_layers", "view_legs_surface", "tfm_views", "leg_amplitudes_surface",
            "view_amplitudes_surface", "tfm_weighted", "travel_time_pipe", "pipe_wall_grid", "skip_travel_time_pipe",

@@ -171,6 +171,9 @@ PROTOTYPES = (
     ("rtus_fmc_sim", i, [vp, vp, i, i, i, vp, vp, vp, vp, i, i, i, dd, dd, i, vp, u, i], 114),
     ("rtus_fmc_sim_echo_dev", i, [vp, vp, i, i, i, vp, i, i, i, dd, dd, i, vp, u, vp], 114),
     ("rtus_fmc_sim_echo", i, [vp, vp, i, i, i, vp, i, i, i, dd, dd, i, vp, u, i], 114),
+    # phase-coherence imaging
+    ("rtus_tfm_phase_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, vp], 115),
+    ("rtus_tfm_phase", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, i], 115),
 )
 EXPORTS = tuple(p[0] for p in PROTOTYPES)
 

@@ -562,16 +562,8 @@ def _complex_fmc(a):
     return a
 
 
-def tfm_analytic(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, out=None, device=0):
-    """Envelope TFM: tfm_image's delay-and-sum over an analytic FMC (complex64 [n_tx, n_rx, n_t], e.g. from fmc_analytic, or float32
-    [n_tx, n_rx, n_t, 2]) through any travel-time table of this library; tt_rx defaults to tt_tx.  Real and imaginary parts are
-    interpolated separately with tfm_image's sample positions, edge rules and order, so ``image.real`` is tfm_image of
-    ``analytic.real`` bit for bit (and ``image.imag`` of ``analytic.imag``).  The envelope is ``np.abs(image)``.
-    -> complex64 image [n_f]; with ``coherence=True`` -> (image, cf float32 [n_f]): the coherence factor |S|^2 / (N E) of every
-    focal point (Mallart & Fink; S the complex sum, E the sum of |sample|^2 over the N = T R pairs whose legs both have a path; NaN
-    when N = 0).  A CF-weighted image is ``np.abs(image) * cf**p`` (p = 1 is usual).  Definition: include/rtus.h
-    (rtus_tfm_analytic).  Not in the reference."""
-    a = _complex_fmc(analytic)
+def _tfm_tables(a, tt_tx, tt_rx):
+    """the tables of tfm_analytic / tfm_phase against the analytic FMC ``a`` -> (tt_tx, tt_rx, n_f)"""
     tt_tx = np.ascontiguousarray(tt_tx, dtype=np.float64)
     same = tt_rx is None or tt_rx is tt_tx
     tt_rx = tt_tx if same else np.ascontiguousarray(tt_rx, dtype=np.float64)
@@ -579,13 +571,74 @@ def tfm_analytic(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, ou
         raise ValueError("tt_tx / tt_rx must be [n_tx, n_focal] / [n_rx, n_focal]")
     if tt_tx.shape[0] != a.shape[0] or tt_rx.shape[0] != a.shape[1]:
         raise ValueError("the analytic FMC's first two dimensions must match the rows of tt_tx and tt_rx")
-    n_f = tt_tx.shape[1]
+    return tt_tx, tt_rx, tt_tx.shape[1]
+
+
+COHERENCE = ("cf", "vcf", "scf")
+
+
+def _coherence(coherence):
+    """the ``coherence=`` keyword of tfm_analytic / pwi_image / tfm_views -> None, "cf", "vcf" or "scf" (True is "cf")"""
+    if isinstance(coherence, str):
+        if coherence not in COHERENCE:
+            raise ValueError(f"unknown coherence factor {coherence!r}: False, True or one of {COHERENCE}")
+        return coherence
+    if coherence is None or isinstance(coherence, (bool, np.bool_)):
+        return "cf" if coherence else None
+    raise ValueError(f"coherence must be False, True or one of {COHERENCE}")
+
+
+def tfm_analytic(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, out=None, device=0):
+    """Envelope TFM: tfm_image's delay-and-sum over an analytic FMC (complex64 [n_tx, n_rx, n_t], e.g. from fmc_analytic, or float32
+    [n_tx, n_rx, n_t, 2]) through any travel-time table of this library; tt_rx defaults to tt_tx.  Real and imaginary parts are
+    interpolated separately with tfm_image's sample positions, edge rules and order, so ``image.real`` is tfm_image of
+    ``analytic.real`` bit for bit (and ``image.imag`` of ``analytic.imag``).  The envelope is ``np.abs(image)``.
+    -> complex64 image [n_f]; with ``coherence=True`` -> (image, cf float32 [n_f]): the coherence factor |S|^2 / (N E) of every
+    focal point (Mallart & Fink; S the complex sum, E the sum of |sample|^2 over the N = T R pairs whose legs both have a path; NaN
+    when N = 0).  A CF-weighted image is ``np.abs(image) * cf**p`` (p = 1 is usual).  ``coherence="cf"`` is the same as True;
+    ``"vcf"`` / ``"scf"`` -> (image, that phase-coherence factor of tfm_phase): the same image bits.  Definition: include/rtus.h
+    (rtus_tfm_analytic, rtus_tfm_phase).  Not in the reference."""
+    mode = _coherence(coherence)
+    if mode in ("vcf", "scf"):
+        r = _tfm_phase(analytic, fs, tt_tx, tt_rx, t0, (mode,), False, out, device)
+        return r["image"], r[mode]
+    a = _complex_fmc(analytic)
+    tt_tx, tt_rx, n_f = _tfm_tables(a, tt_tx, tt_rx)
     img = _out(out, (n_f,), np.complex64)
-    cf = np.empty(n_f, dtype=np.float32) if coherence else None
+    cf = np.empty(n_f, dtype=np.float32) if mode else None
     st = _lib.lib().rtus_tfm_analytic(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx),
                                       n_f, _ptr(img), _ptr(cf), int(device))
     _lib.check(st, "rtus_tfm_analytic")
-    return (img, cf) if coherence else img
+    return (img, cf) if mode else img
+
+
+def tfm_phase(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, counts=False, out=None, device=0):
+    """Phase-coherence imaging (Camacho, Parrilla & Fritsch 2009): tfm_analytic's delay-and-sum — the same arguments, input rules and
+    image bits — with the two factors that read only the phase of the aperture data at each focal point:
+    ``vcf`` = |sum of the unit phasors p / |p|| / N, the vector coherence factor, and ``scf`` = 1 - sqrt(1 - (B / N)^2), the sign
+    coherence factor, B the sum of sign(Re p) over the pairs; N = T R as for tfm_analytic's cf (pairs outside the record count with
+    a zero phasor and sign; NaN when N = 0).  Both ignore amplitude: saturated echoes, gain differences between elements.
+    -> dict(image complex64 [n_f], vcf float32 [n_f], scf float32 [n_f]); with ``counts=True`` also sign_sum (B) and n_pairs (N),
+    int32 [n_f].  A weighted image is ``np.abs(image) * vcf**p`` (or scf).  Definition: include/rtus.h (rtus_tfm_phase).  Not in the
+    reference."""
+    return _tfm_phase(analytic, fs, tt_tx, tt_rx, t0, ("vcf", "scf"), counts, out, device)
+
+
+def _tfm_phase(analytic, fs, tt_tx, tt_rx, t0, want, counts, out, device):
+    """tfm_phase with only the factors named in ``want`` computed (tfm_analytic(coherence="vcf") asks for one)"""
+    a = _complex_fmc(analytic)
+    tt_tx, tt_rx, n_f = _tfm_tables(a, tt_tx, tt_rx)
+    img = _out(out, (n_f,), np.complex64)
+    r = {"image": img}
+    for k in want:
+        r[k] = np.empty(n_f, dtype=np.float32)
+    cnt = np.empty((n_f, 2), dtype=np.int32) if counts else None
+    st = _lib.lib().rtus_tfm_phase(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f,
+                                   _ptr(img), _ptr(r.get("vcf")), _ptr(r.get("scf")), _ptr(cnt), int(device))
+    _lib.check(st, "rtus_tfm_phase")
+    if counts:
+        r["sign_sum"], r["n_pairs"] = np.ascontiguousarray(cnt[:, 0]), np.ascontiguousarray(cnt[:, 1])
+    return r
 
 
 def adaptive_tfm(fmc, fs, xe, ze, c1, c2, x0, dx, n_s, z_lo, z_hi, dz, xf, zf, *, t0=0.0, threshold=0.1, n_taps=63, envelope=False,
@@ -699,7 +752,8 @@ def pwi_image(pw, fs, tt_pw, tt_rx, *, t0=0.0, envelope=False, coherence=False, 
     pw_delays(...)) or recorded by an instrument with those delays) through the plane-wave table ``tt_pw`` [n_a, n_f]
     (pw_travel_time_*) and an element table ``tt_rx`` [n_rx, n_f].  RF: tfm_image(pw, fs, tt_pw, tt_rx) -> float32 [n_f].  With
     ``envelope=True``: |tfm_analytic(fmc_analytic(pw, n_taps), ...)| -> float32 [n_f], and with ``coherence=True`` also the coherence
-    factor, -> (envelope, cf)."""
+    factor, -> (envelope, cf); ``coherence="cf"`` / ``"vcf"`` / ``"scf"`` name the factor as in tfm_analytic."""
+    coherence = _coherence(coherence)
     if coherence and not envelope:
         raise ValueError("the coherence factor needs envelope=True")
     tt_pw = np.ascontiguousarray(tt_pw, dtype=np.float64)
@@ -825,11 +879,13 @@ def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=F
     """Multi-view TFM: one image per view -> {view: image float32 [n_f]}.  ``legs``: {leg: tt [n_e, n_f]} (view_legs_layers /
     view_legs_surface); a view "A-B" (transmit leg A, then receive leg B from the point to the receiver) is imaged with
     tt_tx = legs[A] and tt_rx = legs[reverse_leg(B)].  RF: tfm_image.  With ``envelope=True``: |tfm_analytic| over the analytic FMC,
-    formed once for all views (``n_taps`` Hilbert taps); with ``coherence=True`` too, each value is (envelope, cf).
+    formed once for all views (``n_taps`` Hilbert taps); with ``coherence=True`` too, each value is (envelope, cf), and with
+    ``coherence="cf"`` / ``"vcf"`` / ``"scf"`` (envelope, that factor of tfm_analytic / tfm_phase).
     ``amplitudes``: {leg: (down, up)} complex64 [n_e, n_f] (view_amplitudes_surface; needs ``envelope=True``, excludes ``coherence``):
     each view is beamformed by tfm_weighted with w_tx = conj(down[A]) and w_rx = conj(up[reverse_leg(B)]) and the value is |S| / P,
     P the view's sensitivity (NaN where P = 0): a unit point scatterer reads 1 in every view that sees it, so views share one scale.
     An unknown view or a leg missing from ``legs`` (or ``amplitudes``) raises ValueError before any GPU call."""
+    coherence = _coherence(coherence)
     if coherence and not envelope:
         raise ValueError("the coherence factor needs envelope=True")
     if amplitudes is not None and not envelope:

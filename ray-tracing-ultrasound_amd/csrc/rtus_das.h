@@ -1,6 +1,6 @@
-// rtus_das.h — the delay-and-sum core shared by rtus_tfm_kernel, rtus_tfm_analytic_kernel, rtus_tfm_weighted_kernel
-// (rtus_tfm.hip) and rtus_surface_find_kernel (rtus_autofocus.hip): the workgroup order, the delay clamp, the two-sample
-// load, its interpolation and the gather loop.  A kernel keeps its tile fill, its accumulate step and its epilogue.
+// rtus_das.h — the delay-and-sum core shared by rtus_tfm_kernel, rtus_tfm_analytic_kernel, rtus_tfm_phase_kernel,
+// rtus_tfm_weighted_kernel (rtus_tfm.hip) and rtus_surface_find_kernel (rtus_autofocus.hip): the workgroup order, the delay
+// clamp, the two-sample load, its interpolation and the gather loop.  A kernel keeps its tile fill, its accumulate step and its epilogue.
 //
 // The common shape: a lane owns one focal point; each receive element's half of the pair's sample position (in samples,
 // fp32) sits in LDS for a tile of elements, lane-major (lane l reads tau[rx][l]: conflict-free); the transmit element's

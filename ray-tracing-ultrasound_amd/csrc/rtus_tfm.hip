@@ -235,6 +235,118 @@ hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------- phase-coherence TFM: vcf, scf
+// rtus_tfm_analytic_kernel's delay-and-sum — the same tile, order and two statements for S, so the image has its bits — and, per
+// pair, what only the gather loop can see: with PHASOR the unit phasor u = p / |p| of the interpolated sample, summed in fp32 into U;
+// with SIGN the sign of Re p, summed as an integer into B.  N = T R as in the CF instantiation.  vcf = |U| / N and
+// scf = 1 - sqrt(1 - (B / N)^2) in fp64 (Camacho, Parrilla & Fritsch 2009).  Definition: include/rtus.h (rtus_tfm_phase).
+struct TfmpArgs {
+    const float* __restrict__ fmc;       // [n_tx][n_rx][n_t][2]
+    const double* __restrict__ tt_tx;    // [n_tx][n_f]
+    const double* __restrict__ tt_rx;    // [n_rx][n_f]
+    float2* __restrict__ image;          // [n_f]
+    float* __restrict__ vcf;             // [n_f] (PHASOR only; not null there)
+    float* __restrict__ scf;             // [n_f] (SIGN only, nullable)
+    int2* __restrict__ counts;           // [n_f] (B, N) (SIGN only, nullable)
+    int n_tx, n_rx, n_t, n_f;
+    double fs, half_t0s;
+};
+
+// p / |p| for every non-zero finite p, (0, 0) for p = 0.  |p|^2 under- or overflows in fp32 from |p| ~ 1e-19 / 1e19 on, so both
+// parts are first scaled by the power of two that brings max(|re|, |im|) into [0.5, 1): exact (the smaller part may lose bits
+// below 2^-126 of the larger: nothing against 0.25 <= x^2 + y^2 < 2).  One v_rsq_f32 (1 ulp), two products.  No contraction: the
+// bits do not depend on what the compiler would fuse.
+__device__ __forceinline__ float2 tfmp_unit(float2 p)
+{
+#pragma clang fp contract(off)
+    const float m = fmaxf(fabsf(p.x), fabsf(p.y));
+    const int e = __builtin_amdgcn_frexp_expf(m);                     // m = [0.5, 1) x 2^e (0 for m = 0)
+    const float x = __builtin_amdgcn_ldexpf(p.x, -e), y = __builtin_amdgcn_ldexpf(p.y, -e);
+    const float r = m > 0.0f ? __builtin_amdgcn_rsqf(fmaf(y, y, x * x)) : 0.0f;   // rsq(0) 0 would be NaN
+    return make_float2(x * r, y * r);
+}
+
+template <bool PHASOR, bool SIGN>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_phase_kernel(TfmpArgs a)
+{
+    __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB, as rtus_tfm_kernel
+    const int f_raw = das_workgroup() * RTUS_BLOCK + threadIdx.x;
+    const bool live = f_raw < a.n_f;
+    const int f = live ? f_raw : a.n_f - 1;
+    const size_t nf = (size_t)a.n_f;
+    const size_t pair_len = (size_t)a.n_t * 2;                        // floats per analytic A-scan
+    const bool tx_in_tile = a.tt_tx == a.tt_rx && a.n_tx == a.n_rx && a.n_rx <= RTUS_TFM_RX_TILE;
+    float re = 0.0f, im = 0.0f, ure = 0.0f, uim = 0.0f;
+    int sgn = 0;                                                      // B[f]: |B| <= n_tx n_rx <= 2^30
+    int n_tx_ok = 0, n_rx_ok = 0;                                     // T[f], R[f]
+    for (int r0 = 0; r0 < a.n_rx; r0 += RTUS_TFM_RX_TILE) {
+        const int nr = min(RTUS_TFM_RX_TILE, a.n_rx - r0);
+        __syncthreads();                                              // the previous tile is no longer read
+        for (int r = 0; r < nr; ++r) {
+            const float v = tfm_tau(a.tt_rx[(size_t)(r0 + r) * nf + f], a.fs, a.half_t0s);
+            tau_rx[r][threadIdx.x] = v;
+            if (PHASOR || SIGN) n_rx_ok += tfm_has_path(v);
+        }
+        __syncthreads();
+        for (int tx = 0; tx < a.n_tx; ++tx) {
+            const float tt = tx_in_tile ? tau_rx[tx][threadIdx.x] : tfm_tau(a.tt_tx[(size_t)tx * nf + f], a.fs, a.half_t0s);
+            if ((PHASOR || SIGN) && r0 == 0) n_tx_ok += tfm_has_path(tt);
+            das_gather<2>(a.fmc + ((size_t)tx * a.n_rx + r0) * pair_len, pair_len, a.n_t, tt, tau_rx, threadIdx.x, nr,
+                          [&](int, das_u32x4 v, float w) {
+                              const float2 p = das_lerp(v, w);
+                              re += p.x;
+                              im += p.y;
+                              if (PHASOR) {
+                                  const float2 u = tfmp_unit(p);
+                                  ure += u.x;
+                                  uim += u.y;
+                              }
+                              if (SIGN) sgn += (p.x > 0.0f) - (p.x < 0.0f);
+                          });
+        }
+    }
+    if (!live) return;
+    a.image[f] = make_float2(re, im);
+    if (PHASOR || SIGN) {
+#pragma clang fp contract(off)
+        const int n = n_tx_ok * n_rx_ok;                              // <= n_tx n_rx <= 2^30 (checked by the C entries)
+        if (PHASOR) {
+            // |U|^2 is exact to fp64 rounding (squares of fp32 values); |U| <= N up to the rounding of the fp32 sums: clamped to 1
+            double c = NAN;                                           // no pair with a path
+            if (n > 0) {
+                c = sqrt((double)ure * (double)ure + (double)uim * (double)uim) / (double)n;
+                c = c > 1.0 ? 1.0 : c;
+            }
+            a.vcf[f] = (float)c;
+        }
+        if (SIGN) {
+            if (a.scf) {
+                double c = NAN;
+                if (n > 0) {
+                    const double q = (double)sgn / (double)n;         // |q| <= 1: |B| <= N
+                    c = 1.0 - sqrt(1.0 - q * q);
+                }
+                a.scf[f] = (float)c;
+            }
+            if (a.counts) a.counts[f] = make_int2(sgn, n);
+        }
+    }
+}
+
+hipError_t rtus_launch_tfm_phase(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                                 const double* tt_rx, int n_f, float* image, float* vcf, float* scf, int* counts, hipStream_t s)
+{
+    TfmpArgs a = tfm_args<TfmpArgs>(an, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f);
+    a.image = (float2*)image; a.vcf = vcf; a.scf = scf; a.counts = (int2*)counts;
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    const bool sign = scf || counts;
+    if (vcf && sign) hipLaunchKernelGGL((rtus_tfm_phase_kernel<true, true>), grid, block, 0, s, a);
+    else if (vcf) hipLaunchKernelGGL((rtus_tfm_phase_kernel<true, false>), grid, block, 0, s, a);
+    else if (sign) hipLaunchKernelGGL((rtus_tfm_phase_kernel<false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((rtus_tfm_phase_kernel<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------- weighted envelope TFM + sensitivity
 // S[f] = sum over (tx, rx) of w_tx[tx][f] w_rx[rx][f] a[tx][rx](s), with rtus_tfm_analytic's sample positions, interpolation and edge
 // rules; a leg without a path or with a non-finite weight contributes nothing.  With SENS, also P[f] = (sum over tx with a path of

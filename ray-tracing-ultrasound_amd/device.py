@@ -393,6 +393,27 @@ def tfm_analytic_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None)
     return out if cf is None else (out, cf)
 
 
+def tfm_phase_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, vcf=None, scf=None, counts=None):
+    """Phase-coherence TFM on device (rtus_tfm_phase_dev; api.tfm_phase's definition): tfm_analytic_dev's tensors -> out float32
+    [n_f, 2] (the complex sum, tfm_analytic_dev's bits); ``vcf`` / ``scf``: optional float32 [n_f] tensors that receive the vector /
+    sign coherence factor, ``counts``: an optional int32 [n_f, 2] tensor that receives (sign sum, number of pairs).  -> out, or the
+    tuple of out followed by the optional tensors given (in that order).  Asynchronous on the current stream (capturable with
+    pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_f = _tables(tt_tx, tt_rx, analytic, analytic=True)
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, vcf=vcf, scf=scf)
+    _optional(2 * n_f, torch.int32, counts=counts)
+    given = [t for t in (vcf, scf, counts) if t is not None]
+    if not all(t.device == analytic.device for t in (tt_tx, tt_rx, out, *given)):
+        raise ValueError("analytic, tt_tx, tt_rx, out, vcf, scf and counts must be on one device")
+    st = _lib.lib().rtus_tfm_phase_dev(_p(analytic), analytic.shape[0], analytic.shape[1], analytic.shape[2], float(fs), float(t0),
+                                       _p(tt_tx), _p(tt_rx), n_f, _p(out), _p(vcf), _p(scf), _p(counts), _stream(analytic))
+    _lib.check(st, "rtus_tfm_phase_dev")
+    return (out, *given) if given else out
+
+
 class LayersPlan:
     """Pre-bound ``rtus_tt_layers_dev`` call for repeated solves of one shape: ``run()`` is a single
     ctypes call (no argument checking, no allocation, no sync) — capturable in a hipGraph."""
