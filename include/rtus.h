@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 115 /* 0.1.14: rtus_tfm_phase* (phase-coherence imaging: vector and sign coherence factors) */
+#define RTUS_VERSION 116 /* 0.1.15: rtus_specular* (specular echo times of sampled reflectors) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -1108,6 +1108,50 @@ int rtus_tfm_phase_dev(const float *d_a, int n_tx, int n_rx, int n_t, double fs,
 int rtus_tfm_phase(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
                    const double *tt_tx, const double *tt_rx, int n_f,
                    float *image, float *vcf, float *scf, int *counts, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_specular: specular echo times of sampled reflectors.  The echo of a reflecting boundary for transmitter i and receiver k
+ * arrives at the stationary value, over the points P of the boundary, of t(i -> P) + t(P -> k) (Fermat).  Every table entry of this
+ * library gives t(element -> P) for arbitrary points — through layers, a measured surface, the lens and the pipe — so the echo
+ * times of a boundary sampled at n_p points, for every pair and for a batch of n_refl candidate boundaries, are a reduction over
+ * two tables: a min-plus product with sub-sample refinement.  The Python layer builds on it the backwall echo under layers and
+ * under a measured surface, the echo of the pipe's bore, and one-parameter fits of the backwall depth and the bore radius
+ * (api.backwall_echo_layers, backwall_echo_surface, bore_echo_pipe, fit_reflector, measure_reflector).  NOT IN THE REFERENCE;
+ * checked bit for bit against tests/specular_numpy.py.
+ *   tt_a    [n_a][n_refl n_p]  times from the n_a transmitters; reflector g owns columns [g n_p, (g + 1) n_p), its points in
+ *                              order along the reflector — the shape a table call over the concatenated points of all
+ *                              candidates returns
+ *   tt_b    [n_b][n_refl n_p]  times to the n_b receivers; NULL: tt_a, and then n_b must equal n_a (-1 otherwise)
+ *   t       [n_refl][n_a][n_b] echo times (rtus_geom_misfit's tt);  pos [n_refl][n_a][n_b] fp64, nullable: the reflection point
+ *                              in units of the point index;  n_min [n_refl][n_a][n_b] int32, nullable
+ * Definition, for reflector g, transmitter i, receiver k:
+ *   S_j = tt_a[i][g n_p + j] + tt_b[k][g n_p + j], one fp64 addition.  S_j is FINITE when isfinite(S_j).
+ *   No S_j finite: t = pos = NaN, n_min = 0.
+ *   j* = the FIRST index attaining the least finite S_j.
+ *   n_min = the number of j in [1, n_p - 2] with S_(j-1), S_j, S_(j+1) all finite, S_j < S_(j-1) and S_j < S_(j+1).  A diagnostic:
+ *           above 1, two reflection paths compete.
+ *   j* = 0 or j* = n_p - 1, or a neighbour of j* not finite: t = NaN, pos = (double) j* — the reflection point is not bracketed by
+ *           the sampled span (rtus_echo_pick's convention at its gate's ends).
+ *   Otherwise, with a = S_(j*-1), b = S_(j*), c = S_(j*+1), in exactly this order and every operation rounded on its own (no
+ *           fused multiply-add; the division correctly rounded):
+ *             d1 = a - c;  d2 = (a - b) + (c - b);  delta = 0.5 d1 / d2;  t = b - (0.25 d1) delta;  pos = j* + delta.
+ *           a > b because j* is the first minimum, so d2 > 0 and |delta| <= 1/2.
+ *   n_p < 3 is legal: every pair comes out NaN by the rules above.
+ *   Accuracy: the parabola's value error is fourth order in the point spacing (a flat reflector 20 mm under 16 elements, +-12 mm
+ *           of points: 6.7e-13 s at 33 points, 1.6e-16 s at 257).
+ *   Determinism: a pair's bits depend only on its own row of tt_a and of tt_b — not on the other pairs or reflectors of the
+ *           call, nor on the launch shape.  With tt_b NULL (or tt_a passed twice) t, pos and n_min are symmetric in (i, k) bit
+ *           for bit.
+ *   Limits: null tt_a or t, a size <= 0: -1; n_refl n_p, n_a n_b or the number of workgroups (ceil(n_a / 8) ceil(n_b / 64) n_refl)
+ *           beyond 2^31 - 1: -5; before any HIP call.  No workspace.  The _dev entry allocates nothing and does not synchronise
+ *           (capturable); the host twin stages through the device's arena (one table uploaded when tt_b is NULL or tt_a, only
+ *           the outputs asked for downloaded).
+ * Kernel, resources and measured figures on MI355X: DESIGN.md section 4 (specular echoes of a sampled reflector).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_specular_dev(const double *d_tt_a, int n_a, const double *d_tt_b, int n_b, int n_refl, int n_p,
+                      double *d_t, double *d_pos, int *d_n_min, void *stream);
+int rtus_specular(const double *tt_a, int n_a, const double *tt_b, int n_b, int n_refl, int n_p,
+                  double *t, double *pos, int *n_min, int device);
 
 #ifdef __cplusplus
 }

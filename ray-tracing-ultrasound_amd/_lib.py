@@ -174,6 +174,9 @@ PROTOTYPES = (
     # phase-coherence imaging
     ("rtus_tfm_phase_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, vp], 115),
     ("rtus_tfm_phase", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, i], 115),
+    # specular echo times of sampled reflectors
+    ("rtus_specular_dev", i, [vp, i, vp, i, i, i, vp, vp, vp, vp], 116),
+    ("rtus_specular", i, [vp, i, vp, i, i, i, vp, vp, vp, i], 116),
 )
 EXPORTS = tuple(p[0] for p in PROTOTYPES)
 

@@ -1421,6 +1421,165 @@ def adaptive_tfm_pipe(fmc, fs, xe, ze, xf, zf, *, t_lo, t_hi, c3, r_inner, t0=0.
     return tfm_image(fmc, fs, tt, t0=t0 - fit["delay"], device=device), fit
 
 
+# ---------------------------------------------------------------------------------------------- specular echoes of a reflector
+def specular_times(tt_a, tt_b=None, *, n_refl=1, return_pos=False, return_minima=False, device=0):
+    """Specular echo times of ``n_refl`` sampled reflectors for every (transmitter, receiver) pair: the stationary value over a
+    reflector's points of tt_a[i, j] + tt_b[k, j], refined by a parabola about the first least sum (include/rtus.h, rtus_specular).
+    ``tt_a`` [n_a, n_refl * n_p]: times from the transmitters to the points, reflector g in columns [g n_p, (g + 1) n_p), its points
+    in order along it — what a table call over the concatenated points returns; ``tt_b`` [n_b, n_refl * n_p]: the receivers' (None:
+    tt_a).  -> t float64 [n_a, n_b], or [n_refl, n_a, n_b] when n_refl > 1; NaN where no sum is finite or the least one is not
+    bracketed by the sampled span.  ``return_pos``: also the reflection point in units of the point index; ``return_minima``: also
+    n_min int32, the number of strict interior minima (above 1: two paths compete) -> (t, pos, n_min), those asked for.  Not in the
+    reference."""
+    tt_a = np.ascontiguousarray(tt_a, dtype=np.float64)
+    tt_b = None if tt_b is None else np.ascontiguousarray(tt_b, dtype=np.float64)
+    n_refl = int(n_refl)
+    if tt_a.ndim != 2 or tt_a.size == 0 or n_refl < 1 or tt_a.shape[1] % n_refl:
+        raise ValueError("tt_a must be [n_a, n_refl * n_p]")
+    if tt_b is not None and (tt_b.ndim != 2 or tt_b.shape[0] == 0 or tt_b.shape[1] != tt_a.shape[1]):
+        raise ValueError("tt_b must be [n_b, n_refl * n_p], the columns of tt_a")
+    n_a, n_b = tt_a.shape[0], tt_a.shape[0] if tt_b is None else tt_b.shape[0]
+    shape = (n_a, n_b) if n_refl == 1 else (n_refl, n_a, n_b)
+    t = np.empty(shape, dtype=np.float64)
+    pos = np.empty(shape, dtype=np.float64) if return_pos else None
+    n_min = np.empty(shape, dtype=np.int32) if return_minima else None
+    st = _lib.lib().rtus_specular(_ptr(tt_a), n_a, _ptr(tt_b), n_b, n_refl, tt_a.shape[1] // n_refl, _ptr(t), _ptr(pos), _ptr(n_min),
+                                  int(device))
+    _lib.check(st, "rtus_specular")
+    extra = [v for v in (pos, n_min) if v is not None]
+    return (t, *extra) if extra else t
+
+
+def _candidates(values, name):
+    v = _f64(values, name)
+    if v.size == 0:
+        raise ValueError(f"{name} must hold at least one candidate")
+    return v
+
+
+def _span_points(lo, hi, n_p):
+    if int(n_p) < 1:
+        raise ValueError("n_p must be positive")
+    return np.linspace(float(lo), float(hi), int(n_p))
+
+
+def _echo(table, c_down, c_up, n_refl, device):
+    """the two legs (one table call when the return leg has the down leg's speed) and one rtus_specular launch -> t [G, n_e, n_e]"""
+    down = table(c_down)
+    up = None if c_up is None or float(c_up) == float(c_down) else table(float(c_up))
+    return specular_times(down, up, n_refl=n_refl, device=device).reshape(n_refl, down.shape[0], down.shape[0])
+
+
+def backwall_echo_layers(z_if, c, z_back, xe, ze, x_lo, x_hi, n_p, *, c_up=None, taup=False, device=0):
+    """Pulse-echo times of a planar backwall under horizontal layers, for every pair of the aperture (xe, ze) and for every
+    candidate depth of ``z_back`` (a scalar or an array [G]) -> t [G, n_e, n_e].  Each backwall is sampled at ``n_p`` points evenly
+    over [x_lo, x_hi]; down leg: travel_time_layers(z_if, c) to the points, up leg the same with ``c[-1]`` replaced by ``c_up``
+    (skip_travel_time_layers' meaning: another speed is a mode conversion at the backwall; default c[-1]); then specular_times.
+    NaN where the reflection point is not inside the sampled span.  Every candidate must lie below the last interface."""
+    z_if, c = _medium(z_if, c)
+    zb = _candidates(z_back, "z_back")
+    if z_if.size and not np.all(zb > z_if[-1]):
+        raise ValueError("the backwall must lie below the last interface (z_back > z_if[-1])")
+    xs = _span_points(x_lo, x_hi, n_p)
+    xf, zf = np.tile(xs, zb.size), np.repeat(zb, xs.size)
+    return _echo(lambda cl: travel_time_layers(z_if, np.r_[c[:-1], cl], xe, ze, xf, zf, taup=taup, device=device), c[-1], c_up, zb.size,
+                 device)
+
+
+def backwall_echo_surface(x0, dx, zs, c1, c2, z_back, xe, ze, x_lo, x_hi, n_p, *, c_up=None, device=0):
+    """backwall_echo_layers under ONE measured front surface (travel_time_surface's profile ``zs`` at x0 + k dx, couplant ``c1``,
+    part ``c2`` on the way down and ``c_up`` on the way up; default c2) -> t [G, n_e, n_e] for the candidate depths ``z_back``."""
+    zb = _candidates(z_back, "z_back")
+    xs = _span_points(x_lo, x_hi, n_p)
+    xf, zf = np.tile(xs, zb.size), np.repeat(zb, xs.size)
+    return _echo(lambda cl: travel_time_surface(x0, dx, zs, c1, cl, xe, ze, xf, zf, device=device), float(c2), c_up, zb.size, device)
+
+
+def bore_echo_pipe(r_inner, xe, ze, theta_lo, theta_hi, n_p, *, c_down, c_up=None, params: Params = None, alpha_lo=None, alpha_hi=None,
+                   n_scan=None, device=0):
+    """Pulse-echo times of the pipe's bore, for every pair of the aperture behind the lens and for every candidate radius of
+    ``r_inner`` (a scalar or an array [G]) -> t [G, n_e, n_e].  Each bore is sampled at ``n_p`` angles evenly over
+    [theta_lo, theta_hi] on the circle of that radius about the pipe's centre (pipe_wall_grid's convention); the legs are
+    travel_time_pipe tables at wall speed ``c_down`` and ``c_up`` (default c_down; another speed is a mode conversion at the bore),
+    called with a solid bar (its own r_inner = 0) so that every candidate lies inside the wall it accepts.  The reference's lens
+    focuses on the pipe's axis: inside the wall an element's wave converges on a point near the axis, and the bore's echo is a
+    LEAST time only for pairs that mirror each other about the lens axis — the others come out NaN."""
+    p = _resolve(params)
+    r = _candidates(r_inner, "r_inner")
+    th = _span_points(theta_lo, theta_hi, n_p)
+    xf = (float(p.pipe_offset) + r[:, None] * np.sin(th)[None]).ravel()
+    zf = (r[:, None] * np.cos(th)[None]).ravel()
+    return _echo(lambda cl: travel_time_pipe(xe, ze, xf, zf, c3=cl, r_inner=0.0, params=p, alpha_lo=alpha_lo, alpha_hi=alpha_hi,
+                                             n_scan=n_scan, device=device), float(c_down), c_up, r.size, device)
+
+
+def fit_reflector(t_meas, model, lo, hi, *, n_grid=33, passes=3, weights=None, fit_delay=False, min_pairs=8, device=0):
+    """One parameter of a reflector (a backwall's depth, a bore's radius) from measured echo times t_meas [n_tx, n_rx] (NaN: no
+    echo), by least squares over [lo, hi].  ``model(values [G]) -> tt [G, n_tx, n_rx]`` is any callable, e.g.
+    ``lambda z: backwall_echo_surface(x0, dx, zs, c1, c2, z, xe, ze, x_lo, x_hi, n_p)``.
+
+    Each of ``passes`` passes takes ``n_grid`` values evenly over the bracket (first [lo, hi]), makes one model call and one
+    rtus_geom_misfit launch, and keeps the first value of least mean squared residual among those with at least ``min_pairs``
+    counting pairs; the next bracket is that value's two neighbours (cut to the bracket).  After the last pass a parabola through
+    the best value and its neighbours (where it is interior and all three count) gives the value, clamped to those neighbours;
+    mse, n and delay are then evaluated at it.
+
+    -> dict(value, mse, n, delay (0 unless ``fit_delay``: t_meas = model + delay), ok, history: per pass dict(values, mse, n,
+    best)).  ``ok`` is False when in some pass no value reaches min_pairs (value is then NaN), or when the first pass's best is
+    lo or hi: the range does not bracket the answer."""
+    tm = np.ascontiguousarray(t_meas, dtype=np.float64)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if tm.ndim != 2 or (w is not None and w.shape != tm.shape):
+        raise ValueError("t_meas must be [n_tx, n_rx] and weights of its shape")
+    n_grid, passes, min_pairs = int(n_grid), int(passes), int(min_pairs)
+    if n_grid < 3 or passes < 1 or not float(hi) > float(lo):
+        raise ValueError("need n_grid >= 3, passes >= 1 and lo < hi")
+    if min_pairs < (3 if fit_delay else 2):
+        raise ValueError(f"min_pairs must be at least {3 if fit_delay else 2}: one more than the fitted parameters")
+
+    def score(values):
+        n, sse, sr, sw = geom_misfit(model(values), tm, w, device=device)
+        mse, delay = _misfit_stats(n, sse, sr, sw, fit_delay)
+        return np.where(n >= min_pairs, mse, np.nan), n, delay
+
+    a, b, ok, history = float(lo), float(hi), True, []
+    fail = dict(value=np.nan, mse=np.nan, n=0, delay=np.nan, ok=False, history=history)
+    for it in range(passes):
+        values = np.linspace(a, b, n_grid)
+        mse, n, _ = score(values)
+        if not np.isfinite(mse).any():
+            return fail
+        k = int(np.nanargmin(mse))                       # the first of least mse
+        history.append(dict(values=values, mse=mse, n=n, best=k))
+        if it == 0 and k in (0, n_grid - 1):
+            ok = False
+        a, b = values[max(k - 1, 0)], values[min(k + 1, n_grid - 1)]
+    value = values[k]
+    if 0 < k < n_grid - 1 and np.isfinite(mse[k - 1]) and np.isfinite(mse[k + 1]):
+        d2 = (mse[k - 1] - mse[k]) + (mse[k + 1] - mse[k])
+        if d2 > 0:
+            value = min(max(value + 0.5 * (mse[k - 1] - mse[k + 1]) / d2 * (values[k + 1] - values[k]), a), b)
+    mse, n, delay = score(np.asarray([value]))
+    if not np.isfinite(mse[0]):
+        return fail
+    return dict(value=float(value), mse=float(mse[0]), n=int(n[0]), delay=float(delay[0]), ok=ok, history=history)
+
+
+def measure_reflector(fmc_or_analytic, fs, model, lo, hi, *, t0=0.0, margin, threshold=0.1, n_taps=63, **fit):
+    """The reflector's parameter from an FMC: per-pair gates from the model over fit_reflector's first-pass candidates (the least
+    model time of a pair minus ``margin`` to the greatest plus ``margin``; a pair without a model time has no gate), pick_echo_times
+    inside them, fit_reflector (options ``**fit``) on the valid picks -> fit_reflector's dict plus ``picks``: the dict of
+    pick_echo_times."""
+    tt = np.asarray(model(np.linspace(float(lo), float(hi), int(fit.get("n_grid", 33)))), dtype=np.float64)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # a pair that is NaN for every candidate: a NaN gate, no pick
+        g_lo, g_hi = np.nanmin(tt, axis=0) - float(margin), np.nanmax(tt, axis=0) + float(margin)
+    picks = pick_echo_times(fmc_or_analytic, fs, g_lo, g_hi, t0=t0, n_taps=n_taps, threshold=threshold, device=fit.get("device", 0))
+    out = fit_reflector(np.where(picks["valid"], picks["t"], np.nan), model, lo, hi, **fit)
+    out["picks"] = picks
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- the forward model: FMC simulator
 SIM_ANALYTIC = 0x1          # RTUS_SIM_ANALYTIC (include/rtus.h)
 SIM_ACCUMULATE = 0x2        # RTUS_SIM_ACCUMULATE

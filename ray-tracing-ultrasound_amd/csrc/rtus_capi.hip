@@ -72,6 +72,9 @@ hipError_t rtus_launch_echo_pick(const float* an, long long n_pairs, int n_t, do
                                  const double* g_lo, const double* g_hi, double* t_pick, float* amp, hipStream_t s);
 hipError_t rtus_launch_geom_misfit(const double* tt, int n_geom, int n_tx, int n_rx, const double* t_meas, const double* w, int* n,
                                    double* sse, double* sum_r, double* sum_w, hipStream_t s);
+hipError_t rtus_launch_specular(const double* tt_a, int n_a, const double* tt_b, int n_b, int n_refl, int n_p, double* t, double* pos,
+                                int* n_min, hipStream_t s);
+long long rtus_specular_blocks(int n_a, int n_b, int n_refl);
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
@@ -1132,6 +1135,47 @@ int rtus_geom_misfit(const double* tt, int n_geom, int n_tx, int n_rx, const dou
     S.out(dsw, sum_w, n_geom);
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_geom_misfit(dtt, n_geom, n_tx, n_rx, dtm, dw, dn, dq, dr, dsw, S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- specular echo times of sampled reflectors
+static int check_specular(const void* tt_a, int n_a, int n_b, int n_refl, int n_p, const void* t)
+{
+    if (!tt_a || !t || n_a <= 0 || n_b <= 0 || n_refl <= 0 || n_p <= 0) return RTUS_ERR_INVALID_ARG;
+    if ((long long)n_refl * n_p > 0x7fffffffLL || (long long)n_a * n_b > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    if (rtus_specular_blocks(n_a, n_b, n_refl) > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;      // one workgroup each, in one grid
+    return RTUS_OK;
+}
+
+int rtus_specular_dev(const double* d_tt_a, int n_a, const double* d_tt_b, int n_b, int n_refl, int n_p, double* d_t, double* d_pos,
+                      int* d_n_min, void* stream)
+{
+    int st = check_specular(d_tt_a, n_a, n_b, n_refl, n_p, d_t);
+    if (st) return st;
+    if (!d_tt_b && n_b != n_a) return RTUS_ERR_INVALID_ARG;
+    LAUNCH_TRY(rtus_launch_specular(d_tt_a, n_a, d_tt_b, n_b, n_refl, n_p, d_t, d_pos, d_n_min, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_specular(const double* tt_a, int n_a, const double* tt_b, int n_b, int n_refl, int n_p, double* t, double* pos, int* n_min,
+                  int device)
+{
+    int st = check_specular(tt_a, n_a, n_b, n_refl, n_p, t);
+    if (st) return st;
+    if (!tt_b && n_b != n_a) return RTUS_ERR_INVALID_ARG;
+    const size_t cols = (size_t)n_refl * n_p, n_out = (size_t)n_refl * n_a * n_b;
+    const bool one = !tt_b || (tt_b == tt_a && n_b == n_a);  // the same table both ways: uploaded once
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *da, *db, *dt, *dp;
+    int* dn;
+    S.in(da, tt_a, cols * n_a);
+    S.in(db, tt_b, one ? 0 : cols * n_b);
+    S.out(dt, t, n_out);
+    S.out(dp, pos, n_out);
+    S.out(dn, n_min, n_out);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_specular(da, n_a, db, n_b, n_refl, n_p, dt, dp, dn, S.a->stream));
     return S.finish();
 }
 

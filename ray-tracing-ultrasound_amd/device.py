@@ -687,6 +687,33 @@ def geom_misfit_dev(tt, t_meas, weights=None, n=None, sse=None, sum_r=None, sum_
     return n, sse, sum_r, sum_w
 
 
+def specular_dev(tt_a, tt_b=None, n_refl=1, out=None, pos=None, n_min=None):
+    """Specular echo times of sampled reflectors on device (rtus_specular_dev; api.specular_times' definition): tt_a float64
+    [n_a, n_refl * n_p], tt_b [n_b, n_refl * n_p] (default: tt_a) -> out float64 [n_refl, n_a, n_b] (geom_misfit_dev's ``tt``);
+    ``pos``: an optional float64 tensor of that size that receives the reflection point's index, ``n_min``: an optional int32 one
+    that receives the number of interior minima.  -> out, or the tuple of out followed by the optional tensors given.
+    Asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    _chk(tt_a, "tt_a")
+    if tt_b is not None:
+        _chk(tt_b, "tt_b")
+    n_refl = int(n_refl)
+    if tt_a.dim() != 2 or tt_a.numel() == 0 or n_refl < 1 or tt_a.shape[1] % n_refl:
+        raise ValueError("tt_a must be [n_a, n_refl * n_p]")
+    if tt_b is not None and (tt_b.dim() != 2 or tt_b.shape[0] == 0 or tt_b.shape[1] != tt_a.shape[1]):
+        raise ValueError("tt_b must be [n_b, n_refl * n_p], the columns of tt_a")
+    n_a, n_b = tt_a.shape[0], tt_a.shape[0] if tt_b is None else tt_b.shape[0]
+    out = _result(out, (n_refl, n_a, n_b), tt_a)
+    _optional(out.numel(), pos=pos)
+    _optional(out.numel(), torch.int32, n_min=n_min)
+    given = [t for t in (pos, n_min) if t is not None]
+    if not all(t.device == tt_a.device for t in (out, *given, *(() if tt_b is None else (tt_b,)))):
+        raise ValueError("tt_a, tt_b, out, pos and n_min must be on one device")
+    st = _lib.lib().rtus_specular_dev(_p(tt_a), n_a, _p(tt_b), n_b, n_refl, tt_a.shape[1] // n_refl, _p(out), _p(pos), _p(n_min),
+                                      _stream(tt_a))
+    _lib.check(st, "rtus_specular_dev")
+    return (out, *given) if given else out
+
+
 def _sim_out(n_tx, n_rx, n_t, pulse, out, analytic, ref):
     """the wavelet and result checks fmc_sim_dev and fmc_sim_echo_dev share -> out"""
     _chk(pulse, "pulse", torch.float32)
