@@ -489,7 +489,11 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
     if (item != (int)blockIdx.x) __syncthreads();           // the previous item's records are still being read by the slower waves
 #else
     {
-    const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    // A launch that carries the row table hands its work items out ALONG THE ROW BLOCKS first (blockIdx.x = bx gy + by: launch_layers
+    // flattens its grid): workgroups that start together then write into gy row blocks at once instead of into neighbouring 2-KB
+    // pieces of the same rows, which is what the store stream wants (DESIGN.md section 4 "Store stream").  Other launches keep x first.
+    const int bx = a.rowtab ? (int)(blockIdx.x / (unsigned)a.gy) : (int)blockIdx.x;
+    const int by = a.rowtab ? (int)(blockIdx.x % (unsigned)a.gy) : (int)blockIdx.y, bz = blockIdx.z;
 #endif
     // batched launch: problem bz
     const double* __restrict__ xe_p = a.xe + (size_t)bz * a.e_stride;
@@ -674,6 +678,9 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
             if ((tid & 63) == 0) hdr.bad[tid >> 6] = badw;
             __syncthreads();
             if (!__builtin_amdgcn_readfirstlane(hdr.bad[0] | hdr.bad[1] | hdr.bad[2] | hdr.bad[3])) {
+                // the rows leave WRITE-THROUGH (sc1, the store's cache-policy operand 16): a table that takes this path is larger than
+                // the L2s together, so a line kept there serves nobody and is only written back later, at the launch's end at the latest
+                constexpr int store_policy = 16;
                 size_t ot = o;
                 unsigned sot = 0;
                 for (int l = 0; l < ne; ++l) {                                           // a row per trip: wave-uniform
@@ -682,7 +689,7 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
                     const RowTabSlot* __restrict__ sl = &tab[(int)tq];
                     const double T = fma(sq, fma(sq, fma(sq, fma(sq, fma(sq, sl->c[5], sl->c[4]), sl->c[3]), sl->c[2]), sl->c[1]), sl->c[0]);
                     const u32x2 bits = {(unsigned)__double2loint(T), (unsigned)__double2hiint(T)};
-                    __builtin_amdgcn_raw_buffer_store_b64(bits, dest_rs(l, ot), f8, dest_so(sot), 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(bits, dest_rs(l, ot), f8, dest_so(sot), store_policy);
                     ot += nf; sot += row_bytes;
                 }
                 return;
@@ -849,7 +856,8 @@ static hipError_t launch_layers(const double* z_if, const double* c, int n_if, c
     }
     const dim3 grid((unsigned)(items < cap ? items : cap)), block(RTUS_BLOCK);
 #else
-    const dim3 grid(a.gx, a.gy, n_batch), block(RTUS_BLOCK);
+    // (row-table launches: x and y flattened into grid.x, y fastest: see the kernel; gx gy <= items < 2^31, within grid.x's limit)
+    const dim3 grid(a.rowtab ? a.gx * a.gy : a.gx, a.rowtab ? 1 : a.gy, n_batch), block(RTUS_BLOCK);
 #endif
     const bool taup = (flags & RTUS_TT_TAUP_TAIL) != 0;
     // Workgroups per CU: what the registers allow (8 for the 64-VGPR kernels).  Capping a launch of two rounds or more BELOW that with
