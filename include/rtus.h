@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 116 /* 0.1.15: rtus_specular* (specular echo times of sampled reflectors) */
+#define RTUS_VERSION 117 /* 0.1.16: rtus_skip_reflector* (skip legs off a sampled backwall) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -1152,6 +1152,60 @@ int rtus_specular_dev(const double *d_tt_a, int n_a, const double *d_tt_b, int n
                       double *d_t, double *d_pos, int *d_n_min, void *stream);
 int rtus_specular(const double *tt_a, int n_a, const double *tt_b, int n_b, int n_refl, int n_p,
                   double *t, double *pos, int *n_min, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_skip_reflector: skip legs off a sampled backwall.  A skip leg element e -> boundary point B -> focal point F is stationary
+ * over B in t(e -> B) + |F - B| / c_up (Fermat).  t(e -> B) is any table of this library over the boundary's points — through
+ * layers, a measured surface, the lens and pipe; the up leg is a straight segment in one medium.  This is rtus_specular's reduction
+ * with focal points in the place of receivers and the up leg formed on the fly: the n_f x n_p table of up legs is never stored.
+ * The Python layer builds on it the skip legs and the leg tables of multi-view TFM under a backwall of any sampled shape, under
+ * layers and under a measured surface (api.skip_travel_time_reflector, skip_travel_time_layers_profile,
+ * skip_travel_time_surface_profile, view_legs_layers_profile, view_legs_surface_profile, reflector_mask, backwall_profile).  NOT IN
+ * THE REFERENCE; checked bit for bit against tests/skip_reflector_numpy.py and against rtus_specular.
+ *   tt_down [n_e][n_p]  times from the n_e elements to the reflector's points, in order along the reflector — the shape any table
+ *                       call over (xb, zb) returns
+ *   xb, zb  [n_p]       the reflector's points;  c_up: the speed of the up leg;  xf, zf [n_f]: the focal points
+ *   tt      [n_e][n_f]  the leg table, row-major like every other leg table;  pos [n_e][n_f] fp64, nullable: the bounce point in
+ *                       units of the point index;  n_min [n_e][n_f] int32, nullable
+ * Definition, for element e and focal point f:
+ *   u_j: dx = xf - xb_j;  dz = zf - zb_j;  r2 = dx dx + dz dz;  d = sqrt(r2);  u_j = d / c_up — in exactly this order, each
+ *           product and the sum rounded on their own (no fused multiply-add), the root and the division correctly rounded.  This is
+ *           NumPy's np.sqrt(dx*dx + dz*dz) / c_up; it is not np.hypot.
+ *   S_j = tt_down[e][j] + u_j, one fp64 addition.  S_j is FINITE when isfinite(S_j).  A coordinate that is not finite makes its
+ *           S_j NaN or infinite, hence not finite: no special case.
+ *   No S_j finite: tt = pos = NaN, n_min = 0.
+ *   j* = the FIRST index attaining the least finite S_j.
+ *   n_min = the number of j in [1, n_p - 2] with S_(j-1), S_j, S_(j+1) all finite, S_j < S_(j-1) and S_j < S_(j+1).  A diagnostic:
+ *           above 1, two bounce points compete.
+ *   j* = 0 or j* = n_p - 1, or a neighbour of j* not finite: tt = NaN, pos = (double) j* — the bounce point is not bracketed by the
+ *           sampled span.
+ *   Otherwise, with a = S_(j*-1), b = S_(j*), c = S_(j*+1), in exactly this order and every operation rounded on its own (no
+ *           fused multiply-add; the division correctly rounded):
+ *             d1 = a - c;  d2 = (a - b) + (c - b);  delta = 0.5 d1 / d2;  tt = b - (0.25 d1) delta;  pos = j* + delta.
+ *   n_p < 3 is legal: every entry comes out NaN by the rules above.
+ *   Consequence: tt, pos and n_min are bit-equal to rtus_specular(tt_down, n_e, U, n_f, 1, n_p, ...) with U[f][j] = u_j.
+ *   Accuracy and sampling: the parabola's value error is third order in the point spacing in general; it is fourth order only where
+ *           S is symmetric about its minimum, the case rtus_specular's section quotes.  The constant grows as the focal point nears
+ *           the reflector.  One medium at 5900 m/s, 16 elements at 0.6 mm pitch on z = 0, a flat backwall at 30 mm sampled over
+ *           +-20 mm, 17 x 21 points over x +-8 mm, z 6 - 26 mm, against the mirror image: 4.3e-10, 6.3e-11, 7.3e-12 s at 41, 81,
+ *           161 points (1, 0.5, 0.25 mm); tilted by 5 degrees: 7.2e-10, 7.3e-11, 1.0e-11 s.  Sample the backwall at a quarter of a
+ *           millimetre or finer for points a few millimetres off the wall.  A point whose bounce falls outside the sampled span is
+ *           NaN, so the span must overhang the image.
+ *   Not checked: the straight up leg against the polyline.  On a strongly re-entrant profile an up leg may cross the reflector; it
+ *           is timed as if the boundary were not in its way.  Stationary maxima are not looked for.
+ *   Determinism: an entry's bits depend only on its own row of tt_down, the reflector and its own focal point — not on the other
+ *           entries of the call, nor on the launch shape, nor on which optional outputs are asked for.
+ *   Limits: null tt_down, xb, zb, xf, zf or tt, a size <= 0, c_up not finite or not > 0: -1; n_e n_f or the number of workgroups
+ *           (ceil(n_e / 8) ceil(n_f / 64)) beyond 2^31 - 1: -5; before any HIP call.  No workspace.  The _dev entry allocates
+ *           nothing and does not synchronise (capturable); the host twin stages through the device's arena and downloads only the
+ *           outputs asked for.
+ * Kernel, resources and measured figures on MI355X: DESIGN.md section 4 (skip legs off a sampled backwall).
+ * ---------------------------------------------------------------------------------------- */
+int rtus_skip_reflector_dev(const double *d_tt_down, int n_e, const double *d_xb, const double *d_zb, int n_p, double c_up,
+                            const double *d_xf, const double *d_zf, int n_f,
+                            double *d_tt, double *d_pos, int *d_n_min, void *stream);
+int rtus_skip_reflector(const double *tt_down, int n_e, const double *xb, const double *zb, int n_p, double c_up,
+                        const double *xf, const double *zf, int n_f, double *tt, double *pos, int *n_min, int device);
 
 #ifdef __cplusplus
 }

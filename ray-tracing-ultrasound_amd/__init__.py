@@ -14,7 +14,9 @@ from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits, 
                   travel_time_pipe, pipe_wall_grid, skip_travel_time_pipe, view_legs_pipe,
                   leg_amplitudes_pipe, view_amplitudes_pipe, pick_echo_times, geom_misfit, pipe_misfit, pipe_clearance, fit_pipe,
                   adaptive_tfm_pipe, gaussian_pulse, simulate_fmc, simulate_echoes, simulate_views, specular_times,
-                  backwall_echo_layers, backwall_echo_surface, bore_echo_pipe, fit_reflector, measure_reflector)
+                  backwall_echo_layers, backwall_echo_surface, bore_echo_pipe, fit_reflector, measure_reflector,
+                  skip_travel_time_reflector, reflector_mask, skip_travel_time_layers_profile, skip_travel_time_surface_profile,
+                  view_legs_layers_profile, view_legs_surface_profile, backwall_profile)
 
 __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "focal_delays", "tfm_image", "fmc_analytic",
            "measure_surface", "adaptive_tfm", "tfm_analytic", "tfm_phase", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
@@ -23,5 +25,7 @@ __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hi
            "view_amplitudes_surface", "tfm_weighted", "travel_time_pipe", "pipe_wall_grid", "skip_travel_time_pipe",
            "view_legs_pipe", "leg_amplitudes_pipe", "view_amplitudes_pipe", "pick_echo_times", "geom_misfit", "pipe_misfit",
            "pipe_clearance", "fit_pipe", "adaptive_tfm_pipe", "gaussian_pulse", "simulate_fmc", "simulate_echoes", "simulate_views", "specular_times",
-           "backwall_echo_layers", "backwall_echo_surface", "bore_echo_pipe", "fit_reflector", "measure_reflector", "Params",
+           "backwall_echo_layers", "backwall_echo_surface", "bore_echo_pipe", "fit_reflector", "measure_reflector",
+           "skip_travel_time_reflector", "reflector_mask", "skip_travel_time_layers_profile", "skip_travel_time_surface_profile",
+           "view_legs_layers_profile", "view_legs_surface_profile", "backwall_profile", "Params",
            "configure", "reference_elements", "ALPHA_MAX", "KEYS", "build", "lib", "RtusError"]

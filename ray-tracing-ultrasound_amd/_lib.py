@@ -177,6 +177,9 @@ PROTOTYPES = (
     # specular echo times of sampled reflectors
     ("rtus_specular_dev", i, [vp, i, vp, i, i, i, vp, vp, vp, vp], 116),
     ("rtus_specular", i, [vp, i, vp, i, i, i, vp, vp, vp, i], 116),
+    # skip legs off a sampled backwall
+    ("rtus_skip_reflector_dev", i, [vp, i, vp, vp, i, dd, vp, vp, i, vp, vp, vp, vp], 117),
+    ("rtus_skip_reflector", i, [vp, i, vp, vp, i, dd, vp, vp, i, vp, vp, vp, i], 117),
 )
 EXPORTS = tuple(p[0] for p in PROTOTYPES)
 

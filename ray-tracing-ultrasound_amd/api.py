@@ -1580,6 +1580,215 @@ def measure_reflector(fmc_or_analytic, fs, model, lo, hi, *, t0=0.0, margin, thr
     return out
 
 
+# ---------------------------------------------------------------------------------------------- skip legs off a sampled backwall
+def skip_travel_time_reflector(tt_down, xb, zb, c_up, xf, zf, *, return_pos=False, return_minima=False, out=None, device=0):
+    """Element x focal-point times of a SKIP leg off a reflector of any sampled shape -> tt [n_e, n_f]: element -> the reflector's
+    point B -> focal point F, stationary over B in tt_down[e, j] + |F - B_j| / c_up, refined by a parabola about the first least
+    sum (include/rtus.h, rtus_skip_reflector: rtus_specular's rules with the up leg formed on the fly).  ``tt_down`` [n_e, n_p]:
+    times from the elements to the reflector's points (xb, zb) in order along it — what any table call over (xb, zb) returns;
+    ``c_up``: the speed of the up leg (another speed than the down leg's is a mode conversion at the reflector).  NaN where no sum
+    is finite or the least one is not bracketed by the sampled span.  ``return_pos``: also the bounce point in units of the point
+    index; ``return_minima``: also n_min int32, the number of strict interior minima (above 1: two bounce points compete) ->
+    (tt, pos, n_min), those asked for.  ``out``: optional float64 [n_e, n_f] buffer for tt.
+
+    Accuracy and sampling: the parabola's value is third order in the point spacing in general, fourth order only where the sum is
+    symmetric about its minimum (the case rtus_specular quotes), and the constant grows as the focal point nears the reflector.
+    One medium at 5900 m/s, 16 elements, a flat backwall at 30 mm sampled over +-20 mm, points at z 6 - 26 mm against the mirror
+    image: 4.3e-10, 6.3e-11, 7.3e-12 s at 41, 81, 161 points; tilted by 5 degrees 7.2e-10, 7.3e-11, 1.0e-11 s.  Sample at a
+    quarter of a millimetre or finer for points a few millimetres off the wall.  A point whose bounce falls outside the sampled
+    span is NaN, so the span must overhang the image.  The straight up leg is not checked against the reflector itself.  Not in
+    the reference."""
+    tt_down = np.ascontiguousarray(tt_down, dtype=np.float64)
+    xb, zb, xf, zf = _points(xb, zb, xf, zf)
+    if tt_down.ndim != 2 or tt_down.size == 0 or tt_down.shape[1] != xb.size:
+        raise ValueError("tt_down must be [n_e, n_p] with one column per reflector point (xb, zb)")
+    if xf.size == 0:
+        raise ValueError("xf / zf must hold at least one focal point")
+    c_up = float(c_up)
+    if not (np.isfinite(c_up) and c_up > 0):
+        raise ValueError("c_up must be finite and positive")
+    shape = (tt_down.shape[0], xf.size)
+    tt = _out(out, shape, np.float64)
+    pos = np.empty(shape, dtype=np.float64) if return_pos else None
+    n_min = np.empty(shape, dtype=np.int32) if return_minima else None
+    st = _lib.lib().rtus_skip_reflector(_ptr(tt_down), shape[0], _ptr(xb), _ptr(zb), xb.size, c_up, _ptr(xf), _ptr(zf), xf.size,
+                                        _ptr(tt), _ptr(pos), _ptr(n_min), int(device))
+    _lib.check(st, "rtus_skip_reflector")
+    extra = [v for v in (pos, n_min) if v is not None]
+    return (tt, *extra) if extra else tt
+
+
+def _reflector(xb, zb):
+    xb, zb = _f64(xb, "xb"), _f64(zb, "zb")
+    if xb.shape != zb.shape or xb.size < 2 or not np.all(np.diff(xb) > 0):
+        raise ValueError("xb / zb must pair up, hold at least two points, and xb must be strictly increasing")
+    return xb, zb
+
+
+def reflector_mask(xb, zb, xf, zf):
+    """Which focal points a skip leg off the sampled reflector (xb, zb) can serve -> bool [n_f]: True where xb[0] <= xf <= xb[-1]
+    and zf < np.interp(xf, xb, zb) — the point lies strictly above the polyline through the reflector's points (z down).  ``xb``
+    must be strictly increasing.  Host only."""
+    xb, zb = _reflector(xb, zb)
+    xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
+    if xf.shape != zf.shape:
+        raise ValueError("xf / zf must pair up")
+    with np.errstate(invalid="ignore"):
+        return (xf >= xb[0]) & (xf <= xb[-1]) & (zf < np.interp(xf, xb, zb))
+
+
+def _skip_profile(down, xb, zb, c_up, xf, zf, mask, return_pos, device):
+    """the kernel on a down table, the validity mask, and the bounce point in metres"""
+    r = skip_travel_time_reflector(down, xb, zb, c_up, xf, zf, return_pos=return_pos, device=device)
+    tt = r[0] if return_pos else r
+    tt[:, ~mask] = np.nan
+    if not return_pos:
+        return tt
+    pos = r[1]
+    x_back = np.full(pos.shape, np.nan)
+    fin = np.isfinite(pos)
+    x_back[fin] = np.interp(pos[fin], np.arange(xb.size, dtype=np.float64), xb)
+    x_back[:, ~mask] = np.nan
+    return tt, x_back
+
+
+def _layers_profile_args(z_if, xb, zb, xf, zf):
+    """the checks and the mask the layered profile functions share -> (xb, zb, xf, zf, mask)"""
+    xb, zb = _reflector(xb, zb)
+    xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
+    if xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    front = float(z_if[-1]) if len(z_if) else -np.inf
+    if not np.all(zb > front):
+        raise ValueError("the backwall must lie below the last interface (every zb > z_if[-1])")
+    if len(z_if) > MAX_LAYERS:
+        raise ValueError(f"at most {MAX_LAYERS} interfaces above the backwall")
+    with np.errstate(invalid="ignore"):
+        return xb, zb, xf, zf, (zf > front) & reflector_mask(xb, zb, xf, zf)
+
+
+def skip_travel_time_layers_profile(z_if, c, xb, zb, xe, ze, xf, zf, *, c_up=None, taup=False, return_pos=False, device=0):
+    """skip_travel_time_layers under a backwall of any sampled shape -> tt [n_e, n_f]: down through the layers ``z_if`` / ``c`` to
+    the backwall's points (xb, zb) (travel_time_layers; ``xb`` strictly increasing, every ``zb`` below z_if[-1]), then up at
+    ``c_up`` (default c[-1]; another speed is a mode conversion) to the point (skip_travel_time_reflector, which also states the
+    accuracy and the sampling to choose: a quarter of a millimetre or finer, the span overhanging the image).  NaN where the point
+    is not strictly below z_if[-1] or ``reflector_mask`` is False, and where the bounce is not bracketed by the span.
+    ``return_pos``: -> (tt, x_back), the bounce point's x in metres (np.interp of the bounce index over xb).  A tapered, corroded
+    or machined backwall, a weld root; the profile may come from ``backwall_profile``.  Not in the reference."""
+    z_if, c = _medium(z_if, c)
+    xb, zb, xf, zf, mask = _layers_profile_args(z_if, xb, zb, xf, zf)
+    c_up = float(c[-1]) if c_up is None else float(c_up)
+    down = travel_time_layers(z_if, c, xe, ze, xb, zb, taup=taup, device=device)
+    return _skip_profile(down, xb, zb, c_up, xf, zf, mask, return_pos, device)
+
+
+def _surface_profile_args(x0, dx, zs, xb, zb, xf, zf):
+    """the checks and the mask the profile functions under a measured surface share -> (xb, zb, xf, zf, mask)"""
+    zs = _f64(zs, "zs")
+    xb, zb = _reflector(xb, zb)
+    xf, zf = _f64(xf, "xf"), _f64(zf, "zf")
+    if xf.shape != zf.shape:
+        raise ValueError("xe/ze and xf/zf must pair up")
+    if zs.size < 2 or not float(dx) > 0:
+        raise ValueError("the front profile needs at least two samples and dx > 0")
+    xs = float(x0) + np.arange(zs.size) * float(dx)
+    if not (xb[0] >= xs[0] and xb[-1] <= xs[-1] and np.all(zb > np.interp(xb, xs, zs))):
+        raise ValueError("the backwall must lie inside the front profile's extent and strictly below it")
+    with np.errstate(invalid="ignore"):
+        below = (xf >= xs[0]) & (xf <= xs[-1]) & (zf > np.interp(xf, xs, zs))
+    return xb, zb, xf, zf, below & reflector_mask(xb, zb, xf, zf)
+
+
+def skip_travel_time_surface_profile(x0, dx, zs, c1, c2, xb, zb, xe, ze, xf, zf, *, c_up=None, return_pos=False, device=0):
+    """skip_travel_time_layers_profile under ONE measured front surface (travel_time_surface's profile ``zs`` at x0 + k dx, couplant
+    ``c1``, part ``c2`` on the way down and ``c_up`` on the way up; default c2) -> tt [n_e, n_f], with ``return_pos`` (tt, x_back).
+    The down table is travel_time_surface to the backwall's points.  NaN where the point is outside the front profile's extent, not
+    strictly below the front profile, or where ``reflector_mask`` is False.  This mask is the POLYLINE through the front profile's
+    samples, not travel_time_surface's spline: a point between the two is masked by one and not the other.  The backwall must lie
+    inside the extent and strictly below the polyline.  Accuracy and sampling: skip_travel_time_reflector.  Not in the reference."""
+    xb, zb, xf, zf, mask = _surface_profile_args(x0, dx, zs, xb, zb, xf, zf)
+    c_up = float(c2) if c_up is None else float(c_up)
+    down = travel_time_surface(x0, dx, zs, c1, c2, xe, ze, xb, zb, device=device)
+    return _skip_profile(down, xb, zb, c_up, xf, zf, mask, return_pos, device)
+
+
+def _view_legs_profile(legs, direct, down_table, skip):
+    """{leg: tt}: direct legs as today, one down table per down mode shared by the two skip legs that start in it"""
+    out, down = {}, {}
+    for g in legs:
+        if len(g) == 1:
+            out[g] = direct(g)
+        else:
+            if g[0] not in down:
+                down[g[0]] = down_table(g[0])
+            out[g] = skip(down[g[0]], g[1])
+    return out
+
+
+def view_legs_layers_profile(z_if, c_above, c_l, c_t, xb, zb, xe, ze, xf, zf, *, legs=LEGS, device=0):
+    """view_legs_layers under a backwall of any sampled shape (xb, zb) -> {leg: tt [n_e, n_f]} in the shape tfm_views and
+    simulate_views take.  Direct legs: travel_time_layers; skip legs: skip_travel_time_layers_profile's, the down table made once
+    per down mode (LL and LT share the L table, TL and TT the T table)."""
+    legs = _legs_wanted(legs)
+    z_if = list(np.atleast_1d(np.asarray(z_if, dtype=np.float64)))
+    c_above = list(np.atleast_1d(np.asarray(c_above, dtype=np.float64)))
+    if len(c_above) != len(z_if):
+        raise ValueError("need len(c_above) == len(z_if)")
+    sp = {"L": float(c_l), "T": float(c_t)}
+    xb, zb, xf, zf, mask = _layers_profile_args(z_if, xb, zb, xf, zf)
+    return _view_legs_profile(
+        legs, lambda m: travel_time_layers(z_if, c_above + [sp[m]], xe, ze, xf, zf, device=device),
+        lambda m: travel_time_layers(z_if, c_above + [sp[m]], xe, ze, xb, zb, device=device),
+        lambda down, m: _skip_profile(down, xb, zb, sp[m], xf, zf, mask, False, device))
+
+
+def view_legs_surface_profile(x0, dx, zs, c1, c_l, c_t, xb, zb, xe, ze, xf, zf, *, legs=LEGS, device=0):
+    """view_legs_surface under a backwall of any sampled shape (xb, zb) -> {leg: tt [n_e, n_f]}.  Direct legs: travel_time_surface;
+    skip legs: skip_travel_time_surface_profile's, the down table made once per down mode.  Measure the front (measure_surface),
+    the back (backwall_profile on the L-L image), then image the views through both."""
+    legs = _legs_wanted(legs)
+    sp = {"L": float(c_l), "T": float(c_t)}
+    xb, zb, xf, zf, mask = _surface_profile_args(x0, dx, zs, xb, zb, xf, zf)
+    return _view_legs_profile(
+        legs, lambda m: travel_time_surface(x0, dx, zs, c1, sp[m], xe, ze, xf, zf, device=device),
+        lambda m: travel_time_surface(x0, dx, zs, c1, sp[m], xe, ze, xb, zb, device=device),
+        lambda down, m: _skip_profile(down, xb, zb, sp[m], xf, zf, mask, False, device))
+
+
+def backwall_profile(image, x0, dx, z_lo, dz, *, z_min=None, threshold=0.1):
+    """The backwall's depth profile read off an envelope image on the host.  ``image`` [n_x, n_z]: column x0 + k dx, depth
+    z_lo + j dz — measure_surface's ``image`` layout, e.g. the L-L envelope TFM of the part.  In every column the brightest pixel
+    at a depth >= ``z_min`` (default: the whole column; the first of equals) is refined by the three-point parabola on the
+    amplitudes a, b, c about it, delta = 0.5 (a - c) / ((a - b) + (c - b)) (0 where the three are equal), depth
+    z_lo + (j + delta) dz; NaN when the brightest pixel is the first allowed or the last one (the peak is not inside the window).
+    Then surface_profile's rules: valid where the depth is finite and the amplitude at least ``threshold`` times the largest,
+    trimmed to the first through last valid column, interior invalid columns filled by linear interpolation in x; ValueError when
+    fewer than 4 columns remain.  -> dict(x0, dx, zs, valid [n_x], z_peak [n_x], amplitude [n_x]): xb = x0 + arange(len(zs)) dx and
+    zb = zs feed skip_travel_time_layers_profile, view_legs_layers_profile and their surface twins."""
+    img = np.asarray(image, dtype=np.float64)
+    if img.ndim != 2 or img.shape[0] < 1:
+        raise ValueError("image must be [n_x, n_z]")
+    if not (np.isfinite(dz) and dz > 0 and np.isfinite(z_lo) and np.isfinite(x0) and np.isfinite(dx) and dx > 0):
+        raise ValueError("need finite x0, z_lo and dx, dz > 0")
+    n_z = img.shape[1]
+    j_min = 0 if z_min is None else max(int(np.ceil((float(z_min) - float(z_lo)) / float(dz) - 1e-9)), 0)
+    if n_z - j_min < 3:
+        raise ValueError("the depth window at or below z_min must hold at least 3 pixels")
+    j = j_min + np.argmax(np.where(np.isnan(img[:, j_min:]), -np.inf, img[:, j_min:]), axis=1)
+    inside = (j > j_min) & (j < n_z - 1)
+    jc = np.clip(j, 1, n_z - 2)
+    k = np.arange(img.shape[0])
+    a, b, c = img[k, jc - 1], img[k, jc], img[k, jc + 1]
+    with np.errstate(all="ignore"):
+        den = (a - b) + (c - b)
+        delta = np.where(den != 0, 0.5 * (a - c) / den, 0.0)
+    z_peak = np.where(inside, float(z_lo) + (jc + delta) * float(dz), np.nan)
+    amp = img[k, j]
+    r = surface_profile(x0, dx, z_peak, amp, threshold)
+    r.update(z_peak=z_peak, amplitude=amp)
+    return r
+
+
 # ---------------------------------------------------------------------------------------------- the forward model: FMC simulator
 SIM_ANALYTIC = 0x1          # RTUS_SIM_ANALYTIC (include/rtus.h)
 SIM_ACCUMULATE = 0x2        # RTUS_SIM_ACCUMULATE

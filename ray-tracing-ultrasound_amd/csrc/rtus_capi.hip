@@ -75,6 +75,9 @@ hipError_t rtus_launch_geom_misfit(const double* tt, int n_geom, int n_tx, int n
 hipError_t rtus_launch_specular(const double* tt_a, int n_a, const double* tt_b, int n_b, int n_refl, int n_p, double* t, double* pos,
                                 int* n_min, hipStream_t s);
 long long rtus_specular_blocks(int n_a, int n_b, int n_refl);
+hipError_t rtus_launch_skip_reflector(const double* tt_down, int n_e, const double* xb, const double* zb, int n_p, double c_up,
+                                      const double* xf, const double* zf, int n_f, double* tt, double* pos, int* n_min, hipStream_t s);
+long long rtus_skip_reflector_blocks(int n_e, int n_f);
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
@@ -1176,6 +1179,50 @@ int rtus_specular(const double* tt_a, int n_a, const double* tt_b, int n_b, int 
     S.out(dn, n_min, n_out);
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_specular(da, n_a, db, n_b, n_refl, n_p, dt, dp, dn, S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- skip legs off a sampled backwall
+static int check_skip_reflector(const void* tt_down, int n_e, const void* xb, const void* zb, int n_p, double c_up, const void* xf,
+                                const void* zf, int n_f, const void* tt)
+{
+    if (!tt_down || !xb || !zb || !xf || !zf || !tt || n_e <= 0 || n_p <= 0 || n_f <= 0) return RTUS_ERR_INVALID_ARG;
+    if (!isfinite(c_up) || !(c_up > 0)) return RTUS_ERR_INVALID_ARG;
+    if ((long long)n_e * n_f > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    if (rtus_skip_reflector_blocks(n_e, n_f) > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;        // one workgroup each, in one grid
+    return RTUS_OK;
+}
+
+int rtus_skip_reflector_dev(const double* d_tt_down, int n_e, const double* d_xb, const double* d_zb, int n_p, double c_up,
+                            const double* d_xf, const double* d_zf, int n_f, double* d_tt, double* d_pos, int* d_n_min, void* stream)
+{
+    int st = check_skip_reflector(d_tt_down, n_e, d_xb, d_zb, n_p, c_up, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_skip_reflector(d_tt_down, n_e, d_xb, d_zb, n_p, c_up, d_xf, d_zf, n_f, d_tt, d_pos, d_n_min,
+                                          (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_skip_reflector(const double* tt_down, int n_e, const double* xb, const double* zb, int n_p, double c_up, const double* xf,
+                        const double* zf, int n_f, double* tt, double* pos, int* n_min, int device)
+{
+    int st = check_skip_reflector(tt_down, n_e, xb, zb, n_p, c_up, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t n_out = (size_t)n_e * n_f;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dd, *dxb, *dzb, *dxf, *dzf, *dt, *dp;
+    int* dn;
+    S.in(dd, tt_down, (size_t)n_e * n_p);
+    S.in(dxb, xb, n_p);
+    S.in(dzb, zb, n_p);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dt, tt, n_out);
+    S.out(dp, pos, n_out);
+    S.out(dn, n_min, n_out);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_skip_reflector(dd, n_e, dxb, dzb, n_p, c_up, dxf, dzf, n_f, dt, dp, dn, S.a->stream));
     return S.finish();
 }
 

@@ -10,7 +10,7 @@
 // operands.  A lane carries, per transmit row, the least sum so far, its index, the previous sum and whether that one fell below
 // its predecessor (for n_min); the three sums about j* are formed again from the tables at the end — the same fp64 addition, the
 // same bits.  A pair's bits depend on its own two rows only: not on the tile it falls into, nor on the launch shape.
-#include "rtus_device.h"
+#include "rtus_specular.h"         // spec_finite_or_nan, SpecRow, spec_row_step, spec_refine: shared with rtus_skip_reflector.hip
 
 #define SPEC_TI 8                    // transmit rows per workgroup (2 per wave)
 #define SPEC_JC 32                   // points per LDS tile (16.6 KB: eight workgroups per CU, the VGPR limit)
@@ -28,20 +28,6 @@ struct SpecArgs {
     size_t ld;                       // n_refl * n_p
 };
 
-// a sum that is not finite becomes NaN: every comparison with it is then false (an infinity has a zero low word, so the high word
-// alone turns it into a quiet NaN)
-__device__ __forceinline__ double spec_finite_or_nan(double s)
-{
-    const bool inf = __builtin_amdgcn_class(s, 0x204);       // -inf | +inf: one v_cmp_class_f64
-    return __hiloint2double(inf ? 0x7ff80000 : __double2hiint(s), __double2loint(s));
-}
-
-struct SpecRow {
-    double best, prev;
-    int jbest, n_min;
-    bool prev_down;
-};
-
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_specular_kernel(SpecArgs a)
 {
     __shared__ double tile[SPEC_JC * SPEC_LD];
@@ -55,10 +41,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_specular_kernel(SpecArgs a)
 
     SpecRow row[SPEC_ROWS];
 #pragma unroll
-    for (int r = 0; r < SPEC_ROWS; ++r) {
-        row[r].best = __builtin_inf(); row[r].prev = __builtin_nan("");
-        row[r].jbest = -1; row[r].n_min = 0; row[r].prev_down = false;
-    }
+    for (int r = 0; r < SPEC_ROWS; ++r) spec_row_init(row[r]);
 
     for (int j0 = 0; j0 < a.n_p; j0 += SPEC_JC) {
         const int nj = min(SPEC_JC, a.n_p - j0);
@@ -78,14 +61,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_specular_kernel(SpecArgs a)
             const double* __restrict__ ar = a.ta + (size_t)i * a.ld + col0 + j0;
             SpecRow w = row[r];
 #pragma unroll 8
-            for (int c = 0; c < nj; ++c) {
-                const double s = spec_finite_or_nan(ar[c] + tile[c * SPEC_LD + lane]);
-                const bool down = s < w.prev, up = w.prev < s;
-                w.n_min += (w.prev_down && up) ? 1 : 0;      // the point before this one is a strict interior minimum
-                w.prev_down = down;
-                w.prev = s;
-                if (s < w.best) { w.best = s; w.jbest = j0 + c; }   // strict: the first index of the least sum
-            }
+            for (int c = 0; c < nj; ++c) spec_row_step<true>(w, spec_finite_or_nan(ar[c] + tile[c * SPEC_LD + lane]), j0 + c);
             row[r] = w;
         }
     }
@@ -104,14 +80,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_specular_kernel(SpecArgs a)
                 const double* __restrict__ pa = a.ta + (size_t)i * a.ld + col0 + js;
                 const double* __restrict__ pb = a.tb + (size_t)k * a.ld + col0 + js;
                 const double sa = pa[-1] + pb[-1], sb = pa[0] + pb[0], sc = pa[1] + pb[1];
-                if (fabs(sa) <= 1.7976931348623157e308 && fabs(sc) <= 1.7976931348623157e308) {
-#pragma clang fp contract(off)                               // the header's order, every operation rounded on its own
-                    const double d1 = sa - sc;
-                    const double d2 = (sa - sb) + (sc - sb);
-                    const double delta = 0.5 * d1 / d2;
-                    t = sb - (0.25 * d1) * delta;
-                    p = (double)js + delta;
-                }
+                spec_refine(sa, sb, sc, js, t, p);
             }
         }
         const size_t o = (g * a.n_a + i) * a.n_b + k;

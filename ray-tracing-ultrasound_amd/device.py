@@ -714,6 +714,34 @@ def specular_dev(tt_a, tt_b=None, n_refl=1, out=None, pos=None, n_min=None):
     return (out, *given) if given else out
 
 
+def skip_reflector_dev(tt_down, xb, zb, c_up, xf, zf, out=None, pos=None, n_min=None):
+    """Skip legs off a sampled backwall on device (rtus_skip_reflector_dev; api.skip_travel_time_reflector's definition): tt_down
+    float64 [n_e, n_p], the reflector's points xb / zb [n_p], the up leg's speed ``c_up``, focal points xf / zf [n_f] -> out float64
+    [n_e, n_f]; ``pos``: an optional float64 tensor of that size that receives the bounce point's index, ``n_min``: an optional
+    int32 one that receives the number of interior minima.  -> out, or the tuple of out followed by the optional tensors given.
+    Asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    _chk(tt_down, "tt_down")
+    n_p, n_f = _pair(xb, zb, xf, zf)
+    if tt_down.dim() != 2 or tt_down.numel() == 0 or tt_down.shape[1] != n_p:
+        raise ValueError("tt_down must be [n_e, n_p] with one column per reflector point (xb, zb)")
+    if n_f == 0:
+        raise ValueError("xf / zf must hold at least one focal point")
+    c_up = float(c_up)
+    if not (np.isfinite(c_up) and c_up > 0):
+        raise ValueError("c_up must be finite and positive")
+    n_e = tt_down.shape[0]
+    out = _result(out, (n_e, n_f), tt_down)
+    _optional(out.numel(), pos=pos)
+    _optional(out.numel(), torch.int32, n_min=n_min)
+    given = [t for t in (pos, n_min) if t is not None]
+    if not all(t.device == tt_down.device for t in (xb, zb, xf, zf, out, *given)):
+        raise ValueError("tt_down, xb, zb, xf, zf, out, pos and n_min must be on one device")
+    st = _lib.lib().rtus_skip_reflector_dev(_p(tt_down), n_e, _p(xb), _p(zb), n_p, c_up, _p(xf), _p(zf), n_f, _p(out), _p(pos),
+                                            _p(n_min), _stream(tt_down))
+    _lib.check(st, "rtus_skip_reflector_dev")
+    return (out, *given) if given else out
+
+
 def _sim_out(n_tx, n_rx, n_t, pulse, out, analytic, ref):
     """the wavelet and result checks fmc_sim_dev and fmc_sim_echo_dev share -> out"""
     _chk(pulse, "pulse", torch.float32)
