@@ -477,7 +477,10 @@ int rtus_tt_lens_f32_multi_dev(const rtus_lens *lens, double alpha_lo, double al
  * Guarantee: every interior local minimum whose basin spans at least one profile segment dx centred on it is found — the basin
  * running from the minimum to its neighbouring stationary points of T or to the ends of the extent; a minimum qualifies when
  * each neighbouring STATIONARY point is at least dx / 2 away (an end of the extent always does).  Narrower minima may be
- * missed; a missed minimum can only make the reported time later (or NaN), never earlier.
+ * missed; a missed minimum can only make the reported time later (or NaN), never earlier.  The entry is the least T over the
+ * found minima where there are at most three of them.  With four or more, the three are chosen by a lower bound of each one's T
+ * taken at a scan point next to it (spacing dx / 4: within T'' (dx / 4)^2 of the minimum's own T, ~2e-8 s on a 1 mm grid); the
+ * least minimum can be left out where it is within that of the third chosen one, and the entry is then late by at most that much.
  * Determinism: an entry depends only on its element, its focal point, the profile and the speeds — not on which other elements
  * or focal points share the call (the bits of a row block or a focal-point subset are those of the whole table).
  *

@@ -13,15 +13,25 @@
 //      so the scan tests the SIGN of T' at every P_j:  g2 (the focal point's term: one v_rsq_f32 per lane and point) is shared
 //      by the workgroup's elements, -(c2 / c1) g1 (the element's term) is computed once per (element, point) into LDS and read
 //      as a broadcast.  Per (element, point) that is one compare plus lane-mask logic on the scalar unit; a lane whose sign
-//      goes from - to + ranks the bracket [P_j, P_j+1] by an fp32 estimate of T there and keeps the SURF_K best.
-//   3. Each kept bracket within the fp32 ranking margin of the best (and always the best two) is refined in fp64: safeguarded
-//      Newton (bisection when a step leaves the bracket or T'' <= 0) on T'(x) = 0 with the cubic's analytic s' and s''.  The
-//      entry is the least refined time.  Where the fp32 sign at a bracket end was wrong (|T'| below fp32 resolution: within
-//      ~1e-8 m of the root) the fp64 signs pick the neighbouring interval instead.
+//      goes from - to + ranks the bracket [P_j, P_j+1] by an fp32 lower bound of its minimum's T (step 3) and keeps the SURF_K best.
+//   3. The kept brackets are refined in fp64: safeguarded Newton (bisection when a step leaves the bracket or T'' <= 0) on
+//      T'(x) = 0 with the cubic's analytic s' and s''.  The entry is the least refined time.  Where the fp32 sign at a bracket
+//      end was wrong (|T'| below fp32 resolution: within ~1e-8 m of the root) the fp64 signs pick the neighbouring interval
+//      instead.  The first two are refined always, the third unless it cannot win: the scan's figure for a bracket is a LOWER
+//      BOUND of its minimum's time, T(P_j+1) - (dx / 4) T'(P_j+1) at the bracket's right scan point (T' grows from 0 at the
+//      root to T'(P_j+1) over less than dx / 4: exact where T' is monotone there, and where T'' is linear as long as the next
+//      stationary point is dx / 2 away), and the third bracket is skipped when its bound is later than the best REFINED time by
+//      more than the fp32 error of the bound (4e-6 relative).  (T(P_j+1) itself is above the minimum's time by up to
+//      T'' (dx / 4)^2 / 2, ~1e-8 s on a 1 mm grid, a different amount for each bracket: a third bracket skipped on that figure
+//      against the best such figure — as it was — loses the entry's least minimum where three minima lie within that error of
+//      each other: DESIGN.md, tests/test_gpu_surface_branches.py.)
 //
 // Guarantee: a minimum whose neighbouring stationary points are at least dx / 2 away on both sides (the ends of the extent do
 // not count) has a scan point in its decreasing part and the next one in its increasing part (spacing dx / 4: a quarter of
-// margin for the fp32 signs) and is found.  Narrower minima may be missed, which can only make the entry later (or NaN).
+// margin for the fp32 signs) and is bracketed; the entry is the least T over such minima WHERE THE ENTRY HAS AT MOST SURF_K = 3
+// BRACKETS.  With four or more, the fourth and later are still dropped on the scan's figure (the three least bounds are kept):
+// the least minimum can be dropped where its time is within T'' (dx / 4)^2 of the third kept one's, and the entry is then late
+// by at most that.  Narrower minima may be missed.  Either can only make the entry later (or NaN).
 //
 // Determinism: every value an entry is made of is computed from its own element, focal point, the profile and the speeds,
 // by code that does not depend on the element's slot in the workgroup or on the lane: the entry has the same bits whatever
@@ -57,7 +67,7 @@
 struct SurfArgs {
     double x0, dx, hq, inv_dx, xend;   // hq = dx / SURF_SUB
     double c1, c2, xo, zo;             // (xo, zo): origin of the fp32 scan coordinates
-    float ic1f, ic2f, k21f;            // 1 / c1, 1 / c2, c2 / c1
+    float ic1f, ic2f, k21f, hqic2f;    // 1 / c1, 1 / c2, c2 / c1, hq / c2
     int n_s, m, n_e, n_f;
     const double* __restrict__ xe;
     const double* __restrict__ ze;
@@ -282,16 +292,14 @@ __device__ __forceinline__ PwAngle pw_angle(double th, double xlo, double xhi)
 // the least refined time over the kept brackets of one (element, focal point); written to tt (and xent).  T(x): the travel time
 // and its derivatives at x; band(x): whether a root at x counts (always, for elements)
 template <class TF, class BF>
-__device__ __forceinline__ double surf_refine(TF T_at, BF band, int m, double x0, double hq, bool ok, float t0, float t1,
-                                         float t2, int j0, int j1, int j2, double* __restrict__ tt_out, double* __restrict__ xent_out)
+__device__ __forceinline__ double surf_refine(TF T_at, BF band, int m, double x0, double hq, bool ok, float lb2, int j0, int j1, int j2,
+                                              double* __restrict__ tt_out, double* __restrict__ xent_out)
 {
-    // fp32 ranking margin: the estimates carry ~1e-7 relative error (fp32 coordinates and legs); keep what might be the best
-    const float margin = 4e-6f * t0;
     double best = NAN, bx = NAN;
     for (int k = 0; k < SURF_K; ++k) {
         const int j = k == 0 ? j0 : (k == 1 ? j1 : j2);
-        const float tk = k == 0 ? t0 : (k == 1 ? t1 : t2);
-        if (!ok || j < 0 || (k >= 2 && !(tk <= t0 + margin))) continue;
+        // the third: not when the lower bound of its minimum's time (less the bound's fp32 error) is after the best refined time
+        if (!ok || j < 0 || (k >= 2 && (double)lb2 > fma(4e-6, best, best))) continue;       // (best NaN: refined)
         int jl, jh;
         if (!rtus_bracket_fix(j, m, [&](int jp) { return T_at(fma((double)jp, hq, x0)).d1; }, jl, jh)) continue;
         double x;
@@ -427,7 +435,8 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
             for (int e = 0; e < SURF_EB; ++e) {
                 const bool pos = g2 > ng[e];
                 if (pos && neg[e]) {                                    // - -> + between P_j-1 and P_j: a minimum
-                    const float t = fmaf(tin, a.ic2f, ((const float*)&st1[jj][0])[e]);
+                    // T(P_j) - hq T'(P_j): a lower bound of the minimum's time (T' c2 = g2 - ng)
+                    const float t = fmaf(ng[e] - g2, a.hqic2f, fmaf(tin, a.ic2f, ((const float*)&st1[jj][0])[e]));
                     RTUS_KEEP3(t, j - 1, bt[e], bj[e]);
                 }
                 if constexpr (MODE == SURF_PW) neg[e] = !pos && ng[e] == ng[e];       // out of band (NaN): neither side of a bracket
@@ -465,8 +474,8 @@ __global__ void __launch_bounds__(RTUS_BLOCK) rtus_surface_kernel(SurfArgs a)
                 return true;
             };
             const bool ok = fok && ze < smin && (MODE != SURF_PW || w.ok) && (MODE != SURF_SKIP || a.zb > smax);
-            const double bx = surf_refine(T_at, band, a.m, a.x0, a.hq, ok, bt[e][0], bt[e][1], bt[e][2], bj[e][0], bj[e][1], bj[e][2],
-                                          a.tt + o, a.xent ? a.xent + o : nullptr);
+            const double bx = surf_refine(T_at, band, a.m, a.x0, a.hq, ok, bt[e][2], bj[e][0], bj[e][1], bj[e][2], a.tt + o,
+                                          a.xent ? a.xent + o : nullptr);
             if (MODE == SURF_SKIP && a.xback) {                         // the reflection point of the winning root
                 double xb = NAN;
                 if (!isnan(bx)) {
@@ -495,7 +504,7 @@ static SurfArgs surf_args(double x0, double dx, int n_s, double c1, double c2, i
     a.x0 = x0; a.dx = dx; a.hq = dx / SURF_SUB; a.inv_dx = 1.0 / dx; a.xend = fma((double)(n_s - 1), dx, x0);
     a.c1 = c1; a.c2 = c2;
     a.xo = surf_xo(x0, dx, n_s); a.zo = surf_zo;
-    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1);
+    a.ic1f = (float)(1.0 / c1); a.ic2f = (float)(1.0 / c2); a.k21f = (float)(c2 / c1); a.hqic2f = (float)(a.hq / c2);
     a.n_s = n_s; a.m = surf_points(n_s); a.n_e = n_rows; a.n_f = n_f;
     a.xf = xf; a.zf = zf; a.tt = tt; a.xent = xent;
     a.coef = w.coef; a.pts = w.pts; a.smin = w.smin;
