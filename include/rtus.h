@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 117 /* 0.1.16: rtus_skip_reflector* (skip legs off a sampled backwall) */
+#define RTUS_VERSION 118 /* 0.1.17: rtus_tfm_hmc*, rtus_tfm_analytic_hmc* (half-matrix capture) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -603,6 +603,49 @@ int rtus_tfm_analytic_dev(const float *d_a, int n_tx, int n_rx, int n_t, double 
 int rtus_tfm_analytic(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0,
                       const double *tt_tx, const double *tt_rx, int n_f,
                       float *image, float *cf, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_hmc, rtus_tfm_analytic_hmc: rtus_tfm and rtus_tfm_analytic over a HALF-MATRIX CAPTURE.  By reciprocity the A-scan of
+ * (tx i, rx j) is that of (tx j, rx i), and most array controllers store only the records with i <= j.  NOT IN THE REFERENCE;
+ * checked against tests/tfm_hmc_numpy.py.
+ *   hmc     [n_pairs][n_t] float32 (analytic: [n_pairs][n_t][2]), n_pairs = n_e (n_e + 1) / 2.  The record of (i, j),
+ *           0 <= i <= j < n_e, is number p(i, j) = i n_e - i (i - 1) / 2 + (j - i): the order of numpy.triu_indices(n_e); for a fixed
+ *           i the records j = i .. n_e - 1 are contiguous.  fs, t0 as in rtus_tfm.
+ *   tt_tx, tt_rx  [n_e][n_f] both: the same n_e elements transmit and receive.  The two may be one table (the same pointer).
+ *   Sample position, interpolation, edge rules and the no-path rule: rtus_tfm's / rtus_tfm_analytic's (each leg's half of the
+ *           position formed in fp64 and rounded once to fp32, the halves added in fp32).  With a_ij(s) the interpolated sample of
+ *           record (i, j), s_ij built from tt_tx[i] and tt_rx[j], s_ji from tt_tx[j] and tt_rx[i]:
+ *             S[f] = the sum of c_ij,   c_ii = a_ii(s_ii),   c_ij = a_ij(s_ij) + a_ij(s_ji) for i < j
+ *           — the two of a pair added to each other FIRST, then to the running sum as one term.  In exact arithmetic this is rtus_tfm
+ *           on the symmetric full matrix.  Order of the sum: blocks of 16 columns ascending; inside the block [c0, c0 + 16) first
+ *           the rows i < c0 (i ascending, j ascending through the block), then the rows of the block (i ascending, j ascending
+ *           from i).  Up to 16 elements this is: i ascending, j ascending from i.
+ *   One table (tt_tx == tt_rx as pointers): s_ij == s_ji bit for bit and c_ij = 2 a_ij(s_ij) exactly, so the record is gathered
+ *           ONCE and counted twice — 2080 gathers per focal point at 64 elements instead of 4096 — and the result has the bits of
+ *           the two-table form called with two equal tables (samples whose double overflows fp32 apart).
+ *   image   [n_f] float32 (analytic: [n_f][2], S = (sum re, sum im); each plane is rtus_tfm_hmc on that plane of the data, bit for
+ *           bit)
+ *   cf      [n_f] float32, nullable (analytic only): |S|^2 / (N E) with rtus_tfm_analytic's N = T R, formula, clamp and NaN rule;
+ *           E = the sum, in the same order, of e_ii = |a_ii|^2, e_ij = |a_ij(s_ij)|^2 + |a_ij(s_ji)|^2 (pair first), each square
+ *           formed as fmaf(im, im, re re).  Passing cf does not change the bits of image.
+ *   Determinism: the bits of a focal point depend only on its own columns of the tables.
+ *   Limits: 1 <= n_e <= 32768 (n_pairs fits an int; -1 otherwise) and rtus_tfm's / rtus_tfm_analytic's limits and codes for the
+ *           rest.  The _dev entries allocate nothing and do not synchronise (capturable).  The host twins stage through the arena
+ *           (one table uploaded when tt_tx == tt_rx).
+ * Measured on MI355X (DESIGN.md §4 "Half-matrix capture", profiles/tfm_hmc_kernel.txt): 64 elements x 2048 samples, one table,
+ * 256^2 focal points: 101 us real, 143 us analytic, 144 us with cf (0.54x / 0.53x / 0.53x rtus_tfm / rtus_tfm_analytic on the
+ * unpacked block in the same run); 1024^2: 1.02 / 1.05 / 1.07 ms (0.54x / 0.55x / 0.55x).  Two tables: about the full-matrix time.
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tfm_hmc_dev(const float *d_hmc, int n_e, int n_t, double fs, double t0,
+                     const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_image, void *stream);
+int rtus_tfm_hmc(const float *hmc, int n_e, int n_t, double fs, double t0,
+                 const double *tt_tx, const double *tt_rx, int n_f, float *image, int device);
+int rtus_tfm_analytic_hmc_dev(const float *d_a, int n_e, int n_t, double fs, double t0,
+                              const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                              float *d_image, float *d_cf, void *stream);
+int rtus_tfm_analytic_hmc(const float *a, int n_e, int n_t, double fs, double t0,
+                          const double *tt_tx, const double *tt_rx, int n_f,
+                          float *image, float *cf, int device);
 
 /* ------------------------------------------------------------------------------------------
  * Plane-wave imaging (PWI): a few dozen plane waves, each fired by the whole aperture with a linear delay law and received on every

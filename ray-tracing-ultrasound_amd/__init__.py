@@ -16,7 +16,8 @@ from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits, 
                   adaptive_tfm_pipe, gaussian_pulse, simulate_fmc, simulate_echoes, simulate_views, specular_times,
                   backwall_echo_layers, backwall_echo_surface, bore_echo_pipe, fit_reflector, measure_reflector,
                   skip_travel_time_reflector, reflector_mask, skip_travel_time_layers_profile, skip_travel_time_surface_profile,
-                  view_legs_layers_profile, view_legs_surface_profile, backwall_profile)
+                  view_legs_layers_profile, view_legs_surface_profile, backwall_profile,
+                  hmc_index, hmc_pack, hmc_unpack, hmc_analytic, tfm_hmc, tfm_analytic_hmc)
 
 __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "focal_delays", "tfm_image", "fmc_analytic",
            "measure_surface", "adaptive_tfm", "tfm_analytic", "tfm_phase", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
@@ -27,5 +28,6 @@ __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hi
            "pipe_clearance", "fit_pipe", "adaptive_tfm_pipe", "gaussian_pulse", "simulate_fmc", "simulate_echoes", "simulate_views", "specular_times",
            "backwall_echo_layers", "backwall_echo_surface", "bore_echo_pipe", "fit_reflector", "measure_reflector",
            "skip_travel_time_reflector", "reflector_mask", "skip_travel_time_layers_profile", "skip_travel_time_surface_profile",
-           "view_legs_layers_profile", "view_legs_surface_profile", "backwall_profile", "Params",
+           "view_legs_layers_profile", "view_legs_surface_profile", "backwall_profile", "hmc_index", "hmc_pack",
+           "hmc_unpack", "hmc_analytic", "tfm_hmc", "tfm_analytic_hmc", "Params",
            "configure", "reference_elements", "ALPHA_MAX", "KEYS", "build", "lib", "RtusError"]

@@ -133,6 +133,11 @@ PROTOTYPES = (
     ("rtus_surface_find", i, [vp, i, i, dd, dd, vp, vp, dd, dd, dd, i, dd, dd, i, vp, vp, vp, i], 100),
     ("rtus_tfm_analytic_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, vp], 100),
     ("rtus_tfm_analytic", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp, i], 100),
+    # half-matrix capture
+    ("rtus_tfm_hmc_dev", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp], 118),
+    ("rtus_tfm_hmc", i, [vp, i, i, dd, dd, vp, vp, i, vp, i], 118),
+    ("rtus_tfm_analytic_hmc_dev", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, vp], 118),
+    ("rtus_tfm_analytic_hmc", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, i], 118),
     # plane-wave imaging
     ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
     ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),

@@ -612,6 +612,125 @@ def tfm_analytic(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, ou
     return (img, cf) if mode else img
 
 
+# ---------------------------------------------------------------------------------------------- half-matrix capture
+def _hmc_elements(n_pairs):
+    """n_e with n_e (n_e + 1) / 2 == n_pairs; ValueError when n_pairs is not a triangular number"""
+    n_e = (int(np.sqrt(8.0 * n_pairs + 1.0)) - 1) // 2
+    for n in (n_e - 1, n_e, n_e + 1):
+        if n >= 1 and n * (n + 1) // 2 == n_pairs:
+            return n
+    raise ValueError(f"a half-matrix capture holds n_e (n_e + 1) / 2 records: {n_pairs} is not a triangular number")
+
+
+def hmc_index(n_e):
+    """The (i, j) of every record of a half-matrix capture of ``n_e`` elements, in packed order -> two int arrays [n_pairs]:
+    0 <= i <= j < n_e, record (i, j) at p = i n_e - i (i - 1) / 2 + (j - i) — numpy.triu_indices' order."""
+    n_e = int(n_e)
+    if n_e < 1:
+        raise ValueError("need n_e >= 1")
+    return np.triu_indices(n_e)
+
+
+def hmc_pack(fmc, mode="upper"):
+    """A square FMC block [n_e, n_e, n_t] (real or complex) -> its half-matrix capture [n_pairs, n_t] in hmc_index's order.
+    ``mode="upper"`` keeps fmc[i, j] for i <= j; ``"mean"`` stores (fmc[i, j] + fmc[j, i]) * 0.5 in the block's precision (float32 /
+    complex64): the reciprocal pairs averaged."""
+    fmc = np.asarray(fmc)
+    if fmc.ndim != 3 or fmc.shape[0] != fmc.shape[1]:
+        raise ValueError("fmc must be a square block [n_e, n_e, n_t]")
+    if mode not in ("upper", "mean"):
+        raise ValueError(f"unknown mode {mode!r}: 'upper' or 'mean'")
+    fmc = fmc.astype(np.complex64 if np.iscomplexobj(fmc) else np.float32, copy=False)
+    i, j = hmc_index(fmc.shape[0])
+    if mode == "upper":
+        return np.ascontiguousarray(fmc[i, j])
+    return np.ascontiguousarray((fmc[i, j] + fmc[j, i]) * np.float32(0.5))
+
+
+def hmc_unpack(hmc):
+    """A half-matrix capture [n_pairs, n_t] -> the symmetric full matrix [n_e, n_e, n_t] (record (i, j) at [i, j] and [j, i])."""
+    hmc = np.asarray(hmc)
+    if hmc.ndim != 2:
+        raise ValueError("hmc must be [n_pairs, n_t]")
+    n_e = _hmc_elements(hmc.shape[0])
+    i, j = hmc_index(n_e)
+    fmc = np.empty((n_e, n_e, hmc.shape[1]), dtype=hmc.dtype)
+    fmc[i, j] = hmc
+    fmc[j, i] = hmc
+    return fmc
+
+
+def _hmc_tables(n_pairs, tt_tx, tt_rx):
+    """the tables of tfm_hmc / tfm_analytic_hmc against a block of n_pairs records -> (n_e, tt_tx, tt_rx, n_f)"""
+    n_e = _hmc_elements(n_pairs)
+    tt_tx = np.ascontiguousarray(tt_tx, dtype=np.float64)
+    same = tt_rx is None or tt_rx is tt_tx
+    tt_rx = tt_tx if same else np.ascontiguousarray(tt_rx, dtype=np.float64)
+    if tt_tx.ndim != 2 or tt_rx.ndim != 2 or tt_tx.shape[1] != tt_rx.shape[1]:
+        raise ValueError("tt_tx / tt_rx must be [n_e, n_focal] both")
+    if tt_tx.shape[0] != n_e or tt_rx.shape[0] != n_e:
+        raise ValueError(f"{n_pairs} records are a capture of {n_e} elements: tt_tx and tt_rx must have {n_e} rows")
+    return n_e, tt_tx, tt_rx, tt_tx.shape[1]
+
+
+def tfm_hmc(hmc, fs, tt_tx, tt_rx=None, *, t0=0.0, out=None, device=0):
+    """tfm_image over a half-matrix capture: ``hmc`` float32 [n_pairs, n_t] holds the A-scans of the pairs i <= j in hmc_index's order
+    (hmc_pack makes one from a square block); tt_tx / tt_rx [n_e, n_f], tt_rx defaults to tt_tx.  Each record counts for (i, j) and
+    for (j, i): image[f] = sum of a_ii(s_ii) and of a_ij(s_ij) + a_ij(s_ji) for i < j, with tfm_image's positions, interpolation and
+    edge rules — tfm_image of hmc_unpack(hmc) up to the order of the fp32 sum.  With one table (tt_rx None or tt_tx itself) every
+    record is gathered once and counted twice: half the gathers of tfm_image, and the bits of the two-table call with equal tables.
+    -> float32 [n_f].  Definition: include/rtus.h (rtus_tfm_hmc).  Not in the reference."""
+    hmc = np.ascontiguousarray(hmc, dtype=np.float32)
+    if hmc.ndim != 2:
+        raise ValueError("hmc must be [n_pairs, n_t]")
+    n_e, tt_tx, tt_rx, n_f = _hmc_tables(hmc.shape[0], tt_tx, tt_rx)
+    img = _out(out, (n_f,), np.float32)
+    st = _lib.lib().rtus_tfm_hmc(_ptr(hmc), n_e, hmc.shape[1], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f, _ptr(img), int(device))
+    _lib.check(st, "rtus_tfm_hmc")
+    return img
+
+
+def _complex_hmc(a):
+    """complex64 [n_pairs, n_t] (a float32 [n_pairs, n_t, 2] array is viewed as one)"""
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.float32 and a.ndim == 3 and a.shape[2] == 2:
+        a = a.view(np.complex64)[..., 0]
+    if a.dtype != np.complex64 or a.ndim != 2:
+        raise ValueError("the analytic capture must be complex64 [n_pairs, n_t] (or float32 [n_pairs, n_t, 2])")
+    return a
+
+
+def tfm_analytic_hmc(analytic_hmc, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, out=None, device=0):
+    """tfm_analytic over a half-matrix capture: complex64 [n_pairs, n_t] (hmc_analytic's, or float32 [n_pairs, n_t, 2]) -> complex64
+    image [n_f], each plane tfm_hmc of that plane bit for bit; with ``coherence=True`` (or "cf") -> (image, cf float32 [n_f]), the
+    coherence factor of tfm_analytic with E summed over both legs of every record.  "vcf" / "scf" raise ValueError: the
+    phase-coherence kernel has no half-matrix form.  Definition: include/rtus.h (rtus_tfm_analytic_hmc).  Not in the reference."""
+    mode = _coherence(coherence)
+    if mode in ("vcf", "scf"):
+        raise ValueError(f"coherence={mode!r} is not available on a half-matrix capture (tfm_phase has no HMC form): use 'cf'")
+    a = _complex_hmc(analytic_hmc)
+    n_e, tt_tx, tt_rx, n_f = _hmc_tables(a.shape[0], tt_tx, tt_rx)
+    img = _out(out, (n_f,), np.complex64)
+    cf = np.empty(n_f, dtype=np.float32) if mode else None
+    st = _lib.lib().rtus_tfm_analytic_hmc(_ptr(a), n_e, a.shape[1], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f, _ptr(img),
+                                          _ptr(cf), int(device))
+    _lib.check(st, "rtus_tfm_analytic_hmc")
+    return (img, cf) if mode else img
+
+
+def hmc_analytic(hmc, n_taps=63, *, out=None, device=0):
+    """Analytic signal of every A-scan of a half-matrix capture -> complex64 [n_pairs, n_t]: fmc_analytic on the block seen as
+    [1, n_pairs, n_t] (the Hilbert transformer works per A-scan; rtus_fmc_analytic limits the number of A-scans, not either
+    dimension)."""
+    hmc = np.ascontiguousarray(hmc, dtype=np.float32)
+    if hmc.ndim != 2:
+        raise ValueError("hmc must be [n_pairs, n_t]")
+    _hmc_elements(hmc.shape[0])
+    a = _out(out, hmc.shape, np.complex64)
+    fmc_analytic(hmc[None], n_taps, out=a.reshape(1, *hmc.shape), device=device)
+    return a
+
+
 def tfm_phase(analytic, fs, tt_tx, tt_rx=None, *, t0=0.0, counts=False, out=None, device=0):
     """Phase-coherence imaging (Camacho, Parrilla & Fritsch 2009): tfm_analytic's delay-and-sum — the same arguments, input rules and
     image bits — with the two factors that read only the phase of the aperture data at each focal point:
@@ -875,7 +994,7 @@ def view_legs_surface(x0, dx, zs, c1, c_l, c_t, z_back, xe, ze, xf, zf, *, legs=
     return out
 
 
-def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=False, n_taps=63, amplitudes=None, device=0):
+def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=False, n_taps=63, amplitudes=None, hmc=False, device=0):
     """Multi-view TFM: one image per view -> {view: image float32 [n_f]}.  ``legs``: {leg: tt [n_e, n_f]} (view_legs_layers /
     view_legs_surface); a view "A-B" (transmit leg A, then receive leg B from the point to the receiver) is imaged with
     tt_tx = legs[A] and tt_rx = legs[reverse_leg(B)].  RF: tfm_image.  With ``envelope=True``: |tfm_analytic| over the analytic FMC,
@@ -884,8 +1003,14 @@ def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=F
     ``amplitudes``: {leg: (down, up)} complex64 [n_e, n_f] (view_amplitudes_surface; needs ``envelope=True``, excludes ``coherence``):
     each view is beamformed by tfm_weighted with w_tx = conj(down[A]) and w_rx = conj(up[reverse_leg(B)]) and the value is |S| / P,
     P the view's sensitivity (NaN where P = 0): a unit point scatterer reads 1 in every view that sees it, so views share one scale.
+    ``hmc=True``: ``fmc`` is a half-matrix capture [n_pairs, n_t] (hmc_pack) and every view goes through tfm_hmc / tfm_analytic_hmc;
+    ``amplitudes`` and ``coherence="vcf"`` / ``"scf"`` have no half-matrix form and raise ValueError.
     An unknown view or a leg missing from ``legs`` (or ``amplitudes``) raises ValueError before any GPU call."""
     coherence = _coherence(coherence)
+    if hmc and amplitudes is not None:
+        raise ValueError("amplitude weighting is not available on a half-matrix capture (tfm_weighted has no HMC form)")
+    if hmc and coherence in ("vcf", "scf"):
+        raise ValueError(f"coherence={coherence!r} is not available on a half-matrix capture (tfm_phase has no HMC form)")
     if coherence and not envelope:
         raise ValueError("the coherence factor needs envelope=True")
     if amplitudes is not None and not envelope:
@@ -901,6 +1026,15 @@ def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=F
         missing = sorted({g for p in pairs.values() for g in p if g not in amplitudes})
         if missing:
             raise ValueError(f"legs {missing} are needed by the views and missing from ``amplitudes``")
+    if hmc:
+        if not envelope:
+            return {v: tfm_hmc(fmc, fs, legs[a], legs[b], t0=t0, device=device) for v, (a, b) in pairs.items()}
+        analytic = hmc_analytic(fmc, n_taps, device=device)
+        out = {}
+        for v, (a, b) in pairs.items():
+            r = tfm_analytic_hmc(analytic, fs, legs[a], legs[b], t0=t0, coherence=coherence, device=device)
+            out[v] = (np.abs(r[0]), r[1]) if coherence else np.abs(r)
+        return out
     if not envelope:
         return {v: tfm_image(fmc, fs, legs[a], legs[b], t0=t0, device=device) for v, (a, b) in pairs.items()}
     analytic = fmc_analytic(fmc, n_taps, device=device)

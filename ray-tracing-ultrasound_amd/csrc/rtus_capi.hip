@@ -80,6 +80,10 @@ hipError_t rtus_launch_skip_reflector(const double* tt_down, int n_e, const doub
 long long rtus_skip_reflector_blocks(int n_e, int n_f);
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
+hipError_t rtus_launch_tfm_hmc(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                               int n_f, float* image, hipStream_t s);
+hipError_t rtus_launch_tfm_analytic_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                        const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s);
@@ -1348,6 +1352,69 @@ int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
     return S.finish();
+}
+
+// ---------------------------------------------------------------------------- TFM and envelope TFM over a half-matrix capture
+#define RTUS_HMC_MAX_ELEMENTS 32768                                   // n_e (n_e + 1) / 2 records fit an int
+static int check_tfm_hmc(const void* hmc, int n_e, int n_t, double fs, double t0, const void* tt_tx, const void* tt_rx, int n_f,
+                         const void* image, bool analytic)
+{
+    if (n_e < 1 || n_e > RTUS_HMC_MAX_ELEMENTS) return RTUS_ERR_INVALID_ARG;
+    return analytic ? check_tfm_analytic(hmc, n_e, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image)
+                    : check_tfm(hmc, n_e, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image);
+}
+
+int rtus_tfm_hmc_dev(const float* d_hmc, int n_e, int n_t, double fs, double t0, const double* d_tt_tx, const double* d_tt_rx, int n_f,
+                     float* d_image, void* stream)
+{
+    int st = check_tfm_hmc(d_hmc, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, false);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_hmc(d_hmc, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_analytic_hmc_dev(const float* d_a, int n_e, int n_t, double fs, double t0, const double* d_tt_tx, const double* d_tt_rx,
+                              int n_f, float* d_image, float* d_cf, void* stream)
+{
+    int st = check_tfm_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, true);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_analytic_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, d_cf, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+// the two host twins: c = floats per sample (1 real, 2 analytic); cf only with c == 2
+static int tfm_hmc_host(const float* hmc, int c, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                        int n_f, float* image, float* cf, int device)
+{
+    int st = check_tfm_hmc(hmc, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, c == 2);
+    if (st) return st;
+    const size_t n_pairs = (size_t)n_e * ((size_t)n_e + 1) / 2;
+    const bool same = tt_tx == tt_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    float *dh, *dimg, *dcf = nullptr;
+    double *dtx, *drx = nullptr;
+    S.in(dh, hmc, n_pairs * n_t * c);
+    S.in(dtx, tt_tx, (size_t)n_e * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_e * n_f);
+    S.out(dimg, image, (size_t)c * n_f);
+    if (c == 2) S.out(dcf, cf, n_f);
+    if ((st = S.flush())) return st;
+    if (c == 2) LAUNCH_TRY(rtus_launch_tfm_analytic_hmc(dh, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
+    else LAUNCH_TRY(rtus_launch_tfm_hmc(dh, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
+    return S.finish();
+}
+
+int rtus_tfm_hmc(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
+                 float* image, int device)
+{
+    return tfm_hmc_host(hmc, 1, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, nullptr, device);
+}
+
+int rtus_tfm_analytic_hmc(const float* a, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
+                          float* image, float* cf, int device)
+{
+    return tfm_hmc_host(a, 2, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, cf, device);
 }
 
 // ---------------------------------------------------------------------------- phase-coherence TFM: vcf, scf

@@ -1,6 +1,6 @@
 // rtus_das.h — the delay-and-sum core shared by rtus_tfm_kernel, rtus_tfm_analytic_kernel, rtus_tfm_phase_kernel,
-// rtus_tfm_weighted_kernel (rtus_tfm.hip) and rtus_surface_find_kernel (rtus_autofocus.hip): the workgroup order, the delay
-// clamp, the two-sample load, its interpolation and the gather loop.  A kernel keeps its tile fill, its accumulate step and its epilogue.
+// rtus_tfm_weighted_kernel (rtus_tfm.hip), the half-matrix kernels (rtus_tfm_hmc.hip) and rtus_surface_find_kernel
+// (rtus_autofocus.hip): the workgroup order, the delay clamp, the two-sample load, its interpolation and the gather loops.  A kernel keeps its tile fill, its accumulate step and its epilogue.
 //
 // The common shape: a lane owns one focal point; each receive element's half of the pair's sample position (in samples,
 // fp32) sits in LDS for a tile of elements, lane-major (lane l reads tau[rx][l]: conflict-free); the transmit element's
@@ -32,6 +32,12 @@ __device__ __forceinline__ float das_clamp(float v)
 {
     return fabsf(v) < -RTUS_DAS_NO_PATH ? v : RTUS_DAS_NO_PATH;       // NaN fails the compare
 }
+
+// travel time -> half of the pair's sample position (formed in fp64, rounded once); no path, a non-finite or an absurd time ->
+// RTUS_DAS_NO_PATH.  half_t0s = t0 fs / 2: each of the pair's two delays carries half of the time origin
+__device__ __forceinline__ float tfm_tau(double t, double fs, double half_t0s) { return das_clamp((float)(t * fs - half_t0s)); }
+
+__device__ __forceinline__ int tfm_has_path(float tau) { return tau > RTUS_DAS_NO_PATH; }   // a path's |tau| < 1e8
 
 // Two neighbouring samples i, i + 1 of one A-scan (wave-uniform base) in one load: C = 1 real samples (8 bytes), C = 2
 // complex samples (16 bytes).  An index outside the record (negative, huge, the sum of two no-path values) is dropped by
@@ -97,4 +103,27 @@ __device__ __forceinline__ void das_gather(const float* rec, size_t stride, int 
         const float fl = floorf(s);
         accum(r, das_load2<C>(rec + (size_t)r * stride, n_t, (int)fl), s - fl);
     }
+}
+
+// RTUS_DAS_GROUP gathers issued as ONE batch whose records and positions the caller walks: at(k, rec) -> the sample position of
+// slot k and its record (wave-uniform), called for k ascending before any load is consumed; then accum(k, samples, weight) for k
+// ascending.  For gathers that are not one row against a tile: the packed triangle of a half-matrix capture, where a group runs
+// on across the ends of the (ragged) rows.  A caller with fewer than RTUS_DAS_GROUP records left fills the other slots with a
+// position that the range check drops (2 RTUS_DAS_NO_PATH: the samples read as zeros, the weight is 0) and keeps them out of its
+// sums: the partial group is still one batch (das_gather's tail issues its loads one by one, ~1 us each).
+template <int C, class At, class Accum>
+__device__ __forceinline__ void das_batch(int n_t, At&& at, Accum&& accum)
+{
+    decltype(das_load2<C>(nullptr, n_t, 0)) v[RTUS_DAS_GROUP];
+    float w[RTUS_DAS_GROUP];
+#pragma unroll
+    for (int k = 0; k < RTUS_DAS_GROUP; ++k) {
+        const float* rec;
+        const float s = at(k, rec);
+        const float fl = floorf(s);
+        w[k] = s - fl;
+        v[k] = das_load2<C>(rec, n_t, (int)fl);
+    }
+#pragma unroll
+    for (int k = 0; k < RTUS_DAS_GROUP; ++k) accum(k, v[k], w[k]);
 }

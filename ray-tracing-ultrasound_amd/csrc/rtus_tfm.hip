@@ -119,12 +119,6 @@ static Args tfm_args(const float* fmc, int n_tx, int n_rx, int n_t, double fs, d
     return a;
 }
 
-// travel time -> half of the pair's sample position (formed in fp64, rounded once); no path, a non-finite or an absurd time ->
-// RTUS_DAS_NO_PATH
-__device__ __forceinline__ float tfm_tau(double t, double fs, double half_t0s) { return das_clamp((float)(t * fs - half_t0s)); }
-
-__device__ __forceinline__ int tfm_has_path(float tau) { return tau > RTUS_DAS_NO_PATH; }   // a path's |tau| < 1e8
-
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_kernel(TfmArgs a)
 {
     __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB: 2 workgroups per CU; a 64-element receive

@@ -1,0 +1,275 @@
+// rtus_tfm_hmc.hip — TFM and envelope TFM over a half-matrix capture (HMC): by reciprocity the A-scan of (tx i, rx j) is that of
+// (tx j, rx i), so an array controller stores only the n_e (n_e + 1) / 2 records with i <= j, packed in np.triu_indices' order.
+// Definition: include/rtus.h (rtus_tfm_hmc).  NOT IN THE REFERENCE; checked against tests/tfm_hmc_numpy.py.
+//
+// rtus_tfm_kernel's shape over the delay-and-sum core of rtus_das.h — a lane owns a focal point, das_workgroup()'s order, the
+// delays of a tile of elements in LDS, sixteen gathers in flight per lane — and two things of its own:
+//   * one table for both legs (tt_tx == tt_rx): s_ij == s_ji bit for bit, so ONE gather serves both and its sample counts with
+//     weight 2 (1 on the diagonal): fmaf(2, a, sum) is sum + (a + a) — the pair summed first — in one rounding, because a + a is
+//     exact (an a whose double overflows fp32 apart).  Two tables: two gathers per record, eight records per batch, the tile
+//     holds (tau_tx, tau_rx) of its elements as a float2; the gain is the packed block alone;
+//   * ragged rows: row i has n_e - i records, so a walk by rows would end almost every row in a partial group.  The columns go
+//     in blocks of sixteen instead.  A row above a block meets it in exactly one batch of sixteen gathers of fixed shape —
+//     rtus_tfm_kernel's instruction stream: the record and the LDS offset of slot k are compile-time steps from the row's.  Only
+//     a block's own 16 x 16 triangle (136 records; 4 x 136 of 2080 at 64 elements) is ragged: it is walked as ONE run of records
+//     across the row ends, unrolled, so that every (i, j), weight and LDS offset of the run is a constant too.  A block of fewer
+//     than sixteen columns (n_e not a multiple of 16) takes the same walk with its state in scalar registers and a padded last
+//     batch.  2112 gather requests per focal point at 64 elements (2080 and four half-empty batches), against 4096.
+// A focal point's order of summation: blocks of sixteen columns ascending; in the block [c0, c0 + 16) first the rows above it
+// (i < c0 ascending, j ascending through the block), then the block's own triangle (i ascending, j ascending from i).  The tile
+// size decides only where a row's delays come from (LDS, or the tables for rows of earlier tiles): not a bit of the result.
+#include <type_traits>
+#include "rtus_das.h"
+
+// Elements whose delays a workgroup holds in LDS at a time: 64 KiB either way, two workgroups per CU.  One table: 64 floats per
+// lane (a 64-element aperture is one tile: no delay is formed twice).  Two tables: 32 float2.  Measured (profiles/
+// tfm_hmc_kernel.txt): a 64-element float2 tile (128 KiB, one workgroup per CU) is 8-11 % faster at 256^2 focal points, where
+// a CU has one workgroup anyway, and 22-29 % slower at 1024^2.
+#define RTUS_HMC_TILE 64
+#ifndef RTUS_HMC_TILE2
+#define RTUS_HMC_TILE2 32
+#endif
+
+struct HmcArgs {
+    const float* __restrict__ hmc;       // [n_pairs][n_t] (analytic: [n_pairs][n_t][2])
+    const double* __restrict__ tt_tx;    // [n_e][n_f]
+    const double* __restrict__ tt_rx;    // [n_e][n_f]
+    float* __restrict__ image;           // [n_f] (analytic: [n_f][2])
+    float* __restrict__ cf;              // [n_f] (read by the CF instantiations only)
+    int n_e, n_t, n_f;
+    double fs, half_t0s;
+};
+
+// the sums of one focal point: C = 1 S alone (re), C = 2 S = (re, im) and with CF E (en).  A record's kind: off the diagonal, on
+// it, or none (the unused slots of a partial batch: they add -0, which changes no sum, not even a -0)
+enum { HMC_PAIR = 0, HMC_DIAG = 1, HMC_NONE = 2 };
+template <int C, bool CF>
+struct HmcSum {
+    float re = 0.0f, im = 0.0f, en = 0.0f;
+    // one gather for both legs: c = wgt a, wgt = 2, 1 or -0 by the record's kind
+    __device__ __forceinline__ void one(float p, float wgt) { re = fmaf(wgt, p, re); }
+    __device__ __forceinline__ void one(float2 p, float wgt)
+    {
+        re = fmaf(wgt, p.x, re);
+        im = fmaf(wgt, p.y, im);
+        if (CF) en = fmaf(wgt, fmaf(p.y, p.y, p.x * p.x), en);
+    }
+    // two gathers: c = a(s_ij) + a(s_ji), the pair first; the diagonal's second one is not counted
+    static __device__ __forceinline__ float term(float p, float q, int kind) { return kind == HMC_PAIR ? p + q : kind == HMC_DIAG ? p : -0.0f; }
+    __device__ __forceinline__ void two(float p, float q, int kind) { re += term(p, q, kind); }
+    __device__ __forceinline__ void two(float2 p, float2 q, int kind)
+    {
+        re += term(p.x, q.x, kind);
+        im += term(p.y, q.y, kind);
+        if (CF) en += term(fmaf(p.y, p.y, p.x * p.x), fmaf(q.y, q.y, q.x * q.x), kind);
+    }
+};
+
+// the delays of an element in the tile: one table a float, two tables (tau_tx, tau_rx)
+template <bool TWO> struct HmcTau { typedef float type; };
+template <> struct HmcTau<true> { typedef float2 type; };
+
+// One run of records in batches of RTUS_DAS_GROUP gathers: with TRI a block's own triangle (nr rows; row r from column r on),
+// else one row, of delays tr, against the block's nr columns.  Rows and columns are local to the block (tile: the tile from the
+// block's first column on); rec: the first record; step: floats from a row's last record to the next row's first.  The last
+// batch may be partial: its unused slots repeat the last record at a position that the range check drops, as HMC_NONE.
+// The walk (r, c, rec) is wave-uniform and written as integer arithmetic and selects, not branches: a batch's LDS reads and
+// gathers stay in ONE basic block, where the scheduler can issue the reads ahead.  A row of the triangle starts on the diagonal,
+// where the row's delays are the column's: one LDS read per record, the row's delays kept in a register.
+// NR: the block's size when it is known at compile time (a full block's triangle), else 0.  With it the walk is unrolled: every
+// (r, c), kind, weight and LDS offset becomes a constant, and the triangle's batches have the fixed-shape batches' instruction
+// stream (the walk itself costs ~25 scalar and 2 vector instructions per record).
+template <int C, bool CF, bool TWO, bool TRI, int NR = 0>
+__device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, size_t len, size_t step, int n_t, int nr_,
+                                         const typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], int lane, typename HmcTau<TWO>::type tr)
+{
+    constexpr int PER = TWO ? RTUS_DAS_GROUP / 2 : RTUS_DAS_GROUP;    // records per batch
+    const int nr = NR ? NR : nr_;
+    int left = TRI ? nr * (nr + 1) / 2 : nr;                          // (<= 2080)
+    int r = 0, c = 0;
+    // One batch; LAST: the run's last one, with left < PER records; past the run's last record (r, c, rec) stay on it
+    auto batch = [&](auto last) {
+        constexpr bool LAST = decltype(last)::value;
+        int kind[PER];
+        float wgt[PER];                                               // one table: 2, 1 or -0 by the record's kind
+        auto open = [&](int m) {
+            kind[m] = LAST && m >= left ? HMC_NONE : TRI && r == c ? HMC_DIAG : HMC_PAIR;
+            // (in a scalar register: 1.0f's bits plus one exponent step off the diagonal, c - r >= 1 there)
+            if constexpr (LAST || !TRI) wgt[m] = kind[m] == HMC_PAIR ? 2.0f : kind[m] == HMC_DIAG ? 1.0f : -0.0f;
+            else wgt[m] = __int_as_float(0x3f800000 + (min(c - r, 1) << 23));
+        };
+        auto next = [&](int m) {
+            if constexpr (LAST) {
+                const bool go = m + 1 < left, wrap = TRI && c + 1 == nr;
+                const int r1 = wrap ? r + 1 : r, c1 = wrap ? r1 : c + 1;
+                r = go ? r1 : r;
+                c = go ? c1 : c;
+                rec += go ? (wrap ? len + step : len) : 0;
+            } else if constexpr (TRI) {
+                const int c1 = c + 1, on = min(nr - c1, 1);           // 1: the row goes on; 0: that was its last record
+                r += 1 - on;                                          // (sums and a product: a compare would come back from
+                c = r + on * (c1 - r);                                //  the compiler as a vector select and a read-lane)
+                rec += len;
+                rec += step * (size_t)(1 - on);
+            } else {
+                ++c;
+                rec += len;
+            }
+        };
+        if constexpr (!TWO) {
+            auto at = [&](int k, const float*& q) {
+                open(k);
+                const float tc = tile[c][lane];
+                if constexpr (TRI) tr = kind[k] == HMC_DIAG ? tc : tr;
+                q = rec;
+                next(k);
+                return LAST && kind[k] == HMC_NONE ? 2.0f * RTUS_DAS_NO_PATH : tr + tc;
+            };
+            das_batch<C>(n_t, at, [&](int k, auto v, float w) {
+                sum.one(das_lerp(v, w), wgt[k]);
+            });
+        } else {
+            decltype(das_lerp(das_load2<C>(rec, n_t, 0), 0.0f)) first;
+            float s_ji = 0.0f;
+            auto at = [&](int k, const float*& q) {                   // slot 2 m: s_ij of the batch's record m, slot 2 m + 1: s_ji
+                const int m = k >> 1;
+                q = rec;
+                if (k & 1) {
+                    next(m);
+                    return s_ji;
+                }
+                open(m);
+                const float2 tc = tile[c][lane];
+                if constexpr (TRI) {
+                    tr.x = kind[m] == HMC_DIAG ? tc.x : tr.x;
+                    tr.y = kind[m] == HMC_DIAG ? tc.y : tr.y;
+                }
+                s_ji = kind[m] == HMC_PAIR ? tc.x + tr.y : 2.0f * RTUS_DAS_NO_PATH;   // (the diagonal has one position)
+                return LAST && kind[m] == HMC_NONE ? 2.0f * RTUS_DAS_NO_PATH : tr.x + tc.y;
+            };
+            das_batch<C>(n_t, at, [&](int k, auto v, float w) {
+                if (!(k & 1)) first = das_lerp(v, w);
+                else sum.two(first, das_lerp(v, w), kind[k >> 1]);
+            });
+        }
+    };
+    if constexpr (NR != 0) {
+#pragma unroll
+        for (; left >= PER; left -= PER) batch(std::false_type());
+    } else {
+        for (; left >= PER; left -= PER) batch(std::false_type());   // (after the run's last record the walk's state is not read)
+    }
+    if (left) batch(std::true_type());
+}
+
+template <int C, bool CF, bool TWO>
+__device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK])
+{
+    constexpr int TILE = TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE;
+    static_assert(TILE % RTUS_DAS_GROUP == 0, "a tile is a whole number of column blocks");
+    typedef typename HmcTau<TWO>::type Tau;
+    const int lane = threadIdx.x;
+    const int f_raw = das_workgroup() * RTUS_BLOCK + lane;
+    const bool live = f_raw < a.n_f;
+    const int f = live ? f_raw : a.n_f - 1;
+    const size_t nf = (size_t)a.n_f, ne = (size_t)a.n_e;
+    const size_t len = (size_t)a.n_t * C;                             // floats per record
+    auto tau = [&](int e) -> Tau {                                    // element e's delays, from the tables
+        const float t = tfm_tau(a.tt_tx[(size_t)e * nf + f], a.fs, a.half_t0s);
+        if constexpr (TWO) return make_float2(t, tfm_tau(a.tt_rx[(size_t)e * nf + f], a.fs, a.half_t0s));
+        else return t;
+    };
+    HmcSum<C, CF> sum;
+    int n_tx_ok = 0, n_rx_ok = 0;                                     // T[f], R[f] (CF only)
+    for (int r0 = 0; r0 < a.n_e; r0 += TILE) {
+        const int nr = min(TILE, a.n_e - r0);
+        __syncthreads();                                              // the previous tile is no longer read
+        for (int r = 0; r < nr; ++r) {
+            const Tau v = tau(r0 + r);
+            tile[r][lane] = v;
+            if constexpr (CF && TWO) { n_tx_ok += tfm_has_path(v.x); n_rx_ok += tfm_has_path(v.y); }
+            else if constexpr (CF) n_tx_ok += tfm_has_path(v);
+        }
+        __syncthreads();
+        // the tile's columns in blocks of RTUS_DAS_GROUP: a row above a block meets it in ONE batch of fixed shape (the record
+        // and the LDS offset of slot k are compile-time steps from the row's: rtus_tfm_kernel's instruction stream); only the
+        // block's own triangle (136 records of 2080 at 64 elements: 4 x 136 in all) pays for the walk across ragged rows
+        for (int cb = 0; cb < nr; cb += RTUS_DAS_GROUP) {
+            const int nb = min(RTUS_DAS_GROUP, nr - cb), cg = r0 + cb;   // the block's columns, its first one
+            const float* row = a.hmc + (size_t)cg * len;                 // record (i, cg): p(i, cg) = i n_e - i (i + 1) / 2 + cg
+            size_t down = (ne - 1) * len;                                 // from (i, cg) to (i + 1, cg): n_e - 1 - i records
+            // rows of earlier tiles: their delays come from memory (a load that a gather's batch must not wait for)
+            for (int i = 0; i < r0; ++i, row += down, down -= len)
+                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tau(i));
+            // rows of this tile above the block: their delays are in the tile
+            for (int i = r0; i < cg; ++i, row += down, down -= len)
+                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tile[i - r0][lane]);
+            // the block's own triangle from (cg, cg) on; a row's records to the right of the block are stepped over
+            const size_t past = (ne - (size_t)(cg + nb)) * len;
+            if (nb == RTUS_DAS_GROUP) hmc_walk<C, CF, TWO, true, RTUS_DAS_GROUP>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau());
+            else hmc_walk<C, CF, TWO, true>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau());
+        }
+    }
+    if (!live) return;
+    if constexpr (C == 1) a.image[f] = sum.re;
+    else ((float2*)a.image)[f] = make_float2(sum.re, sum.im);
+    if constexpr (CF) {
+        // as rtus_tfm_analytic_kernel: |S|^2 exact in fp64, N = T R, clamped to 1
+        if constexpr (!TWO) n_rx_ok = n_tx_ok;
+        const double n = (double)n_tx_ok * (double)n_rx_ok;
+        double c = NAN;                                               // no pair with a path
+        if (n > 0.0) {
+            const double s2 = (double)sum.re * (double)sum.re + (double)sum.im * (double)sum.im;
+            c = sum.en > 0.0f ? s2 / (n * (double)sum.en) : 0.0;
+            c = c > 1.0 ? 1.0 : c;
+        }
+        a.cf[f] = (float)c;
+    }
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_hmc_kernel(HmcArgs a)
+{
+    __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
+    hmc_body<1, false, TWO>(a, tile);
+}
+
+template <bool CF, bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_hmc_kernel(HmcArgs a)
+{
+    __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
+    hmc_body<2, CF, TWO>(a, tile);
+}
+
+static HmcArgs hmc_args(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
+                        float* image, float* cf)
+{
+    HmcArgs a;
+    a.hmc = hmc; a.tt_tx = tt_tx; a.tt_rx = tt_rx; a.image = image; a.cf = cf;
+    a.n_e = n_e; a.n_t = n_t; a.n_f = n_f;
+    a.fs = fs; a.half_t0s = 0.5 * t0 * fs;
+    return a;
+}
+
+hipError_t rtus_launch_tfm_hmc(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                               int n_f, float* image, hipStream_t s)
+{
+    const HmcArgs a = hmc_args(hmc, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, nullptr);
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    if (tt_tx == tt_rx) hipLaunchKernelGGL(rtus_tfm_hmc_kernel<false>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(rtus_tfm_hmc_kernel<true>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t rtus_launch_tfm_analytic_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                        const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s)
+{
+    const HmcArgs a = hmc_args(an, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, cf);
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    const bool two = tt_tx != tt_rx;
+    if (cf && two) hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<true, true>), grid, block, 0, s, a);
+    else if (cf) hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<true, false>), grid, block, 0, s, a);
+    else if (two) hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}

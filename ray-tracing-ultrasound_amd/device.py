@@ -393,6 +393,50 @@ def tfm_analytic_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None)
     return out if cf is None else (out, cf)
 
 
+def _hmc_tables(tt_tx, tt_rx, data, analytic):
+    """a half-matrix capture [n_pairs, n_t] (analytic: [.., 2]) against tt_tx, tt_rx [n_e, n] both -> (n_e, n)"""
+    ok = tt_tx.dim() == 2 and tt_rx.dim() == 2 and tt_tx.shape == tt_rx.shape \
+        and data.dim() == (3 if analytic else 2) and (not analytic or data.shape[2] == 2)
+    n_e = tt_tx.shape[0] if ok else 0
+    if not ok or n_e < 1 or n_e * (n_e + 1) // 2 != data.shape[0]:
+        what = "analytic [n_pairs, n_t, 2]" if analytic else "hmc [n_pairs, n_t]"
+        raise ValueError(f"need {what} with n_pairs = n_e (n_e + 1) / 2, tt_tx [n_e, n], tt_rx [n_e, n]")
+    return n_e, tt_tx.shape[1]
+
+
+def tfm_hmc_dev(hmc, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
+    """TFM over a half-matrix capture on device (rtus_tfm_hmc_dev; api.tfm_hmc's definition): hmc float32 [n_pairs, n_t], tt_tx /
+    tt_rx [n_e, n_f] (default: tt_tx — one table: every record gathered once) -> image float32 [n_f].  Asynchronous on the
+    current stream (capturable with a pre-allocated output)."""
+    _chk(hmc, "hmc", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_e, n_f = _hmc_tables(tt_tx, tt_rx, hmc, False)
+    out = _result(out, (n_f,), hmc, torch.float32)
+    if not (out.device == hmc.device == tt_tx.device == tt_rx.device):
+        raise ValueError("out must be on the device of hmc / tt_tx / tt_rx")
+    st = _lib.lib().rtus_tfm_hmc_dev(_p(hmc), n_e, hmc.shape[1], float(fs), float(t0), _p(tt_tx), _p(tt_rx), n_f, _p(out), _stream(hmc))
+    _lib.check(st, "rtus_tfm_hmc_dev")
+    return out
+
+
+def tfm_analytic_hmc_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None):
+    """Envelope TFM over a half-matrix capture on device (rtus_tfm_analytic_hmc_dev; api.tfm_analytic_hmc's definition): analytic
+    float32 [n_pairs, n_t, 2], tt_tx / tt_rx [n_e, n_f] (default: tt_tx) -> out float32 [n_f, 2] (the complex sum); ``cf``: an
+    optional float32 [n_f] tensor that receives the coherence factor (then -> (out, cf)).  Asynchronous on the current stream
+    (capturable with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_e, n_f = _hmc_tables(tt_tx, tt_rx, analytic, True)
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, cf=cf)
+    if not (out.device == analytic.device == tt_tx.device == tt_rx.device and (cf is None or cf.device == analytic.device)):
+        raise ValueError("analytic, tt_tx, tt_rx, out and cf must be on one device")
+    st = _lib.lib().rtus_tfm_analytic_hmc_dev(_p(analytic), n_e, analytic.shape[1], float(fs), float(t0), _p(tt_tx), _p(tt_rx), n_f,
+                                              _p(out), _p(cf), _stream(analytic))
+    _lib.check(st, "rtus_tfm_analytic_hmc_dev")
+    return out if cf is None else (out, cf)
+
+
 def tfm_phase_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, vcf=None, scf=None, counts=None):
     """Phase-coherence TFM on device (rtus_tfm_phase_dev; api.tfm_phase's definition): tfm_analytic_dev's tensors -> out float32
     [n_f, 2] (the complex sum, tfm_analytic_dev's bits); ``vcf`` / ``scf``: optional float32 [n_f] tensors that receive the vector /
