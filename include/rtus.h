@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 118 /* 0.1.17: rtus_tfm_hmc*, rtus_tfm_analytic_hmc* (half-matrix capture) */
+#define RTUS_VERSION 119 /* 0.1.18: rtus_tfm_iq*, rtus_tfm_iq_hmc* (carrier-aware interpolation) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -646,6 +646,55 @@ int rtus_tfm_analytic_hmc_dev(const float *d_a, int n_e, int n_t, double fs, dou
 int rtus_tfm_analytic_hmc(const float *a, int n_e, int n_t, double fs, double t0,
                           const double *tt_tx, const double *tt_rx, int n_f,
                           float *image, float *cf, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_iq, rtus_tfm_iq_hmc: rtus_tfm_analytic and rtus_tfm_analytic_hmc with CARRIER-AWARE (IQ) interpolation.  The analytic
+ * signal is an envelope times a carrier, and a straight line between two samples cuts the corner of the carrier's rotation: up
+ * to 1 - cos(pi f0 / fs) per term (29 % at 4 samples per cycle), a different loss at every pixel.  Here the baseband signal is
+ * interpolated and the carrier put back exactly, on the two samples the kernels load anyway.  NOT IN THE REFERENCE; checked
+ * against tests/tfm_iq_numpy.py.
+ *   f_demod [Hz], 0 <= f_demod < fs / 2: the carrier (demodulation) frequency.  nu = f_demod / fs in cycles per sample;
+ *           R = (cos 2 pi nu, -sin 2 pi nu), formed on the host in fp64 and rounded to fp32; nu rounded to fp32.
+ *   Every other argument: rtus_tfm_analytic's (rtus_tfm_analytic_hmc's).  Unchanged from there: the sample positions and their
+ *           fp32 rounding; the edge rules (sample n_t reads as zero, a negative position contributes nothing, positions outside
+ *           the record count in N with value zero); the no-path rule; the order of the sums (HMC: the pair first, one table: the
+ *           record gathered once and counted twice); N = T R; cf's formula, clamp and NaN rule.
+ *   The step, for a pair with a0, a1 the two loaded complex samples and w the fraction, all in fp32, every product and sum rounded
+ *   by itself but the fmaf's:
+ *             q = a1 R                     q.re = fmaf(a1.im, sin, a1.re cos),  q.im = fmaf(-a1.re, sin, a1.im cos)
+ *             b = a0 + w (q - a0)          each part fmaf(w, q - a0, a0)
+ *             p = b (cos 2 pi x, sin 2 pi x),  x = nu w in fp32
+ *                                          p.re = fmaf(-b.im, sin, b.re cos),   p.im = fmaf(b.re, sin, b.im cos)
+ *             S += p;  E += |p|^2;  cf = |S|^2 / (N E) as rtus_tfm_analytic
+ *           with the phasor from the hardware's sine and cosine (argument in revolutions, x in [0, 0.5]).  For a(t) = e(t) exp(2 pi
+ *           i f0 t) and f_demod = f0 this is the linear interpolation of the envelope e times the exact carrier.
+ *   Consequences:
+ *           f_demod = 0 gives rtus_tfm_analytic's (rtus_tfm_analytic_hmc's) image and cf BIT FOR BIT on finite data: R = (1, +0)
+ *           and the phasor is (1, 0) exactly, and every product above is then exact.
+ *           A position in [n_t - 1, n_t) gives (1 - w) a0 rotated by the phasor (the zero sample stays zero under R).
+ *           Determinism: the bits of a focal point depend only on its own columns of the tables, not on n_f or on which other focal
+ *           points share the call; passing cf does not change the bits of image.
+ *   A wrong f_demod costs little: 10 % off costs 0.2 % of a TFM peak at 4 samples per cycle (DESIGN.md §4 "Carrier-aware
+ *           interpolation"); the power-weighted mean frequency of the data is close enough.
+ *   Limits: f_demod not finite, negative or >= fs / 2: -1; everything else rtus_tfm_analytic's (rtus_tfm_analytic_hmc's) codes;
+ *           before any HIP call.  The _dev entries allocate nothing and do not synchronise (capturable).  The host twins stage
+ *           through the arena as their twins do.
+ * Measured on MI355X (DESIGN.md §4 "Carrier-aware interpolation", profiles/tfm_iq_kernel.txt; the linear twin in the same run = 1):
+ * 64 elements x 2048 samples, 256^2 focal points: 272 us (1.02x), 280 us with cf (1.04x); half matrix, one table: 146 us (1.03x),
+ * 155 us with cf (1.08x); two tables: 282 / 301 us (1.38x / 1.39x: VALU issue binds there).  Largest |image - oracle| / A: 2.3e-6.
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tfm_iq_dev(const float *d_a, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                    const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                    float *d_image, float *d_cf, void *stream);
+int rtus_tfm_iq(const float *a, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                const double *tt_tx, const double *tt_rx, int n_f,
+                float *image, float *cf, int device);
+int rtus_tfm_iq_hmc_dev(const float *d_a, int n_e, int n_t, double fs, double t0, double f_demod,
+                        const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                        float *d_image, float *d_cf, void *stream);
+int rtus_tfm_iq_hmc(const float *a, int n_e, int n_t, double fs, double t0, double f_demod,
+                    const double *tt_tx, const double *tt_rx, int n_f,
+                    float *image, float *cf, int device);
 
 /* ------------------------------------------------------------------------------------------
  * Plane-wave imaging (PWI): a few dozen plane waves, each fired by the whole aperture with a linear delay law and received on every

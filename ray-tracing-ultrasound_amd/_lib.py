@@ -138,6 +138,11 @@ PROTOTYPES = (
     ("rtus_tfm_hmc", i, [vp, i, i, dd, dd, vp, vp, i, vp, i], 118),
     ("rtus_tfm_analytic_hmc_dev", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, vp], 118),
     ("rtus_tfm_analytic_hmc", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, i], 118),
+    # carrier-aware (IQ) interpolation
+    ("rtus_tfm_iq_dev", i, [vp, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, vp], 119),
+    ("rtus_tfm_iq", i, [vp, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, i], 119),
+    ("rtus_tfm_iq_hmc_dev", i, [vp, i, i, dd, dd, dd, vp, vp, i, vp, vp, vp], 119),
+    ("rtus_tfm_iq_hmc", i, [vp, i, i, dd, dd, dd, vp, vp, i, vp, vp, i], 119),
     # plane-wave imaging
     ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
     ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),

@@ -84,6 +84,10 @@ hipError_t rtus_launch_tfm_hmc(const float* hmc, int n_e, int n_t, double fs, do
                                int n_f, float* image, hipStream_t s);
 hipError_t rtus_launch_tfm_analytic_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx,
                                         const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
+hipError_t rtus_launch_tfm_iq(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
+                              const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
+hipError_t rtus_launch_tfm_iq_hmc(const float* an, int n_e, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
+                                  const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s);
@@ -1333,8 +1337,9 @@ int rtus_tfm_analytic_dev(const float* d_a, int n_tx, int n_rx, int n_t, double 
     return RTUS_OK;
 }
 
-int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
-                      int n_f, float* image, float* cf, int device)
+// the host twins of rtus_tfm_analytic and rtus_tfm_iq: f_demod < 0 stands for the former
+static int tfm_analytic_host(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
+                             const double* tt_rx, int n_f, float* image, float* cf, int device)
 {
     int st = check_tfm_analytic(a, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, image);
     if (st) return st;
@@ -1350,8 +1355,15 @@ int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     S.out(dimg, image, 2 * (size_t)n_f);
     S.out(dcf, cf, n_f);
     if ((st = S.flush())) return st;
-    LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
+    if (f_demod < 0.0) LAUNCH_TRY(rtus_launch_tfm_analytic(da, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
+    else LAUNCH_TRY(rtus_launch_tfm_iq(da, n_tx, n_rx, n_t, fs, t0, f_demod, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
     return S.finish();
+}
+
+int rtus_tfm_analytic(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                      int n_f, float* image, float* cf, int device)
+{
+    return tfm_analytic_host(a, n_tx, n_rx, n_t, fs, t0, -1.0, tt_tx, tt_rx, n_f, image, cf, device);
 }
 
 // ---------------------------------------------------------------------------- TFM and envelope TFM over a half-matrix capture
@@ -1384,7 +1396,7 @@ int rtus_tfm_analytic_hmc_dev(const float* d_a, int n_e, int n_t, double fs, dou
 
 // the two host twins: c = floats per sample (1 real, 2 analytic); cf only with c == 2
 static int tfm_hmc_host(const float* hmc, int c, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
-                        int n_f, float* image, float* cf, int device)
+                        int n_f, float* image, float* cf, int device, double f_demod = -1.0)   // >= 0: rtus_tfm_iq_hmc (c == 2)
 {
     int st = check_tfm_hmc(hmc, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, c == 2);
     if (st) return st;
@@ -1400,7 +1412,9 @@ static int tfm_hmc_host(const float* hmc, int c, int n_e, int n_t, double fs, do
     S.out(dimg, image, (size_t)c * n_f);
     if (c == 2) S.out(dcf, cf, n_f);
     if ((st = S.flush())) return st;
-    if (c == 2) LAUNCH_TRY(rtus_launch_tfm_analytic_hmc(dh, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
+    if (c == 2 && f_demod >= 0.0)
+        LAUNCH_TRY(rtus_launch_tfm_iq_hmc(dh, n_e, n_t, fs, t0, f_demod, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
+    else if (c == 2) LAUNCH_TRY(rtus_launch_tfm_analytic_hmc(dh, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dcf, S.a->stream));
     else LAUNCH_TRY(rtus_launch_tfm_hmc(dh, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
     return S.finish();
 }
@@ -1415,6 +1429,50 @@ int rtus_tfm_analytic_hmc(const float* a, int n_e, int n_t, double fs, double t0
                           float* image, float* cf, int device)
 {
     return tfm_hmc_host(a, 2, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, cf, device);
+}
+
+// ---------------------------------------------------------------------------- carrier-aware (IQ) envelope TFM, full and half matrix
+static int check_f_demod(double f_demod, double fs)
+{
+    return f_demod >= 0.0 && f_demod < 0.5 * fs ? RTUS_OK : RTUS_ERR_INVALID_ARG;   // (NaN and +inf fail the compares)
+}
+
+int rtus_tfm_iq_dev(const float* d_a, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod, const double* d_tt_tx,
+                    const double* d_tt_rx, int n_f, float* d_image, float* d_cf, void* stream)
+{
+    int st = check_tfm_analytic(d_a, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image);
+    if (!st) st = check_f_demod(f_demod, fs);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_iq(d_a, n_tx, n_rx, n_t, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, d_image, d_cf, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_iq(const float* a, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
+                const double* tt_rx, int n_f, float* image, float* cf, int device)
+{
+    int st = check_tfm_analytic(a, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, image);
+    if (!st) st = check_f_demod(f_demod, fs);
+    if (st) return st;
+    return tfm_analytic_host(a, n_tx, n_rx, n_t, fs, t0, f_demod, tt_tx, tt_rx, n_f, image, cf, device);
+}
+
+int rtus_tfm_iq_hmc_dev(const float* d_a, int n_e, int n_t, double fs, double t0, double f_demod, const double* d_tt_tx,
+                        const double* d_tt_rx, int n_f, float* d_image, float* d_cf, void* stream)
+{
+    int st = check_tfm_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, true);
+    if (!st) st = check_f_demod(f_demod, fs);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_iq_hmc(d_a, n_e, n_t, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, d_image, d_cf, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_iq_hmc(const float* a, int n_e, int n_t, double fs, double t0, double f_demod, const double* tt_tx, const double* tt_rx,
+                    int n_f, float* image, float* cf, int device)
+{
+    int st = check_tfm_hmc(a, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, true);
+    if (!st) st = check_f_demod(f_demod, fs);
+    if (st) return st;
+    return tfm_hmc_host(a, 2, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, cf, device, f_demod);
 }
 
 // ---------------------------------------------------------------------------- phase-coherence TFM: vcf, scf

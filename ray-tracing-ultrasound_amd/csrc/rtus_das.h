@@ -69,6 +69,33 @@ __device__ __forceinline__ float2 das_lerp(das_u32x4 v, float w)
     return make_float2(fmaf(w, r1 - r0, r0), fmaf(w, i1 - i0, i0));
 }
 
+// The interpolation step of a kernel over the loaded pair, as an object: DasLerp is das_lerp.  DasIq is the carrier-aware step of
+// rtus_tfm_iq (include/rtus.h) on complex samples: the second sample turned back by one sample of the carrier, q = a1 R with
+// R = (cs, -sn) = exp(-2 pi i nu); das_lerp's form between a0 and q — the baseband signal interpolated; and the carrier put back,
+// p = b exp(2 pi i nu w).  nu = f_demod / fs in cycles per sample, nu w in [0, 0.5]: the hardware's sine and cosine take their
+// argument in revolutions, no range reduction and no 2 pi.  cs, sn (fp64 on the host, rounded once) and nu are wave-uniform.
+// Every product is a statement of its own (no contraction: the bits do not depend on what the compiler would fuse), arranged so
+// that nu = 0 — cs = 1, sn = +0, phasor (1, 0) exactly — multiplies exactly: p is then das_lerp's (a signed zero apart, which no
+// running sum that starts at +0 can see).  A sample that reads as zero (sample n_t, a dropped load) stays zero under R: a position
+// in [n_t - 1, n_t) gives (1 - w) a0 times the phasor, a dropped pair gives 0.
+struct DasLerp {
+    template <class V>
+    __device__ __forceinline__ auto operator()(V v, float w) const { return das_lerp(v, w); }
+};
+struct DasIq {
+    float cs, sn, nu;
+    __device__ __forceinline__ float2 operator()(das_u32x4 v, float w) const
+    {
+#pragma clang fp contract(off)
+        const float r0 = __uint_as_float(v.x), i0 = __uint_as_float(v.y), r1 = __uint_as_float(v.z), i1 = __uint_as_float(v.w);
+        const float qr = fmaf(i1, sn, r1 * cs), qi = fmaf(-r1, sn, i1 * cs);
+        const float br = fmaf(w, qr - r0, r0), bi = fmaf(w, qi - i0, i0);
+        const float x = nu * w;
+        const float c = __builtin_amdgcn_cosf(x), s = __builtin_amdgcn_sinf(x);
+        return make_float2(fmaf(-bi, s, br * c), fmaf(br, s, bi * c));
+    }
+};
+
 // One transmit element against the nr receive elements of the tile: accum(r, samples, weight) for r = 0 .. nr - 1 in
 // ascending order, samples = the two at floor(tt + tau[r]) of the record rec + r * stride (rec, stride: wave-uniform, in
 // floats), weight = the position's fraction.  The lane's column of the LDS tile is tau[.][lane].

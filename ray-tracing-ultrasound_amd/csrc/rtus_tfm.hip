@@ -169,10 +169,11 @@ struct TfmaArgs {
     double fs, half_t0s;
 };
 
-template <bool CF>
-__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs a)
+// Lerp: the step from a loaded pair to the interpolated sample p (rtus_das.h): DasLerp, or DasIq for rtus_tfm_iq_kernel
+// (the arguments by value: by reference rtus_tfm_analytic_kernel's register allocation moves, scripts/asm_body_digest.py)
+template <bool CF, class Lerp>
+__device__ __forceinline__ void tfma_body(TfmaArgs a, float (*tau_rx)[RTUS_BLOCK], Lerp lerp)
 {
-    __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB, as rtus_tfm_kernel
     const int f_raw = das_workgroup() * RTUS_BLOCK + threadIdx.x;
     const bool live = f_raw < a.n_f;
     const int f = live ? f_raw : a.n_f - 1;
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs 
             if (CF && r0 == 0) n_tx_ok += tfm_has_path(tt);
             das_gather<2>(a.fmc + ((size_t)tx * a.n_rx + r0) * pair_len, pair_len, a.n_t, tt, tau_rx, threadIdx.x, nr,
                           [&](int, das_u32x4 v, float w) {
-                              const float2 p = das_lerp(v, w);
+                              const float2 p = lerp(v, w);
                               re += p.x;
                               im += p.y;
                               if (CF) en = fmaf(p.y, p.y, fmaf(p.x, p.x, en));
@@ -218,6 +219,32 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs 
     }
 }
 
+template <bool CF>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_kernel(TfmaArgs a)
+{
+    __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB, as rtus_tfm_kernel
+    tfma_body<CF>(a, tau_rx, DasLerp());
+}
+
+// The carrier-aware envelope TFM (include/rtus.h, rtus_tfm_iq): the same kernel with DasIq's step between the load and the sums —
+// four products for R, the lerp, one product and two transcendentals for the phasor, four products to apply it: VALU work under
+// gathers that the vector-memory address path paces.
+template <bool CF>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_iq_kernel(TfmaArgs a, DasIq iq)
+{
+    __shared__ float tau_rx[RTUS_TFM_RX_TILE][RTUS_BLOCK];           // 64 KB, as rtus_tfm_kernel
+    tfma_body<CF>(a, tau_rx, iq);
+}
+
+// f_demod -> (R, nu) of DasIq; 0 <= f_demod < fs / 2 (checked by the C entries).  f_demod = 0: (1, +0, 0)
+DasIq rtus_das_iq(double f_demod, double fs)
+{
+    const double nu = f_demod / fs, ph = 6.283185307179586476925 * nu;
+    DasIq q;
+    q.cs = (float)cos(ph); q.sn = (float)sin(ph); q.nu = (float)nu;
+    return q;
+}
+
 hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s)
 {
@@ -226,6 +253,18 @@ hipError_t rtus_launch_tfm_analytic(const float* an, int n_tx, int n_rx, int n_t
     const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
     if (cf) hipLaunchKernelGGL(rtus_tfm_analytic_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(rtus_tfm_analytic_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t rtus_launch_tfm_iq(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
+                              const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s)
+{
+    TfmaArgs a = tfm_args<TfmaArgs>(an, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f);
+    a.image = (float2*)image; a.cf = cf;
+    const DasIq iq = rtus_das_iq(f_demod, fs);
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    if (cf) hipLaunchKernelGGL(rtus_tfm_iq_kernel<true>, grid, block, 0, s, a, iq);
+    else hipLaunchKernelGGL(rtus_tfm_iq_kernel<false>, grid, block, 0, s, a, iq);
     return hipGetLastError();
 }
 

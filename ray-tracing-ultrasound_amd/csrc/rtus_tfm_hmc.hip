@@ -79,9 +79,11 @@ template <> struct HmcTau<true> { typedef float2 type; };
 // NR: the block's size when it is known at compile time (a full block's triangle), else 0.  With it the walk is unrolled: every
 // (r, c), kind, weight and LDS offset becomes a constant, and the triangle's batches have the fixed-shape batches' instruction
 // stream (the walk itself costs ~25 scalar and 2 vector instructions per record).
-template <int C, bool CF, bool TWO, bool TRI, int NR = 0>
+// lerp: the step from a loaded pair to the interpolated sample (rtus_das.h: DasLerp, or DasIq for the carrier-aware kernels).
+template <int C, bool CF, bool TWO, bool TRI, int NR = 0, class Lerp>
 __device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, size_t len, size_t step, int n_t, int nr_,
-                                         const typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], int lane, typename HmcTau<TWO>::type tr)
+                                         const typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], int lane, typename HmcTau<TWO>::type tr,
+                                         const Lerp& lerp)
 {
     constexpr int PER = TWO ? RTUS_DAS_GROUP / 2 : RTUS_DAS_GROUP;    // records per batch
     const int nr = NR ? NR : nr_;
@@ -126,7 +128,7 @@ __device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, s
                 return LAST && kind[k] == HMC_NONE ? 2.0f * RTUS_DAS_NO_PATH : tr + tc;
             };
             das_batch<C>(n_t, at, [&](int k, auto v, float w) {
-                sum.one(das_lerp(v, w), wgt[k]);
+                sum.one(lerp(v, w), wgt[k]);
             });
         } else {
             decltype(das_lerp(das_load2<C>(rec, n_t, 0), 0.0f)) first;
@@ -148,8 +150,8 @@ __device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, s
                 return LAST && kind[m] == HMC_NONE ? 2.0f * RTUS_DAS_NO_PATH : tr.x + tc.y;
             };
             das_batch<C>(n_t, at, [&](int k, auto v, float w) {
-                if (!(k & 1)) first = das_lerp(v, w);
-                else sum.two(first, das_lerp(v, w), kind[k >> 1]);
+                if (!(k & 1)) first = lerp(v, w);
+                else sum.two(first, lerp(v, w), kind[k >> 1]);
             });
         }
     };
@@ -162,8 +164,8 @@ __device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, s
     if (left) batch(std::true_type());
 }
 
-template <int C, bool CF, bool TWO>
-__device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK])
+template <int C, bool CF, bool TWO, class Lerp>
+__device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], const Lerp& lerp)
 {
     constexpr int TILE = TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE;
     static_assert(TILE % RTUS_DAS_GROUP == 0, "a tile is a whole number of column blocks");
@@ -200,14 +202,14 @@ __device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>:
             size_t down = (ne - 1) * len;                                 // from (i, cg) to (i + 1, cg): n_e - 1 - i records
             // rows of earlier tiles: their delays come from memory (a load that a gather's batch must not wait for)
             for (int i = 0; i < r0; ++i, row += down, down -= len)
-                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tau(i));
+                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tau(i), lerp);
             // rows of this tile above the block: their delays are in the tile
             for (int i = r0; i < cg; ++i, row += down, down -= len)
-                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tile[i - r0][lane]);
+                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tile[i - r0][lane], lerp);
             // the block's own triangle from (cg, cg) on; a row's records to the right of the block are stepped over
             const size_t past = (ne - (size_t)(cg + nb)) * len;
-            if (nb == RTUS_DAS_GROUP) hmc_walk<C, CF, TWO, true, RTUS_DAS_GROUP>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau());
-            else hmc_walk<C, CF, TWO, true>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau());
+            if (nb == RTUS_DAS_GROUP) hmc_walk<C, CF, TWO, true, RTUS_DAS_GROUP>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau(), lerp);
+            else hmc_walk<C, CF, TWO, true>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau(), lerp);
         }
     }
     if (!live) return;
@@ -231,14 +233,23 @@ template <bool TWO>
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_hmc_kernel(HmcArgs a)
 {
     __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
-    hmc_body<1, false, TWO>(a, tile);
+    hmc_body<1, false, TWO>(a, tile, DasLerp());
 }
 
 template <bool CF, bool TWO>
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_analytic_hmc_kernel(HmcArgs a)
 {
     __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
-    hmc_body<2, CF, TWO>(a, tile);
+    hmc_body<2, CF, TWO>(a, tile, DasLerp());
+}
+
+// the carrier-aware form (include/rtus.h, rtus_tfm_iq_hmc): DasIq's step on every gathered pair, in every form of the walk; a
+// padded slot reads zeros, which the step leaves zero
+template <bool CF, bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_hmc_iq_kernel(HmcArgs a, DasIq iq)
+{
+    __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
+    hmc_body<2, CF, TWO>(a, tile, iq);
 }
 
 static HmcArgs hmc_args(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
@@ -271,5 +282,21 @@ hipError_t rtus_launch_tfm_analytic_hmc(const float* an, int n_e, int n_t, doubl
     else if (cf) hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<true, false>), grid, block, 0, s, a);
     else if (two) hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<false, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((rtus_tfm_analytic_hmc_kernel<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+DasIq rtus_das_iq(double f_demod, double fs);                          // rtus_tfm.hip
+
+hipError_t rtus_launch_tfm_iq_hmc(const float* an, int n_e, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
+                                  const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s)
+{
+    const HmcArgs a = hmc_args(an, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, cf);
+    const DasIq iq = rtus_das_iq(f_demod, fs);
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    const bool two = tt_tx != tt_rx;
+    if (cf && two) hipLaunchKernelGGL((rtus_tfm_hmc_iq_kernel<true, true>), grid, block, 0, s, a, iq);
+    else if (cf) hipLaunchKernelGGL((rtus_tfm_hmc_iq_kernel<true, false>), grid, block, 0, s, a, iq);
+    else if (two) hipLaunchKernelGGL((rtus_tfm_hmc_iq_kernel<false, true>), grid, block, 0, s, a, iq);
+    else hipLaunchKernelGGL((rtus_tfm_hmc_iq_kernel<false, false>), grid, block, 0, s, a, iq);
     return hipGetLastError();
 }

@@ -393,6 +393,32 @@ def tfm_analytic_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None)
     return out if cf is None else (out, cf)
 
 
+def _f_demod(f_demod, fs):
+    """0 <= f_demod < fs / 2, finite (api.tfm_iq's rule) -> float"""
+    f_demod, fs = float(f_demod), float(fs)
+    if not (f_demod == f_demod and fs == fs and 0.0 <= f_demod < 0.5 * fs):
+        raise ValueError(f"f_demod must be finite with 0 <= f_demod < fs / 2 (got {f_demod!r} at fs = {fs!r})")
+    return f_demod
+
+
+def tfm_iq_dev(analytic, fs, f_demod, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None):
+    """Envelope TFM with carrier-aware interpolation on device (rtus_tfm_iq_dev; api.tfm_iq's definition): tfm_analytic_dev's
+    tensors and returns, ``f_demod`` [Hz] the carrier frequency, 0 <= f_demod < fs / 2 (0: tfm_analytic_dev's bits).  Asynchronous
+    on the current stream (capturable with pre-allocated outputs)."""
+    f_demod = _f_demod(f_demod, fs)
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_f = _tables(tt_tx, tt_rx, analytic, analytic=True)
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, cf=cf)
+    if not (out.device == analytic.device == tt_tx.device == tt_rx.device and (cf is None or cf.device == analytic.device)):
+        raise ValueError("analytic, tt_tx, tt_rx, out and cf must be on one device")
+    st = _lib.lib().rtus_tfm_iq_dev(_p(analytic), analytic.shape[0], analytic.shape[1], analytic.shape[2], float(fs), float(t0), f_demod,
+                                    _p(tt_tx), _p(tt_rx), n_f, _p(out), _p(cf), _stream(analytic))
+    _lib.check(st, "rtus_tfm_iq_dev")
+    return out if cf is None else (out, cf)
+
+
 def _hmc_tables(tt_tx, tt_rx, data, analytic):
     """a half-matrix capture [n_pairs, n_t] (analytic: [.., 2]) against tt_tx, tt_rx [n_e, n] both -> (n_e, n)"""
     ok = tt_tx.dim() == 2 and tt_rx.dim() == 2 and tt_tx.shape == tt_rx.shape \
@@ -434,6 +460,23 @@ def tfm_analytic_hmc_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=N
     st = _lib.lib().rtus_tfm_analytic_hmc_dev(_p(analytic), n_e, analytic.shape[1], float(fs), float(t0), _p(tt_tx), _p(tt_rx), n_f,
                                               _p(out), _p(cf), _stream(analytic))
     _lib.check(st, "rtus_tfm_analytic_hmc_dev")
+    return out if cf is None else (out, cf)
+
+
+def tfm_iq_hmc_dev(analytic, fs, f_demod, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None):
+    """tfm_iq_dev over a half-matrix capture (rtus_tfm_iq_hmc_dev; api.tfm_iq_hmc's definition): tfm_analytic_hmc_dev's tensors
+    and returns, ``f_demod`` [Hz] as in tfm_iq_dev.  Asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    f_demod = _f_demod(f_demod, fs)
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_e, n_f = _hmc_tables(tt_tx, tt_rx, analytic, True)
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, cf=cf)
+    if not (out.device == analytic.device == tt_tx.device == tt_rx.device and (cf is None or cf.device == analytic.device)):
+        raise ValueError("analytic, tt_tx, tt_rx, out and cf must be on one device")
+    st = _lib.lib().rtus_tfm_iq_hmc_dev(_p(analytic), n_e, analytic.shape[1], float(fs), float(t0), f_demod, _p(tt_tx), _p(tt_rx), n_f,
+                                        _p(out), _p(cf), _stream(analytic))
+    _lib.check(st, "rtus_tfm_iq_hmc_dev")
     return out if cf is None else (out, cf)
 
 
