@@ -15,7 +15,10 @@ def focal_delays(tt):
 
 def tfm(fmc, fs, t0, tt_tx, tt_rx):
     """image[f] = sum_{tx, rx} fmc[tx, rx] interpolated linearly at sample (tt_tx[tx, f] + tt_rx[rx, f] - t0) * fs;
-    samples outside the record are zero, NaN travel times contribute nothing.  float64 accumulation."""
+    samples outside the record are zero.  A leg without a path contributes nothing: one whose half of the position,
+    float32(t * fs - t0 * fs / 2), is not finite or has |.| >= 1e8 (include/rtus.h, rtus_tfm: "NaN — or any non-finite or
+    absurd travel time") — without this rule two absurd legs of opposite sign would meet inside the record.  The position
+    itself is formed in fp64 here (the kernels add the two float32 halves).  float64 accumulation."""
     fmc = np.asarray(fmc, dtype=np.float32)
     n_tx, n_rx, n_t = fmc.shape
     tt_tx = np.asarray(tt_tx, dtype=np.float64)
@@ -23,9 +26,14 @@ def tfm(fmc, fs, t0, tt_tx, tt_rx):
     n_f = tt_tx.shape[1]
     img = np.zeros(n_f)
     pad = np.concatenate([fmc.astype(np.float64), np.zeros((n_tx, n_rx, 1))], axis=2)   # sample n_t = 0
+    with np.errstate(all="ignore"):
+        leg_tx, leg_rx = ((t * fs - 0.5 * t0 * fs).astype(np.float32) for t in (tt_tx, tt_rx))
+        ok_tx, ok_rx = (np.isfinite(v) & (np.abs(v) < np.float32(1e8)) for v in (leg_tx, leg_rx))
     for tx in range(n_tx):
-        s = (tt_tx[tx][None, :] + tt_rx - t0) * fs                      # [n_rx, n_f]
-        ok = np.isfinite(s) & (s >= 0) & (s < n_t)
+        with np.errstate(all="ignore"):
+            s = (tt_tx[tx][None, :] + tt_rx - t0) * fs                  # [n_rx, n_f]
+            ok = ok_tx[tx][None, :] & ok_rx & np.isfinite(s) & (s >= 0) & (s < n_t)
+        s = np.where(ok, s, 0.0)
         i = np.where(ok, np.floor(s), 0).astype(np.int64)
         w = np.where(ok, s - i, 0.0)
         rows = np.arange(n_rx)[:, None]

@@ -44,9 +44,10 @@ __device__ __forceinline__ int tfm_has_path(float tau) { return tau > RTUS_DAS_N
 // the descriptor's range check and reads as zeros.
 // Edges, as oracle/tfm_numpy.py defines them: a position in [n_t - 1, n_t) interpolates towards a zero sample n_t (the
 // second half of the load is out of range by itself); a NEGATIVE position contributes nothing — index -1 must not wrap:
-// its second sample would sit at byte offset 2^32, which the range check sees as 0 — so negative indices (as unsigned:
-// >= 2^31) are clamped to one that is out of range with every dword.  |i| stays below 2^28 (das_clamp: each leg within
-// +-1e8 samples), n_t <= 2^26.
+// its second sample sits at byte offset 2^32, which a range check in 32 bits would see as 0 — so negative indices (as
+// unsigned: >= 2^31) are clamped to one that is out of range with every dword.  (Observed on MI355X: without the clamp the
+// same load at offset 0xFFFFFFFC still returns zeros for both samples — tests/test_gpu_das_exact.py, change M1; the clamp is
+// the guard that does not depend on it.)  |i| stays below 2^28 (das_clamp: each leg within +-1e8 samples), n_t <= 2^26.
 typedef unsigned int das_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int das_u32x4 __attribute__((ext_vector_type(4)));
 template <int C>

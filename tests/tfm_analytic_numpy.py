@@ -2,7 +2,7 @@
 
 Definitions (the header's): S[f] = sum over (tx, rx) of the analytic FMC a[tx, rx] interpolated linearly at the sample position
 (tt_tx[tx, f] + tt_rx[rx, f] - t0) fs, real and imaginary parts separately, with oracle/tfm_numpy.py's edge rules; a leg has a path
-when t fs - t0 fs / 2 is finite with |.| < 1e8; N[f] = T[f] R[f] (tx and rx with a path); E[f] = the sum of |a(s)|^2 over the pairs;
+when float32(t fs - t0 fs / 2) is finite with |.| < 1e8; N[f] = T[f] R[f] (tx and rx with a path); E[f] = the sum of |a(s)|^2 over the pairs;
 cf = |S|^2 / (N E) clamped to 1, NaN when N = 0, 0 when E = 0 < N.  Pairs whose position falls outside the record count in N with
 value zero.
 """
@@ -10,10 +10,12 @@ import numpy as np
 
 
 def leg_has_path(tt, fs, t0):
-    """[n_e, n_f] bool: the leg's half sample position is finite and below 1e8 in magnitude"""
+    """[n_e, n_f] bool: the leg's half sample position, ROUNDED TO FLOAT32 as the header has it, is finite and below 1e8 in
+    magnitude.  The rounding decides for the fp64 values in (99999996, 1e8): they round onto the float32 1e8 and have no path
+    (tests/das_exact_numpy.py puts legs there)."""
     with np.errstate(all="ignore"):
-        v = np.asarray(tt, dtype=np.float64) * fs - 0.5 * t0 * fs
-        return np.isfinite(v) & (np.abs(v) < 1e8)
+        v = (np.asarray(tt, dtype=np.float64) * fs - 0.5 * t0 * fs).astype(np.float32)
+        return np.isfinite(v) & (np.abs(v) < np.float32(1e8))
 
 
 def coherence(S, N, E):

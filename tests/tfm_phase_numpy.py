@@ -68,7 +68,8 @@ def samples(a, fs, t0, tt_tx, tt_rx=None, fp32=False):
         return P, ok_tx, ok_rx
     a = a.astype(np.complex128)
     with np.errstate(all="ignore"):
-        ok_tx, ok_rx = (np.isfinite(v) & (np.abs(v) < 1e8) for v in (tt_tx * fs - 0.5 * t0 * fs, tt_rx * fs - 0.5 * t0 * fs))
+        ok_tx, ok_rx = (np.isfinite(v) & (np.abs(v) < np.float32(1e8))     # (the leg rule reads the float32 value: the header's)
+                        for v in ((tt_tx * fs - 0.5 * t0 * fs).astype(np.float32), (tt_rx * fs - 0.5 * t0 * fs).astype(np.float32)))
     pad = np.concatenate([a, np.zeros((n_tx, n_rx, 1))], axis=2)
     P = np.zeros((n_tx, n_rx, n_f), dtype=np.complex128)
     for tx in range(n_tx):
