@@ -86,6 +86,27 @@ extern "C" int rtus_dbg_read_planar(unsigned long long* out)
 }
 #endif
 
+#ifdef RTUS_EXP_STAMPS   // experiment builds only (scripts/stamps_planar.py): where a row-table workgroup's time goes, phase by phase
+#define RTUS_STAMP_WGS 8192
+// six stamps per workgroup (rows of eight words): entry, after the records' barrier, after the node pass, after the check pass, first store, last store
+static __device__ unsigned long long planar_stamps[RTUS_STAMP_WGS * 8];
+extern "C" int rtus_dbg_read_stamps(unsigned long long* out, int n_wg)
+{
+    if (n_wg < 0 || n_wg > RTUS_STAMP_WGS) return 1;
+    void* dev = nullptr;
+    const size_t bytes = sizeof(unsigned long long) * 8 * (size_t)n_wg;
+    if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&dev, HIP_SYMBOL(planar_stamps)) != hipSuccess ||
+        hipMemcpy(out, dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    // (cleared for the next launch: a workgroup that took the solver leaves zeros)
+    return hipMemset(dev, 0, bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : 2;
+}
+// The device's constant-rate clock (100 MHz: the same on every CU), lane 0 of the workgroup, an ordinary vector store.  The row is
+// blockIdx.x alone: a batched launch (grid.z > 1) writes every problem's stamps over problem 0's — stamp single-problem launches.
+#define RTUS_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < RTUS_STAMP_WGS) planar_stamps[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
+#else
+#define RTUS_STAMP(i) do { } while (0)
+#endif
+
 // One element's record in LDS: every lane of the workgroup reads the same address (broadcast, no VALU slot —
 // a v_readlane costs 4.2 cycles and leaves its value in an SGPR, which halves the rate of every fp32 op reading it).
 struct __attribute__((aligned(16))) ElemRec {
@@ -456,6 +477,81 @@ __device__ __forceinline__ bool rowtab_point(const Lane<NL>& L, double X, double
     return ok;
 }
 
+// The positions a record is formed from: an element and its four predecessors inside the workgroup's block (one element per lane
+// of the first wave).  All loads are issued together.
+struct ElemPos { double x0, x1, x2, x3, x4, z0, z1, z2, z3, z4; };
+__device__ __forceinline__ ElemPos load_elem_pos(const double* __restrict__ xe_p, const double* __restrict__ ze_p, int e0, int el)
+{
+    const int b1 = max(el - 1, e0), b2 = max(el - 2, e0), b3 = max(el - 3, e0), b4 = max(el - 4, e0);
+    ElemPos P;
+    P.x0 = xe_p[el]; P.z0 = ze_p[el];
+    P.x1 = xe_p[b1]; P.x2 = xe_p[b2]; P.x3 = xe_p[b3]; P.x4 = xe_p[b4];
+    P.z1 = ze_p[b1]; P.z2 = ze_p[b2]; P.z3 = ze_p[b3]; P.z4 = ze_p[b4];
+    return P;
+}
+
+// The solver's record of one element (lane `lane` of the first wave, all 64 lanes active: the ballots below are the wave's): how much
+// history it has, the predictor's weights, the length of the four-history run that starts at it, whether HOLD may run over it.
+template <bool TAUP>
+__device__ __forceinline__ ElemRec elem_record(const LayerArgs& a, int lane, int ne, const ElemPos& P, int row)
+{
+    const double x0 = P.x0, x1 = P.x1, x2 = P.x2, x3 = P.x3, x4 = P.x4, z0 = P.z0, z1 = P.z1, z2 = P.z2, z3 = P.z3, z4 = P.z4;
+    // how many predecessors inside this workgroup share the element's depth (the history restarts when ze changes)
+    // (a predecessor at a non-finite position is no history either — its solution is NaN, and 0 x NaN in the predictor's unused
+    // terms would carry it into up to four rows behind it: scripts/exp_nan_rows.py, tests/test_gpu_edge_sizes.py)
+    const bool s1 = (lane >= 1) & (z1 == z0) & isfinite(x1), s2 = s1 & (lane >= 2) & (z2 == z0) & isfinite(x2),
+               s3 = s2 & (lane >= 3) & (z3 == z0) & isfinite(x3), s4 = s3 & (lane >= 4) & (z4 == z0) & isfinite(x4);
+    int hist = s4 ? 4 : (s3 ? 3 : (s2 ? 2 : (s1 ? 1 : 0)));
+    // Lagrange weights of the extrapolation to x0 from the nodes x1 .. x_m (differences in fp64, products in fp32)
+    const float t1 = (float)(x0 - x1), t2 = (float)(x0 - x2), t3 = (float)(x0 - x3), t4 = (float)(x0 - x4);
+    const float d12 = (float)(x1 - x2), d13 = (float)(x1 - x3), d14 = (float)(x1 - x4), d23 = (float)(x2 - x3),
+                d24 = (float)(x2 - x4), d34 = (float)(x3 - x4);
+    // duplicate positions leave no slope: use as many nodes as are pairwise distinct, at least the latest one
+    const bool ok2 = d12 != 0.0f, ok3 = ok2 & (d13 != 0.0f) & (d23 != 0.0f),
+               ok4 = ok3 & (d14 != 0.0f) & (d24 != 0.0f) & (d34 != 0.0f);
+    const int m = (hist >= 4 && ok4) ? 4 : ((hist >= 3 && ok3) ? 3 : ((hist >= 2 && ok2) ? 2 : (hist >= 1 ? 1 : 0)));
+    float w1 = 0.0f, w2 = 0.0f, w3 = 0.0f, w4 = 0.0f;
+    if (m == 4) {
+        w1 = t2 * t3 * t4 / (d12 * d13 * d14);
+        w2 = -t1 * t3 * t4 / (d12 * d23 * d24);
+        w3 = t1 * t2 * t4 / (d13 * d23 * d34);
+        w4 = -t1 * t2 * t3 / (d14 * d24 * d34);
+    } else if (m == 3) {
+        w1 = t2 * t3 / (d12 * d13);
+        w2 = -t1 * t3 / (d12 * d23);
+        w3 = t1 * t2 / (d13 * d23);
+    } else if (m == 2) {
+        w1 = t2 / d12;
+        w2 = -t1 / d12;
+    } else if (m == 1) {
+        w1 = 1.0f;
+    }
+    // run of consecutive elements (from this one on) that all have four distinct same-depth predecessors
+    const unsigned long long m4 = __ballot(m == 4 && lane < ne);
+    const unsigned long long rest = ~(m4 >> lane);
+    const int run = (m == 4 && lane < ne) ? (rest ? __ffsll((long long)rest) - 1 : 64 - lane) : 0;
+    // HOLD (tau-p tier) extrapolates along the ELEMENT INDEX: only where the pitch is uniform (2 %) over the four elements behind
+    // and the three ahead (an aperture of random spacing put 4.5e-9 relative on a table before this test existed —
+    // tests/test_gpu_irregular_apertures.py::test_planar_taup_tier_irregular_and_coarse_apertures).  Behind: this lane's own
+    // differences; ahead: the same statement of the lane three further on (they share the step x_i - x_(i-1)).  No loads, no LDS
+    // word of its own: the workgroup's start-up is not overlapped with anything (0.1 us there is 1 % of a configs[1] launch).
+    bool uni = false;
+    if (TAUP && a.eb >= 8) {                            // (a block of fewer rows has no group of four behind four cold rows)
+        const float tolu = 0.02f * fabsf(t1);
+        const bool ub = m == 4 && lane < ne && fabsf(d12 - t1) <= tolu && fabsf(d23 - t1) <= tolu && fabsf(d34 - t1) <= tolu;
+        const unsigned long long ubm = __ballot(ub);
+        uni = __builtin_amdgcn_inverse_ballot_w64(ubm & (ubm >> 3));
+    }
+    ElemRec r;
+#ifdef RTUS_EXP_BAD_PREDICTOR                               // experiment builds only (scripts/selftest_predictor.sh): the continuation tests must notice
+    w1 *= 1.02f; w3 *= 0.97f;
+#endif
+    r.w1 = w1; r.w2 = w2; r.w3 = w3; r.w4 = w4; r.xe = x0;
+    r.info = m | (hist == 0 ? 8 : 0) | (uni ? 16 : 0) | (run << 8);
+    r.row = row;
+    return r;
+}
+
 // A workgroup = 256 focal points x `eb` consecutive elements (loop).  Besides re-using the layer
 // set-up while ze repeats, the loop gives each lane a CONTINUATION PREDICTOR: the signed solution
 // qs = sign(xf - xe) q is a smooth function of the element position, so the four previous
@@ -515,87 +611,43 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
     // a table of short blocks, configs[1] for one, pays nothing further).  Each wave leaves the range of its targets' x and whether
     // they share the first target's depth; the first wave does the same for the elements below.
     const bool try_tab = ROWTAB && a.rowtab && min((long long)(gb + 1) * a.eb, a.n_rows) - (long long)gb * a.eb >= RTUS_ROWTAB_MIN_ROWS;
+    RTUS_STAMP(0);
+    const bool first_wave = threadIdx.x < 64;
+    const int el = min(e0 + (int)(threadIdx.x & 63), a.n_e - 1);   // the first wave: its lane's element
+    // A workgroup that tries the table forms the solver's records only if it turns out to need them (behind the table path below):
+    // before the barrier it leaves what serving reads — the element's position and, PERM, its row — and the header's words.
     double zfv = 0.0;
     if (try_tab) {
+        // The first wave's element loads go out WITH the targets', before anything waits on either: behind the wait for xf and zf,
+        // which the reductions need, they were a second round trip to the L2 with three waves at the barrier meanwhile.
+        ElemPos P;                                           // (the first wave's, x0 and z0 alone: no other wave reads it)
+        int prow = 0;
+        if (first_wave) {
+            P.x0 = xe_p[el]; P.z0 = ze_p[el];
+            if (PERM) prow = a.row_of[el];
+        }
         zfv = zf_p[f];
         const bool okl = zfv == zf_p[bx * RTUS_BLOCK] && isfinite(xf);
         const bool okw = !__builtin_amdgcn_ballot_w64(!okl);
         double lo = 0.0, hi = 0.0;
         if (okw) { lo = wave_min_f64(xf); hi = wave_max_f64(xf); }       // (wave-uniform: random targets pay the load and the ballot only)
         if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; hdr.flo[w] = lo; hdr.fhi[w] = hi; hdr.fok[w] = okw; }
-    }
-
-    // ---- per-element records: the first wave works them out, one element per lane ----------------------
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        const int el = min(e0 + lane, a.n_e - 1);
-        const int b1 = max(el - 1, e0), b2 = max(el - 2, e0), b3 = max(el - 3, e0), b4 = max(el - 4, e0);
-        const double x0 = xe_p[el], z0 = ze_p[el];
-        const double x1 = xe_p[b1], x2 = xe_p[b2], x3 = xe_p[b3], x4 = xe_p[b4];
-        const double z1 = ze_p[b1], z2 = ze_p[b2], z3 = ze_p[b3], z4 = ze_p[b4];     // all loads issued together
-        if (try_tab) {
+        if (first_wave) {
+            const int lane = threadIdx.x;
             const bool in = lane < ne;
-            const double zfirst = __shfl(z0, 0);
-            const bool oke = !__builtin_amdgcn_ballot_w64(in && !(z0 == zfirst && isfinite(x0)));
-            const double lo = wave_min_f64(in ? x0 : (double)INFINITY), hi = wave_max_f64(in ? x0 : -(double)INFINITY);
-            if (lane == 0) { hdr.elo = lo; hdr.ehi = hi; hdr.ze = zfirst; hdr.eok = oke; }
+            const double zfirst = __shfl(P.z0, 0);
+            const bool oke = !__builtin_amdgcn_ballot_w64(in && !(P.z0 == zfirst && isfinite(P.x0)));
+            const double elo = wave_min_f64(in ? P.x0 : (double)INFINITY), ehi = wave_max_f64(in ? P.x0 : -(double)INFINITY);
+            if (lane == 0) { hdr.elo = elo; hdr.ehi = ehi; hdr.ze = zfirst; hdr.eok = oke; }
+            rec[lane].xe = P.x0;
+            if (PERM) rec[lane].row = prow;
         }
-        // how many predecessors inside this workgroup share the element's depth (the history restarts when ze changes)
-        // (a predecessor at a non-finite position is no history either — its solution is NaN, and 0 x NaN in the predictor's unused
-        // terms would carry it into up to four rows behind it: scripts/exp_nan_rows.py, tests/test_gpu_edge_sizes.py)
-        const bool s1 = (lane >= 1) & (z1 == z0) & isfinite(x1), s2 = s1 & (lane >= 2) & (z2 == z0) & isfinite(x2),
-                   s3 = s2 & (lane >= 3) & (z3 == z0) & isfinite(x3), s4 = s3 & (lane >= 4) & (z4 == z0) & isfinite(x4);
-        int hist = s4 ? 4 : (s3 ? 3 : (s2 ? 2 : (s1 ? 1 : 0)));
-        // Lagrange weights of the extrapolation to x0 from the nodes x1 .. x_m (differences in fp64, products in fp32)
-        const float t1 = (float)(x0 - x1), t2 = (float)(x0 - x2), t3 = (float)(x0 - x3), t4 = (float)(x0 - x4);
-        const float d12 = (float)(x1 - x2), d13 = (float)(x1 - x3), d14 = (float)(x1 - x4), d23 = (float)(x2 - x3),
-                    d24 = (float)(x2 - x4), d34 = (float)(x3 - x4);
-        // duplicate positions leave no slope: use as many nodes as are pairwise distinct, at least the latest one
-        const bool ok2 = d12 != 0.0f, ok3 = ok2 & (d13 != 0.0f) & (d23 != 0.0f),
-                   ok4 = ok3 & (d14 != 0.0f) & (d24 != 0.0f) & (d34 != 0.0f);
-        const int m = (hist >= 4 && ok4) ? 4 : ((hist >= 3 && ok3) ? 3 : ((hist >= 2 && ok2) ? 2 : (hist >= 1 ? 1 : 0)));
-        float w1 = 0.0f, w2 = 0.0f, w3 = 0.0f, w4 = 0.0f;
-        if (m == 4) {
-            w1 = t2 * t3 * t4 / (d12 * d13 * d14);
-            w2 = -t1 * t3 * t4 / (d12 * d23 * d24);
-            w3 = t1 * t2 * t4 / (d13 * d23 * d34);
-            w4 = -t1 * t2 * t3 / (d14 * d24 * d34);
-        } else if (m == 3) {
-            w1 = t2 * t3 / (d12 * d13);
-            w2 = -t1 * t3 / (d12 * d23);
-            w3 = t1 * t2 / (d13 * d23);
-        } else if (m == 2) {
-            w1 = t2 / d12;
-            w2 = -t1 / d12;
-        } else if (m == 1) {
-            w1 = 1.0f;
-        }
-        // run of consecutive elements (from this one on) that all have four distinct same-depth predecessors
-        const unsigned long long m4 = __ballot(m == 4 && lane < ne);
-        const unsigned long long rest = ~(m4 >> lane);
-        const int run = (m == 4 && lane < ne) ? (rest ? __ffsll((long long)rest) - 1 : 64 - lane) : 0;
-        // HOLD (tau-p tier) extrapolates along the ELEMENT INDEX: only where the pitch is uniform (2 %) over the four elements behind
-        // and the three ahead (an aperture of random spacing put 4.5e-9 relative on a table before this test existed —
-        // tests/test_gpu_irregular_apertures.py::test_planar_taup_tier_irregular_and_coarse_apertures).  Behind: this lane's own
-        // differences; ahead: the same statement of the lane three further on (they share the step x_i - x_(i-1)).  No loads, no LDS
-        // word of its own: the workgroup's start-up is not overlapped with anything (0.1 us there is 1 % of a configs[1] launch).
-        bool uni = false;
-        if (TAUP && a.eb >= 8) {                            // (a block of fewer rows has no group of four behind four cold rows)
-            const float tolu = 0.02f * fabsf(t1);
-            const bool ub = m == 4 && lane < ne && fabsf(d12 - t1) <= tolu && fabsf(d23 - t1) <= tolu && fabsf(d34 - t1) <= tolu;
-            const unsigned long long ubm = __ballot(ub);
-            uni = __builtin_amdgcn_inverse_ballot_w64(ubm & (ubm >> 3));
-        }
-        ElemRec r;
-#ifdef RTUS_EXP_BAD_PREDICTOR                               // experiment builds only (scripts/selftest_predictor.sh): the continuation tests must notice
-        w1 *= 1.02f; w3 *= 0.97f;
-#endif
-        r.w1 = w1; r.w2 = w2; r.w3 = w3; r.w4 = w4; r.xe = x0;
-        r.info = m | (hist == 0 ? 8 : 0) | (uni ? 16 : 0) | (run << 8);
-        r.row = PERM ? a.row_of[el] : 0;
-        rec[lane] = r;
+    } else if (first_wave) {
+        // ---- per-element records: the first wave works them out, one element per lane (nothing waits on the targets here) ----
+        rec[threadIdx.x] = elem_record<TAUP>(a, threadIdx.x, ne, load_elem_pos(xe_p, ze_p, e0, el), PERM ? a.row_of[el] : 0);
     }
     __syncthreads();
+    RTUS_STAMP(1);
 
     const RecPtr rec3 = (RecPtr)rec;
     const size_t nf = (size_t)a.n_f;
@@ -656,6 +708,7 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
                 tab[k].c[0] = T; tab[k].c[1] = p * h; tab[k].c[2] = pp * (0.5 * h * h);   // (lanes past the last node redo it: same values)
             }
             __syncthreads();
+            RTUS_STAMP(2);
             for (int base = w0; base < n_int; base += RTUS_BLOCK) {
                 const int j = min(base + (tid & 63), n_int - 1);
                 double Tc, pc, ppc;                                                      // (the solve first: the coefficients are not live across it)
@@ -677,6 +730,7 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
             const bool badw = __builtin_amdgcn_ballot_w64(bad) != 0;
             if ((tid & 63) == 0) hdr.bad[tid >> 6] = badw;
             __syncthreads();
+            RTUS_STAMP(3);
             if (!__builtin_amdgcn_readfirstlane(hdr.bad[0] | hdr.bad[1] | hdr.bad[2] | hdr.bad[3])) {
                 // the rows leave WRITE-THROUGH (sc1, the store's cache-policy operand 16): a table that takes this path is larger than
                 // the L2s together, so a line kept there serves nobody and is only written back later, at the launch's end at the latest
@@ -689,12 +743,23 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
                     const RowTabSlot* __restrict__ sl = &tab[(int)tq];
                     const double T = fma(sq, fma(sq, fma(sq, fma(sq, fma(sq, sl->c[5], sl->c[4]), sl->c[3]), sl->c[2]), sl->c[1]), sl->c[0]);
                     const u32x2 bits = {(unsigned)__double2loint(T), (unsigned)__double2hiint(T)};
+                    if (l == 0) RTUS_STAMP(4);                                           // (nothing in a product build)
                     __builtin_amdgcn_raw_buffer_store_b64(bits, dest_rs(l, ot), f8, dest_so(sot), store_policy);
                     ot += nf; sot += row_bytes;
                 }
+                RTUS_STAMP(5);
                 return;
             }
         }
+    }
+    // The workgroup tried the table and does not serve from it (ineligible, too wide a span, a rejected build): the solver needs
+    // the full records now.  Every wave arrives here together (the decisions above are the workgroup's), none has read a record.
+    if (try_tab) {
+        if (first_wave) {
+            const ElemPos PF = load_elem_pos(xe_p, ze_p, e0, el);
+            rec[threadIdx.x] = elem_record<TAUP>(a, threadIdx.x, ne, PF, PERM ? a.row_of[el] : 0);
+        }
+        __syncthreads();
     }
     Lane<NL> L;
     L.tau = INFINITY; L.rS3 = 0.0f; L.G = L.dG = 0.0f; L.hic = 0.0f; L.inv_cm = 0.0; L.hr0 = L.hc0 = 0.0; L.hr0f = L.rs0f = L.rhmf = L.asymf = 0.0f;
