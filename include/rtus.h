@@ -848,7 +848,14 @@ int rtus_tt_surface_skip(double x0, double dx, const double *zs, int n_s, double
  *   Invalid entries: NaN + NaN i exactly where x_entry (or, for skip legs, x_back) is NaN — where the time table is NaN.  A stationary
  *   path that does not cross the surface from the couplant into the part (E - S or the segment below S not pointing along +n: the
  *   time solvers do not check occlusion, and on a steep facet a point may lie above the local tangent) carries no ray: 0 + 0 i.  At
- *   a caustic (J = 0) ray theory fails and the entry is +inf + inf i (rtus_tfm_weighted drops such a leg).
+ *   a caustic (J = 0) ray theory fails and the entry is +inf + inf i (rtus_tfm_weighted drops such a leg).  An infinite x_entry or
+ *   x_back names no point of the surface or the backwall: its segments have no direction, the crossing test above fails, 0 + 0 i.
+ *   The path is an input and is not put to Snell's law: each coefficient is evaluated at the slowness of the segment that arrives,
+ *   whatever the segment that leaves does, and every other wave of the boundary problem may be evanescent, the transmitted one
+ *   included (UP with p c1 > 1, possible where c_t < c1: the coefficient is that of the evanescent wave in the couplant, finite and
+ *   not zero).  Conditioning: the T coefficients vanish at p = 0 and the first-mode-T amplitude like sqrt|p c_l - 1| at the first
+ *   critical angle; a segment at the cosine k on a normal has the vertical slowness k / c, formed as sqrt(1 / c^2 - p^2), which
+ *   fp64 holds to 1e-16 / k^2 relative: below k = 3e-5 the entry of a grazing path is not good to 1e-7.
  *
  * rtus_leg_amp_surface: amp [n_e][n_f] complex64 (interleaved float32 pairs) of one leg in one direction.
  *   x0, dx, zs, n_s, xe, ze, xf, zf: rtus_tt_surface's; x_entry [n_e][n_f] the leg's entry points; x_back [n_e][n_f] its backwall points

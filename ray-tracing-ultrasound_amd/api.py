@@ -1179,7 +1179,8 @@ def leg_amplitudes_surface(x0, dx, zs, c1, rho1, c_l, c_t, rho2, z_back, leg, xe
     skip_travel_time_surface(return_entry=True) return them.  ``up``: the wave travels point -> element along the leg's path (the
     receive direction) instead of element -> point.  ``element_width`` [m] > 0 needs ``f_c`` [Hz], the centre frequency of the
     directivity.  The couplant has speed ``c1`` and density ``rho1``, the part ``c_l`` > ``c_t`` and ``rho2`` with a traction-free
-    backwall at ``z_back``.  NaN where x_entry (or x_back) is NaN.  Definition: include/rtus.h (rtus_leg_amp_surface).  Not in the
+    backwall at ``z_back``.  NaN where x_entry (or x_back) is NaN; 0 where either is infinite, as for any path that does not cross
+    the surface into the part.  The path is not put to Snell's law.  Definition: include/rtus.h (rtus_leg_amp_surface).  Not in the
     reference."""
     if leg not in LEGS:
         raise ValueError(f"unknown leg {leg!r}: legs are {LEGS}")

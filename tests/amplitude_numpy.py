@@ -165,9 +165,13 @@ def amplitude(x0, dx, zs, media, leg, up, xe, ze, xf, zf, xent, xback=None, widt
             ux, uz = -fx, -fz
         p = (ux * tx + uz * tz) / sp[X]
         cs = solid_fluid(X, p, r1, c1, r2, cl, ct)[2]
-    amp = np.conj(D * G * cs * cb)
+    with np.errstate(invalid="ignore"):
+        amp = np.conj(D * G * cs * cb)
+        amp = np.where(J == 0, complex(np.inf, np.inf), amp)              # a caustic: +inf + inf i (include/rtus.h)
     ox, oz = (bx, bz) if skip else (fx, fz)
-    crosses = (ex * nx + ez * nz > 0) & (ox * nx + oz * nz > 0)        # else not a refraction into the part: no ray, amplitude 0
+    # else not a refraction into the part: no ray, amplitude 0 (an infinite x_entry / x_back: the cosines are NaN, the test fails)
+    with np.errstate(invalid="ignore"):
+        crosses = (ex * nx + ez * nz > 0) & (ox * nx + oz * nz > 0)
     amp = np.where(crosses, amp, 0j)
     bad = np.isnan(xent) | (np.isnan(xb) if skip else False)
     amp = np.where(bad, np.nan + 1j * np.nan, amp)

@@ -37,7 +37,9 @@ def spline(x0, dx, zs):
 
 def spline_eval(coef, x0, dx, x):
     x = np.asarray(x, dtype=np.float64)
-    k = np.clip(np.floor((x - x0) / dx), 0, coef.shape[0] - 1).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        kf = np.floor((x - x0) / dx)
+    k = np.clip(np.where(np.isnan(kf), 0.0, kf), 0, coef.shape[0] - 1).astype(np.int64)    # (NaN -> segment 0; the result is NaN)
     t = x - (x0 + k * dx)
     a, b, c, d = (coef[k, i] for i in range(4))
     return a + t * (b + t * (c + t * d)), b + t * (2 * c + 3 * t * d), 2 * c + 6 * t * d
