@@ -111,7 +111,8 @@ def table(lens, pipe, c_up, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, 
     without a winner) fail rule 1; no_arc, entries of points in the wall for which no beta of the grid shares an arc of the bore
     with the point; graze, entries with an arc somewhere and yet no interior minimum of T (the least time over the betas that have
     a W sits where the bounce grazes); n_gamma, the most local minima of the inner problem seen on a dense gamma grid, at every
-    eighth beta of the dense grid and at the winner's."""
+    eighth beta of the dense grid and at the winner's; minima, every refined interior minimum of T as flat arrays: entry (the flat index
+    into the table), t (inf without W), alpha, beta, gamma, rule1."""
     xe, ze, xf, zf = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (xe, ze, xf, zf))
     if pairs is None:
         ie, jf = (a.ravel() for a in np.meshgrid(np.arange(xe.size), np.arange(xf.size), indexing="ij"))
@@ -136,7 +137,7 @@ def table(lens, pipe, c_up, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, 
     flag = np.zeros(P, dtype=bool)
     no_arc, has_w = np.zeros(P, dtype=bool), np.zeros(P, dtype=bool)
     n_gamma = np.zeros(P, dtype=np.int64)
-    m_p, m_T, m_1 = [], [], []
+    m_p, m_T, m_1, m_a, m_b, m_g = [], [], [], [], [], []
     fx, fz = xf[jf], zf[jf]
     rf = np.hypot(fx - pipe.x0, fz)
     inwall = (rf > pipe.ri) & (rf < pipe.r) & np.isfinite(xe[ie]) & np.isfinite(ze[ie])
@@ -199,6 +200,7 @@ def table(lens, pipe, c_up, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, 
         r1, _ = O.rules(px_, pz_, qx_, qz_, xf[ja], zf[ja], pipe)
         ok = r1 & np.isfinite(T)
         m_p.append(p); m_T.append(np.where(np.isfinite(T), T, np.inf)); m_1.append(r1)
+        m_a.append(a_); m_b.append(x); m_g.append(g_)
         for n in np.nonzero(ok)[0]:
             if not (T[n] >= out["t"][p[n]]):
                 out["t"][p[n]], out["alpha"][p[n]], out["beta"][p[n]], out["gamma"][p[n]] = T[n], a_[n], x[n], g_[n]
@@ -213,6 +215,8 @@ def table(lens, pipe, c_up, xe, ze, xf, zf, *, a_lo=-ALPHA_MAX, a_hi=ALPHA_MAX, 
         o["n_min"] = n_min.reshape(shape)
         o["rank"] = np.where(np.isfinite(out["t"]), count(earlier), -1).reshape(shape)
         o["rej1"] = count(earlier & ~m_1).reshape(shape)
+        m_a, m_b, m_g = (np.concatenate(v) if v else np.zeros(0) for v in (m_a, m_b, m_g))
+        o["minima"] = {"entry": m_p, "t": m_T, "alpha": m_a, "beta": m_b, "gamma": m_g, "rule1": m_1}
         o["no_arc"] = no_arc.reshape(shape)
         o["graze"] = (inwall & ~no_arc & has_w & (n_min == 0)).reshape(shape)
         won = np.isfinite(out["t"])

@@ -7,7 +7,10 @@ Tolerances are tests/test_gpu_pipe.py's: 1e-17 + 1e-13 t for times, 1e-9 rad for
 outside the entries the oracle flags, of which there may be at most 0.2 % in any set (asserted first).  Counted input conditions
 (the oracle's ``detail``), asserted before each comparison: the inner problem has at most one minimum in gamma everywhere; the
 corner sets hold entries whose only minima graze (TL, past the critical angle of the conversion) and the production set none; no
-set holds an entry without a visible arc or a winner that is not the earliest minimum."""
+set holds an entry without a visible arc or a winner that is not the earliest minimum.
+
+The kernel's decision points - two qualifying minima, alpha past +-1 rad, the scan's edges and tile seams, windows without an arc,
+points micrometres off the circles, bad inputs - are in tests/test_gpu_pipe_skip_branches.py."""
 from importlib import import_module
 
 import numpy as np
