@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 119 /* 0.1.18: rtus_tfm_iq*, rtus_tfm_iq_hmc* (carrier-aware interpolation) */
+#define RTUS_VERSION 120 /* 0.1.19: rtus_solve_path (which refinement a solve call gets) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -194,8 +194,24 @@ int rtus_shoot(const rtus_lens *lens, const double *geoms, int n_geom,
  * polyline's — a workgroup per (geometry, transmit point) row, landing points and pair masks in LDS.  RTUS_SOLVE_THREE_LAUNCHES
  * keeps the grid trace and the refinement as separate launches (the same bits: the refinement's arithmetic is one function). */
 #define RTUS_SOLVE_THREE_LAUNCHES 0x20u
+/* Which refinement a call of this size and these flags gets (host code, launches nothing; the launcher itself switches on it).
+ * With rows = n_geom * n_tx and tasks = rows * n_rx:
+ *   ROW         tasks <= 32,768, n_rays <= 1,024, n_rx <= 128, neither flag above: one kernel, a workgroup per row, three lanes per bracket
+ *   TRIO_MASKS  tasks <= 32,768, n_rx <= 512, not ROW, no RTUS_SOLVE_ONE_LANE: separate launches, pair masks, three lanes per bracket
+ *   TRIO_SCAN   tasks <= 32,768, n_rx > 512, no RTUS_SOLVE_ONE_LANE: the landing points are scanned in the kernel, three lanes per bracket
+ *   HALF        n_rx <= 512, tasks <= 131,072 (and > 32,768, or RTUS_SOLVE_ONE_LANE): one lane per bracket, 128 element lanes per workgroup
+ *   FULL        n_rx <= 512, tasks > 131,072: one lane per bracket, 256 element lanes per workgroup
+ *   SCAN        n_rx > 512, tasks > 32,768 or RTUS_SOLVE_ONE_LANE: one lane per bracket, scanned landing points
+ * -1: a size rtus_solve refuses (non-positive, n_rays < 2, or beyond its 2^31 limits). */
+#define RTUS_SOLVE_PATH_ROW 0
+#define RTUS_SOLVE_PATH_TRIO_MASKS 1
+#define RTUS_SOLVE_PATH_TRIO_SCAN 2
+#define RTUS_SOLVE_PATH_HALF 3
+#define RTUS_SOLVE_PATH_FULL 4
+#define RTUS_SOLVE_PATH_SCAN 5
 
 size_t rtus_solve_workspace_bytes(int n_rays, int n_geom, int n_tx, int n_rx);
+int rtus_solve_path(int n_geom, int n_tx, int n_rays, int n_rx, unsigned flags);
 
 int rtus_solve_dev(const rtus_lens *lens, const double *d_geoms, int n_geom,
                    const double *d_x_a, const double *d_z_a, int n_tx,

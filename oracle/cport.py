@@ -172,6 +172,38 @@ def trace_alpha(x_a, z_a, z_f, a, alpha_grid, r_outer, pipe_offset, flags=0, len
     return o
 
 
+_polylines = {}
+
+
+def land_alphas(x_a, z_a, z_f, a, alpha_grid, r_outer, pipe_offset, flags=0, lens=REF_LENS):
+    """Landing x of rays at arbitrary launch angles ``a`` (any shape) against the polyline of alpha_grid, built once."""
+    alpha_grid = _f64(alpha_grid)
+    a = np.asarray(a, dtype=np.float64)
+    L = _lens(**lens)
+    key = (alpha_grid.tobytes(), tuple(sorted(lens.items())))
+    pl = _polylines.get(key)
+    if pl is None:
+        xc = np.empty(alpha_grid.size); zc = np.empty(alpha_grid.size)
+        x, z = C.c_double(), C.c_double()
+        for i, al in enumerate(alpha_grid):
+            lib().orc_lens_point(C.byref(L), float(al), C.byref(x), C.byref(z))
+            xc[i], zc[i] = x.value, z.value
+        _polylines.clear()                                    # (one grid at a time is what callers loop over)
+        pl = _polylines[key] = (xc, zc)
+    xc, zc = pl
+    o = np.empty(8)
+    out = np.empty(a.size)
+    # (the same function through plain pointers: ndpointer's per-call checks of three arrays cost ten times the trace itself)
+    proto = C.CFUNCTYPE(None, C.POINTER(_Lens), *([C.c_double] * 6), C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_void_p)
+    fn = C.cast(lib().orc_trace_alpha, proto)
+    Lp, pxc, pzc, po, n = C.pointer(L), xc.ctypes.data, zc.ctypes.data, o.ctypes.data, alpha_grid.size
+    r_outer, pipe_offset, x_a, z_a, z_f = float(r_outer), float(pipe_offset), float(x_a), float(z_a), float(z_f)
+    for i, ai in enumerate(a.ravel().tolist()):
+        fn(Lp, r_outer, pipe_offset, x_a, z_a, z_f, ai, pxc, pzc, n, flags, po)
+        out[i] = o[6]
+    return out.reshape(a.shape)
+
+
 def set_trig_noise(mode):
     """Sensitivity probe of the forward trace (see rt_oracle.c): two bits per trigonometric call site move its result by
     0 / +1 / -1 / +2 ulp.  0 = plain libm — ALWAYS reset it after use."""

@@ -7,7 +7,7 @@ module at the repo root) or ``importlib.import_module("ray-tracing-ultrasound_am
 from ._lib import EXPORTS, LIB_PATH, Lens, Pipe, PipeMedia, RtusError, build, lib  # noqa: F401
 from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits,  # noqa: F401
                   reference_elements, shoot_batch, shoot_rays, travel_time_layers, travel_time_lens, travel_time_surface,
-                  fmc_table_layers, solve_travel_times, focal_delays, tfm_image, sweep_batch, fmc_analytic, measure_surface,
+                  fmc_table_layers, solve_travel_times, solve_path, SOLVE_PATHS, focal_delays, tfm_image, sweep_batch, fmc_analytic, measure_surface,
                   adaptive_tfm, tfm_analytic, tfm_phase, pw_delays, pw_travel_time_layers, pw_travel_time_surface, fmc_synth_tx, pwi_image,
                   LEGS, VIEWS, reverse_leg, view_tables, skip_travel_time_layers, skip_travel_time_surface, view_legs_layers,
                   view_legs_surface, tfm_views, leg_amplitudes_surface, view_amplitudes_surface, tfm_weighted,
@@ -20,7 +20,7 @@ from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits, 
                   hmc_index, hmc_pack, hmc_unpack, hmc_analytic, tfm_hmc, tfm_analytic_hmc, tfm_iq, tfm_iq_hmc,
                   centre_frequency)
 
-__all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "focal_delays", "tfm_image", "fmc_analytic",
+__all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "solve_path", "SOLVE_PATHS", "focal_delays", "tfm_image", "fmc_analytic",
            "measure_surface", "adaptive_tfm", "tfm_analytic", "tfm_phase", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
            "fmc_synth_tx", "pwi_image", "LEGS", "VIEWS", "reverse_leg", "view_tables", "skip_travel_time_layers",
            "skip_travel_time_surface", "view_legs_layers", "view_legs_surface", "tfm_views", "leg_amplitudes_surface",

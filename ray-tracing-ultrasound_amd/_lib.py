@@ -78,6 +78,7 @@ PROTOTYPES = (
     ("rtus_shoot", i, [LP, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, vp, vp, u, i], 100),
     # pulse-echo travel times by root-finding
     ("rtus_solve_workspace_bytes", sz, [i, i, i, i], 100),
+    ("rtus_solve_path", i, [i, i, i, i, u], 120),
     ("rtus_solve_dev", i, [LP, vp, i, vp, vp, i, vp, i, vp, i, dd, vp, vp, vp, vp, vp, vp, sz, u, vp], 100),
     ("rtus_solve", i, [LP, vp, i, vp, vp, i, vp, i, vp, i, dd, vp, vp, vp, vp, vp, u, i], 100),
     # element matcher

@@ -373,6 +373,17 @@ def fmc_table_layers(z_if, c, x_tx, x_rx, z_reflector, *, z_array=0.0, device=0,
 
 SOLVE_ONE_LANE = 0x10       # RTUS_SOLVE_ONE_LANE (include/rtus.h)
 SOLVE_THREE_LAUNCHES = 0x20
+SOLVE_PATHS = ("ROW", "TRIO_MASKS", "TRIO_SCAN", "HALF", "FULL", "SCAN")      # RTUS_SOLVE_PATH_* (include/rtus.h), by value
+
+
+def solve_path(n_geom, n_tx, n_rays, n_rx, *, one_lane=False, three_launches=False):
+    """The refinement a solve_travel_times / SolvePlan call of this size takes (rtus_solve_path: host code, no GPU needed): one of
+    SOLVE_PATHS.  ValueError for a size rtus_solve refuses."""
+    r = _lib.lib().rtus_solve_path(int(n_geom), int(n_tx), int(n_rays), int(n_rx),
+                                   (SOLVE_ONE_LANE if one_lane else 0) | (SOLVE_THREE_LAUNCHES if three_launches else 0))
+    if not 0 <= r < len(SOLVE_PATHS):
+        raise ValueError(f"no solve of {n_geom} x {n_tx} rows, {n_rays} rays, {n_rx} elements")
+    return SOLVE_PATHS[r]
 
 
 def solve_travel_times(x_a, z_a, x_rx, alpha, geoms=None, *, z_land=None, params: Params = None, fast=False,

@@ -772,6 +772,26 @@ size_t rtus_solve_ws_bytes(int n, int n_geom, int n_tx, int n_rx)
     return sws_box_off(n, n_geom, n_tx) + (size_t)n_geom * n_tx * (size_t)((n + 63) / 64) * per_block;
 }
 
+// Which refinement a call gets: a function of its SIZE and of the two scheme flags, nothing else (include/rtus.h).  Host code, no
+// launch; rtus_launch_solve below switches on it, so what is reported is what runs.
+int rtus_solve_path(int n_geom, int n_tx, int n, int n_rx, unsigned flags)
+{
+    if (n_geom <= 0 || n_tx <= 0 || n < 2 || n_rx <= 0) return -1;
+    const long long rows = (long long)n_geom * n_tx;
+    if (rows > 0x7fffffffLL / n_rx || rows * ((n + 63) / 64) > 0x7fffffffLL) return -1;      // (what rtus_solve refuses as unsupported)
+    const long long tasks = rows * n_rx;
+    const bool masks = n_rx <= RTUS_SOLVE_MASK_MAX_RX;
+    // small calls with a grid of <= 1,024 rays and <= 128 elements (the reference's own sweep): ONE launch, a workgroup per row
+    if (tasks <= 32768 && n <= RTUS_ROW_TPB && n_rx <= RTUS_ROW_MAX_RX && !(flags & (RTUS_SOLVE_ONE_LANE | RTUS_SOLVE_THREE_LAUNCHES)))
+        return RTUS_SOLVE_PATH_ROW;
+    // three lanes per bracket where one lane per bracket leaves the chip mostly idle (<= 32,768 elements: ~1.5 waves per SIMD with
+    // three lanes per bracket), with either bracket-finding path
+    if (tasks <= 32768 && !(flags & RTUS_SOLVE_ONE_LANE)) return masks ? RTUS_SOLVE_PATH_TRIO_MASKS : RTUS_SOLVE_PATH_TRIO_SCAN;
+    if (!masks) return RTUS_SOLVE_PATH_SCAN;
+    // mask mode, launches that leave SIMDs idle anyway (fewer than two waves of elements per SIMD): 128 element lanes per workgroup
+    return tasks <= 2LL * 1024 * 64 ? RTUS_SOLVE_PATH_HALF : RTUS_SOLVE_PATH_FULL;
+}
+
 // Four launches: polyline, box records, grid trace (landing points + which elements each ray pair brackets), refine.
 hipError_t rtus_launch_solve(const rtus_lens& lens, const double* geoms, int n_geom, const double* x_a,
                              const double* z_a, int n_tx, const double* alpha, int n, const double* x_rx, int n_rx,
@@ -780,10 +800,11 @@ hipError_t rtus_launch_solve(const rtus_lens& lens, const double* geoms, int n_g
 {
     char* w = (char*)ws;
     double* land = (double*)(w + sws_land_off(n));
-    const bool masks = n_rx <= RTUS_SOLVE_MASK_MAX_RX;
-    // small calls with a grid of <= 1,024 rays and <= 128 elements (the reference's own sweep): ONE launch, a workgroup per row
+    const int path = rtus_solve_path(n_geom, n_tx, n, n_rx, flags);
+    if (path < 0) return hipErrorInvalidValue;
+    const bool masks = path != RTUS_SOLVE_PATH_TRIO_SCAN && path != RTUS_SOLVE_PATH_SCAN;      // (= n_rx <= RTUS_SOLVE_MASK_MAX_RX)
     const long long rows = (long long)n_geom * n_tx;
-    if (rows * n_rx <= 32768 && n <= RTUS_ROW_TPB && n_rx <= RTUS_ROW_MAX_RX && rows <= 0x7fffffffLL && !(flags & (RTUS_SOLVE_ONE_LANE | RTUS_SOLVE_THREE_LAUNCHES))) {
+    if (path == RTUS_SOLVE_PATH_ROW) {                               // ONE launch, a workgroup per row
         SolveArgs q;
         ShootArgs& a = q.s;
         a.k = make_lens_k(lens);
@@ -818,28 +839,34 @@ hipError_t rtus_launch_solve(const rtus_lens& lens, const double* geoms, int n_g
     q.chunks = (n_rx + 63) / 64;
     q.n_tasks = masks ? (long long)n_geom * n_tx * n_rx : (long long)n_geom * n_tx * q.chunks;
     q.tt = tt; q.alpha_root = alpha_root; q.tt_all = tt_all; q.alpha_all = alpha_all; q.n_roots = n_roots;
-    // mask mode, launches that leave SIMDs idle anyway (fewer than two waves of elements per SIMD): 128 element lanes per workgroup
-    const bool half = masks && q.n_tasks <= 2LL * 1024 * 64;
-    // ... and three lanes per bracket where even that leaves the chip mostly idle (<= 32,768 elements: ~1.5 waves per SIMD with
-    // three lanes per bracket): 32 element lanes per workgroup, so that its brackets x 3 lanes fit ONE trip of its four waves (84
-    // brackets) even where most elements have two or three — a workgroup that needs a second trip doubles the kernel's critical
-    // path (measured with 64 element lanes: the first evaluation of the slowest waves started 31 us into a 43 us kernel)
-    const bool trio = rows * n_rx <= 32768 && !(flags & RTUS_SOLVE_ONE_LANE);   // (either bracket-finding path)
-    const long long epb = (trio && masks) ? RTUS_SOLVE_TPB / 8 : (half ? RTUS_SOLVE_TPB / 2 : RTUS_SOLVE_TPB);
+    // element lanes per workgroup (mask mode).  TRIO: 32, so that its brackets x 3 lanes fit ONE trip of its four waves (84 brackets)
+    // even where most elements have two or three — a workgroup that needs a second trip doubles the kernel's critical path (measured
+    // with 64 element lanes: the first evaluation of the slowest waves started 31 us into a 43 us kernel); HALF: 128; FULL: 256
+    const long long epb = path == RTUS_SOLVE_PATH_TRIO_MASKS ? RTUS_SOLVE_TPB / 8 : (path == RTUS_SOLVE_PATH_HALF ? RTUS_SOLVE_TPB / 2 : RTUS_SOLVE_TPB);
     const long long blocks = masks ? (q.n_tasks + epb - 1) / epb : (q.n_tasks + RTUS_SOLVE_WAVES - 1) / RTUS_SOLVE_WAVES;
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks);
     const bool fast = (flags & RTUS_SHOOT_FAST_MATH) != 0;
-#define RTUS_SOLVE_LAUNCH(F, M, E) hipLaunchKernelGGL((rtus_solve_kernel<F, M, E>), grid, dim3(RTUS_SOLVE_TPB), 0, s, q)
-    if (trio && masks) {
-        if (fast) hipLaunchKernelGGL((rtus_solve_kernel<true, true, RTUS_SOLVE_TPB / 8, true>), grid, dim3(RTUS_SOLVE_TPB), 0, s, q);
-        else hipLaunchKernelGGL((rtus_solve_kernel<false, true, RTUS_SOLVE_TPB / 8, true>), grid, dim3(RTUS_SOLVE_TPB), 0, s, q);
-    } else if (trio) {
-        if (fast) hipLaunchKernelGGL((rtus_solve_kernel<true, false, RTUS_SOLVE_TPB, true>), grid, dim3(RTUS_SOLVE_TPB), 0, s, q);
-        else hipLaunchKernelGGL((rtus_solve_kernel<false, false, RTUS_SOLVE_TPB, true>), grid, dim3(RTUS_SOLVE_TPB), 0, s, q);
-    } else if (half) { if (fast) RTUS_SOLVE_LAUNCH(true, true, RTUS_SOLVE_TPB / 2); else RTUS_SOLVE_LAUNCH(false, true, RTUS_SOLVE_TPB / 2); }
-    else if (masks) { if (fast) RTUS_SOLVE_LAUNCH(true, true, RTUS_SOLVE_TPB); else RTUS_SOLVE_LAUNCH(false, true, RTUS_SOLVE_TPB); }
-    else { if (fast) RTUS_SOLVE_LAUNCH(true, false, RTUS_SOLVE_TPB); else RTUS_SOLVE_LAUNCH(false, false, RTUS_SOLVE_TPB); }
+#define RTUS_SOLVE_LAUNCH(F, M, E, T) hipLaunchKernelGGL((rtus_solve_kernel<F, M, E, T>), grid, dim3(RTUS_SOLVE_TPB), 0, s, q)
+    switch (path) {
+    case RTUS_SOLVE_PATH_TRIO_MASKS:
+        if (fast) RTUS_SOLVE_LAUNCH(true, true, RTUS_SOLVE_TPB / 8, true); else RTUS_SOLVE_LAUNCH(false, true, RTUS_SOLVE_TPB / 8, true);
+        break;
+    case RTUS_SOLVE_PATH_TRIO_SCAN:
+        if (fast) RTUS_SOLVE_LAUNCH(true, false, RTUS_SOLVE_TPB, true); else RTUS_SOLVE_LAUNCH(false, false, RTUS_SOLVE_TPB, true);
+        break;
+    case RTUS_SOLVE_PATH_HALF:
+        if (fast) RTUS_SOLVE_LAUNCH(true, true, RTUS_SOLVE_TPB / 2, false); else RTUS_SOLVE_LAUNCH(false, true, RTUS_SOLVE_TPB / 2, false);
+        break;
+    case RTUS_SOLVE_PATH_FULL:
+        if (fast) RTUS_SOLVE_LAUNCH(true, true, RTUS_SOLVE_TPB, false); else RTUS_SOLVE_LAUNCH(false, true, RTUS_SOLVE_TPB, false);
+        break;
+    case RTUS_SOLVE_PATH_SCAN:
+        if (fast) RTUS_SOLVE_LAUNCH(true, false, RTUS_SOLVE_TPB, false); else RTUS_SOLVE_LAUNCH(false, false, RTUS_SOLVE_TPB, false);
+        break;
+    default:
+        return hipErrorInvalidValue;
+    }
 #undef RTUS_SOLVE_LAUNCH
     return hipGetLastError();
 }

@@ -12,6 +12,15 @@ from conftest import D_PLANE, load_golden
 pytestmark = pytest.mark.gpu
 
 
+def _clean(cport, tx, alpha, x, r_outer, offset, ota):
+    """tests/solve_scale_cases.py's rule: the elements where the oracle itself is unambiguous — at most four brackets in its grid trace,
+    as many roots as brackets, no grid ray within 1e-9 m of the element.  There a root count is a fact, not a share."""
+    from solve_scale_cases import MAX_ROOTS, brackets
+    land = cport.shoot(tx, D_PLANE, np.full(alpha.size, D_PLANE), alpha, r_outer, offset)[0][6]
+    cnt, _, near = brackets(land[None, :], x)
+    return (cnt[0] <= MAX_ROOTS) & (cnt[0] == np.isfinite(ota).sum(1)) & ~near[0]
+
+
 def _solve(rtus, x_rx, geoms, txs, alpha):
     return rtus.solve_travel_times(txs, np.full(len(txs), D_PLANE), x_rx, alpha, geoms, params=rtus.Params(), all_roots=True)
 
@@ -54,7 +63,8 @@ def test_duplicate_and_single_elements(rtus):
 
 
 def test_long_grid_with_block_boundary_pairs(rtus):
-    """N = 4097 rays: 65 blocks of 64 pairs; brackets that straddle two blocks come from the solve kernel's own check."""
+    """N = 4097 rays: 65 blocks of 64 pairs; brackets that straddle two blocks come from the solve kernel's own check.  Besides the
+    share of elements with the oracle's root count: the SAME count on every clean element (_clean)."""
     from oracle import cport
     n = 4097
     alpha = np.linspace(-rtus.ALPHA_MAX, rtus.ALPHA_MAX, n)
@@ -63,6 +73,8 @@ def test_long_grid_with_block_boundary_pairs(rtus):
     otm, ota, oaa = cport.solve(0.0021, D_PLANE, D_PLANE, alpha, x, 0.037, 0.0038)
     same = np.isfinite(ota).sum(1) == nr[0, 0]
     assert same.mean() > 0.97
+    clean = _clean(cport, 0.0021, alpha, x, 0.037, 0.0038, ota)
+    assert clean.mean() >= 0.99 and same[clean].all(), np.flatnonzero(clean & ~same)
     m = same[:, None] & np.isfinite(ota)
     assert np.max(np.abs(ta[0, 0] - ota)[m]) < 1e-13
     # some bracket's lower ray is the last ray of a 64-ray block
@@ -102,7 +114,9 @@ def test_one_launch_three_launches_and_one_lane(rtus):
 def test_one_launch_path_ragged_sizes(rtus, n, n_rx):
     """The one-launch kernel at the edges of its domain (grid of up to 1,024 rays = one workgroup, up to 128 elements, the last 64-ray
     block partly filled, a single element, an unsorted aperture with a duplicate and a NaN): the same bits as the separate launches,
-    the same roots as the oracle's bisection."""
+    the same roots as the oracle's bisection.  Besides the share of elements with the oracle's root count: the SAME count on every clean
+    element (_clean) — also in the sizes with fewer than a hundred elements or rays, where the share says little: the single element of
+    (70, 1) is clean in all six rows, and every other size has at least 60 clean elements per row (asserted)."""
     from oracle import cport
     rng = np.random.default_rng(n * 131 + n_rx)
     alpha = np.linspace(-rtus.ALPHA_MAX, rtus.ALPHA_MAX, n)
@@ -126,5 +140,7 @@ def test_one_launch_path_ragged_sizes(rtus, n, n_rx):
             otm, ota, oaa = cport.solve(txs[t], D_PLANE, D_PLANE, alpha, x[ok], geoms[g, 0], geoms[g, 1])
             same = np.isfinite(ota).sum(1) == one[4][g, t][ok]
             assert same.mean() > 0.9 or n < 100
+            clean = _clean(cport, txs[t], alpha, x[ok], geoms[g, 0], geoms[g, 1], ota)
+            assert clean.sum() >= min(60, n_rx) and same[clean].all(), (g, t, np.flatnonzero(clean & ~same))
             m = same[:, None] & np.isfinite(ota)
             assert np.max(np.abs(one[2][g, t][ok] - ota)[m], initial=0) < 1e-13
