@@ -231,6 +231,10 @@ int rtus_solve(const rtus_lens *lens, const double *geoms, int n_geom,
  * ray (ascending index) with np.isclose(land_x[ray], x_rx[e], rtol, atol), i.e.
  * |land_x - x_rx| <= atol + rtol*|x_rx| for finite operands, land_x == x_rx when either is infinite,
  * never with a NaN (np.isclose's rules).  n_batch = n_geom*n_tx rows.
+ * atol and rtol may be any values >= 0, rtol >= 1 included (there the fused sweep tests every element of an ascending chunk
+ * instead of pruning it).  The decisions are np.isclose's to the last bit — atol + rtol*|x_rx| in two roundings, the difference
+ * in one — also for landing points within an ulp of the tolerance's edge: what the kernels skip unseen is bounded by the
+ * tolerance widened by a few ulp of its operands, never by a rounded x_rx +- tol alone (tests/test_gpu_match_edges.py).
  *
  *   land_x, tof [n_batch][n_rays]    (outputs of rtus_shoot*)
  *   x_rx        [n_rx]

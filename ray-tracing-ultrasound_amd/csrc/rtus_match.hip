@@ -7,6 +7,12 @@
 // bit-identical to the sequential scan); a second tiny kernel turns the winner into hit / tof.
 #include "rtus_device.h"
 
+// np.isclose forms atol + rtol*|x_rx| in two roundings.  Under the default -ffp-contract=fast the compiler makes one v_fma_f64 of
+// that — also when it is spelled __dadd_rn(atol, __dmul_rn(rtol, |x|)), which are a plain + and * in an inlined header function:
+// a tolerance one ulp off wherever the product's rounding shows (rtol = 3: on a quarter of the elements).  So: no contraction
+// of anything written in this file, and the tolerances written with the operators the pragma governs.
+#pragma clang fp contract(off)
+
 #define RTUS_NO_RAY 0x7f7f7f7f   // hipMemsetAsync(0x7f) sentinel; larger than any ray index (also rtus_trace.h: the fused sweep)
 
 struct MatchArgs {
@@ -22,7 +28,7 @@ struct MatchArgs {
 
 // Workgroup = 256 rays of one batch row.  LDS: x_rx[n_rx] then tol[n_rx] (dynamic).
 // While staging the aperture the workgroup also finds out whether x_rx is ascending (arrays are):
-// then each ray binary-searches the window [x - win, x + win], win = atol + rtol*max|x_rx|, instead
+// then each ray binary-searches the window [x - win, x + win], win = atol + rtol*max|x_rx| and a few ulp, instead
 // of testing every element.  Any other order falls back to the full scan — same result either way.
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_match_kernel(MatchArgs a)
 {
@@ -37,7 +43,7 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_match_kernel(MatchArgs a)
         sx[e] = xe;
         // np.isclose(a, b): |a - b| <= atol + rtol*|b|, b = elem_x (two roundings, as NumPy) for finite operands, a == b when either
         // is infinite, never with a NaN.  A negative tolerance keeps an infinite element out of the first test.
-        stol[e] = isfinite(xe) ? __dadd_rn(a.atol, __dmul_rn(a.rtol, fabs(xe))) : -1.0;
+        stol[e] = isfinite(xe) ? a.atol + a.rtol * fabs(xe) : -1.0;
         asc = asc && isfinite(xe) && (e == 0 || a.x_rx[e - 1] <= xe);
         amax = fmax(amax, fabs(xe));
     }
@@ -46,7 +52,12 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_match_kernel(MatchArgs a)
     if ((threadIdx.x & 63) == 0) s_amax[threadIdx.x >> 6] = amax;
     const bool sorted = __syncthreads_and(asc);    // also publishes sx / stol / s_amax
     amax = fmax(fmax(s_amax[0], s_amax[1]), fmax(s_amax[2], s_amax[3]));
-    const double win = a.atol + a.rtol * amax;
+    // The window only says which elements are SKIPPED; the test below is np.isclose's.  tolmax is the largest stol[e] (the same two
+    // roundings, no FMA), and win adds a few ulp of the operands of x -+ win to it — the margin of the fused matcher's prune
+    // (rtus_shoot.hip) — because fl(x - tolmax) can lie one grid step ABOVE an element whose rounded |x - xe| is exactly its
+    // tolerance (element 257.7 u, u = ulp(1e-4); x = 1e-4 + 258 u; atol = 1e-4, rtol = 0: fl(x - xe) == atol, fl(x - atol) = 258 u)
+    const double tolmax = a.atol + a.rtol * amax;
+    const double win = tolmax + 8.0 * 2.220446049250313e-16 * (amax + tolmax);
 
     const int row = a.row0 + blockIdx.y;
     // `chunks` consecutive 256-ray chunks of the row per workgroup: staging the aperture (a dependent chain of loads, two
