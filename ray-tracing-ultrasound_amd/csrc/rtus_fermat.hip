@@ -32,7 +32,14 @@
 // (h a power of two chosen from zf - ze alone) from fp64 nodes (T, p, p'), checks every interval against a solved point at
 // s = 0.3 to 1e-11 relative, and serves its rows from LDS: ~10 VALU instructions and 48 B of LDS per solve instead of 62 and a
 // root-find.  Anything else — mixed depths, a non-finite x, a span beyond 351 intervals, an interval that fails — runs the solver
-// exactly as before, the whole workgroup.  A served solve's bits are a function of (X, depths, medium) alone: see the kernel.
+// exactly as before, the whole workgroup.  A served solve's bits are a function of (X, depths, medium) alone: see "row table: the
+// phases".
+//
+// Structure.  solve_elem is one (element, target) solve; rowtab_point one fp64 node of the table; elem_record one element's record.
+// The kernel, rtus_tt_layers_kernel, is a sequence of inlined phases, one function each: work_item (decode), rowtab_ranges or
+// solver_records (before the only barrier), rowtab_lattice, rowtab_build, rowtab_serve (the table path), and — where the table is
+// not tried or does not serve — solver_records behind a second barrier and solve_block (the element loop).  RowDest says where a
+// row of the block is stored, for the serving loop and the solver alike.
 //
 // Layout: tt[e][f], f fastest — each wave stores 512 contiguous bytes; xf/zf loads are coalesced; the
 // per-element data of a workgroup (coordinates, extrapolation weights) sits in LDS and is broadcast to the lanes.
@@ -58,8 +65,8 @@ struct LayerArgs {
                                        // launch or in row shards
     // batched entry (rtus_tt_layers_batch): problem b = blockIdx.z uses elements / targets / output shifted by these
     long long e_stride, f_stride, t_stride;   // in elements of the respective arrays (0: shared by all problems)
-    int gx, gy, n_items;               // work items: gx columns of 256 targets x gy blocks of rows (x n_batch problems) = n_items
-    long long n_rows;                  // rows of the WHOLE table (a shard's launch: more than its n_e) — the row table's threshold, see the kernel
+    int gy;                            // blocks of rows in this launch (a launch with the row table flattens columns x row blocks into grid.x)
+    long long n_rows;                  // rows of the WHOLE table (a shard's launch: more than its n_e) — the row table's threshold, see work_item
     int rowtab;                        // the launch carries the row table's LDS: tau-p tier and eb >= RTUS_ROWTAB_MIN_ROWS (else no block qualifies)
 };
 
@@ -246,7 +253,7 @@ __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL
                 S3 = fmaf(hw, y[i] * y[i], S3);
             }
         }
-        // 1 / X'(q): v_rcp_f32 — or, HOLD = 2, the reciprocal of the group's first element as it is (see the kernel).  (Round 3 took
+        // 1 / X'(q): v_rcp_f32 — or, HOLD = 2, the reciprocal of the group's first element as it is (see solve_block).  (Round 3 took
         // ONE Newton step from the previous element's reciprocal instead, error = the change of X' squared: fine on a fine regular
         // pitch, but on a coarse or random one — X' moving by tens of per cent per element, the predictor missing by ~tau — it put
         // 2.8e-10 relative on a table: scripts/fuzz_layers.py --taup with tables large enough for four-history runs found it.)
@@ -352,7 +359,7 @@ __device__ __forceinline__ float solve_elem(uint8_t* __restrict__ iters, Lane<NL
             const double t = fma(-g, g, d) * yi;            // ... and one Newton step: sqrt(d) = g + t / 2 (error ~1e-14)
             ST = fma(L.hc[i], fma(t, 0.5, g), ST);
         }
-        // the second-order term = G dXf^2 with G = u^3 / (2 cm X'(q)); HOLD = 2: the G of the group's first element (see the kernel)
+        // the second-order term = G dXf^2 with G = u^3 / (2 cm X'(q)); HOLD = 2: the G of the group's first element (see solve_block)
         float G;
         if (HOLD == 2) G = L.G = L.G + L.dG;                // one element further along the secant through the last two G formed exactly
         else {
@@ -552,6 +559,7 @@ __device__ __forceinline__ ElemRec elem_record(const LayerArgs& a, int lane, int
     return r;
 }
 
+// ---- The kernel's phases ---------------------------------------------------------------------------------------------------
 // A workgroup = 256 focal points x `eb` consecutive elements (loop).  Besides re-using the layer
 // set-up while ze repeats, the loop gives each lane a CONTINUATION PREDICTOR: the signed solution
 // qs = sign(xf - xe) q is a smooth function of the element position, so the four previous
@@ -560,216 +568,282 @@ __device__ __forceinline__ ElemRec elem_record(const LayerArgs& a, int lane, int
 // the workgroup works them out once for element e0 + t and parks them in LDS.
 // The predictor is only a guess: iterates are clamped to the rigorous lower bound of the root,
 // from which Newton is monotone, so convergence never depends on the elements being evenly spaced.
-// NL = number of layers the medium has (n_if + 1); TAUP: the tau-p tail (accuracy tier); PERM: the elements arrive sorted by
-// (depth, position) and element i's row of the table is a.row_of[i] — an aperture handed over in any order gets the predictor.
-template <int NL, bool ITERS, bool TAUP = false, bool PERM = false>
-__global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_tt_layers_kernel(LayerArgs a)
+// The kernel (at the end of this part) is a sequence of the functions below: decode the work item; before the only barrier leave
+// either the solver's records or, where the row table is tried, the ranges it is decided on; choose the lattice, build and verify
+// the table and serve the rows from it; failing that, form the records behind a second barrier and run the solver over the block.
+// Every function is inlined into the kernel; the LDS they share is the kernel's and is handed down by pointer.
+
+// A work item = (column of 256 targets, block of rows, problem of a batch): one per workgroup, decoded once.
+struct WorkItem {
+    const double* __restrict__ xe;     // the problem's arrays (a batched launch: problem blockIdx.z)
+    const double* __restrict__ ze;
+    const double* __restrict__ xf;
+    const double* __restrict__ zf;
+    double* __restrict__ tt;
+    uint8_t* __restrict__ iters;       // (ITERS kernels, else null)
+    int bx;                            // the column of targets
+    int f;                             // this lane's target; lanes beyond the last target redo the last one (live = false)
+    unsigned f8;                       // its byte offset in a row of the table (n_f x 8 < 2^32: the launcher checks)
+    bool live;
+    int gb;                            // the workgroup's block of the whole table
+    int e0, ne;                        // its first element in this launch's rows, and how many (<= 64)
+    bool try_tab;                      // the row table is tried
+};
+
+template <bool ITERS, bool ROWTAB>
+__device__ __forceinline__ WorkItem work_item(const LayerArgs& a)
 {
-    __shared__ ElemRec rec[64];
-#if defined(RTUS_EXP_PERSIST) || defined(RTUS_EXP_NO_ROWTAB)   // experiment builds only: the solver path everywhere
-    constexpr bool ROWTAB = false;
-#else
-    constexpr bool ROWTAB = TAUP && !ITERS;                  // the row table is a path of the tau-p tier (see rowtab_point)
-#endif
-    // the table itself is DYNAMIC LDS, asked for by launch_layers only where a block can qualify (a.rowtab): a table of short blocks
-    // — configs[1], configs[4] — launches with the 2 KB of records it always had
-    extern __shared__ __attribute__((aligned(16))) RowTabSlot tab[];
-    __shared__ RowTabHdr hdr;
-    // Work items = (column of 256 targets, block of rows, problem of a batch): one per workgroup.  -DRTUS_EXP_PERSIST (experiment
-    // builds only, scripts/gpu_planar_r04.sh) runs them as a PERSISTENT grid instead — 8 workgroups per CU, workgroup w takes items
-    // w, w + gridDim.x, ... — to find out whether the half-empty wave slots between the two rounds of a configs[2] launch cost time:
-    // they do not (round 4: slots full, launch 1-2 % SLOWER) — the kernel is bound by VALU issue, not by residency.
-#ifdef RTUS_EXP_PERSIST
-    for (int item = blockIdx.x; item < a.n_items; item += gridDim.x) {
-    const int bx = item % a.gx, byz = item / a.gx, by = byz % a.gy, bz = byz / a.gy;
-    if (item != (int)blockIdx.x) __syncthreads();           // the previous item's records are still being read by the slower waves
-#else
-    {
     // A launch that carries the row table hands its work items out ALONG THE ROW BLOCKS first (blockIdx.x = bx gy + by: launch_layers
     // flattens its grid): workgroups that start together then write into gy row blocks at once instead of into neighbouring 2-KB
     // pieces of the same rows, which is what the store stream wants (DESIGN.md section 4 "Store stream").  Other launches keep x first.
     const int bx = a.rowtab ? (int)(blockIdx.x / (unsigned)a.gy) : (int)blockIdx.x;
     const int by = a.rowtab ? (int)(blockIdx.x % (unsigned)a.gy) : (int)blockIdx.y, bz = blockIdx.z;
-#endif
-    // batched launch: problem bz
-    const double* __restrict__ xe_p = a.xe + (size_t)bz * a.e_stride;
-    const double* __restrict__ ze_p = a.ze + (size_t)bz * a.e_stride;
-    const double* __restrict__ xf_p = a.xf + (size_t)bz * a.f_stride;
-    const double* __restrict__ zf_p = a.zf + (size_t)bz * a.f_stride;
-    double* __restrict__ tt_p = a.tt + (size_t)bz * a.t_stride;
-    uint8_t* __restrict__ it_p = ITERS ? a.iters + (size_t)bz * a.t_stride : nullptr;
-
+    WorkItem wi;
+    wi.bx = bx;
+    wi.xe = a.xe + (size_t)bz * a.e_stride;
+    wi.ze = a.ze + (size_t)bz * a.e_stride;
+    wi.xf = a.xf + (size_t)bz * a.f_stride;
+    wi.zf = a.zf + (size_t)bz * a.f_stride;
+    wi.tt = a.tt + (size_t)bz * a.t_stride;
+    wi.iters = ITERS ? a.iters + (size_t)bz * a.t_stride : nullptr;
     const int f_raw = bx * RTUS_BLOCK + threadIdx.x;
-    const bool live = f_raw < a.n_f;
-    const int f = live ? f_raw : a.n_f - 1;
-    double xf = xf_p[f];
-    const unsigned f8 = (unsigned)f * 8u;                   // the target's byte offset in a row of the table (n_f x 8 < 2^32: the launcher checks)
-    const int gb = a.row0 / a.eb + by;                      // the workgroup's block of the whole table
-    const int e0 = max(gb * a.eb - a.row0, 0);              // ... in this launch's rows (a shard that starts inside a block keeps its tail)
-    const int ne = min((gb + 1) * a.eb - a.row0, a.n_e) - e0;   // elements of this workgroup (<= 64)
+    wi.live = f_raw < a.n_f;
+    wi.f = wi.live ? f_raw : a.n_f - 1;
+    wi.f8 = (unsigned)wi.f * 8u;
+    wi.gb = a.row0 / a.eb + by;
+    wi.e0 = max(wi.gb * a.eb - a.row0, 0);                   // (a shard that starts inside a block keeps its tail)
+    wi.ne = min((wi.gb + 1) * a.eb - a.row0, a.n_e) - wi.e0;
     // Row table: tried where the block OF THE WHOLE TABLE has enough rows for it to pay (a scalar test on the launch's arguments:
-    // a table of short blocks, configs[1] for one, pays nothing further).  Each wave leaves the range of its targets' x and whether
-    // they share the first target's depth; the first wave does the same for the elements below.
-    const bool try_tab = ROWTAB && a.rowtab && min((long long)(gb + 1) * a.eb, a.n_rows) - (long long)gb * a.eb >= RTUS_ROWTAB_MIN_ROWS;
-    RTUS_STAMP(0);
+    // a table of short blocks, configs[1] for one, pays nothing further).
+    wi.try_tab = ROWTAB && a.rowtab && min((long long)(wi.gb + 1) * a.eb, a.n_rows) - (long long)wi.gb * a.eb >= RTUS_ROWTAB_MIN_ROWS;
+    return wi;
+}
+
+// Where element `idx` of the block is stored: its row inside the workgroup's block of rows (one descriptor, the row as the
+// instruction's scalar offset) or, PERM, a descriptor of the row it belongs to (a few scalar instructions per element).  The callers
+// walk the block and pass the running offsets of row idx — `off` in elements from the table's start, `soff` in bytes from the block's.
+template <bool PERM>
+struct RowDest {
+    double* __restrict__ tt;
+    const ElemRec* rec;                // PERM: the records hold each element's row
+    size_t nf, o0;                     // elements per row; offset of the block's first row (wave-uniform)
+    unsigned row_bytes;                // (li x row_bytes < 2^32: the launcher sizes eb for it)
+    __amdgpu_buffer_rsrc_t rs;         // the block's rows
+    __device__ __forceinline__ size_t row(int idx, size_t off) const    // the row's offset: of the iteration counts too
+    {
+        return PERM ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(rec[idx].row) * nf : off;
+    }
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(int idx, size_t off) const
+    {
+        if (!PERM) return rs;
+        return __builtin_amdgcn_make_buffer_rsrc(tt + row(idx, off), 0, row_bytes, 0x00020000);
+    }
+    __device__ __forceinline__ unsigned soff(unsigned off) const { return PERM ? 0u : off; }
+};
+
+template <bool PERM>
+__device__ __forceinline__ RowDest<PERM> row_dest(const LayerArgs& a, const WorkItem& wi, const ElemRec* rec)
+{
+    RowDest<PERM> d;
+    d.tt = wi.tt; d.rec = rec;
+    d.nf = (size_t)a.n_f;
+    d.o0 = (size_t)wi.e0 * d.nf;
+    d.row_bytes = (unsigned)a.n_f * 8u;
+    d.rs = __builtin_amdgcn_make_buffer_rsrc(wi.tt + d.o0, 0, (unsigned)wi.ne * d.row_bytes, 0x00020000);
+    return d;
+}
+
+// The solver's records of the block: the first wave works them out, one element per lane (`el`: the lane's element).  Called before
+// the only barrier where the table is not tried (nothing waits on the targets there), and behind a second barrier where it was tried
+// and does not serve.
+template <bool TAUP, bool PERM>
+__device__ __forceinline__ void solver_records(const LayerArgs& a, const WorkItem& wi, int el, ElemRec* rec)
+{
+    rec[threadIdx.x] = elem_record<TAUP>(a, threadIdx.x, wi.ne, load_elem_pos(wi.xe, wi.ze, wi.e0, el), PERM ? a.row_of[el] : 0);
+}
+
+// ---- row table: the phases -------------------------------------------------------------------------------------------------
+// ELIGIBLE: every target of the workgroup at one depth zf, every element of the block at one depth ze < zf, every x finite, the
+// block long enough (try_tab).  LATTICE: nodes X_j = j h anchored at X = 0, h the power of two nearest (zf - ze) / 128: a
+// function of the two depths alone.  The workgroup builds the intervals [tlo, thi] that its |xf - xe| can touch — from the
+// extreme pairs: fl(xf - xe) is monotone in both, so every solve's index floor(X / h) lies between theirs and no lane needs a
+// range check — one node per lane (T, h p, h^2 p' / 2: the first three coefficients of the interval that starts there), then
+// one interval per lane: the upper three coefficients from the two nodes, and a solved point at s = 0.3 against the
+// interpolant.  A node that did not reach its residual, an interval beyond 1e-11, more intervals than the table holds: the
+// WHOLE workgroup takes the solver path, before a row is stored (its history needs every row).
+// BITS.  A served solve is a function of (X, j, h, the depths, the medium): X / h, X / h - tlo and the fraction are exact, a
+// node is solved cold from X_j, an interval's coefficients come from its own two nodes — no trace of tlo, of the lane that
+// built it, of the launch.  So a row served here has the same bits from one launch, from row shards, from the batched entry
+// and from the sorted entry in any order of the aperture, and the row of an element at +x mirrors that of one at -x.  What is
+// left is the DECISION, which must not depend on the launch either.  It is a function of the block's rows: of their number
+// IN THE WHOLE TABLE (gb, eb, n_rows: not the rows this launch holds), and of conditions that are all MONOTONE in the set of
+// elements — one depth, finite x, [tlo, thi] inside the capacity, every interval of [tlo, thi] good (an interval's verdict is
+// a function of j).  A launch that holds the whole block (any shard cut at multiples of eb, the batched and the sorted
+// entries) decides on the same elements as the whole table's launch.  One that holds PART of a block sees a subset: where the
+// whole block qualifies so does every part of it, and the rows agree bit for bit wherever the shard is cut; where the whole
+// block does not, the whole table's launch ran the solver — whose bits in a block cut apart were never those of the whole
+// (its history starts at the cut: rtus_launch_tt_layers_rows promises equal bits for cuts at multiples of eb only).
+
+// Before the only barrier.  Each wave leaves the range of its targets' x and whether they share the first target's depth; the first
+// wave does the same for the elements.  A workgroup that tries the table forms the solver's records only if it turns out to need
+// them: here it leaves what serving reads — the element's position and, PERM, its row — and the header's words.  Returns the depth
+// of the lane's target.
+template <bool PERM>
+__device__ __forceinline__ double rowtab_ranges(const LayerArgs& a, const WorkItem& wi, double xf, int el, ElemRec* rec, RowTabHdr& hdr)
+{
     const bool first_wave = threadIdx.x < 64;
-    const int el = min(e0 + (int)(threadIdx.x & 63), a.n_e - 1);   // the first wave: its lane's element
-    // A workgroup that tries the table forms the solver's records only if it turns out to need them (behind the table path below):
-    // before the barrier it leaves what serving reads — the element's position and, PERM, its row — and the header's words.
-    double zfv = 0.0;
-    if (try_tab) {
-        // The first wave's element loads go out WITH the targets', before anything waits on either: behind the wait for xf and zf,
-        // which the reductions need, they were a second round trip to the L2 with three waves at the barrier meanwhile.
-        ElemPos P;                                           // (the first wave's, x0 and z0 alone: no other wave reads it)
-        int prow = 0;
-        if (first_wave) {
-            P.x0 = xe_p[el]; P.z0 = ze_p[el];
-            if (PERM) prow = a.row_of[el];
-        }
-        zfv = zf_p[f];
-        const bool okl = zfv == zf_p[bx * RTUS_BLOCK] && isfinite(xf);
-        const bool okw = !__builtin_amdgcn_ballot_w64(!okl);
-        double lo = 0.0, hi = 0.0;
-        if (okw) { lo = wave_min_f64(xf); hi = wave_max_f64(xf); }       // (wave-uniform: random targets pay the load and the ballot only)
-        if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; hdr.flo[w] = lo; hdr.fhi[w] = hi; hdr.fok[w] = okw; }
-        if (first_wave) {
-            const int lane = threadIdx.x;
-            const bool in = lane < ne;
-            const double zfirst = __shfl(P.z0, 0);
-            const bool oke = !__builtin_amdgcn_ballot_w64(in && !(P.z0 == zfirst && isfinite(P.x0)));
-            const double elo = wave_min_f64(in ? P.x0 : (double)INFINITY), ehi = wave_max_f64(in ? P.x0 : -(double)INFINITY);
-            if (lane == 0) { hdr.elo = elo; hdr.ehi = ehi; hdr.ze = zfirst; hdr.eok = oke; }
-            rec[lane].xe = P.x0;
-            if (PERM) rec[lane].row = prow;
-        }
-    } else if (first_wave) {
-        // ---- per-element records: the first wave works them out, one element per lane (nothing waits on the targets here) ----
-        rec[threadIdx.x] = elem_record<TAUP>(a, threadIdx.x, ne, load_elem_pos(xe_p, ze_p, e0, el), PERM ? a.row_of[el] : 0);
+    // The first wave's element loads go out WITH the targets', before anything waits on either: behind the wait for xf and zf,
+    // which the reductions need, they were a second round trip to the L2 with three waves at the barrier meanwhile.
+    ElemPos P;                                               // (the first wave's, x0 and z0 alone: no other wave reads it)
+    int prow = 0;
+    if (first_wave) {
+        P.x0 = wi.xe[el]; P.z0 = wi.ze[el];
+        if (PERM) prow = a.row_of[el];
+    }
+    const double zfv = wi.zf[wi.f];
+    const bool okl = zfv == wi.zf[wi.bx * RTUS_BLOCK] && isfinite(xf);
+    const bool okw = !__builtin_amdgcn_ballot_w64(!okl);
+    double lo = 0.0, hi = 0.0;
+    if (okw) { lo = wave_min_f64(xf); hi = wave_max_f64(xf); }           // (wave-uniform: random targets pay the load and the ballot only)
+    if ((threadIdx.x & 63) == 0) { const int w = threadIdx.x >> 6; hdr.flo[w] = lo; hdr.fhi[w] = hi; hdr.fok[w] = okw; }
+    if (first_wave) {
+        const int lane = threadIdx.x;
+        const bool in = lane < wi.ne;
+        const double zfirst = __shfl(P.z0, 0);
+        const bool oke = !__builtin_amdgcn_ballot_w64(in && !(P.z0 == zfirst && isfinite(P.x0)));
+        const double elo = wave_min_f64(in ? P.x0 : (double)INFINITY), ehi = wave_max_f64(in ? P.x0 : -(double)INFINITY);
+        if (lane == 0) { hdr.elo = elo; hdr.ehi = ehi; hdr.ze = zfirst; hdr.eok = oke; }
+        rec[lane].xe = P.x0;
+        if (PERM) rec[lane].row = prow;
+    }
+    return zfv;
+}
+
+// Behind the barrier: what the waves left says whether the workgroup is eligible (wave-uniform)
+__device__ __forceinline__ bool rowtab_eligible(const RowTabHdr& hdr)
+{
+    return __builtin_amdgcn_readfirstlane(hdr.fok[0] & hdr.fok[1] & hdr.fok[2] & hdr.fok[3] & hdr.eok);
+}
+
+// The lattice of an eligible workgroup, from the header (wave-uniform).  fits: the span is within the capacity.
+struct RowTabLattice {
+    double ze;                         // the elements' depth
+    double h, inv_h, tlo;              // node X_j = j h; the table's first interval starts at node tlo
+    int n_int;                         // intervals; nodes 0 .. n_int (<= the slots)
+    bool fits;
+};
+__device__ __forceinline__ RowTabLattice rowtab_lattice(const RowTabHdr& hdr, double zfv)
+{
+    const double zE = hdr.ze, D = zfv - zE, elo = hdr.elo, ehi = hdr.ehi;
+    const double flo = fmin(fmin(hdr.flo[0], hdr.flo[1]), fmin(hdr.flo[2], hdr.flo[3]));
+    const double fhi = fmax(fmax(hdr.fhi[0], hdr.fhi[1]), fmax(hdr.fhi[2], hdr.fhi[3]));
+    const double gap = fmax(fmax(flo - ehi, elo - fhi), 0.0), far = fmax(fhi - elo, ehi - flo);
+    const double h = __longlong_as_double(__double_as_longlong(D * RTUS_ROWTAB_DIV) & 0x7ff0000000000000ll);
+    const double inv_h = __longlong_as_double(0x7fe0000000000000ll - __double_as_longlong(h));      // exact: h is a power of two
+    const double tlo = floor(gap * inv_h), thi = floor(far * inv_h);
+    // (D > 0 is zf > ze; the limits keep h and 1 / h normal and the indices in an int; NaN fails every comparison)
+    const bool fits = D > 1e-290 && D < 1e290 && thi < 1073741824.0 && thi - tlo < (double)(RTUS_ROWTAB_SLOTS - 1);
+    return {zE, h, inv_h, tlo, __builtin_amdgcn_readfirstlane(fits ? (int)(thi - tlo) : 0) + 1, __builtin_amdgcn_readfirstlane((int)fits) != 0};
+}
+
+// The build: the node pass, the interval pass with its check, the workgroup's vote.  Returns whether the workgroup serves.
+template <int NL>
+__device__ __forceinline__ bool rowtab_build(const LayerArgs& a, const WorkItem& wi, const RowTabLattice& lat, RowTabSlot* tab,
+                                             RowTabHdr& hdr, double& xf)
+{
+    const double h = lat.h, tlo = lat.tlo;
+    const int n_int = lat.n_int;
+    const int tid = threadIdx.x, w0 = __builtin_amdgcn_readfirstlane(tid) & ~63;
+    Lane<NL> LT;
+    layer_setup<NL>(a, lat.ze, wi.zf, wi.f8, LT);
+    bool bad = false;
+    for (int base = w0; base <= n_int; base += RTUS_BLOCK) {                     // (wave-uniform: a wave without a node skips)
+        const int k = min(base + (tid & 63), n_int);
+        double T, p, pp;
+        bad |= !rowtab_point<NL>(LT, (tlo + (double)k) * h, T, p, pp);
+        tab[k].c[0] = T; tab[k].c[1] = p * h; tab[k].c[2] = pp * (0.5 * h * h);   // (lanes past the last node redo it: same values)
     }
     __syncthreads();
-    RTUS_STAMP(1);
+    RTUS_STAMP(2);
+    for (int base = w0; base < n_int; base += RTUS_BLOCK) {
+        const int j = min(base + (tid & 63), n_int - 1);
+        double Tc, pc, ppc;                                                      // (the solve first: the coefficients are not live across it)
+        const bool okc = rowtab_point<NL>(LT, ((tlo + (double)j) + RTUS_ROWTAB_CHECK_S) * h, Tc, pc, ppc);
+        const double c0 = tab[j].c[0], c1 = tab[j].c[1], c2 = tab[j].c[2];
+        const double d = ((tab[j + 1].c[0] - c0) - c1) - c2, e = (tab[j + 1].c[1] - c1) - 2.0 * c2, g = 2.0 * (tab[j + 1].c[2] - c2);
+        const double c3 = fma(10.0, d, fma(-4.0, e, 0.5 * g)), c4 = fma(-15.0, d, fma(7.0, e, -g)), c5 = fma(6.0, d, fma(-3.0, e, 0.5 * g));
+        // (the upper three: words no node pass wrote and no other lane reads now — no barrier between the reads and these)
+        tab[j].c[3] = c3; tab[j].c[4] = c4; tab[j].c[5] = c5;
+        const double sc = RTUS_ROWTAB_CHECK_S;
+        const double Ti = fma(sc, fma(sc, fma(sc, fma(sc, fma(sc, c5, c4), c3), c2), c1), c0);
+        bad |= !(okc && fabs(Ti - Tc) <= RTUS_ROWTAB_BOUND * Tc);
+    }
+    // (the target's x is LOADED again here — an L2 hit, through an offset the compiler cannot see through, as layer_setup
+    // does with zf — instead of being held across the build, which has no register to spare for it: two went to scratch)
+    unsigned f8r = wi.f8;
+    asm volatile("" : "+v"(f8r));
+    xf = *(const double*)((const char*)wi.xf + f8r);
+    const bool badw = __builtin_amdgcn_ballot_w64(bad) != 0;
+    if ((tid & 63) == 0) hdr.bad[tid >> 6] = badw;
+    __syncthreads();
+    RTUS_STAMP(3);
+    return !__builtin_amdgcn_readfirstlane(hdr.bad[0] | hdr.bad[1] | hdr.bad[2] | hdr.bad[3]);
+}
 
+// Serving: a row per trip (wave-uniform), every lane its own target.
+template <bool PERM>
+__device__ __forceinline__ void rowtab_serve(const WorkItem& wi, const RowTabLattice& lat, const RowTabSlot* tab, const RowDest<PERM>& dest,
+                                             double xf)
+{
+    // the rows leave WRITE-THROUGH (sc1, the store's cache-policy operand 16): a table that takes this path is larger than
+    // the L2s together, so a line kept there serves nobody and is only written back later, at the launch's end at the latest
+    constexpr int store_policy = 16;
+    const RecPtr rec3 = (RecPtr)dest.rec;
+    const double inv_h = lat.inv_h, tlo = lat.tlo;
+    size_t ot = dest.o0;
+    unsigned sot = 0;
+    for (int l = 0; l < wi.ne; ++l) {
+        const double tq = fma(fabs(xf - rec3[l].xe), inv_h, -tlo);              // X / h - tlo, exact
+        const double sq = __builtin_amdgcn_fract(tq);
+        const RowTabSlot* __restrict__ sl = &tab[(int)tq];
+        const double T = fma(sq, fma(sq, fma(sq, fma(sq, fma(sq, sl->c[5], sl->c[4]), sl->c[3]), sl->c[2]), sl->c[1]), sl->c[0]);
+        const u32x2 bits = {(unsigned)__double2loint(T), (unsigned)__double2hiint(T)};
+        if (l == 0) RTUS_STAMP(4);                                               // (nothing in a product build)
+        __builtin_amdgcn_raw_buffer_store_b64(bits, dest.rsrc(l, ot), wi.f8, dest.soff(sot), store_policy);
+        ot += dest.nf; sot += dest.row_bytes;
+    }
+}
+
+// ---- the solver over the block -----------------------------------------------------------------------------------------------
+template <int V> struct HoldMode { static constexpr int value = V; };
+
+template <int NL, bool ITERS, bool TAUP, bool PERM>
+__device__ __forceinline__ void solve_block(const LayerArgs& a, const WorkItem& wi, double xf, const RowDest<PERM>& dest)
+{
+#ifdef RTUS_EXP_NO_HOLD                                     // experiment builds only (scripts/build_variant.sh nohold): every solve forms its own X' and u^3
+    constexpr bool HOLDS = false;
+#else
+    constexpr bool HOLDS = TAUP;
+#endif
+    const ElemRec* rec = dest.rec;
     const RecPtr rec3 = (RecPtr)rec;
-    const size_t nf = (size_t)a.n_f;
-    size_t o = (size_t)e0 * nf;                              // output row of element e0 + li (wave-uniform; ITERS only)
-    const unsigned row_bytes = (unsigned)a.n_f * 8u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(tt_p + o, 0, (unsigned)ne * row_bytes, 0x00020000);
-    unsigned so = 0;                                         // li * row_bytes (< 2^32: the launcher sizes eb for it)
+    uint8_t* __restrict__ it_p = wi.iters;
+    const unsigned f8 = wi.f8;
+    const bool live = wi.live;
+    const size_t nf = dest.nf;
+    const unsigned row_bytes = dest.row_bytes;
+    size_t o = dest.o0;                                      // output row of element e0 + li (wave-uniform; ITERS only)
+    unsigned so = 0;                                         // li * row_bytes
     int li = 0;
-    // where element `idx` of the block is stored: its row inside the workgroup's block of rows (one descriptor, the row as the
-    // instruction's scalar offset) or, PERM, a descriptor of the row it belongs to (a few scalar instructions per element)
-    auto dest_o = [&](int idx, size_t off) { return PERM ? (size_t)(unsigned)__builtin_amdgcn_readfirstlane(rec[idx].row) * nf : off; };
-    auto dest_rs = [&](int idx, size_t off) {
-        if (!PERM) return rs;
-        return __builtin_amdgcn_make_buffer_rsrc(tt_p + dest_o(idx, off), 0, row_bytes, 0x00020000);
-    };
-    auto dest_so = [&](unsigned off) { return PERM ? 0u : off; };
-    // ---- row table ---------------------------------------------------------------------------------------------------------
-    // ELIGIBLE: every target of the workgroup at one depth zf, every element of the block at one depth ze < zf, every x finite, the
-    // block long enough (try_tab).  LATTICE: nodes X_j = j h anchored at X = 0, h the power of two nearest (zf - ze) / 128: a
-    // function of the two depths alone.  The workgroup builds the intervals [tlo, thi] that its |xf - xe| can touch — from the
-    // extreme pairs: fl(xf - xe) is monotone in both, so every solve's index floor(X / h) lies between theirs and no lane needs a
-    // range check — one node per lane (T, h p, h^2 p' / 2: the first three coefficients of the interval that starts there), then
-    // one interval per lane: the upper three coefficients from the two nodes, and a solved point at s = 0.3 against the
-    // interpolant.  A node that did not reach its residual, an interval beyond 1e-11, more intervals than the table holds: the
-    // WHOLE workgroup takes the solver path below, before a row is stored (its history needs every row).
-    // BITS.  A served solve is a function of (X, j, h, the depths, the medium): X / h, X / h - tlo and the fraction are exact, a
-    // node is solved cold from X_j, an interval's coefficients come from its own two nodes — no trace of tlo, of the lane that
-    // built it, of the launch.  So a row served here has the same bits from one launch, from row shards, from the batched entry
-    // and from the sorted entry in any order of the aperture, and the row of an element at +x mirrors that of one at -x.  What is
-    // left is the DECISION, which must not depend on the launch either.  It is a function of the block's rows: of their number
-    // IN THE WHOLE TABLE (gb, eb, n_rows: not the rows this launch holds), and of conditions that are all MONOTONE in the set of
-    // elements — one depth, finite x, [tlo, thi] inside the capacity, every interval of [tlo, thi] good (an interval's verdict is
-    // a function of j).  A launch that holds the whole block (any shard cut at multiples of eb, the batched and the sorted
-    // entries) decides on the same elements as the whole table's launch.  One that holds PART of a block sees a subset: where the
-    // whole block qualifies so does every part of it, and the rows agree bit for bit wherever the shard is cut; where the whole
-    // block does not, the whole table's launch ran the solver — whose bits in a block cut apart were never those of the whole
-    // (its history starts at the cut: rtus_launch_tt_layers_rows promises equal bits for cuts at multiples of eb only).
-    if (try_tab && __builtin_amdgcn_readfirstlane(hdr.fok[0] & hdr.fok[1] & hdr.fok[2] & hdr.fok[3] & hdr.eok)) {
-        const double zE = hdr.ze, D = zfv - zE, elo = hdr.elo, ehi = hdr.ehi;
-        const double flo = fmin(fmin(hdr.flo[0], hdr.flo[1]), fmin(hdr.flo[2], hdr.flo[3]));
-        const double fhi = fmax(fmax(hdr.fhi[0], hdr.fhi[1]), fmax(hdr.fhi[2], hdr.fhi[3]));
-        const double gap = fmax(fmax(flo - ehi, elo - fhi), 0.0), far = fmax(fhi - elo, ehi - flo);
-        const double h = __longlong_as_double(__double_as_longlong(D * RTUS_ROWTAB_DIV) & 0x7ff0000000000000ll);
-        const double inv_h = __longlong_as_double(0x7fe0000000000000ll - __double_as_longlong(h));      // exact: h is a power of two
-        const double tlo = floor(gap * inv_h), thi = floor(far * inv_h);
-        // (D > 0 is zf > ze; the limits keep h and 1 / h normal and the indices in an int; NaN fails every comparison)
-        const bool fits = D > 1e-290 && D < 1e290 && thi < 1073741824.0 && thi - tlo < (double)(RTUS_ROWTAB_SLOTS - 1);
-        if (__builtin_amdgcn_readfirstlane((int)fits)) {
-            const int n_int = __builtin_amdgcn_readfirstlane((int)(thi - tlo)) + 1;      // intervals; nodes 0 .. n_int (<= the slots)
-            const int tid = threadIdx.x, w0 = __builtin_amdgcn_readfirstlane(tid) & ~63;
-            Lane<NL> LT;
-            layer_setup<NL>(a, zE, zf_p, f8, LT);
-            bool bad = false;
-            for (int base = w0; base <= n_int; base += RTUS_BLOCK) {                     // (wave-uniform: a wave without a node skips)
-                const int k = min(base + (tid & 63), n_int);
-                double T, p, pp;
-                bad |= !rowtab_point<NL>(LT, (tlo + (double)k) * h, T, p, pp);
-                tab[k].c[0] = T; tab[k].c[1] = p * h; tab[k].c[2] = pp * (0.5 * h * h);   // (lanes past the last node redo it: same values)
-            }
-            __syncthreads();
-            RTUS_STAMP(2);
-            for (int base = w0; base < n_int; base += RTUS_BLOCK) {
-                const int j = min(base + (tid & 63), n_int - 1);
-                double Tc, pc, ppc;                                                      // (the solve first: the coefficients are not live across it)
-                const bool okc = rowtab_point<NL>(LT, ((tlo + (double)j) + RTUS_ROWTAB_CHECK_S) * h, Tc, pc, ppc);
-                const double c0 = tab[j].c[0], c1 = tab[j].c[1], c2 = tab[j].c[2];
-                const double d = ((tab[j + 1].c[0] - c0) - c1) - c2, e = (tab[j + 1].c[1] - c1) - 2.0 * c2, g = 2.0 * (tab[j + 1].c[2] - c2);
-                const double c3 = fma(10.0, d, fma(-4.0, e, 0.5 * g)), c4 = fma(-15.0, d, fma(7.0, e, -g)), c5 = fma(6.0, d, fma(-3.0, e, 0.5 * g));
-                // (the upper three: words no node pass wrote and no other lane reads now — no barrier between the reads and these)
-                tab[j].c[3] = c3; tab[j].c[4] = c4; tab[j].c[5] = c5;
-                const double sc = RTUS_ROWTAB_CHECK_S;
-                const double Ti = fma(sc, fma(sc, fma(sc, fma(sc, fma(sc, c5, c4), c3), c2), c1), c0);
-                bad |= !(okc && fabs(Ti - Tc) <= RTUS_ROWTAB_BOUND * Tc);
-            }
-            // (the target's x is LOADED again here — an L2 hit, through an offset the compiler cannot see through, as layer_setup
-            // does with zf — instead of being held across the build, which has no register to spare for it: two went to scratch)
-            unsigned f8r = f8;
-            asm volatile("" : "+v"(f8r));
-            xf = *(const double*)((const char*)xf_p + f8r);
-            const bool badw = __builtin_amdgcn_ballot_w64(bad) != 0;
-            if ((tid & 63) == 0) hdr.bad[tid >> 6] = badw;
-            __syncthreads();
-            RTUS_STAMP(3);
-            if (!__builtin_amdgcn_readfirstlane(hdr.bad[0] | hdr.bad[1] | hdr.bad[2] | hdr.bad[3])) {
-                // the rows leave WRITE-THROUGH (sc1, the store's cache-policy operand 16): a table that takes this path is larger than
-                // the L2s together, so a line kept there serves nobody and is only written back later, at the launch's end at the latest
-                constexpr int store_policy = 16;
-                size_t ot = o;
-                unsigned sot = 0;
-                for (int l = 0; l < ne; ++l) {                                           // a row per trip: wave-uniform
-                    const double tq = fma(fabs(xf - rec3[l].xe), inv_h, -tlo);          // X / h - tlo, exact
-                    const double sq = __builtin_amdgcn_fract(tq);
-                    const RowTabSlot* __restrict__ sl = &tab[(int)tq];
-                    const double T = fma(sq, fma(sq, fma(sq, fma(sq, fma(sq, sl->c[5], sl->c[4]), sl->c[3]), sl->c[2]), sl->c[1]), sl->c[0]);
-                    const u32x2 bits = {(unsigned)__double2loint(T), (unsigned)__double2hiint(T)};
-                    if (l == 0) RTUS_STAMP(4);                                           // (nothing in a product build)
-                    __builtin_amdgcn_raw_buffer_store_b64(bits, dest_rs(l, ot), f8, dest_so(sot), store_policy);
-                    ot += nf; sot += row_bytes;
-                }
-                RTUS_STAMP(5);
-                return;
-            }
-        }
-    }
-    // The workgroup tried the table and does not serve from it (ineligible, too wide a span, a rejected build): the solver needs
-    // the full records now.  Every wave arrives here together (the decisions above are the workgroup's), none has read a record.
-    if (try_tab) {
-        if (first_wave) {
-            const ElemPos PF = load_elem_pos(xe_p, ze_p, e0, el);
-            rec[threadIdx.x] = elem_record<TAUP>(a, threadIdx.x, ne, PF, PERM ? a.row_of[el] : 0);
-        }
-        __syncthreads();
-    }
     Lane<NL> L;
     L.tau = INFINITY; L.rS3 = 0.0f; L.G = L.dG = 0.0f; L.hic = 0.0f; L.inv_cm = 0.0; L.hr0 = L.hc0 = 0.0; L.hr0f = L.rs0f = L.rhmf = L.asymf = 0.0f;
 #pragma unroll
     for (int i = 0; i < NL; ++i) { L.hr[i] = L.kk[i] = L.hc[i] = 0.0; L.hrf[i] = L.kkf[i] = 0.0f; }
     float qa = 0.0f, qb = 0.0f, qc = 0.0f, qd = 0.0f;       // signed solutions of the four previous elements, qa the latest
-    while (li < ne) {                                        // wave-uniform loop
+    while (li < wi.ne) {                                     // wave-uniform loop
         const int info = __builtin_amdgcn_readfirstlane(rec[li].info);
         if (info & 8) {                                      // depth changed: redo the layer set-up, forget the history
-            layer_setup<NL>(a, ze_p[e0 + li], zf_p, f8, L);
+            layer_setup<NL>(a, wi.ze[wi.e0 + li], wi.zf, f8, L);
             qa = qb = qc = qd = 0.0f;                        // a lane may carry NaN history from a depth at which its target
                                                              // was not below the element
         }
@@ -781,6 +855,15 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
             unsigned rp_off = (unsigned)li * (unsigned)sizeof(ElemRec);
             asm volatile("" : "+v"(rp_off));
             RecPtr rp = (RecPtr)((const __attribute__((address_space(3))) char*)rec3 + rp_off);
+            // the group of four at rows i .. i + 3 of the block, in two pieces: its first solve, and the other three
+            auto first = [&](auto hold, int i, bool after_held, bool* ok) {
+                qd = solve_elem<NL, ITERS, true, TAUP, decltype(hold)::value>(it_p, L, rp + 0, 4, xf, qa, qb, qc, qd, live, dest.row(i, o), f8, dest.rsrc(i, o), dest.soff(so), after_held, ok);
+            };
+            auto others = [&](auto hold, int i) {
+                qc = solve_elem<NL, ITERS, true, TAUP, decltype(hold)::value>(it_p, L, rp + 1, 4, xf, qd, qa, qb, qc, live, dest.row(i + 1, o + nf), f8, dest.rsrc(i + 1, o + nf), dest.soff(so + row_bytes));
+                qb = solve_elem<NL, ITERS, true, TAUP, decltype(hold)::value>(it_p, L, rp + 2, 4, xf, qc, qd, qa, qb, live, dest.row(i + 2, o + 2 * nf), f8, dest.rsrc(i + 2, o + 2 * nf), dest.soff(so + 2 * row_bytes));
+                qa = solve_elem<NL, ITERS, true, TAUP, decltype(hold)::value>(it_p, L, rp + 3, 4, xf, qb, qc, qd, qa, live, dest.row(i + 3, o + 3 * nf), f8, dest.rsrc(i + 3, o + 3 * nf), dest.soff(so + 3 * row_bytes));
+            };
             // HOLD (tau-p tier).  The untaken Newton step dq = dXf / X' and the tail's second-order term G dXf^2 need X'(q) and u^3
             // only to a few per cent — dq moves the history by <= tau q, the term is <= (tau^2 / 8) T — and both drift by ~1-2 % from
             // one element to the next.  So the FIRST solve of a group of four forms them exactly (HOLD = 1: the sum for X', v_rcp_f32,
@@ -794,44 +877,73 @@ __global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_
             // aperture and of the rows per block).
             bool held = false;                              // the previous group of this run was held: L.G is extrapolated (see HOLD = 1)
             for (int r = 0; r < run4; r += 4) {
-#ifdef RTUS_EXP_NO_HOLD
-                if (false) {
-#else
-                if (TAUP) {
-#endif
+                if (HOLDS) {
                     bool ok = false;
-                    qd = solve_elem<NL, ITERS, true, TAUP, TAUP ? 1 : 0>(it_p, L, rp + 0, 4, xf, qa, qb, qc, qd, live, dest_o(li + r, o), f8, dest_rs(li + r, o), dest_so(so), held, &ok);
-                    if (ok) {
-                        qc = solve_elem<NL, ITERS, true, TAUP, TAUP ? 2 : 0>(it_p, L, rp + 1, 4, xf, qd, qa, qb, qc, live, dest_o(li + r + 1, o + nf), f8, dest_rs(li + r + 1, o + nf), dest_so(so + row_bytes));
-                        qb = solve_elem<NL, ITERS, true, TAUP, TAUP ? 2 : 0>(it_p, L, rp + 2, 4, xf, qc, qd, qa, qb, live, dest_o(li + r + 2, o + 2 * nf), f8, dest_rs(li + r + 2, o + 2 * nf), dest_so(so + 2 * row_bytes));
-                        qa = solve_elem<NL, ITERS, true, TAUP, TAUP ? 2 : 0>(it_p, L, rp + 3, 4, xf, qb, qc, qd, qa, live, dest_o(li + r + 3, o + 3 * nf), f8, dest_rs(li + r + 3, o + 3 * nf), dest_so(so + 3 * row_bytes));
-                    } else {
-                        qc = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 1, 4, xf, qd, qa, qb, qc, live, dest_o(li + r + 1, o + nf), f8, dest_rs(li + r + 1, o + nf), dest_so(so + row_bytes));
-                        qb = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 2, 4, xf, qc, qd, qa, qb, live, dest_o(li + r + 2, o + 2 * nf), f8, dest_rs(li + r + 2, o + 2 * nf), dest_so(so + 2 * row_bytes));
-                        qa = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 3, 4, xf, qb, qc, qd, qa, live, dest_o(li + r + 3, o + 3 * nf), f8, dest_rs(li + r + 3, o + 3 * nf), dest_so(so + 3 * row_bytes));
-                    }
+                    first(HoldMode<HOLDS ? 1 : 0>{}, li + r, held, &ok);
+                    if (ok) others(HoldMode<HOLDS ? 2 : 0>{}, li + r);
+                    else others(HoldMode<0>{}, li + r);
                     held = ok;
 #ifdef RTUS_EXP_COUNT   // groups of four, and how many of them reused the first solve's X' and u^3
                     if ((threadIdx.x & 63) == 0) { atomicAdd(&planar_dbg[5], 1ull); if (ok) atomicAdd(&planar_dbg[6], 1ull); }
 #endif
                 } else {
-                    qd = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 0, 4, xf, qa, qb, qc, qd, live, dest_o(li + r, o), f8, dest_rs(li + r, o), dest_so(so));
-                    qc = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 1, 4, xf, qd, qa, qb, qc, live, dest_o(li + r + 1, o + nf), f8, dest_rs(li + r + 1, o + nf), dest_so(so + row_bytes));
-                    qb = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 2, 4, xf, qc, qd, qa, qb, live, dest_o(li + r + 2, o + 2 * nf), f8, dest_rs(li + r + 2, o + 2 * nf), dest_so(so + 2 * row_bytes));
-                    qa = solve_elem<NL, ITERS, true, TAUP>(it_p, L, rp + 3, 4, xf, qb, qc, qd, qa, live, dest_o(li + r + 3, o + 3 * nf), f8, dest_rs(li + r + 3, o + 3 * nf), dest_so(so + 3 * row_bytes));
+                    first(HoldMode<0>{}, li + r, false, nullptr);
+                    others(HoldMode<0>{}, li + r);
                 }
                 o += 4 * nf; so += 4 * row_bytes;
                 rp += 4;
             }
             li += run4;
         } else {
-            const float qn = solve_elem<NL, ITERS, false, TAUP>(it_p, L, rec3 + li, info & 7, xf, qa, qb, qc, qd, live, dest_o(li, o), f8, dest_rs(li, o), dest_so(so));
+            const float qn = solve_elem<NL, ITERS, false, TAUP>(it_p, L, rec3 + li, info & 7, xf, qa, qb, qc, qd, live, dest.row(li, o), f8, dest.rsrc(li, o), dest.soff(so));
             qd = qc; qc = qb; qb = qa; qa = qn;
             o += nf; so += row_bytes;
             ++li;
         }
     }
-    }   // items
+}
+
+// NL = number of layers the medium has (n_if + 1); TAUP: the tau-p tail (accuracy tier); PERM: the elements arrive sorted by
+// (depth, position) and element i's row of the table is a.row_of[i] — an aperture handed over in any order gets the predictor.
+template <int NL, bool ITERS, bool TAUP = false, bool PERM = false>
+__global__ __launch_bounds__(RTUS_BLOCK, (NL <= 3 && !ITERS) ? 8 : 1) void rtus_tt_layers_kernel(LayerArgs a)
+{
+    __shared__ ElemRec rec[64];
+#ifdef RTUS_EXP_NO_ROWTAB                                   // experiment builds only: the solver path everywhere
+    constexpr bool ROWTAB = false;
+#else
+    constexpr bool ROWTAB = TAUP && !ITERS;                  // the row table is a path of the tau-p tier (see rowtab_point)
+#endif
+    // the table itself is DYNAMIC LDS, asked for by launch_layers only where a block can qualify (a.rowtab): a table of short blocks
+    // — configs[1], configs[4] — launches with the 2 KB of records it always had
+    extern __shared__ __attribute__((aligned(16))) RowTabSlot tab[];
+    __shared__ RowTabHdr hdr;
+    const WorkItem wi = work_item<ITERS, ROWTAB>(a);
+    double xf = wi.xf[wi.f];
+    RTUS_STAMP(0);
+    const bool first_wave = threadIdx.x < 64;
+    const int el = min(wi.e0 + (int)(threadIdx.x & 63), a.n_e - 1);   // the first wave: its lane's element
+    double zfv = 0.0;
+    if (wi.try_tab) zfv = rowtab_ranges<PERM>(a, wi, xf, el, rec, hdr);
+    else if (first_wave) solver_records<TAUP, PERM>(a, wi, el, rec);
+    __syncthreads();
+    RTUS_STAMP(1);
+    const RowDest<PERM> dest = row_dest<PERM>(a, wi, rec);
+    if (wi.try_tab) {
+        if (rowtab_eligible(hdr)) {
+            const RowTabLattice lat = rowtab_lattice(hdr, zfv);
+            if (lat.fits && rowtab_build<NL>(a, wi, lat, tab, hdr, xf)) {
+                rowtab_serve<PERM>(wi, lat, tab, dest, xf);
+                RTUS_STAMP(5);
+                return;
+            }
+        }
+        // The workgroup tried the table and does not serve from it (ineligible, too wide a span, a rejected build): the solver needs
+        // the full records now.  Every wave arrives here together (the decisions above are the workgroup's), none has read a record.
+        if (first_wave) solver_records<TAUP, PERM>(a, wi, el, rec);
+        __syncthreads();
+    }
+    solve_block<NL, ITERS, TAUP, PERM>(a, wi, xf, dest);
 }
 
 // Order of the aperture.  The predictor extrapolates from the four previous elements of a workgroup's block, which only works when
@@ -888,9 +1000,17 @@ int rtus_rows_per_block(long long n_rows_total, int n_f, int n_batch, int elem_b
     return eb;
 }
 
-#ifndef RTUS_PLANAR_SHAPE_LDS
-#define RTUS_PLANAR_SHAPE_LDS 0u   // experiment builds: unused LDS per workgroup = fewer workgroups per CU (see launch_layers)
-#endif
+// One launch of the instantiation that (iters, perm, taup) name, for a medium of NL layers
+template <int NL>
+static void launch_nl(bool iters, bool perm, bool taup, dim3 grid, dim3 block, unsigned lds, hipStream_t s, const LayerArgs& a)
+{
+    if (iters) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, true, false, false>), grid, block, lds, s, a);
+    else if (perm && taup) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, true, true>), grid, block, lds, s, a);
+    else if (perm) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, false, true>), grid, block, lds, s, a);
+    else if (taup) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, true, false>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, false, false>), grid, block, lds, s, a);
+}
+
 static hipError_t launch_layers(const double* z_if, const double* c, int n_if, const double* xe, const double* ze, int n_e,
                                 const double* xf, const double* zf, int n_f, double* tt, uint8_t* iters, int n_batch,
                                 long long e_stride, long long f_stride, long long t_stride, int row0, long long n_rows_total,
@@ -909,37 +1029,28 @@ static hipError_t launch_layers(const double* z_if, const double* c, int n_if, c
     a.eb = eb;
     a.n_rows = n_rows_total;
     a.rowtab = (flags & RTUS_TT_TAUP_TAIL) != 0 && !iters && eb >= RTUS_ROWTAB_MIN_ROWS;
-    a.gx = (n_f + RTUS_BLOCK - 1) / RTUS_BLOCK; a.gy = (row0 + n_e - 1) / eb - row0 / eb + 1;
-    const long long items = (long long)a.gx * a.gy * n_batch;
-    if (items > 0x7fffffffLL) return hipErrorInvalidValue;
-    a.n_items = (int)items;
-#ifdef RTUS_EXP_PERSIST                                      // experiment builds only: see the kernel
-    long long cap = items;
-    if (n_if + 1 <= 3 && !iters) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cap = 8LL * n;
-    }
-    const dim3 grid((unsigned)(items < cap ? items : cap)), block(RTUS_BLOCK);
-#else
-    // (row-table launches: x and y flattened into grid.x, y fastest: see the kernel; gx gy <= items < 2^31, within grid.x's limit)
-    const dim3 grid(a.rowtab ? a.gx * a.gy : a.gx, a.rowtab ? 1 : a.gy, n_batch), block(RTUS_BLOCK);
-#endif
+    // work items: gx columns of 256 targets x gy blocks of rows (x n_batch problems), one workgroup each
+    const int gx = (n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    a.gy = (row0 + n_e - 1) / eb - row0 / eb + 1;
+    if ((long long)gx * a.gy * n_batch > 0x7fffffffLL) return hipErrorInvalidValue;
+    // (row-table launches: x and y flattened into grid.x, y fastest: see work_item; gx gy < 2^31, within grid.x's limit)
+    const dim3 grid(a.rowtab ? gx * a.gy : gx, a.rowtab ? 1 : a.gy, n_batch), block(RTUS_BLOCK);
     const bool taup = (flags & RTUS_TT_TAUP_TAIL) != 0;
     // Workgroups per CU: what the registers allow (8 for the 64-VGPR kernels).  Capping a launch of two rounds or more BELOW that with
-    // LDS the kernel never touches (-DRTUS_PLANAR_SHAPE_LDS=bytes, experiment builds) was worth -3.5 % at six per CU while the kernel
-    // still parked set-up values in scratch and loaded extra header words (start-up that nothing overlapped when every wave of a SIMD
-    // began at once); on the kernel as it is now six per CU is 0.5 - 1.6 % SLOWER than eight and seven is even: no shaping.
-    const unsigned lds = ((n_if + 1 <= 3 && !iters && items >= 4096) ? RTUS_PLANAR_SHAPE_LDS : 0u) +
-                         (a.rowtab ? (unsigned)(RTUS_ROWTAB_SLOTS * sizeof(RowTabSlot)) : 0u);
+    // LDS the kernel never touches was worth -3.5 % at six per CU while the kernel still parked set-up values in scratch and loaded
+    // extra header words (start-up that nothing overlapped when every wave of a SIMD began at once); on the kernel as it is now six
+    // per CU is 0.5 - 1.6 % SLOWER than eight and seven is even: no shaping.
+    const unsigned lds = a.rowtab ? (unsigned)(RTUS_ROWTAB_SLOTS * sizeof(RowTabSlot)) : 0u;
     switch (n_if + 1) {
-#define RTUS_CASE(NL) case NL: if (iters) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, true, false, false>), grid, block, lds, s, a); \
-                               else if (row_of && taup) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, true, true>), grid, block, lds, s, a); \
-                               else if (row_of) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, false, true>), grid, block, lds, s, a); \
-                               else if (taup) hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, true, false>), grid, block, lds, s, a); \
-                               else hipLaunchKernelGGL((rtus_tt_layers_kernel<NL, false, false, false>), grid, block, lds, s, a); break;
-        RTUS_CASE(1) RTUS_CASE(2) RTUS_CASE(3) RTUS_CASE(4) RTUS_CASE(5) RTUS_CASE(6) RTUS_CASE(7) RTUS_CASE(8)
-        RTUS_CASE(9)
-#undef RTUS_CASE
+        case 1: launch_nl<1>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 2: launch_nl<2>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 3: launch_nl<3>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 4: launch_nl<4>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 5: launch_nl<5>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 6: launch_nl<6>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 7: launch_nl<7>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 8: launch_nl<8>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
+        case 9: launch_nl<9>(iters != nullptr, row_of != nullptr, taup, grid, block, lds, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -973,17 +1084,22 @@ hipError_t rtus_launch_tt_layers_batch(const double* z_if, const double* c, int 
 // The whole table with the aperture in ANY order: sorted copies of the coordinates + each element's row in `ws`
 // (rtus_layers_sort_ws_bytes), then the PERM kernel.  `presorted_row_of`: the caller (the host-buffer twin) has sorted on the
 // host and uploaded sorted xe / ze and the row indices itself — no rank launch.
-size_t rtus_layers_sort_ws_bytes(int n_e) { return ((size_t)n_e * 8 + 255) / 256 * 256 * 2 + ((size_t)n_e * 4 + 255) / 256 * 256; }
+struct SortWs { double* xs; double* zs; int* row_of; };
+static size_t sort_ws(void* ws, int n_e, SortWs* w)         // the layout of `ws`, carved in ONE place: three 256-byte-aligned segments; returns its size
+{
+    const size_t seg = rtus_al256((size_t)n_e * 8);
+    if (w) { w->xs = (double*)ws; w->zs = (double*)((char*)ws + seg); w->row_of = (int*)((char*)ws + 2 * seg); }
+    return 2 * seg + rtus_al256((size_t)n_e * 4);
+}
+size_t rtus_layers_sort_ws_bytes(int n_e) { return sort_ws(nullptr, n_e, nullptr); }
 hipError_t rtus_launch_tt_layers_sorted(const double* z_if, const double* c, int n_if, const double* xe, const double* ze, int n_e,
                                         const double* xf, const double* zf, int n_f, double* tt, void* ws, const int* presorted_row_of,
                                         unsigned flags, hipStream_t s)
 {
     if (presorted_row_of)
         return launch_layers(z_if, c, n_if, xe, ze, n_e, xf, zf, n_f, tt, nullptr, 1, 0, 0, 0, 0, n_e, flags, presorted_row_of, s);
-    const size_t seg = ((size_t)n_e * 8 + 255) / 256 * 256;
-    double* xs = (double*)ws;
-    double* zs = (double*)((char*)ws + seg);
-    int* row_of = (int*)((char*)ws + 2 * seg);
-    hipLaunchKernelGGL(rtus_rank_kernel, dim3((n_e + 3) / 4), dim3(256), 0, s, xe, ze, n_e, xs, zs, row_of);
-    return launch_layers(z_if, c, n_if, xs, zs, n_e, xf, zf, n_f, tt, nullptr, 1, 0, 0, 0, 0, n_e, flags, row_of, s);
+    SortWs w;
+    sort_ws(ws, n_e, &w);
+    hipLaunchKernelGGL(rtus_rank_kernel, dim3((n_e + 3) / 4), dim3(256), 0, s, xe, ze, n_e, w.xs, w.zs, w.row_of);
+    return launch_layers(z_if, c, n_if, w.xs, w.zs, n_e, xf, zf, n_f, tt, nullptr, 1, 0, 0, 0, 0, n_e, flags, w.row_of, s);
 }

@@ -1,6 +1,6 @@
 """A/B of two builds of librtus.so on the planar Fermat workloads, interleaved rounds in ONE process
 (cdna_hip_programming.md rule 24): python scripts/ab_planar.py scripts/librtus_r01.so ray-tracing-ultrasound_amd/librtus.so
-Prints per workload: median / min ms per launch for each build, the ratio, and the max |dt| between the two results and
+Prints per workload: median / min / max per launch over the rounds for each build, the ratio, and the max |dt| between the two results and
 against the long-double oracle on a seeded sample."""
 import ctypes as C
 import os
@@ -75,9 +75,10 @@ def main():
             got = o[torch.as_tensor(re, device=dev)][:, torch.as_tensor(cf, device=dev)].cpu().numpy()
             errs.append(float(np.nanmax(np.abs(got - ref))))
         dab = float(torch.max(torch.abs(outs[0] - outs[1])).item()) if len(outs) == 2 else 0.0
-        print(f"{wl}: " + "  ".join(f"[{os.path.basename(p)}] median {m*1e3:8.2f} us  min {k*1e3:8.2f} us  {n/m/1e3:9.0f} Mrays/s  "
-                                    f"hbm {n*8/(m*1e-3)/8e12:.4f}  max|dt| vs oracle {e:.2e}"
-                                    for p, m, k, e in zip(paths, med, mn, errs)) +
+        mx = [float(np.max(t)) for t in times]                 # (min .. max over the rounds: the only noise figure an A/B has)
+        print(f"{wl}: " + "  ".join(f"[{os.path.basename(p)}] median {m*1e3:8.2f} us  min {k*1e3:8.2f} us  max {x*1e3:8.2f} us  "
+                                    f"{n/m/1e3:9.0f} Mrays/s  hbm {n*8/(m*1e-3)/8e12:.4f}  max|dt| vs oracle {e:.2e}"
+                                    for p, m, k, x, e in zip(paths, med, mn, mx, errs)) +
               (f"  | B/A time {med[1]/med[0]:.3f}  max|A-B| {dab:.2e} s" if len(libs) == 2 else ""), flush=True)
 
 

@@ -1,9 +1,16 @@
-"""sha256 of every output array of the bracket-and-refine tables (rtus_tt_surface, rtus_pw_surface, rtus_tt_surface_skip, rtus_tt_pipe)
-at the shapes that scripts/surface_throughput.py, pwi_throughput.py, skip_throughput.py and pipe_throughput.py time at their
-defaults, and of rtus_tt_pipe on the thin-wall geometries and the alpha = +-1.05 rad window of tests/test_gpu_pipe_branches.py (the
-general-trigonometry instantiation).  The bytes are hashed, NaNs included.  Run once per library and compare the lines:
+"""sha256 of every output array of the project's travel-time tables on fixed inputs, one line per array; the bytes are hashed,
+NaNs included.  Run once per library and compare the lines:
     python scripts/table_digests.py > this.txt;  RTUS_LIB=variants/librtus_prev.so python scripts/table_digests.py > prev.txt
-A change that only moves code gives the same digests; one differing line means arithmetic or evaluation order changed."""
+A change that only moves code gives the same digests; one differing line means arithmetic or evaluation order changed.
+
+Sections, named on the command line (none named: `bracket`, what this script has always printed):
+  bracket  the bracket-and-refine tables (rtus_tt_surface, rtus_pw_surface, rtus_tt_surface_skip, rtus_tt_pipe) at the shapes that
+           scripts/surface_throughput.py, pwi_throughput.py, skip_throughput.py and pipe_throughput.py time at their defaults, and
+           rtus_tt_pipe on the thin-wall geometries and the alpha = +-1.05 rad window of tests/test_gpu_pipe_branches.py (the
+           general-trigonometry instantiation)
+  planar   the planar Fermat kernel (rtus_tt_layers and its sorted, batched and row-shard entries) on every path it has, at the
+           shapes of tests/test_gpu_planar_rowtable*.py: 150 elements x 65,536 targets on a 256-column grid in the configs[2] medium
+           — both tiers, the row table served, over its capacity and ineligible — and 16 x 4,096 at one, two, five and nine layers"""
 import hashlib
 import os
 import sys
@@ -26,47 +33,109 @@ def show(case, **arrays):
               flush=True)
 
 
-# the curved-interface tables: 256-sample profile, 256^2 focal points
-x0, dx = -0.032, 0.064 / 255
-zs = 0.02 + 0.0015 * torch.sin(2 * torch.pi * (x0 + dx * torch.arange(256, **f64)) / 0.010)
-gx, gz = torch.meshgrid(torch.linspace(-0.03, 0.03, 256, **f64), torch.linspace(0.025, 0.065, 256, **f64), indexing="xy")
-xf, zf = gx.reshape(-1).contiguous(), gz.reshape(-1).contiguous()
-xe, ze = torch.linspace(-0.0192, 0.0192, 128, **f64), torch.zeros(128, **f64)
-new = lambda rows: torch.empty((rows, xf.numel()), **f64)      # noqa: E731
-tt, xent, xback = new(128), new(128), new(128)
-dev.tt_surface_dev(x0, dx, zs, 1480.0, 5900.0, xe, ze, xf, zf, out=tt, x_entry=xent)
-show("tt_surface", tt=tt, x_entry=xent)
-for mode, (cd, cu) in {"LL": (5900.0, 5900.0), "LT": (5900.0, 3230.0), "TL": (3230.0, 5900.0), "TT": (3230.0, 3230.0)}.items():
-    dev.tt_surface_skip_dev(x0, dx, zs, 1480.0, cd, cu, 0.07, xe, ze, xf, zf, out=tt, x_entry=xent, x_back=xback)
-    show("tt_surface_skip_" + mode, tt=tt, x_entry=xent, x_back=xback)
-xa = (np.arange(64) - 31.5) * 0.6e-3
-ang = torch.as_tensor(np.deg2rad(np.linspace(-15, 15, 31)), **f64)
-tt, xent = new(31), new(31)
-dev.pw_surface_dev(x0, dx, zs, 1480.0, 5900.0, ang, xa.min(), xa.max(), 0.0, xf, zf, out=tt, x_entry=xent)
-show("pw_surface", tt=tt, x_entry=xent)
-
-# the pipe-wall table at the production shape
-p = rtus.Params(r_outer=0.037, pipe_offset=0.0038)
-za = np.full(64, p.d)
-wx, wz = rtus.pipe_wall_grid(0.029 + 3e-5, 0.037 - 3e-5, 128, 256, -np.pi / 6, np.pi / 6, params=p)
-t = lambda v: torch.as_tensor(np.ascontiguousarray(v), **f64)      # noqa: E731
-out = [torch.empty((64, wx.size), **f64) for _ in range(3)]
-dev.tt_pipe_dev(t(xa), t(za), t(wx), t(wz), out=out[0], alpha_out=out[1], beta_out=out[2], r_inner=0.029, params=p)
-show("tt_pipe", tt=out[0], alpha=out[1], beta=out[2])
+def t(v):
+    return torch.as_tensor(np.ascontiguousarray(v), **f64)
 
 
-# tests/test_gpu_pipe_branches.py's sets: thin walls and off-axis pipes, then the window past +-1 rad
-def wall_grid(off, ri, ro, n_r, n_th, th_lo=-1.5, th_hi=1.5, margin=1e-4):
-    rr, th = np.meshgrid(np.linspace(ri + margin, ro - margin, n_r), np.linspace(th_lo, th_hi, n_th), indexing="ij")
-    return (off + rr * np.sin(th)).ravel(), (rr * np.cos(th)).ravel()
+def bracket():
+    # the curved-interface tables: 256-sample profile, 256^2 focal points
+    x0, dx = -0.032, 0.064 / 255
+    zs = 0.02 + 0.0015 * torch.sin(2 * torch.pi * (x0 + dx * torch.arange(256, **f64)) / 0.010)
+    gx, gz = torch.meshgrid(torch.linspace(-0.03, 0.03, 256, **f64), torch.linspace(0.025, 0.065, 256, **f64), indexing="xy")
+    xf, zf = gx.reshape(-1).contiguous(), gz.reshape(-1).contiguous()
+    xe, ze = torch.linspace(-0.0192, 0.0192, 128, **f64), torch.zeros(128, **f64)
+    new = lambda rows: torch.empty((rows, xf.numel()), **f64)      # noqa: E731
+    tt, xent, xback = new(128), new(128), new(128)
+    dev.tt_surface_dev(x0, dx, zs, 1480.0, 5900.0, xe, ze, xf, zf, out=tt, x_entry=xent)
+    show("tt_surface", tt=tt, x_entry=xent)
+    for mode, (cd, cu) in {"LL": (5900.0, 5900.0), "LT": (5900.0, 3230.0), "TL": (3230.0, 5900.0), "TT": (3230.0, 3230.0)}.items():
+        dev.tt_surface_skip_dev(x0, dx, zs, 1480.0, cd, cu, 0.07, xe, ze, xf, zf, out=tt, x_entry=xent, x_back=xback)
+        show("tt_surface_skip_" + mode, tt=tt, x_entry=xent, x_back=xback)
+    xa = (np.arange(64) - 31.5) * 0.6e-3
+    ang = torch.as_tensor(np.deg2rad(np.linspace(-15, 15, 31)), **f64)
+    tt, xent = new(31), new(31)
+    dev.pw_surface_dev(x0, dx, zs, 1480.0, 5900.0, ang, xa.min(), xa.max(), 0.0, xf, zf, out=tt, x_entry=xent)
+    show("pw_surface", tt=tt, x_entry=xent)
+
+    # the pipe-wall table at the production shape
+    p = rtus.Params(r_outer=0.037, pipe_offset=0.0038)
+    za = np.full(64, p.d)
+    wx, wz = rtus.pipe_wall_grid(0.029 + 3e-5, 0.037 - 3e-5, 128, 256, -np.pi / 6, np.pi / 6, params=p)
+    out = [torch.empty((64, wx.size), **f64) for _ in range(3)]
+    dev.tt_pipe_dev(t(xa), t(za), t(wx), t(wz), out=out[0], alpha_out=out[1], beta_out=out[2], r_inner=0.029, params=p)
+    show("tt_pipe", tt=out[0], alpha=out[1], beta=out[2])
+
+    # tests/test_gpu_pipe_branches.py's sets: thin walls and off-axis pipes, then the window past +-1 rad
+    def wall_grid(off, ri, ro, n_r, n_th, th_lo=-1.5, th_hi=1.5, margin=1e-4):
+        rr, th = np.meshgrid(np.linspace(ri + margin, ro - margin, n_r), np.linspace(th_lo, th_hi, n_th), indexing="ij")
+        return (off + rr * np.sin(th)).ravel(), (rr * np.cos(th)).ravel()
+
+    xe8, ze8 = xa[::9], za[::9]
+    for name, (ro, off, ri, n_th) in {"thin10": (0.01, 0.0038, 0.0095, 241), "wall10": (0.01, 0.0038, 0.008, 61),
+                                      "off37p": (0.037, 0.01, 0.0296, 61), "off37m": (0.037, -0.01, 0.0296, 61)}.items():
+        wx, wz = wall_grid(off, ri, ro, 6, n_th)
+        tt, al, be = rtus.travel_time_pipe(xe8, ze8, wx, wz, r_inner=ri, params=rtus.Params(r_outer=ro, pipe_offset=off), return_path=True)
+        show("tt_pipe_" + name, tt=tt, alpha=al, beta=be)
+    wx, wz = wall_grid(0.0038, 0.029, 0.037, 5, 41, -1.2, 1.2)
+    tt, al, be = rtus.travel_time_pipe(xe8, ze8, wx, wz, r_inner=0.029, params=p, alpha_lo=-1.05, alpha_hi=1.05, return_path=True)
+    show("tt_pipe_wide", tt=tt, alpha=al, beta=be)
 
 
-xe8, ze8 = xa[::9], za[::9]
-for name, (ro, off, ri, n_th) in {"thin10": (0.01, 0.0038, 0.0095, 241), "wall10": (0.01, 0.0038, 0.008, 61),
-                                  "off37p": (0.037, 0.01, 0.0296, 61), "off37m": (0.037, -0.01, 0.0296, 61)}.items():
-    wx, wz = wall_grid(off, ri, ro, 6, n_th)
-    tt, al, be = rtus.travel_time_pipe(xe8, ze8, wx, wz, r_inner=ri, params=rtus.Params(r_outer=ro, pipe_offset=off), return_path=True)
-    show("tt_pipe_" + name, tt=tt, alpha=al, beta=be)
-wx, wz = wall_grid(0.0038, 0.029, 0.037, 5, 41, -1.2, 1.2)
-tt, al, be = rtus.travel_time_pipe(xe8, ze8, wx, wz, r_inner=0.029, params=p, alpha_lo=-1.05, alpha_hi=1.05, return_path=True)
-show("tt_pipe_wide", tt=tt, alpha=al, beta=be)
+def planar():
+    n_e = 150
+    z_if, c = [0.010, 0.025], [2330.0, 1483.0, 5900.0]            # the configs[2] medium
+
+    def grid(zr, width=256, n_rows=256):
+        x = (np.arange(width) - (width - 1) / 2.0) * (0.04 / (width - 1))
+        xs, zs = np.meshgrid(x, np.linspace(zr[0], zr[1], n_rows))
+        return t(xs.ravel()), t(zs.ravel())
+
+    def aperture(pitch, n=n_e):
+        return (np.arange(n) - (n - 1) / 2.0) * pitch, np.zeros(n)
+
+    tiers = (("default", False), ("taup", True))
+    xf, zf = grid((0.026, 0.066))
+    xe, ze = aperture(0.3e-3)
+    eb = dev.rows_per_block(n_e, xf.numel())
+    assert eb >= 32 and 37 % eb != 0, eb                          # blocks long enough for the row table; 37 cuts inside one
+    show("solver_four_history_runs", tt=dev.tt_layers_dev(z_if, c, t(xe), t(ze), xf, zf))
+    show("rowtab_served", tt=dev.tt_layers_dev(z_if, c, t(xe), t(ze), xf, zf, taup=True))
+    # 352 intervals in block 2 on every grid line of these depths (tests/test_gpu_planar_rowtable_startup.py): one over the capacity
+    xw, zw = aperture(3.210e-3)
+    show("rowtab_over_capacity", tt=dev.tt_layers_dev(z_if, c, t(xw), t(zw), *grid((0.026, 0.044)), taup=True))
+    rng = np.random.default_rng(11)
+    xr, zr = t(rng.uniform(-0.02, 0.02, xf.numel())), t(rng.uniform(0.026, 0.066, xf.numel()))
+    show("rowtab_ineligible_random_targets", tt=dev.tt_layers_dev(z_if, c, t(xe), t(ze), xr, zr, taup=True))
+    it = torch.zeros((n_e, xf.numel()), dtype=torch.uint8, device="cuda")
+    show("with_iters", tt=dev.tt_layers_dev(z_if, c, t(xe), t(ze), xf, zf, iters=it), iters=it)
+    perm = np.random.default_rng(5).permutation(n_e)
+    xe2 = np.stack([xe, xe + 0.0021])
+    for name, taup in tiers:
+        show("sorted_shuffled_" + name, tt=dev.tt_layers_sorted_dev(z_if, c, t(xe[perm]), t(ze[perm]), xf, zf, taup=taup))
+        show("batch_of_two_" + name, tt=dev.tt_layers_batch_dev(z_if, c, t(xe2), t(np.zeros_like(xe2)), xf, zf, taup=taup))
+        show("rows_from_37_" + name, tt=dev.tt_layers_dev(z_if, c, t(xe[37:]), t(ze[37:]), xf, zf, row0=37, n_rows_total=n_e, taup=taup))
+    # an aperture that is not a line: two depth changes inside block 1, a duplicated position, one position NaN
+    xi, zi = aperture(0.3e-3)
+    zi[40:50] = 0.0005
+    xi[70] = xi[69]
+    xi[100] = np.nan
+    for name, taup in tiers:
+        show("irregular_aperture_" + name, tt=dev.tt_layers_dev(z_if, c, t(xi), t(zi), xf, zf, taup=taup))
+    # every layer count has its own instantiation: 16 x 4,096, interfaces every 4 mm, the targets across all of them
+    xs, zs = aperture(0.6e-3, 16)
+    xg, zg = grid((0.001, 0.045), 64, 64)
+    for n_l in (1, 2, 5, 9):
+        zl, cl = 0.004 * np.arange(1, n_l), [(1483.0, 5900.0, 2330.0, 3230.0)[i % 4] for i in range(n_l)]
+        for name, taup in tiers:
+            show(f"layers_{n_l}_{name}", tt=dev.tt_layers_dev(zl, cl, t(xs), t(zs), xg, zg, taup=taup))
+
+
+SECTIONS = {"bracket": bracket, "planar": planar}
+
+if __name__ == "__main__":
+    names = sys.argv[1:] or ["bracket"]
+    for name in names:
+        if name not in SECTIONS:
+            sys.exit(f"unknown section {name!r}: one of {', '.join(SECTIONS)}")
+    for name in names:
+        SECTIONS[name]()
