@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 120 /* 0.1.19: rtus_solve_path (which refinement a solve call gets) */
+#define RTUS_VERSION 121 /* 0.1.20: rtus_tfm_frames, rtus_tfm_analytic_frames (TFM over a stack of frames) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -715,6 +715,63 @@ int rtus_tfm_iq_hmc_dev(const float *d_a, int n_e, int n_t, double fs, double t0
 int rtus_tfm_iq_hmc(const float *a, int n_e, int n_t, double fs, double t0, double f_demod,
                     const double *tt_tx, const double *tt_rx, int n_f,
                     float *image, float *cf, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_frames, rtus_tfm_analytic_frames: TFM over a STACK of frames — an encoded scan along a pipe or a weld is hundreds to
+ * thousands of captures of one shape, all imaged through the same travel-time tables on the same grid — in one call (a few
+ * launches on the stream).  NOT IN THE REFERENCE; held bit for bit to the single-frame entries and to tests/das_exact_numpy.py.
+ *   A stack is n_frames captures, frame-major: RF fmc [n_frames][n_tx][n_rx][n_t] float32; analytic a [n_frames][n_tx][n_rx][n_t][2].
+ *   fs, t0, f_demod, tt_tx [n_tx][n_f], tt_rx [n_rx][n_f] (the two may be one table): as in rtus_tfm / rtus_tfm_analytic / rtus_tfm_iq,
+ *           shared by every frame.
+ *   images  [n_frames][n_f] float32 (RF) or [n_frames][n_f][2] (analytic); cf [n_frames][n_f] float32, nullable (analytic only).
+ *   Frame k's output is, BIT FOR BIT, what the single-frame entry returns on frame k alone with the same tables, fs, t0 and
+ *           f_demod: rtus_tfm (RF), rtus_tfm_analytic (f_demod == 0: the linear step itself, not rtus_tfm_iq's at a zero carrier),
+ *           rtus_tfm_iq (f_demod > 0) — the same leg rule, edge rules, no-path rule and order of the sums.
+ *   Determinism: the bits of a frame do not depend on n_frames, on its partner in a pair (below), on how a caller cuts the stack
+ *           into calls, or on whether cf is asked for; the bits of a focal point depend only on its own columns of the tables.
+ *   The PACKED layout of an RF stack: packed [n_pairs][n_tx][n_rx][n_t][2] float32, n_pairs = ceil(n_frames / 2); plane 0 of pair p
+ *           is frame 2 p, plane 1 is frame 2 p + 1; plane 1 of the last pair of an odd stack is +0.0 everywhere.  rtus_tfm_analytic
+ *           promises that S.re is rtus_tfm on the real parts and S.im rtus_tfm on the imaginary parts, so two RF frames stored
+ *           sample-interleaved are imaged by ONE 16-byte gather per (pair of elements, focal point) where two launches of rtus_tfm
+ *           issue two 8-byte ones — and the vector-memory address path, not the bytes, paces the gather.
+ *   rtus_fmc_pack_frames_floats: the floats of the packed stack, 2 n_pairs n_tx n_rx n_t; 0 when a size is not positive or the
+ *           count does not fit 2^62 bytes.
+ *   rtus_fmc_pack_frames_dev: frame-major stack -> packed (writes the zero plane of an odd stack).  n_t >= 1.  d_packed must be
+ *           8-byte aligned and must not overlap d_fmc (-1).  A streaming copy: 4 n_frames n_tx n_rx n_t bytes read, 8 n_pairs ...
+ *           written.  A streaming caller may pack each arriving pair by itself (n_frames = 2 at the pair's place), or have its
+ *           acquisition write the layout directly.
+ *   rtus_tfm_frames_dev takes the PACKED stack (n_frames says whether the last pair has one frame: its images row 2 p + 1 does not
+ *           exist and is not written).  The host twin rtus_tfm_frames takes the FRAME-MAJOR stack, uploads it as it is and packs on
+ *           the device in the arena.
+ *   Limits: a null pointer (cf apart), a non-positive size, n_t < 2, fs not positive and finite, t0 not finite, f_demod outside
+ *           [0, fs / 2): -1.  n_t > 2^26 (rtus_tfm_analytic's limit: 16-byte positions, 32-bit byte offsets), or more than
+ *           2^31 - 1 workgroups — n_pairs ceil(n_f / 256) for RF, n_frames ceil(n_f / 256) for analytic: -5.  All before any HIP
+ *           call.  The _dev entries allocate nothing and do not synchronise (capturable).
+ * Kernels, the workgroup order and the figures: DESIGN.md §4 "TFM over a stack of frames" (profiles/tfm_frames_kernel.txt).
+ *           A call is one launch per about 2304 workgroups (nine images of 256^2 focal points, one of 1024^2): a launch that grows with
+ *           the stack was measured 1.2x to 1.7x slower at 32 frames.
+ * Measured on MI355X, 64 elements x 2048 samples, one table, medians of 50 alternating repetitions, time per frame; the estimate
+ * was 0.73x to 0.5x of a loop over rtus_tfm_dev:
+ *   256^2 focal points:  loop of rtus_tfm_dev 226 us; pack + rtus_tfm_frames_dev 146 us at 8 frames (0.65x), 162 us at 9 (0.72x: the
+ *           fifth pair is half empty), 157 us at 32 (0.69x); on an already packed stack 135 / 149 / 142 us (0.60x / 0.66x / 0.63x);
+ *           the pack alone 12 us per frame.
+ *   1024^2: loop 1.92 ms; pack + stack 1.00 ms at 8 frames (0.52x), 1.11 ms at 9 (0.58x), 0.98 ms at 32 (0.51x); packed 0.97 /
+ *           1.08 / 0.97 ms (0.51x / 0.56x / 0.50x).
+ *   rtus_tfm_analytic_frames_dev against a loop of rtus_tfm_analytic_dev: 0.97x / 0.95x / 0.99x at 256^2 (280 against 289 us per
+ *           frame at 8 frames), 1.00x at 1024^2 (1.94 ms): the same gathers; what it saves is the calls.
+ * ---------------------------------------------------------------------------------------- */
+size_t rtus_fmc_pack_frames_floats(int n_frames, int n_tx, int n_rx, int n_t);
+int rtus_fmc_pack_frames_dev(const float *d_fmc, int n_frames, int n_tx, int n_rx, int n_t, float *d_packed, void *stream);
+int rtus_tfm_frames_dev(const float *d_packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                        const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_images, void *stream);
+int rtus_tfm_frames(const float *fmc, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                    const double *tt_tx, const double *tt_rx, int n_f, float *images, int device);
+int rtus_tfm_analytic_frames_dev(const float *d_a, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                                 const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                                 float *d_images, float *d_cf, void *stream);
+int rtus_tfm_analytic_frames(const float *a, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                             const double *tt_tx, const double *tt_rx, int n_f,
+                             float *images, float *cf, int device);
 
 /* ------------------------------------------------------------------------------------------
  * Plane-wave imaging (PWI): a few dozen plane waves, each fired by the whole aperture with a linear delay law and received on every

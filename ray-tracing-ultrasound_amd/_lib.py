@@ -144,6 +144,13 @@ PROTOTYPES = (
     ("rtus_tfm_iq", i, [vp, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, i], 119),
     ("rtus_tfm_iq_hmc_dev", i, [vp, i, i, dd, dd, dd, vp, vp, i, vp, vp, vp], 119),
     ("rtus_tfm_iq_hmc", i, [vp, i, i, dd, dd, dd, vp, vp, i, vp, vp, i], 119),
+    # a stack of frames
+    ("rtus_fmc_pack_frames_floats", sz, [i, i, i, i], 121),
+    ("rtus_fmc_pack_frames_dev", i, [vp, i, i, i, i, vp, vp], 121),
+    ("rtus_tfm_frames_dev", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, vp], 121),
+    ("rtus_tfm_frames", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, i], 121),
+    ("rtus_tfm_analytic_frames_dev", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, vp], 121),
+    ("rtus_tfm_analytic_frames", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, i], 121),
     # plane-wave imaging
     ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
     ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),

@@ -689,6 +689,89 @@ def tfm_iq(analytic, fs, f_demod, tt_tx, tt_rx=None, *, t0=0.0, coherence=False,
     return (img, cf) if mode else img
 
 
+# ---------------------------------------------------------------------------------------------- a stack of frames
+def frames_pack(stack):
+    """A frame-major RF stack [n_frames, n_tx, n_rx, n_t] -> its packed layout float32 [n_pairs, n_tx, n_rx, n_t, 2],
+    n_pairs = ceil(n_frames / 2): plane 0 of pair p is frame 2 p, plane 1 is frame 2 p + 1; plane 1 of the last pair of an odd stack is
+    +0.0.  The layout rtus_tfm_frames_dev reads (include/rtus.h), restated in NumPy; device.fmc_pack_frames_dev makes it on the GPU."""
+    stack = np.asarray(stack, dtype=np.float32)
+    if stack.ndim != 4 or stack.shape[0] < 1:
+        raise ValueError("the stack must be [n_frames, n_tx, n_rx, n_t] with at least one frame")
+    n_frames = stack.shape[0]
+    packed = np.zeros(((n_frames + 1) // 2,) + stack.shape[1:] + (2,), dtype=np.float32)
+    packed[..., 0] = stack[0::2]
+    packed[:n_frames // 2, ..., 1] = stack[1::2]
+    return packed
+
+
+def frames_unpack(packed, n_frames):
+    """The packed layout [n_pairs, n_tx, n_rx, n_t, 2] -> the frame-major stack float32 [n_frames, n_tx, n_rx, n_t]; ``n_frames`` is
+    2 n_pairs or 2 n_pairs - 1 (the second plane of the last pair is then dropped)."""
+    packed = np.asarray(packed, dtype=np.float32)
+    n_frames = int(n_frames)
+    if packed.ndim != 5 or packed.shape[4] != 2 or packed.shape[0] < 1:
+        raise ValueError("the packed stack must be [n_pairs, n_tx, n_rx, n_t, 2]")
+    if (n_frames + 1) // 2 != packed.shape[0] or n_frames < 1:
+        raise ValueError(f"{packed.shape[0]} pairs hold {2 * packed.shape[0] - 1} or {2 * packed.shape[0]} frames, not {n_frames}")
+    stack = np.empty((n_frames,) + packed.shape[1:4], dtype=np.float32)
+    stack[0::2] = packed[..., 0]
+    stack[1::2] = packed[:n_frames // 2, ..., 1]
+    return stack
+
+
+def _max_frames(max_frames, n_frames):
+    """the ``max_frames=`` keyword of tfm_frames -> frames per call"""
+    if max_frames is None:
+        return n_frames
+    if isinstance(max_frames, (bool, np.bool_)) or int(max_frames) != max_frames or int(max_frames) < 1:
+        raise ValueError("max_frames must be a positive integer or None")
+    return min(int(max_frames), n_frames)
+
+
+def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherence=False, f_demod=None, n_taps=63, max_frames=None,
+               out=None, device=0):
+    """TFM over a stack of frames — an encoded scan: ``stack`` float32 [n_frames, n_tx, n_rx, n_t], every frame imaged through the
+    same tables on the same grid -> float32 [n_frames, n_f]; row k is tfm_image(stack[k], ...) bit for bit.  The frames are paired
+    on the device and each pair imaged by one 16-byte gather per (tx, rx, focal point), all pairs in one call (rtus_tfm_frames).
+    ``envelope=True``: the analytic stack is formed first (fmc_analytic over the n_frames n_tx transmit rows, ``n_taps`` Hilbert
+    taps) and imaged by rtus_tfm_analytic_frames -> complex64 [n_frames, n_f], row k = tfm_analytic(fmc_analytic(stack[k])) bit for
+    bit; with ``coherence=True`` (or "cf") -> (images, cf float32 [n_frames, n_f]).  ``f_demod`` [Hz] as on tfm_views: the frames go
+    through tfm_iq's carrier-aware interpolation instead; it needs ``envelope=True``.  "vcf" / "scf" have no stack form (ValueError).
+    ``max_frames``: the stack is run in chunks of that many frames, which bounds device memory; no bit depends on it.  ``out``:
+    the images' buffer.  Definition: include/rtus.h (rtus_tfm_frames, rtus_tfm_analytic_frames).  Not in the reference."""
+    mode = _iq_coherence(coherence)
+    if mode and not envelope:
+        raise ValueError("the coherence factor needs envelope=True")
+    if f_demod is not None:
+        if not envelope:
+            raise ValueError("f_demod (carrier-aware interpolation) needs envelope=True")
+        f_demod = _f_demod(f_demod, fs)
+    stack = np.ascontiguousarray(stack, dtype=np.float32)
+    if stack.ndim != 4 or stack.shape[0] < 1:
+        raise ValueError("the stack must be [n_frames, n_tx, n_rx, n_t] with at least one frame")
+    n_frames, n_tx, n_rx, n_t = stack.shape
+    tt_tx, tt_rx, n_f = _tfm_tables(stack[0], tt_tx, tt_rx)
+    per = _max_frames(max_frames, n_frames)
+    if envelope and (int(n_taps) != n_taps or not 3 <= int(n_taps) <= 255 or not int(n_taps) & 1):
+        raise ValueError("n_taps must be odd in [3, 255]")
+    imgs = _out(out, (n_frames, n_f), np.complex64 if envelope else np.float32)
+    cf = np.empty((n_frames, n_f), dtype=np.float32) if mode else None
+    L = _lib.lib()
+    for k in range(0, n_frames, per):
+        n = min(per, n_frames - k)
+        if not envelope:
+            st = L.rtus_tfm_frames(_ptr(stack[k:k + n]), n, n_tx, n_rx, n_t, float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f,
+                                   _ptr(imgs[k:k + n]), int(device))
+            _lib.check(st, "rtus_tfm_frames")
+            continue
+        a = fmc_analytic(stack[k:k + n].reshape(n * n_tx, n_rx, n_t), n_taps, device=device)
+        st = L.rtus_tfm_analytic_frames(_ptr(a), n, n_tx, n_rx, n_t, float(fs), float(t0), 0.0 if f_demod is None else f_demod,
+                                        _ptr(tt_tx), _ptr(tt_rx), n_f, _ptr(imgs[k:k + n]), None if cf is None else _ptr(cf[k:k + n]),
+                                        int(device))
+        _lib.check(st, "rtus_tfm_analytic_frames")
+    return (imgs, cf) if mode else imgs
+
+
 # ---------------------------------------------------------------------------------------------- half-matrix capture
 def _hmc_elements(n_pairs):
     """n_e with n_e (n_e + 1) / 2 == n_pairs; ValueError when n_pairs is not a triangular number"""

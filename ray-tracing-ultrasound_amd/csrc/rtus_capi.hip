@@ -88,6 +88,12 @@ hipError_t rtus_launch_tfm_iq(const float* an, int n_tx, int n_rx, int n_t, doub
                               const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
 hipError_t rtus_launch_tfm_iq_hmc(const float* an, int n_e, int n_t, double fs, double t0, double f_demod, const double* tt_tx,
                                   const double* tt_rx, int n_f, float* image, float* cf, hipStream_t s);
+hipError_t rtus_launch_fmc_pack_frames(const float* stack, int n_frames, size_t n, float* packed, hipStream_t s);
+hipError_t rtus_launch_tfm_frames(const float* packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                                  const double* tt_tx, const double* tt_rx, int n_f, float* images, hipStream_t s);
+hipError_t rtus_launch_tfm_analytic_frames(const float* an, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                                           const double* tt_tx, const double* tt_rx, int n_f, float* images, float* cf, hipStream_t s);
+long long rtus_tfm_frames_blocks(int n_slow, int n_f);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s);
@@ -1473,6 +1479,102 @@ int rtus_tfm_iq_hmc(const float* a, int n_e, int n_t, double fs, double t0, doub
     if (!st) st = check_f_demod(f_demod, fs);
     if (st) return st;
     return tfm_hmc_host(a, 2, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, cf, device, f_demod);
+}
+
+// ---------------------------------------------------------------------------- TFM over a stack of frames
+size_t rtus_fmc_pack_frames_floats(int n_frames, int n_tx, int n_rx, int n_t)
+{
+    if (n_frames <= 0 || n_tx <= 0 || n_rx <= 0 || n_t <= 0) return 0;
+    const unsigned __int128 n = (unsigned __int128)((n_frames + 1LL) / 2 * 2) * (unsigned)n_tx * (unsigned)n_rx * (unsigned)n_t;
+    return n <= ((size_t)1 << 60) ? (size_t)n : 0;                    // (4-byte floats: 2^62 bytes)
+}
+
+int rtus_fmc_pack_frames_dev(const float* d_fmc, int n_frames, int n_tx, int n_rx, int n_t, float* d_packed, void* stream)
+{
+    if (!d_fmc || !d_packed || n_frames <= 0 || n_tx <= 0 || n_rx <= 0 || n_t <= 0) return RTUS_ERR_INVALID_ARG;
+    const size_t tot = rtus_fmc_pack_frames_floats(n_frames, n_tx, n_rx, n_t);
+    if (!tot) return RTUS_ERR_UNSUPPORTED;
+    const size_t n = tot / ((n_frames + 1LL) / 2 * 2);                // floats per frame
+    if ((uintptr_t)d_packed & 7) return RTUS_ERR_INVALID_ARG;         // 8-byte stores
+    const uintptr_t i0 = (uintptr_t)d_fmc, i1 = i0 + 4 * n * (size_t)n_frames, o0 = (uintptr_t)d_packed, o1 = o0 + 4 * tot;
+    if (i0 < o1 && o0 < i1) return RTUS_ERR_INVALID_ARG;              // the output must not overlap the input
+    LAUNCH_TRY(rtus_launch_fmc_pack_frames(d_fmc, n_frames, n, d_packed, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+// n_slow: the images (RF: pairs of them) of the launch, each ceil(n_f / 256) workgroups
+static int check_tfm_frames(const void* data, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, const void* tt_tx,
+                            const void* tt_rx, int n_f, const void* images, bool pairs)
+{
+    if (n_frames <= 0) return RTUS_ERR_INVALID_ARG;
+    int st = check_tfm_analytic(data, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, images);   // (16-byte positions in both forms)
+    if (st) return st;
+    if (rtus_tfm_frames_blocks(pairs ? (int)((n_frames + 1LL) / 2) : n_frames, n_f) > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+int rtus_tfm_frames_dev(const float* d_packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, const double* d_tt_tx,
+                        const double* d_tt_rx, int n_f, float* d_images, void* stream)
+{
+    int st = check_tfm_frames(d_packed, n_frames, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, true);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_frames(d_packed, n_frames, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_frames(const float* fmc, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                    const double* tt_rx, int n_f, float* images, int device)
+{
+    int st = check_tfm_frames(fmc, n_frames, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, images, true);
+    if (st) return st;
+    const size_t n = (size_t)n_tx * n_rx * n_t;                       // floats per frame
+    const bool same = tt_tx == tt_rx && n_tx == n_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    float *dstack, *dpacked, *dimg;
+    double *dtx, *drx = nullptr;
+    S.in(dstack, fmc, n * n_frames);
+    S.in(dtx, tt_tx, (size_t)n_tx * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_rx * n_f);
+    S.out(dimg, images, (size_t)n_frames * n_f);
+    S.scratch(dpacked, rtus_fmc_pack_frames_floats(n_frames, n_tx, n_rx, n_t));
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_fmc_pack_frames(dstack, n_frames, n, dpacked, S.a->stream));
+    LAUNCH_TRY(rtus_launch_tfm_frames(dpacked, n_frames, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
+    return S.finish();
+}
+
+int rtus_tfm_analytic_frames_dev(const float* d_a, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                                 const double* d_tt_tx, const double* d_tt_rx, int n_f, float* d_images, float* d_cf, void* stream)
+{
+    int st = check_tfm_frames(d_a, n_frames, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, false);
+    if (!st) st = check_f_demod(f_demod, fs);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_analytic_frames(d_a, n_frames, n_tx, n_rx, n_t, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, d_images, d_cf,
+                                               (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_analytic_frames(const float* a, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
+                             const double* tt_tx, const double* tt_rx, int n_f, float* images, float* cf, int device)
+{
+    int st = check_tfm_frames(a, n_frames, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, images, false);
+    if (!st) st = check_f_demod(f_demod, fs);
+    if (st) return st;
+    const bool same = tt_tx == tt_rx && n_tx == n_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    float *da, *dimg, *dcf;
+    double *dtx, *drx = nullptr;
+    S.in(da, a, (size_t)n_frames * n_tx * n_rx * n_t * 2);
+    S.in(dtx, tt_tx, (size_t)n_tx * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_rx * n_f);
+    S.out(dimg, images, 2 * (size_t)n_frames * n_f);
+    S.out(dcf, cf, (size_t)n_frames * n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tfm_analytic_frames(da, n_frames, n_tx, n_rx, n_t, fs, t0, f_demod, dtx, same ? dtx : drx, n_f, dimg, dcf,
+                                               S.a->stream));
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- phase-coherence TFM: vcf, scf

@@ -419,6 +419,67 @@ def tfm_iq_dev(analytic, fs, f_demod, tt_tx, tt_rx=None, t0=0.0, out=None, cf=No
     return out if cf is None else (out, cf)
 
 
+def fmc_pack_frames_dev(stack, out=None):
+    """A frame-major RF stack on device, float32 [n_frames, n_tx, n_rx, n_t] -> its packed layout float32
+    [n_pairs, n_tx, n_rx, n_t, 2] (rtus_fmc_pack_frames_dev; api.frames_pack's definition: frame 2 p and frame 2 p + 1 interleaved in
+    pair p, the missing partner of an odd stack +0.0).  ``out`` must not overlap ``stack``.  Asynchronous on the current stream
+    (capturable with a pre-allocated output)."""
+    _chk(stack, "stack", torch.float32)
+    if stack.dim() != 4 or stack.shape[0] < 1:
+        raise ValueError("stack must be [n_frames, n_tx, n_rx, n_t] with at least one frame")
+    n_frames, n_tx, n_rx, n_t = stack.shape
+    out = _result(out, ((n_frames + 1) // 2, n_tx, n_rx, n_t, 2), stack, torch.float32)
+    if out.device != stack.device:
+        raise ValueError("out must be on the device of stack")
+    st = _lib.lib().rtus_fmc_pack_frames_dev(_p(stack), n_frames, n_tx, n_rx, n_t, _p(out), _stream(stack))
+    _lib.check(st, "rtus_fmc_pack_frames_dev")
+    return out
+
+
+def tfm_frames_dev(packed, n_frames, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
+    """TFM over a stack of RF frames on device (rtus_tfm_frames_dev; api.tfm_frames' definition): ``packed`` float32
+    [n_pairs, n_tx, n_rx, n_t, 2] as fmc_pack_frames_dev makes it, ``n_frames`` = 2 n_pairs or 2 n_pairs - 1 (the last pair then
+    holds one frame), tt_tx [n_tx, n_f], tt_rx [n_rx, n_f] (default: tt_tx) -> out float32 [n_frames, n_f]; row k has tfm_dev's bits
+    on frame k.  One call, a few launches; asynchronous on the current stream (capturable with a pre-allocated output)."""
+    _chk(packed, "packed", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_frames = int(n_frames)
+    if packed.dim() != 5 or packed.shape[4] != 2 or packed.shape[0] < 1 or (n_frames + 1) // 2 != packed.shape[0] or n_frames < 1:
+        raise ValueError("need packed [n_pairs, n_tx, n_rx, n_t, 2] and n_frames = 2 n_pairs or 2 n_pairs - 1")
+    n_f = _tables(tt_tx, tt_rx, packed[0], analytic=True)
+    out = _result(out, (n_frames, n_f), packed, torch.float32)
+    if not (out.device == packed.device == tt_tx.device == tt_rx.device):
+        raise ValueError("out must be on the device of packed / tt_tx / tt_rx")
+    st = _lib.lib().rtus_tfm_frames_dev(_p(packed), n_frames, packed.shape[1], packed.shape[2], packed.shape[3], float(fs), float(t0),
+                                        _p(tt_tx), _p(tt_rx), n_f, _p(out), _stream(packed))
+    _lib.check(st, "rtus_tfm_frames_dev")
+    return out
+
+
+def tfm_analytic_frames_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, f_demod=0.0, out=None, cf=None):
+    """Envelope TFM over a stack of analytic frames on device (rtus_tfm_analytic_frames_dev): ``analytic`` float32
+    [n_frames, n_tx, n_rx, n_t, 2] (fmc_analytic_dev on the stack viewed as [n_frames n_tx, n_rx, n_t] makes it), tt_tx [n_tx, n_f],
+    tt_rx [n_rx, n_f] (default: tt_tx) -> out float32 [n_frames, n_f, 2]; ``cf``: an optional float32 [n_frames, n_f] tensor that
+    receives the coherence factors (then -> (out, cf)).  ``f_demod`` = 0: row k has tfm_analytic_dev's bits on frame k; > 0 (below
+    fs / 2): tfm_iq_dev's.  One call, a few launches; asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    f_demod = _f_demod(f_demod, fs)
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    if analytic.dim() != 5 or analytic.shape[0] < 1:
+        raise ValueError("analytic must be [n_frames, n_tx, n_rx, n_t, 2] with at least one frame")
+    n_frames = analytic.shape[0]
+    n_f = _tables(tt_tx, tt_rx, analytic[0], analytic=True)
+    out = _result(out, (n_frames, n_f, 2), analytic, torch.float32)
+    _optional(n_frames * n_f, torch.float32, cf=cf)
+    if not (out.device == analytic.device == tt_tx.device == tt_rx.device and (cf is None or cf.device == analytic.device)):
+        raise ValueError("analytic, tt_tx, tt_rx, out and cf must be on one device")
+    st = _lib.lib().rtus_tfm_analytic_frames_dev(_p(analytic), n_frames, analytic.shape[1], analytic.shape[2], analytic.shape[3],
+                                                 float(fs), float(t0), f_demod, _p(tt_tx), _p(tt_rx), n_f, _p(out), _p(cf),
+                                                 _stream(analytic))
+    _lib.check(st, "rtus_tfm_analytic_frames_dev")
+    return out if cf is None else (out, cf)
+
+
 def _hmc_tables(tt_tx, tt_rx, data, analytic):
     """a half-matrix capture [n_pairs, n_t] (analytic: [.., 2]) against tt_tx, tt_rx [n_e, n] both -> (n_e, n)"""
     ok = tt_tx.dim() == 2 and tt_rx.dim() == 2 and tt_tx.shape == tt_rx.shape \

@@ -1,0 +1,125 @@
+"""Throughput of TFM over a stack of frames (rtus_fmc_pack_frames_dev, rtus_tfm_frames_dev, rtus_tfm_analytic_frames_dev) next to the
+loops over the single-frame entries that it replaces, in the same run: 64 x 64 x 2048 samples, n_frames 8 and 9, at 256^2 and 1024^2
+focal points (four shapes).  Routes, RF:  (a) n_frames calls of tfm_dev;  (b) pack + tfm_frames_dev;  (c) tfm_frames_dev on an
+already packed stack.  Envelope:  n_frames calls of tfm_analytic_dev against one tfm_analytic_frames_dev.
+
+Each shape is one child process under its own time limit (the parent never touches the GPU and stops at the first child that fails).
+In the child: CUDA events around each route, outputs preallocated, a warm-up of every route, then `--reps` repetitions with the routes
+timed in turn WITHIN each repetition, so that a drift of the clocks falls on all of them alike.  One JSON line per shape: median and
+[5 %, 95 %] of each route in us, the ratios of the medians, whether the stack calls gave the loops' bits, and the pass bar: a stack
+route is "no slower" when its median is within the run-to-run spread of its loop, i.e. not above the loop's 95th percentile.
+    python scripts/tfm_frames_throughput.py [--reps 50] [--rf-only] > profiles/tfm_frames_kernel.txt"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(8, 256), (9, 256), (8, 1024), (9, 1024)]                          # (n_frames, pixels per side)
+ap = argparse.ArgumentParser()
+ap.add_argument("--elements", type=int, default=64)
+ap.add_argument("--samples", type=int, default=2048)
+ap.add_argument("--reps", type=int, default=50)
+ap.add_argument("--rf-only", action="store_true", help="skip the envelope routes (A/B runs of an RF kernel variant through RTUS_LIB)")
+ap.add_argument("--limit", type=int, default=240, help="seconds a shape's child process may take")
+ap.add_argument("--frames", type=int, nargs="+", help="stack lengths instead of 8 and 9 (a long scan: --frames 32)")
+ap.add_argument("--shape", type=int, nargs=2, metavar=("N_FRAMES", "N"), help="(child) measure this one shape")
+a = ap.parse_args()
+
+if a.shape is None:
+    if a.frames:
+        SHAPES = [(k, n) for n in (256, 1024) for k in a.frames]
+    for n_frames, n in SHAPES:
+        cmd = [sys.executable, os.path.abspath(__file__), "--shape", str(n_frames), str(n), "--elements", str(a.elements),
+               "--samples", str(a.samples), "--reps", str(a.reps)] + (["--rf-only"] if a.rf_only else [])
+        try:
+            r = subprocess.run(cmd, timeout=a.limit)
+        except subprocess.TimeoutExpired:
+            sys.exit(f"{n_frames} frames at {n}^2: not finished after {a.limit} s; nothing more is started")
+        if r.returncode:
+            sys.exit(f"{n_frames} frames at {n}^2: exit status {r.returncode}; nothing more is started")
+    sys.exit(0)
+
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+from importlib import import_module  # noqa: E402
+
+dev = import_module("ray-tracing-ultrasound_amd.device")
+n_frames, n = a.shape
+n_e, n_t = a.elements, a.samples
+fs, c1 = 50e6, 1480.0
+g = torch.Generator(device="cuda").manual_seed(1)
+stack = torch.randn((n_frames, n_e, n_e, n_t), generator=g, dtype=torch.float32, device="cuda")
+xe = ((torch.arange(n_e, dtype=torch.float64, device="cuda") - (n_e - 1) / 2) * 0.25e-3).contiguous()
+ze = torch.zeros(n_e, dtype=torch.float64, device="cuda")
+x0, dx, z_lo, dz = -0.008, 0.016 / (n - 1), 0.004, 0.016 / (n - 1)           # the record holds 30 mm of water: all inside
+px = (x0 + dx * torch.arange(n, dtype=torch.float64, device="cuda"))[:, None].expand(n, n).reshape(-1)
+pz = (z_lo + dz * torch.arange(n, dtype=torch.float64, device="cuda"))[None, :].expand(n, n).reshape(-1)
+tt = (torch.hypot(xe[:, None] - px[None, :], ze[:, None] - pz[None, :]) / c1).contiguous()         # straight-ray table, one for both legs
+n_f = n * n
+new = lambda *shape: torch.empty(shape, dtype=torch.float32, device="cuda")   # noqa: E731
+packed = dev.fmc_pack_frames_dev(stack)
+loop_out, stack_out, packed_out = new(n_frames, n_f), new(n_frames, n_f), new(n_frames, n_f)
+
+
+def rf_loop():
+    for k in range(n_frames):
+        dev.tfm_dev(stack[k], fs, tt, out=loop_out[k])
+
+
+def rf_pack_and_stack():
+    dev.fmc_pack_frames_dev(stack, out=packed)
+    dev.tfm_frames_dev(packed, n_frames, fs, tt, out=stack_out)
+
+
+routes = {"a_loop_of_tfm_dev": rf_loop, "b_pack_and_tfm_frames_dev": rf_pack_and_stack,
+          "c_tfm_frames_dev_packed": lambda: dev.tfm_frames_dev(packed, n_frames, fs, tt, out=packed_out),
+          "pack_alone": lambda: dev.fmc_pack_frames_dev(stack, out=packed)}
+if not a.rf_only:
+    an = dev.fmc_analytic_dev(stack.view(n_frames * n_e, n_e, n_t)).view(n_frames, n_e, n_e, n_t, 2)
+    env_loop_out, env_stack_out = new(n_frames, n_f, 2), new(n_frames, n_f, 2)
+
+    def env_loop():
+        for k in range(n_frames):
+            dev.tfm_analytic_dev(an[k], fs, tt, out=env_loop_out[k])
+    routes["env_loop_of_tfm_analytic_dev"] = env_loop
+    routes["env_tfm_analytic_frames_dev"] = lambda: dev.tfm_analytic_frames_dev(an, fs, tt, out=env_stack_out)
+
+for fn in routes.values():                                                   # every code object loaded, every buffer touched
+    fn()
+torch.cuda.synchronize()
+same = dict(rf_b=bool(torch.equal(stack_out, loop_out)), rf_c=bool(torch.equal(packed_out, loop_out)))
+if not a.rf_only:
+    same["env"] = bool(torch.equal(env_stack_out, env_loop_out))
+for fn in routes.values():
+    fn()
+runs = {k: [] for k in routes}
+for _ in range(a.reps):
+    for k, fn in routes.items():
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        runs[k].append(t0.elapsed_time(t1) * 1e3)                            # us
+
+
+def pct(v, q):
+    v = sorted(v)
+    return v[min(len(v) - 1, max(0, round(q * (len(v) - 1))))]
+
+
+med = {k: pct(v, 0.5) for k, v in runs.items()}
+ratios = {"b_over_a": med["b_pack_and_tfm_frames_dev"] / med["a_loop_of_tfm_dev"],
+          "c_over_a": med["c_tfm_frames_dev_packed"] / med["a_loop_of_tfm_dev"]}
+no_slower = {"b": med["b_pack_and_tfm_frames_dev"] <= pct(runs["a_loop_of_tfm_dev"], 0.95)}
+if not a.rf_only:
+    ratios["env_stack_over_loop"] = med["env_tfm_analytic_frames_dev"] / med["env_loop_of_tfm_analytic_dev"]
+    no_slower["env"] = med["env_tfm_analytic_frames_dev"] <= pct(runs["env_loop_of_tfm_analytic_dev"], 0.95)
+print(json.dumps(dict(lib=os.environ.get("RTUS_LIB", "in-tree"), elements=n_e, samples=n_t, n_frames=n_frames, pixels=f"{n}x{n}", reps=a.reps,
+                      median_us={k: round(v, 1) for k, v in med.items()},
+                      per_frame_us={k: round(v / n_frames, 1) for k, v in med.items()},
+                      p05_p95_us={k: [round(pct(v, 0.05), 1), round(pct(v, 0.95), 1)] for k, v in runs.items()},
+                      ratio={k: round(v, 3) for k, v in ratios.items()}, bits_equal_the_loop=same, no_slower_than_the_loop=no_slower)),
+      flush=True)
