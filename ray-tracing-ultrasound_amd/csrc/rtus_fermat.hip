@@ -596,7 +596,13 @@ __device__ __forceinline__ WorkItem work_item(const LayerArgs& a)
     // A launch that carries the row table hands its work items out ALONG THE ROW BLOCKS first (blockIdx.x = bx gy + by: launch_layers
     // flattens its grid): workgroups that start together then write into gy row blocks at once instead of into neighbouring 2-KB
     // pieces of the same rows, which is what the store stream wants (DESIGN.md section 4 "Store stream").  Other launches keep x first.
-    const int bx = a.rowtab ? (int)(blockIdx.x / (unsigned)a.gy) : (int)blockIdx.x;
+    // Within every whole group of four columns the two middle ones change places (bits 0 and 1 of the column swapped): workgroups are
+    // dealt round-robin over the eight XCDs, so with gy = 4 (the 64-row regime's 256-row table) XCD k would hold by = k mod 4 and every
+    // SECOND 2-KB piece of its rows for the whole launch; with the swap its pieces come in adjacent pairs, 4 KB.  Measured: -4.4 us of
+    // 98 (DESIGN.md section 4 "Order across rows and XCDs").  A permutation of the columns inside the window that is in flight: with
+    // another gy the XCDs are dealt other columns and no gain was measured.  The ragged last group (gx no multiple of four) keeps its order.
+    int bx = a.rowtab ? (int)(blockIdx.x / (unsigned)a.gy) : (int)blockIdx.x;
+    if (ROWTAB && a.rowtab && (bx | 3) < (a.n_f + RTUS_BLOCK - 1) / RTUS_BLOCK) bx = (bx & ~3) | ((bx & 1) << 1) | ((bx >> 1) & 1);
     const int by = a.rowtab ? (int)(blockIdx.x % (unsigned)a.gy) : (int)blockIdx.y, bz = blockIdx.z;
     WorkItem wi;
     wi.bx = bx;
