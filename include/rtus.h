@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 121 /* 0.1.20: rtus_tfm_frames, rtus_tfm_analytic_frames (TFM over a stack of frames) */
+#define RTUS_VERSION 122 /* 0.1.21: rtus_tfm_frames_i16 (TFM over a stack of int16 frames, four per gather) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -772,6 +772,52 @@ int rtus_tfm_analytic_frames_dev(const float *d_a, int n_frames, int n_tx, int n
 int rtus_tfm_analytic_frames(const float *a, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
                              const double *tt_tx, const double *tt_rx, int n_f,
                              float *images, float *cf, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_frames_i16: rtus_tfm_frames over a stack of INT16 frames — the samples as an array controller delivers them — with
+ * four frames per 16-byte gather, half the bytes uploaded and half the device memory of the float32 route.  NOT IN THE REFERENCE;
+ * held bit for bit to rtus_tfm on the frames converted to float32 and to tests/das_exact_numpy.py.
+ *   A stack is n_frames captures, frame-major: fmc [n_frames][n_tx][n_rx][n_t] int16.  fs, t0, tt_tx, tt_rx, images [n_frames][n_f]
+ *           float32: as in rtus_tfm_frames.
+ *   Frame k's image is, BIT FOR BIT, rtus_tfm on frame k converted to float32 (the conversion is exact): the same leg rule, edge
+ *           rules, no-path rule and order of the sums.  There is no gain argument: the image is linear in the data, so a caller
+ *           scales the image.  Determinism: as rtus_tfm_frames — no bit depends on n_frames, on the other frames of a quad, or on
+ *           how a caller cuts the stack into calls.
+ *   The PACKED layout: packed [n_quads][n_tx][n_rx][n_t][4] int16, n_quads = ceil(n_frames / 4); plane c of quad q is frame 4 q + c;
+ *           the planes of the absent frames of the last quad are 0.  A sample position is 8 bytes — the record shape of a pair of
+ *           float32 frames — so ONE 16-byte gather brings two neighbouring samples of FOUR frames.
+ *   rtus_fmc_pack_frames_i16_words: the int16 values of the packed stack, 4 n_quads n_tx n_rx n_t; 0 when a size is not positive
+ *           or the count does not fit 2^62 bytes.
+ *   rtus_fmc_pack_frames_i16_dev: frame-major stack -> packed (writes the zero planes of a ragged last quad).  n_t >= 1.  d_packed
+ *           must be 8-byte aligned, d_fmc 2-byte aligned, and the two must not overlap (-1).  A streaming interleave: 2 n_frames
+ *           n_tx n_rx n_t bytes read, 8 n_quads ... written; 16-byte loads and stores when a frame is a multiple of 8 samples and
+ *           both pointers are 16-byte aligned, 2-byte loads and 8-byte stores otherwise.
+ *   rtus_tfm_frames_i16_dev takes the PACKED stack (n_frames says how many frames the last quad holds: the images rows of its
+ *           absent frames do not exist and are not written).  The host twin rtus_tfm_frames_i16 takes the FRAME-MAJOR int16 stack,
+ *           uploads it as int16 and packs on the device in the arena.
+ *   Limits: rtus_tfm_frames' — a null pointer, a non-positive size, n_t < 2, fs not positive and finite, t0 not finite: -1.
+ *           n_t > 2^26, or more than 2^31 - 1 workgroups, n_quads ceil(n_f / 256): -5.  All before any HIP call.  The _dev entries
+ *           allocate nothing and do not synchronise (capturable).
+ * Kernels and the figures: DESIGN.md §4 "TFM over int16 frame stacks" (profiles/tfm_frames_i16_kernel.txt).
+ *           A call is one launch per about 2304 workgroups, counted in quads (rtus_tfm_frames' rule; measured again for quads: the
+ *           whole stack in one launch was equal at 256^2 and 1 % to 2.5 % faster at 1024^2, one quad per launch 2 % to 6 % slower at 256^2).
+ * Measured on MI355X, 64 elements x 2048 samples, one table, medians of 50 alternating repetitions, time per frame, against
+ * rtus_tfm_frames_dev on a float32-packed stack in the same run (= 1); the estimate before the measurement was 0.55x to 0.7x:
+ *   256^2 focal points:  packed float32 133 / 149 / 138 us at 8 / 9 / 32 frames; rtus_tfm_frames_i16_dev on a packed int16 stack
+ *           71 / 91 / 74 us (0.53x / 0.61x / 0.54x; 9 frames are three quads, the third a quarter full); int16 pack + stack 78 / 101 /
+ *           101 us (0.54x / 0.62x / 0.66x of float32 pack + stack); the int16 pack alone 7 to 10 us per frame (float32: 12).
+ *   1024^2: packed float32 0.97 / 1.08 / 0.98 ms; packed int16 0.72 / 0.97 / 0.72 ms (0.74x / 0.89x / 0.74x: outside the estimate — a
+ *           quad's launch takes 1.48x a pair's there, the decode is not hidden behind the gathers); int16 pack + stack 0.73 / 0.97 /
+ *           0.73 ms (0.74x / 0.88x / 0.74x of float32 pack + stack).
+ *   The host twins on 8 frames from pageable memory (268 MB as float32, 134 MB as int16), wall time: 6.6 ms against 3.7 ms at 256^2
+ *           (0.56x), 24.0 ms against 19.5 ms at 1024^2 (0.81x).
+ * ---------------------------------------------------------------------------------------- */
+size_t rtus_fmc_pack_frames_i16_words(int n_frames, int n_tx, int n_rx, int n_t);
+int rtus_fmc_pack_frames_i16_dev(const short *d_fmc, int n_frames, int n_tx, int n_rx, int n_t, short *d_packed, void *stream);
+int rtus_tfm_frames_i16_dev(const short *d_packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                            const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_images, void *stream);
+int rtus_tfm_frames_i16(const short *fmc, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                        const double *tt_tx, const double *tt_rx, int n_f, float *images, int device);
 
 /* ------------------------------------------------------------------------------------------
  * Plane-wave imaging (PWI): a few dozen plane waves, each fired by the whole aperture with a linear delay law and received on every

@@ -151,6 +151,11 @@ PROTOTYPES = (
     ("rtus_tfm_frames", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, i], 121),
     ("rtus_tfm_analytic_frames_dev", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, vp], 121),
     ("rtus_tfm_analytic_frames", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, vp, vp, i], 121),
+    # a stack of int16 frames
+    ("rtus_fmc_pack_frames_i16_words", sz, [i, i, i, i], 122),
+    ("rtus_fmc_pack_frames_i16_dev", i, [vp, i, i, i, i, vp, vp], 122),
+    ("rtus_tfm_frames_i16_dev", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, vp], 122),
+    ("rtus_tfm_frames_i16", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, i], 122),
     # plane-wave imaging
     ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
     ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),

@@ -719,6 +719,35 @@ def frames_unpack(packed, n_frames):
     return stack
 
 
+def frames_pack_i16(stack):
+    """A frame-major int16 stack [n_frames, n_tx, n_rx, n_t] -> its packed layout int16 [n_quads, n_tx, n_rx, n_t, 4],
+    n_quads = ceil(n_frames / 4): plane c of quad q is frame 4 q + c; the planes of the absent frames of the last quad are 0.  The
+    layout rtus_tfm_frames_i16_dev reads (include/rtus.h), restated in NumPy; device.fmc_pack_frames_i16_dev makes it on the GPU."""
+    stack = np.asarray(stack)
+    if stack.dtype != np.int16 or stack.ndim != 4 or stack.shape[0] < 1:
+        raise ValueError("the stack must be int16 [n_frames, n_tx, n_rx, n_t] with at least one frame")
+    n_frames = stack.shape[0]
+    packed = np.zeros(((n_frames + 3) // 4,) + stack.shape[1:] + (4,), dtype=np.int16)
+    for c in range(4):
+        packed[:(n_frames - c + 3) // 4, ..., c] = stack[c::4]
+    return packed
+
+
+def frames_unpack_i16(packed, n_frames):
+    """The packed layout int16 [n_quads, n_tx, n_rx, n_t, 4] -> the frame-major stack int16 [n_frames, n_tx, n_rx, n_t];
+    ``n_frames`` is in [4 n_quads - 3, 4 n_quads] (the planes past it in the last quad are dropped)."""
+    packed = np.asarray(packed)
+    n_frames = int(n_frames)
+    if packed.dtype != np.int16 or packed.ndim != 5 or packed.shape[4] != 4 or packed.shape[0] < 1:
+        raise ValueError("the packed stack must be int16 [n_quads, n_tx, n_rx, n_t, 4]")
+    if (n_frames + 3) // 4 != packed.shape[0] or n_frames < 1:
+        raise ValueError(f"{packed.shape[0]} quads hold {4 * packed.shape[0] - 3} to {4 * packed.shape[0]} frames, not {n_frames}")
+    stack = np.empty((n_frames,) + packed.shape[1:4], dtype=np.int16)
+    for c in range(4):
+        stack[c::4] = packed[:(n_frames - c + 3) // 4, ..., c]
+    return stack
+
+
 def _max_frames(max_frames, n_frames):
     """the ``max_frames=`` keyword of tfm_frames -> frames per call"""
     if max_frames is None:
@@ -733,6 +762,8 @@ def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherenc
     """TFM over a stack of frames — an encoded scan: ``stack`` float32 [n_frames, n_tx, n_rx, n_t], every frame imaged through the
     same tables on the same grid -> float32 [n_frames, n_f]; row k is tfm_image(stack[k], ...) bit for bit.  The frames are paired
     on the device and each pair imaged by one 16-byte gather per (tx, rx, focal point), all pairs in one call (rtus_tfm_frames).
+    A stack of dtype int16 (without ``envelope``) is uploaded as int16 and imaged four frames per gather (rtus_tfm_frames_i16): half
+    the upload and the device memory, the bits of the float32 call on the same samples.
     ``envelope=True``: the analytic stack is formed first (fmc_analytic over the n_frames n_tx transmit rows, ``n_taps`` Hilbert
     taps) and imaged by rtus_tfm_analytic_frames -> complex64 [n_frames, n_f], row k = tfm_analytic(fmc_analytic(stack[k])) bit for
     bit; with ``coherence=True`` (or "cf") -> (images, cf float32 [n_frames, n_f]).  ``f_demod`` [Hz] as on tfm_views: the frames go
@@ -746,7 +777,8 @@ def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherenc
         if not envelope:
             raise ValueError("f_demod (carrier-aware interpolation) needs envelope=True")
         f_demod = _f_demod(f_demod, fs)
-    stack = np.ascontiguousarray(stack, dtype=np.float32)
+    i16 = not envelope and getattr(stack, "dtype", None) == np.int16   # (fmc_analytic needs float32: an envelope stack is widened)
+    stack = np.ascontiguousarray(stack, dtype=np.int16 if i16 else np.float32)
     if stack.ndim != 4 or stack.shape[0] < 1:
         raise ValueError("the stack must be [n_frames, n_tx, n_rx, n_t] with at least one frame")
     n_frames, n_tx, n_rx, n_t = stack.shape
@@ -760,9 +792,10 @@ def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherenc
     for k in range(0, n_frames, per):
         n = min(per, n_frames - k)
         if not envelope:
-            st = L.rtus_tfm_frames(_ptr(stack[k:k + n]), n, n_tx, n_rx, n_t, float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f,
+            entry = "rtus_tfm_frames_i16" if i16 else "rtus_tfm_frames"
+            st = getattr(L, entry)(_ptr(stack[k:k + n]), n, n_tx, n_rx, n_t, float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f,
                                    _ptr(imgs[k:k + n]), int(device))
-            _lib.check(st, "rtus_tfm_frames")
+            _lib.check(st, entry)
             continue
         a = fmc_analytic(stack[k:k + n].reshape(n * n_tx, n_rx, n_t), n_taps, device=device)
         st = L.rtus_tfm_analytic_frames(_ptr(a), n, n_tx, n_rx, n_t, float(fs), float(t0), 0.0 if f_demod is None else f_demod,

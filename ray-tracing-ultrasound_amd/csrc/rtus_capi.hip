@@ -94,6 +94,9 @@ hipError_t rtus_launch_tfm_frames(const float* packed, int n_frames, int n_tx, i
 hipError_t rtus_launch_tfm_analytic_frames(const float* an, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, double f_demod,
                                            const double* tt_tx, const double* tt_rx, int n_f, float* images, float* cf, hipStream_t s);
 long long rtus_tfm_frames_blocks(int n_slow, int n_f);
+hipError_t rtus_launch_fmc_pack_frames_i16(const short* stack, int n_frames, size_t n, short* packed, hipStream_t s);
+hipError_t rtus_launch_tfm_frames_i16(const short* packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                                      const double* tt_tx, const double* tt_rx, int n_f, float* images, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s);
@@ -1574,6 +1577,71 @@ int rtus_tfm_analytic_frames(const float* a, int n_frames, int n_tx, int n_rx, i
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tfm_analytic_frames(da, n_frames, n_tx, n_rx, n_t, fs, t0, f_demod, dtx, same ? dtx : drx, n_f, dimg, dcf,
                                                S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- TFM over a stack of int16 frames
+size_t rtus_fmc_pack_frames_i16_words(int n_frames, int n_tx, int n_rx, int n_t)
+{
+    if (n_frames <= 0 || n_tx <= 0 || n_rx <= 0 || n_t <= 0) return 0;
+    const unsigned __int128 n = (unsigned __int128)((n_frames + 3LL) / 4 * 4) * (unsigned)n_tx * (unsigned)n_rx * (unsigned)n_t;
+    return n <= ((size_t)1 << 61) ? (size_t)n : 0;                    // (2-byte values: 2^62 bytes)
+}
+
+int rtus_fmc_pack_frames_i16_dev(const short* d_fmc, int n_frames, int n_tx, int n_rx, int n_t, short* d_packed, void* stream)
+{
+    if (!d_fmc || !d_packed || n_frames <= 0 || n_tx <= 0 || n_rx <= 0 || n_t <= 0) return RTUS_ERR_INVALID_ARG;
+    const size_t tot = rtus_fmc_pack_frames_i16_words(n_frames, n_tx, n_rx, n_t);
+    if (!tot) return RTUS_ERR_UNSUPPORTED;
+    const size_t n = tot / ((n_frames + 3LL) / 4 * 4);                // samples per frame
+    if (((uintptr_t)d_packed & 7) || ((uintptr_t)d_fmc & 1)) return RTUS_ERR_INVALID_ARG;   // 8-byte stores, 2-byte loads
+    const uintptr_t i0 = (uintptr_t)d_fmc, i1 = i0 + 2 * n * (size_t)n_frames, o0 = (uintptr_t)d_packed, o1 = o0 + 2 * tot;
+    if (i0 < o1 && o0 < i1) return RTUS_ERR_INVALID_ARG;              // the output must not overlap the input
+    LAUNCH_TRY(rtus_launch_fmc_pack_frames_i16(d_fmc, n_frames, n, d_packed, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+// check_tfm_frames with the images of a launch counted in quads
+static int check_tfm_frames_i16(const void* data, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, const void* tt_tx,
+                                const void* tt_rx, int n_f, const void* images)
+{
+    if (n_frames <= 0) return RTUS_ERR_INVALID_ARG;
+    int st = check_tfm_analytic(data, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, images);   // (8-byte positions, 16-byte loads)
+    if (st) return st;
+    if (rtus_tfm_frames_blocks((int)((n_frames + 3LL) / 4), n_f) > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+int rtus_tfm_frames_i16_dev(const short* d_packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, const double* d_tt_tx,
+                            const double* d_tt_rx, int n_f, float* d_images, void* stream)
+{
+    int st = check_tfm_frames_i16(d_packed, n_frames, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_frames_i16(d_packed, n_frames, n_tx, n_rx, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images,
+                                          (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_frames_i16(const short* fmc, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
+                        const double* tt_rx, int n_f, float* images, int device)
+{
+    int st = check_tfm_frames_i16(fmc, n_frames, n_tx, n_rx, n_t, fs, t0, tt_tx, tt_rx, n_f, images);
+    if (st) return st;
+    const size_t n = (size_t)n_tx * n_rx * n_t;                       // samples per frame
+    const bool same = tt_tx == tt_rx && n_tx == n_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    short *dstack, *dpacked;
+    float* dimg;
+    double *dtx, *drx = nullptr;
+    S.in(dstack, fmc, n * n_frames);
+    S.in(dtx, tt_tx, (size_t)n_tx * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_rx * n_f);
+    S.out(dimg, images, (size_t)n_frames * n_f);
+    S.scratch(dpacked, rtus_fmc_pack_frames_i16_words(n_frames, n_tx, n_rx, n_t));
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_fmc_pack_frames_i16(dstack, n_frames, n, dpacked, S.a->stream));
+    LAUNCH_TRY(rtus_launch_tfm_frames_i16(dpacked, n_frames, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
     return S.finish();
 }
 

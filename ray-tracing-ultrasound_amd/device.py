@@ -456,6 +456,48 @@ def tfm_frames_dev(packed, n_frames, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
     return out
 
 
+def fmc_pack_frames_i16_dev(stack, out=None):
+    """A frame-major int16 stack on device, int16 [n_frames, n_tx, n_rx, n_t] -> its packed layout int16
+    [n_quads, n_tx, n_rx, n_t, 4] (rtus_fmc_pack_frames_i16_dev; api.frames_pack_i16's definition: frames 4 q .. 4 q + 3 interleaved
+    in quad q, the planes of absent frames 0).  ``out`` must not overlap ``stack``.  Asynchronous on the current stream (capturable
+    with a pre-allocated output)."""
+    _chk(stack, "stack", torch.int16)
+    if stack.dim() != 4 or stack.shape[0] < 1:
+        raise ValueError("stack must be [n_frames, n_tx, n_rx, n_t] with at least one frame")
+    n_frames, n_tx, n_rx, n_t = stack.shape
+    out = _result(out, ((n_frames + 3) // 4, n_tx, n_rx, n_t, 4), stack, torch.int16)
+    if out.device != stack.device:
+        raise ValueError("out must be on the device of stack")
+    st = _lib.lib().rtus_fmc_pack_frames_i16_dev(_p(stack), n_frames, n_tx, n_rx, n_t, _p(out), _stream(stack))
+    _lib.check(st, "rtus_fmc_pack_frames_i16_dev")
+    return out
+
+
+def tfm_frames_i16_dev(packed, n_frames, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
+    """TFM over a stack of int16 frames on device (rtus_tfm_frames_i16_dev; api.tfm_frames' definition): ``packed`` int16
+    [n_quads, n_tx, n_rx, n_t, 4] as fmc_pack_frames_i16_dev makes it, ``n_frames`` in [4 n_quads - 3, 4 n_quads] (the last quad then
+    holds fewer than four frames), tt_tx [n_tx, n_f], tt_rx [n_rx, n_f] (default: tt_tx) -> out float32 [n_frames, n_f]; row k has
+    tfm_dev's bits on frame k converted to float32.  One call, a few launches; asynchronous on the current stream (capturable with a
+    pre-allocated output)."""
+    _chk(packed, "packed", torch.int16); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_frames = int(n_frames)
+    if packed.dim() != 5 or packed.shape[4] != 4 or packed.shape[0] < 1 or (n_frames + 3) // 4 != packed.shape[0] or n_frames < 1:
+        raise ValueError("need packed [n_quads, n_tx, n_rx, n_t, 4] and n_frames in [4 n_quads - 3, 4 n_quads]")
+    ok = tt_tx.dim() == 2 and tt_rx.dim() == 2 and tt_tx.shape[1] == tt_rx.shape[1] \
+        and packed.shape[1] == tt_tx.shape[0] and packed.shape[2] == tt_rx.shape[0]
+    if not ok:
+        raise ValueError("need packed [n_quads, n_tx, n_rx, n_t, 4], tt_tx [n_tx, n], tt_rx [n_rx, n]")
+    n_f = tt_tx.shape[1]
+    out = _result(out, (n_frames, n_f), packed, torch.float32)
+    if not (out.device == packed.device == tt_tx.device == tt_rx.device):
+        raise ValueError("out must be on the device of packed / tt_tx / tt_rx")
+    st = _lib.lib().rtus_tfm_frames_i16_dev(_p(packed), n_frames, packed.shape[1], packed.shape[2], packed.shape[3], float(fs), float(t0),
+                                            _p(tt_tx), _p(tt_rx), n_f, _p(out), _stream(packed))
+    _lib.check(st, "rtus_tfm_frames_i16_dev")
+    return out
+
+
 def tfm_analytic_frames_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, f_demod=0.0, out=None, cf=None):
     """Envelope TFM over a stack of analytic frames on device (rtus_tfm_analytic_frames_dev): ``analytic`` float32
     [n_frames, n_tx, n_rx, n_t, 2] (fmc_analytic_dev on the stack viewed as [n_frames n_tx, n_rx, n_t] makes it), tt_tx [n_tx, n_f],

@@ -1,7 +1,11 @@
-"""Throughput of TFM over a stack of frames (rtus_fmc_pack_frames_dev, rtus_tfm_frames_dev, rtus_tfm_analytic_frames_dev) next to the
-loops over the single-frame entries that it replaces, in the same run: 64 x 64 x 2048 samples, n_frames 8 and 9, at 256^2 and 1024^2
-focal points (four shapes).  Routes, RF:  (a) n_frames calls of tfm_dev;  (b) pack + tfm_frames_dev;  (c) tfm_frames_dev on an
-already packed stack.  Envelope:  n_frames calls of tfm_analytic_dev against one tfm_analytic_frames_dev.
+"""Throughput of TFM over a stack of frames (rtus_fmc_pack_frames_dev, rtus_tfm_frames_dev, rtus_tfm_analytic_frames_dev, and the
+int16 route rtus_fmc_pack_frames_i16_dev, rtus_tfm_frames_i16_dev) next to the loops over the single-frame entries that it replaces, in
+the same run: 64 x 64 x 2048 samples, n_frames 8, 9 and 32, at 256^2 and 1024^2 focal points (six shapes).  The samples are int16
+values; the float32 routes get them converted, so every route images the same numbers.  Routes, RF:  (a) n_frames calls of tfm_dev;
+(b) pack + tfm_frames_dev;  (c) tfm_frames_dev on an already packed stack;  (d) int16 pack + tfm_frames_i16_dev;  (e)
+tfm_frames_i16_dev on an already packed int16 stack;  the two packs alone.  Envelope:  n_frames calls of tfm_analytic_dev against one
+tfm_analytic_frames_dev.  --host-twins adds, at 8 frames, the wall time of the host twins rtus_tfm_frames and rtus_tfm_frames_i16 from
+pageable host arrays (upload, pack, kernel, download): where the halved upload shows.
 
 Each shape is one child process under its own time limit (the parent never touches the GPU and stops at the first child that fails).
 In the child: CUDA events around each route, outputs preallocated, a warm-up of every route, then `--reps` repetitions with the routes
@@ -16,14 +20,15 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHAPES = [(8, 256), (9, 256), (8, 1024), (9, 1024)]                          # (n_frames, pixels per side)
+SHAPES = [(8, 256), (9, 256), (32, 256), (8, 1024), (9, 1024), (32, 1024)]   # (n_frames, pixels per side)
 ap = argparse.ArgumentParser()
 ap.add_argument("--elements", type=int, default=64)
 ap.add_argument("--samples", type=int, default=2048)
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--rf-only", action="store_true", help="skip the envelope routes (A/B runs of an RF kernel variant through RTUS_LIB)")
 ap.add_argument("--limit", type=int, default=240, help="seconds a shape's child process may take")
-ap.add_argument("--frames", type=int, nargs="+", help="stack lengths instead of 8 and 9 (a long scan: --frames 32)")
+ap.add_argument("--frames", type=int, nargs="+", help="stack lengths instead of 8, 9 and 32")
+ap.add_argument("--host-twins", action="store_true", help="also time the host twins, float32 against int16, on the 8-frame shapes")
 ap.add_argument("--shape", type=int, nargs=2, metavar=("N_FRAMES", "N"), help="(child) measure this one shape")
 a = ap.parse_args()
 
@@ -32,7 +37,8 @@ if a.shape is None:
         SHAPES = [(k, n) for n in (256, 1024) for k in a.frames]
     for n_frames, n in SHAPES:
         cmd = [sys.executable, os.path.abspath(__file__), "--shape", str(n_frames), str(n), "--elements", str(a.elements),
-               "--samples", str(a.samples), "--reps", str(a.reps)] + (["--rf-only"] if a.rf_only else [])
+               "--samples", str(a.samples), "--reps", str(a.reps)] + (["--rf-only"] if a.rf_only else []) \
+            + (["--host-twins"] if a.host_twins else [])
         try:
             r = subprocess.run(cmd, timeout=a.limit)
         except subprocess.TimeoutExpired:
@@ -50,7 +56,8 @@ n_frames, n = a.shape
 n_e, n_t = a.elements, a.samples
 fs, c1 = 50e6, 1480.0
 g = torch.Generator(device="cuda").manual_seed(1)
-stack = torch.randn((n_frames, n_e, n_e, n_t), generator=g, dtype=torch.float32, device="cuda")
+stack_i16 = torch.randint(-32768, 32768, (n_frames, n_e, n_e, n_t), generator=g, dtype=torch.int16, device="cuda")
+stack = stack_i16.to(torch.float32)
 xe = ((torch.arange(n_e, dtype=torch.float64, device="cuda") - (n_e - 1) / 2) * 0.25e-3).contiguous()
 ze = torch.zeros(n_e, dtype=torch.float64, device="cuda")
 x0, dx, z_lo, dz = -0.008, 0.016 / (n - 1), 0.004, 0.016 / (n - 1)           # the record holds 30 mm of water: all inside
@@ -60,7 +67,9 @@ tt = (torch.hypot(xe[:, None] - px[None, :], ze[:, None] - pz[None, :]) / c1).co
 n_f = n * n
 new = lambda *shape: torch.empty(shape, dtype=torch.float32, device="cuda")   # noqa: E731
 packed = dev.fmc_pack_frames_dev(stack)
+packed_i16 = dev.fmc_pack_frames_i16_dev(stack_i16)
 loop_out, stack_out, packed_out = new(n_frames, n_f), new(n_frames, n_f), new(n_frames, n_f)
+i16_out, i16_packed_out = new(n_frames, n_f), new(n_frames, n_f)
 
 
 def rf_loop():
@@ -73,9 +82,17 @@ def rf_pack_and_stack():
     dev.tfm_frames_dev(packed, n_frames, fs, tt, out=stack_out)
 
 
+def i16_pack_and_stack():
+    dev.fmc_pack_frames_i16_dev(stack_i16, out=packed_i16)
+    dev.tfm_frames_i16_dev(packed_i16, n_frames, fs, tt, out=i16_out)
+
+
 routes = {"a_loop_of_tfm_dev": rf_loop, "b_pack_and_tfm_frames_dev": rf_pack_and_stack,
           "c_tfm_frames_dev_packed": lambda: dev.tfm_frames_dev(packed, n_frames, fs, tt, out=packed_out),
-          "pack_alone": lambda: dev.fmc_pack_frames_dev(stack, out=packed)}
+          "d_i16_pack_and_tfm_frames_i16_dev": i16_pack_and_stack,
+          "e_tfm_frames_i16_dev_packed": lambda: dev.tfm_frames_i16_dev(packed_i16, n_frames, fs, tt, out=i16_packed_out),
+          "pack_alone": lambda: dev.fmc_pack_frames_dev(stack, out=packed),
+          "i16_pack_alone": lambda: dev.fmc_pack_frames_i16_dev(stack_i16, out=packed_i16)}
 if not a.rf_only:
     an = dev.fmc_analytic_dev(stack.view(n_frames * n_e, n_e, n_t)).view(n_frames, n_e, n_e, n_t, 2)
     env_loop_out, env_stack_out = new(n_frames, n_f, 2), new(n_frames, n_f, 2)
@@ -89,7 +106,8 @@ if not a.rf_only:
 for fn in routes.values():                                                   # every code object loaded, every buffer touched
     fn()
 torch.cuda.synchronize()
-same = dict(rf_b=bool(torch.equal(stack_out, loop_out)), rf_c=bool(torch.equal(packed_out, loop_out)))
+same = dict(rf_b=bool(torch.equal(stack_out, loop_out)), rf_c=bool(torch.equal(packed_out, loop_out)),
+            i16_d=bool(torch.equal(i16_out, loop_out)), i16_e=bool(torch.equal(i16_packed_out, loop_out)))
 if not a.rf_only:
     same["env"] = bool(torch.equal(env_stack_out, env_loop_out))
 for fn in routes.values():
@@ -112,7 +130,33 @@ def pct(v, q):
 
 med = {k: pct(v, 0.5) for k, v in runs.items()}
 ratios = {"b_over_a": med["b_pack_and_tfm_frames_dev"] / med["a_loop_of_tfm_dev"],
-          "c_over_a": med["c_tfm_frames_dev_packed"] / med["a_loop_of_tfm_dev"]}
+          "c_over_a": med["c_tfm_frames_dev_packed"] / med["a_loop_of_tfm_dev"],
+          "d_over_a": med["d_i16_pack_and_tfm_frames_i16_dev"] / med["a_loop_of_tfm_dev"],
+          "d_over_b": med["d_i16_pack_and_tfm_frames_i16_dev"] / med["b_pack_and_tfm_frames_dev"],
+          "d_over_c": med["d_i16_pack_and_tfm_frames_i16_dev"] / med["c_tfm_frames_dev_packed"],
+          "e_over_c": med["e_tfm_frames_i16_dev_packed"] / med["c_tfm_frames_dev_packed"]}
+# (e) / (c) repetition by repetition (both are timed within each repetition): its spread
+e_over_c = [e / c for e, c in zip(runs["e_tfm_frames_i16_dev_packed"], runs["c_tfm_frames_dev_packed"])]
+spread = {"e_over_c_p05_p95": [round(pct(e_over_c, 0.05), 3), round(pct(e_over_c, 0.95), 3)]}
+host = {}
+if a.host_twins and n_frames == 8:
+    import time
+    import numpy as np
+    rtus = import_module("ray-tracing-ultrasound_amd")
+    h_i16 = stack_i16.cpu().numpy()
+    h_f32, h_tt = h_i16.astype(np.float32), tt.cpu().numpy()
+    h_out = {k: np.empty((n_frames, n_f), dtype=np.float32) for k in ("float32", "int16")}
+    wall = {k: [] for k in h_out}
+    for rep in range(7):                                                     # (the first two: the arena grows, pages are touched)
+        for k, h in (("float32", h_f32), ("int16", h_i16)):
+            t = time.perf_counter()
+            rtus.tfm_frames(h, fs, h_tt, out=h_out[k])
+            if rep >= 2:
+                wall[k].append((time.perf_counter() - t) * 1e3)
+    host = dict(host_twin_wall_ms={k: round(pct(v, 0.5), 2) for k, v in wall.items()},
+                host_twin_wall_ms_min_max={k: [round(min(v), 2), round(max(v), 2)] for k, v in wall.items()},
+                host_twin_bits_equal=bool(np.array_equal(h_out["float32"], h_out["int16"])),
+                host_twin_upload_MB={"float32": round(h_f32.nbytes / 1e6, 1), "int16": round(h_i16.nbytes / 1e6, 1)})
 no_slower = {"b": med["b_pack_and_tfm_frames_dev"] <= pct(runs["a_loop_of_tfm_dev"], 0.95)}
 if not a.rf_only:
     ratios["env_stack_over_loop"] = med["env_tfm_analytic_frames_dev"] / med["env_loop_of_tfm_analytic_dev"]
@@ -121,5 +165,6 @@ print(json.dumps(dict(lib=os.environ.get("RTUS_LIB", "in-tree"), elements=n_e, s
                       median_us={k: round(v, 1) for k, v in med.items()},
                       per_frame_us={k: round(v / n_frames, 1) for k, v in med.items()},
                       p05_p95_us={k: [round(pct(v, 0.05), 1), round(pct(v, 0.95), 1)] for k, v in runs.items()},
-                      ratio={k: round(v, 3) for k, v in ratios.items()}, bits_equal_the_loop=same, no_slower_than_the_loop=no_slower)),
+                      ratio={k: round(v, 3) for k, v in ratios.items()}, **spread, bits_equal_the_loop=same,
+                      no_slower_than_the_loop=no_slower, **host)),
       flush=True)
