@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 122 /* 0.1.21: rtus_tfm_frames_i16 (TFM over a stack of int16 frames, four per gather) */
+#define RTUS_VERSION 123 /* 0.1.22: rtus_tfm_frames_hmc[_i16] (TFM over a stack of half-matrix frames) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -817,6 +817,56 @@ int rtus_fmc_pack_frames_i16_dev(const short *d_fmc, int n_frames, int n_tx, int
 int rtus_tfm_frames_i16_dev(const short *d_packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
                             const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_images, void *stream);
 int rtus_tfm_frames_i16(const short *fmc, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
+                        const double *tt_tx, const double *tt_rx, int n_f, float *images, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_frames_hmc_i16, rtus_tfm_frames_hmc: rtus_tfm_hmc over a STACK of half-matrix frames — what a recorded scan is: int16
+ * (or float32) samples, the n_pairs = n_e (n_e + 1) / 2 records with tx <= rx, hundreds of captures through the same tables —
+ * four int16 frames (two float32 frames) per 16-byte gather and one gather per record.  NOT IN THE REFERENCE; held bit for bit to
+ * rtus_tfm_hmc on each frame and to tests/das_exact_numpy.py.
+ *   A stack is n_frames captures, frame-major: hmc [n_frames][n_pairs][n_t], int16 or float32, the records in rtus_tfm_hmc's
+ *           order.  n_e, fs, t0, tt_tx, tt_rx [n_e][n_f]: as in rtus_tfm_hmc; images [n_frames][n_f] float32.
+ *   The contract.  Frame k's image is, BIT FOR BIT, rtus_tfm_hmc on frame k converted to float32 (exact): its pair rule, weights,
+ *           edge rules, no-path rule and order of summation.  No bit depends on n_frames, on the other planes of a quad or pair, or
+ *           on how the stack is cut into calls or launches.  tt_tx == tt_rx AS POINTERS selects the one-table kernels (one gather
+ *           per record, weight 2 off the diagonal), whose images have the bits of the two-table call with equal tables, as
+ *           rtus_tfm_hmc promises.
+ *   The PACKED layouts are rtus_tfm_frames[_i16]'s with one "transmit row" of n_pairs records: packed [n_quads][n_pairs][n_t][4]
+ *           int16 (plane c of quad q is frame 4 q + c) and packed [n_fpairs][n_pairs][n_t][2] float32 (plane c of pair p is frame
+ *           2 p + c); the planes of absent frames are 0.  rtus_fmc_pack_frames[_i16]_dev make them with (n_tx, n_rx) = (1, n_pairs).
+ *           A sample position is 8 bytes either way — the record shape of analytic HMC data.
+ *   The _dev entries take the PACKED stack (n_frames says how many frames the last quad or pair holds: the images rows of its absent
+ *           frames do not exist and are not written), allocate nothing and do not synchronise (capturable).  The host twins take
+ *           the FRAME-MAJOR stack, upload it in its own type and pack on the device in the arena.
+ *   Limits: a null pointer, a non-positive size, n_e > 32768, n_t < 2, fs not positive and finite, t0 not finite: -1.  n_t > 2^26,
+ *           or more than 2^31 - 1 workgroups (n_quads or n_fpairs times ceil(n_f / 256)): -5.  All before any HIP call.
+ *   Memory: the int16 route uploads and holds half the bytes of a float32 HMC stack and about half (n_e + 1) / (2 n_e) of an int16
+ *           full-matrix stack, by construction.
+ * Kernels, resources and the figures: DESIGN.md §4 "TFM over half-matrix frame stacks" (profiles/tfm_frames_hmc_kernel.txt).  A
+ *           call is one launch per about 2304 workgroups, counted in quads or pairs (rtus_tfm_frames' rule, not measured again).
+ * Measured on MI355X, 64 elements (2080 records) x 2048 samples, medians of 50 alternating repetitions, two separate runs (they differ
+ * by at most 0.012 in a ratio), time per frame with the pack included, against (a) a loop of rtus_tfm_hmc_dev on the float32 frames
+ * and (b) rtus_tfm_frames_i16_dev on the stack expanded to full matrices and already packed, in the same run.  The estimate before
+ * the measurement, from the ratios above: 0.35x to 0.45x of (a) at 256^2.
+ *   one table, 256^2 focal points, 8 / 9 / 32 frames: (a) 116 / 120 / 123 us, (b) 72 / 100 / 83 us, rtus_tfm_frames_hmc_i16_dev with its
+ *           pack 42 / 53 / 39 us: 0.36x / 0.44x / 0.32x of (a), 0.58x / 0.53x / 0.47x of (b); already packed 37 / 48 / 35 us.
+ *   one table, 1024^2: (a) 1.03 / 1.03 / 1.03 ms, (b) 0.74 / 0.98 / 0.73 ms, int16 HMC stack 0.39 / 0.52 / 0.39 ms: 0.38x / 0.51x / 0.38x of
+ *           (a), 0.53x / 0.54x / 0.53x of (b).  The bar — faster than both with one table and whole quads, by more than the runs
+ *           differ — is met at both sizes.
+ *   two tables (reported): 256^2 61 / 80 / 59 us against (a) 223 / 227 / 231 and (b) 74 / 102 / 109; 1024^2 0.78 / 1.04 / 0.78 ms against
+ *           (a) 2.10 / 2.09 / 2.10 and (b) 0.80 / 1.06 / 0.79: two gathers per record, so level with the full matrix there (0.96x to 0.99x).
+ *   float32 pairs with their pack, one table: 75 / 82 / 74 us at 256^2 (0.60x to 0.68x of (a)), 0.53 / 0.59 / 0.53 ms at 1024^2 (0.51x to 0.57x).
+ *   The host twins on 8 frames from pageable memory, wall time: 2.3 ms (68 MB up) against 8.6 ms for a loop of rtus_tfm_hmc on float32
+ *           frames (136 MB up, and the tables with every call) and 3.7 ms for rtus_tfm_frames_i16 on the expanded stack (134 MB up) at
+ *           256^2; 15.1 ms against 88.6 ms and 19.5 ms at 1024^2.
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tfm_frames_hmc_i16_dev(const short *d_packed, int n_frames, int n_e, int n_t, double fs, double t0,
+                                const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_images, void *stream);
+int rtus_tfm_frames_hmc_i16(const short *hmc, int n_frames, int n_e, int n_t, double fs, double t0,
+                            const double *tt_tx, const double *tt_rx, int n_f, float *images, int device);
+int rtus_tfm_frames_hmc_dev(const float *d_packed, int n_frames, int n_e, int n_t, double fs, double t0,
+                            const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_images, void *stream);
+int rtus_tfm_frames_hmc(const float *hmc, int n_frames, int n_e, int n_t, double fs, double t0,
                         const double *tt_tx, const double *tt_rx, int n_f, float *images, int device);
 
 /* ------------------------------------------------------------------------------------------

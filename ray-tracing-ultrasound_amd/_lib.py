@@ -156,6 +156,10 @@ PROTOTYPES = (
     ("rtus_fmc_pack_frames_i16_dev", i, [vp, i, i, i, i, vp, vp], 122),
     ("rtus_tfm_frames_i16_dev", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, vp], 122),
     ("rtus_tfm_frames_i16", i, [vp, i, i, i, i, dd, dd, vp, vp, i, vp, i], 122),
+    ("rtus_tfm_frames_hmc_i16_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp], 123),
+    ("rtus_tfm_frames_hmc_i16", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, i], 123),
+    ("rtus_tfm_frames_hmc_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp], 123),
+    ("rtus_tfm_frames_hmc", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, i], 123),
     # plane-wave imaging
     ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
     ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),

@@ -758,7 +758,7 @@ def _max_frames(max_frames, n_frames):
 
 
 def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherence=False, f_demod=None, n_taps=63, max_frames=None,
-               out=None, device=0):
+               out=None, device=0, hmc=False):
     """TFM over a stack of frames — an encoded scan: ``stack`` float32 [n_frames, n_tx, n_rx, n_t], every frame imaged through the
     same tables on the same grid -> float32 [n_frames, n_f]; row k is tfm_image(stack[k], ...) bit for bit.  The frames are paired
     on the device and each pair imaged by one 16-byte gather per (tx, rx, focal point), all pairs in one call (rtus_tfm_frames).
@@ -769,7 +769,17 @@ def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherenc
     bit; with ``coherence=True`` (or "cf") -> (images, cf float32 [n_frames, n_f]).  ``f_demod`` [Hz] as on tfm_views: the frames go
     through tfm_iq's carrier-aware interpolation instead; it needs ``envelope=True``.  "vcf" / "scf" have no stack form (ValueError).
     ``max_frames``: the stack is run in chunks of that many frames, which bounds device memory; no bit depends on it.  ``out``:
-    the images' buffer.  Definition: include/rtus.h (rtus_tfm_frames, rtus_tfm_analytic_frames).  Not in the reference."""
+    the images' buffer.
+    ``hmc=True``: every frame is a half-matrix capture — ``stack`` [n_frames, n_pairs, n_t], int16 or float32 (other dtypes go to
+    float32), the records in hmc_index's order; tt_tx / tt_rx [n_e, n_f], ``tt_rx`` None or ``tt_tx`` itself means one table (one
+    gather per record).  Row k is tfm_hmc(stack[k] as float32, ...) bit for bit; int16 frames go four per gather
+    (rtus_tfm_frames_hmc_i16), float32 frames two (rtus_tfm_frames_hmc).  The packed layouts the device entries read are
+    frames_pack_i16(stack[:, None])[:, 0] and frames_pack(stack[:, None])[:, 0]; device.fmc_pack_frames[_i16]_dev make them on the
+    GPU from a [n_frames, 1, n_pairs, n_t] view.  ``envelope``, ``coherence`` and ``f_demod`` have no stacked half-matrix form
+    (ValueError: tfm_analytic_hmc frame by frame).
+    Definition: include/rtus.h (rtus_tfm_frames, rtus_tfm_analytic_frames, rtus_tfm_frames_hmc).  Not in the reference."""
+    if hmc:
+        return _tfm_frames_hmc(stack, fs, tt_tx, tt_rx, t0, envelope, coherence, f_demod, max_frames, out, device)
     mode = _iq_coherence(coherence)
     if mode and not envelope:
         raise ValueError("the coherence factor needs envelope=True")
@@ -803,6 +813,28 @@ def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherenc
                                         int(device))
         _lib.check(st, "rtus_tfm_analytic_frames")
     return (imgs, cf) if mode else imgs
+
+
+def _tfm_frames_hmc(stack, fs, tt_tx, tt_rx, t0, envelope, coherence, f_demod, max_frames, out, device):
+    """tfm_frames(hmc=True): a stack of half-matrix frames [n_frames, n_pairs, n_t], int16 or float32"""
+    if envelope or coherence or f_demod is not None:
+        raise ValueError("hmc=True images RF frames only: envelope, coherence and f_demod have no stacked half-matrix form "
+                         "(use tfm_analytic_hmc / tfm_iq_hmc frame by frame)")
+    i16 = getattr(stack, "dtype", None) == np.int16
+    stack = np.ascontiguousarray(stack, dtype=np.int16 if i16 else np.float32)
+    if stack.ndim != 3 or stack.shape[0] < 1:
+        raise ValueError("with hmc=True the stack must be [n_frames, n_pairs, n_t] with at least one frame")
+    n_frames, n_pairs, n_t = stack.shape
+    n_e, tt_tx, tt_rx, n_f = _hmc_tables(n_pairs, tt_tx, tt_rx)
+    per = _max_frames(max_frames, n_frames)
+    imgs = _out(out, (n_frames, n_f), np.float32)
+    entry = "rtus_tfm_frames_hmc_i16" if i16 else "rtus_tfm_frames_hmc"
+    fn = getattr(_lib.lib(), entry)
+    for k in range(0, n_frames, per):
+        n = min(per, n_frames - k)
+        st = fn(_ptr(stack[k:k + n]), n, n_e, n_t, float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f, _ptr(imgs[k:k + n]), int(device))
+        _lib.check(st, entry)
+    return imgs
 
 
 # ---------------------------------------------------------------------------------------------- half-matrix capture

@@ -97,6 +97,10 @@ long long rtus_tfm_frames_blocks(int n_slow, int n_f);
 hipError_t rtus_launch_fmc_pack_frames_i16(const short* stack, int n_frames, size_t n, short* packed, hipStream_t s);
 hipError_t rtus_launch_tfm_frames_i16(const short* packed, int n_frames, int n_tx, int n_rx, int n_t, double fs, double t0,
                                       const double* tt_tx, const double* tt_rx, int n_f, float* images, hipStream_t s);
+hipError_t rtus_launch_tfm_frames_hmc_i16(const short* packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                          const double* tt_rx, int n_f, float* images, hipStream_t s);
+hipError_t rtus_launch_tfm_frames_hmc(const float* packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                      const double* tt_rx, int n_f, float* images, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s);
@@ -1643,6 +1647,83 @@ int rtus_tfm_frames_i16(const short* fmc, int n_frames, int n_tx, int n_rx, int 
     LAUNCH_TRY(rtus_launch_fmc_pack_frames_i16(dstack, n_frames, n, dpacked, S.a->stream));
     LAUNCH_TRY(rtus_launch_tfm_frames_i16(dpacked, n_frames, n_tx, n_rx, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
     return S.finish();
+}
+
+// ---------------------------------------------------------------------------- TFM over a stack of half-matrix frames
+// per: frames per block of the packed stack (4: int16 quads, 2: float32 pairs); 8-byte sample positions, 16-byte loads either way
+static int check_tfm_frames_hmc(const void* data, int n_frames, int n_e, int n_t, double fs, double t0, const void* tt_tx,
+                                const void* tt_rx, int n_f, const void* images, int per)
+{
+    if (n_frames <= 0) return RTUS_ERR_INVALID_ARG;
+    int st = check_tfm_hmc(data, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, true);
+    if (st) return st;
+    if (rtus_tfm_frames_blocks((int)(((long long)n_frames + per - 1) / per), n_f) > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+int rtus_tfm_frames_hmc_i16_dev(const short* d_packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* d_tt_tx,
+                                const double* d_tt_rx, int n_f, float* d_images, void* stream)
+{
+    int st = check_tfm_frames_hmc(d_packed, n_frames, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, 4);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_frames_hmc_i16(d_packed, n_frames, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_frames_hmc_dev(const float* d_packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* d_tt_tx,
+                            const double* d_tt_rx, int n_f, float* d_images, void* stream)
+{
+    int st = check_tfm_frames_hmc(d_packed, n_frames, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, 2);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_frames_hmc(d_packed, n_frames, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_images, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+// the two host twins: the frame-major stack [n_frames][n_pairs][n_t] uploaded in its own type and packed in the arena, the pack
+// kernels called with one "transmit row" of n_pairs records (they see n samples per frame only)
+static int tfm_frames_hmc_host(const void* hmc, bool i16, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                               int n_f, float* images, int device)
+{
+    int st = check_tfm_frames_hmc(hmc, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, i16 ? 4 : 2);
+    if (st) return st;
+    const int n_pairs = n_e * (n_e + 1) / 2;                          // (n_e <= RTUS_HMC_MAX_ELEMENTS: fits an int)
+    const size_t n = (size_t)n_pairs * n_t;                           // samples per frame
+    const size_t words = i16 ? rtus_fmc_pack_frames_i16_words(n_frames, 1, n_pairs, n_t) : rtus_fmc_pack_frames_floats(n_frames, 1, n_pairs, n_t);
+    if (!words) return RTUS_ERR_UNSUPPORTED;
+    const bool same = tt_tx == tt_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    short *dstack16 = nullptr, *dpacked16 = nullptr;
+    float *dstack = nullptr, *dpacked = nullptr, *dimg;
+    double *dtx, *drx = nullptr;
+    if (i16) S.in(dstack16, (const short*)hmc, n * n_frames);
+    else S.in(dstack, (const float*)hmc, n * n_frames);
+    S.in(dtx, tt_tx, (size_t)n_e * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_e * n_f);
+    S.out(dimg, images, (size_t)n_frames * n_f);
+    if (i16) S.scratch(dpacked16, words);
+    else S.scratch(dpacked, words);
+    if ((st = S.flush())) return st;
+    if (i16) {
+        LAUNCH_TRY(rtus_launch_fmc_pack_frames_i16(dstack16, n_frames, n, dpacked16, S.a->stream));
+        LAUNCH_TRY(rtus_launch_tfm_frames_hmc_i16(dpacked16, n_frames, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
+    } else {
+        LAUNCH_TRY(rtus_launch_fmc_pack_frames(dstack, n_frames, n, dpacked, S.a->stream));
+        LAUNCH_TRY(rtus_launch_tfm_frames_hmc(dpacked, n_frames, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, S.a->stream));
+    }
+    return S.finish();
+}
+
+int rtus_tfm_frames_hmc_i16(const short* hmc, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                            int n_f, float* images, int device)
+{
+    return tfm_frames_hmc_host(hmc, true, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, device);
+}
+
+int rtus_tfm_frames_hmc(const float* hmc, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                        int n_f, float* images, int device)
+{
+    return tfm_frames_hmc_host(hmc, false, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, device);
 }
 
 // ---------------------------------------------------------------------------- phase-coherence TFM: vcf, scf

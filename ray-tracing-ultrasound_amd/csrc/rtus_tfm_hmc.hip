@@ -18,6 +18,8 @@
 // A focal point's order of summation: blocks of sixteen columns ascending; in the block [c0, c0 + 16) first the rows above it
 // (i < c0 ascending, j ascending through the block), then the block's own triangle (i ascending, j ascending from i).  The tile
 // size decides only where a row's delays come from (LDS, or the tables for rows of earlier tiles): not a bit of the result.
+// The same body over a block of a packed STACK of half-matrix frames — four int16 frames or two float32 frames per 16-byte gather
+// (include/rtus.h: rtus_tfm_frames_hmc_i16, rtus_tfm_frames_hmc) — is at the end of the kernels: "stacks of half-matrix frames".
 #include <type_traits>
 #include "rtus_das.h"
 
@@ -31,10 +33,10 @@
 #endif
 
 struct HmcArgs {
-    const float* __restrict__ hmc;       // [n_pairs][n_t] (analytic: [n_pairs][n_t][2])
+    const float* __restrict__ hmc;       // [n_pairs][n_t] (analytic: [n_pairs][n_t][2]; a stack: the launch's blocks of [n_pairs][n_t][P])
     const double* __restrict__ tt_tx;    // [n_e][n_f]
     const double* __restrict__ tt_rx;    // [n_e][n_f]
-    float* __restrict__ image;           // [n_f] (analytic: [n_f][2])
+    float* __restrict__ image;           // [n_f] (analytic: [n_f][2]; a stack: the launch's rows of [n_frames][n_f])
     float* __restrict__ cf;              // [n_f] (read by the CF instantiations only)
     int n_e, n_t, n_f;
     double fs, half_t0s;
@@ -80,8 +82,9 @@ template <> struct HmcTau<true> { typedef float2 type; };
 // (r, c), kind, weight and LDS offset becomes a constant, and the triangle's batches have the fixed-shape batches' instruction
 // stream (the walk itself costs ~25 scalar and 2 vector instructions per record).
 // lerp: the step from a loaded pair to the interpolated sample (rtus_das.h: DasLerp, or DasIq for the carrier-aware kernels).
-template <int C, bool CF, bool TWO, bool TRI, int NR = 0, class Lerp>
-__device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, size_t len, size_t step, int n_t, int nr_,
+// Sum: the focal point's sums, one(sample, wgt) / two(sample, sample, kind) on what lerp returns (HmcSum, or HmcSum4 for a quad).
+template <int C, bool TWO, bool TRI, int NR = 0, class Sum, class Lerp>
+__device__ __forceinline__ void hmc_walk(Sum& sum, const float* rec, size_t len, size_t step, int n_t, int nr_,
                                          const typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], int lane, typename HmcTau<TWO>::type tr,
                                          const Lerp& lerp)
 {
@@ -131,7 +134,7 @@ __device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, s
                 sum.one(lerp(v, w), wgt[k]);
             });
         } else {
-            decltype(das_lerp(das_load2<C>(rec, n_t, 0), 0.0f)) first;
+            decltype(lerp(das_load2<C>(rec, n_t, 0), 0.0f)) first;
             float s_ji = 0.0f;
             auto at = [&](int k, const float*& q) {                   // slot 2 m: s_ij of the batch's record m, slot 2 m + 1: s_ji
                 const int m = k >> 1;
@@ -164,14 +167,29 @@ __device__ __forceinline__ void hmc_walk(HmcSum<C, CF>& sum, const float* rec, s
     if (left) batch(std::true_type());
 }
 
-template <int C, bool CF, bool TWO, class Lerp>
-__device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], const Lerp& lerp)
+// Where a body's workgroup stands: its block of 256 focal points, its capture's first record, its sums and where they go.
+// HmcImage: one capture, one image — the launch is the image (das_workgroup()).  HmcFrames (below): a quad or pair of a stack.
+template <int C, bool CF>
+struct HmcImage {
+    typedef HmcSum<C, CF> Sum;
+    __device__ __forceinline__ int block() const { return das_workgroup(); }
+    __device__ __forceinline__ const float* records(const HmcArgs& a, size_t) const { return a.hmc; }
+    __device__ __forceinline__ void store(const HmcArgs& a, int f, const Sum& sum) const
+    {
+        if constexpr (C == 1) a.image[f] = sum.re;
+        else ((float2*)a.image)[f] = make_float2(sum.re, sum.im);
+    }
+};
+
+template <int C, bool CF, bool TWO, class Lerp, class Where = HmcImage<C, CF>>
+__device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], const Lerp& lerp,
+                                         const Where& where = Where())
 {
     constexpr int TILE = TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE;
     static_assert(TILE % RTUS_DAS_GROUP == 0, "a tile is a whole number of column blocks");
     typedef typename HmcTau<TWO>::type Tau;
     const int lane = threadIdx.x;
-    const int f_raw = das_workgroup() * RTUS_BLOCK + lane;
+    const int f_raw = where.block() * RTUS_BLOCK + lane;
     const bool live = f_raw < a.n_f;
     const int f = live ? f_raw : a.n_f - 1;
     const size_t nf = (size_t)a.n_f, ne = (size_t)a.n_e;
@@ -181,7 +199,8 @@ __device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>:
         if constexpr (TWO) return make_float2(t, tfm_tau(a.tt_rx[(size_t)e * nf + f], a.fs, a.half_t0s));
         else return t;
     };
-    HmcSum<C, CF> sum;
+    const float* records = where.records(a, len);                     // record (0, 0) of the workgroup's capture
+    typename Where::Sum sum;
     int n_tx_ok = 0, n_rx_ok = 0;                                     // T[f], R[f] (CF only)
     for (int r0 = 0; r0 < a.n_e; r0 += TILE) {
         const int nr = min(TILE, a.n_e - r0);
@@ -198,23 +217,22 @@ __device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>:
         // block's own triangle (136 records of 2080 at 64 elements: 4 x 136 in all) pays for the walk across ragged rows
         for (int cb = 0; cb < nr; cb += RTUS_DAS_GROUP) {
             const int nb = min(RTUS_DAS_GROUP, nr - cb), cg = r0 + cb;   // the block's columns, its first one
-            const float* row = a.hmc + (size_t)cg * len;                 // record (i, cg): p(i, cg) = i n_e - i (i + 1) / 2 + cg
+            const float* row = records + (size_t)cg * len;                // record (i, cg): p(i, cg) = i n_e - i (i + 1) / 2 + cg
             size_t down = (ne - 1) * len;                                 // from (i, cg) to (i + 1, cg): n_e - 1 - i records
             // rows of earlier tiles: their delays come from memory (a load that a gather's batch must not wait for)
             for (int i = 0; i < r0; ++i, row += down, down -= len)
-                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tau(i), lerp);
+                hmc_walk<C, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tau(i), lerp);
             // rows of this tile above the block: their delays are in the tile
             for (int i = r0; i < cg; ++i, row += down, down -= len)
-                hmc_walk<C, CF, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tile[i - r0][lane], lerp);
+                hmc_walk<C, TWO, false>(sum, row, len, 0, a.n_t, nb, tile + cb, lane, tile[i - r0][lane], lerp);
             // the block's own triangle from (cg, cg) on; a row's records to the right of the block are stepped over
             const size_t past = (ne - (size_t)(cg + nb)) * len;
-            if (nb == RTUS_DAS_GROUP) hmc_walk<C, CF, TWO, true, RTUS_DAS_GROUP>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau(), lerp);
-            else hmc_walk<C, CF, TWO, true>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau(), lerp);
+            if (nb == RTUS_DAS_GROUP) hmc_walk<C, TWO, true, RTUS_DAS_GROUP>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau(), lerp);
+            else hmc_walk<C, TWO, true>(sum, row, len, past, a.n_t, nb, tile + cb, lane, Tau(), lerp);
         }
     }
     if (!live) return;
-    if constexpr (C == 1) a.image[f] = sum.re;
-    else ((float2*)a.image)[f] = make_float2(sum.re, sum.im);
+    where.store(a, f, sum);
     if constexpr (CF) {
         // as rtus_tfm_analytic_kernel: |S|^2 exact in fp64, N = T R, clamped to 1
         if constexpr (!TWO) n_rx_ok = n_tx_ok;
@@ -250,6 +268,96 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_hmc_iq_kernel(HmcArgs a, 
 {
     __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
     hmc_body<2, CF, TWO>(a, tile, iq);
+}
+
+// ---------------------------------------------------------------------------------------------- stacks of half-matrix frames
+// rtus_tfm_frames_hmc[_i16] (include/rtus.h; DESIGN.md §4 "TFM over half-matrix frame stacks"): the body above over one block of a
+// packed stack, packed[n_slow][n_pairs][n_t][P] — P = 2 float32 frames (a pair) or P = 4 int16 frames (a quad) sample-interleaved,
+// 8 bytes per sample position either way: the record shape hmc_body<2, ...> addresses for analytic data, len = 2 n_t floats.
+// Plane c of block q is frame P q + c; every plane has its own sum, fed exactly as HmcSum<1, false> feeds its one: frame k has the
+// bits of rtus_tfm_hmc on frame k as float32.  The workgroup order is rtus_tfm_frames.hip's (tfmf_workgroup, restated here).
+
+// the sums of the four planes of a quad: HmcSum<1, false>'s statements on each
+struct HmcSum4 {
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    __device__ __forceinline__ void one(float4 p, float wgt)
+    {
+        s0 = fmaf(wgt, p.x, s0);
+        s1 = fmaf(wgt, p.y, s1);
+        s2 = fmaf(wgt, p.z, s2);
+        s3 = fmaf(wgt, p.w, s3);
+    }
+    __device__ __forceinline__ void two(float4 p, float4 q, int kind)
+    {
+        s0 += HmcSum<1, false>::term(p.x, q.x, kind);
+        s1 += HmcSum<1, false>::term(p.y, q.y, kind);
+        s2 += HmcSum<1, false>::term(p.z, q.z, kind);
+        s3 += HmcSum<1, false>::term(p.w, q.w, kind);
+    }
+};
+
+// rtus_tfm_frames_i16_kernel's accumulate step up to the sum, as a Lerp: a dword of the 16-byte load holds two planes of one sample
+// (low half the even plane, high half the odd one, both signed); the eight halves sign-extended and converted (exact), then
+// das_lerp's fmaf(w, b - a, a) per plane.  A dropped load reads as zeros: (float)0 = +0.0, as the float kernels' dropped loads.
+struct DasQuadI16 {
+    static __device__ __forceinline__ float lo(unsigned v) { return (float)(int)(short)(v & 0xffffu); }
+    static __device__ __forceinline__ float hi(unsigned v) { return (float)((int)v >> 16); }
+    __device__ __forceinline__ float4 operator()(das_u32x4 v, float w) const
+    {
+        const float a0 = lo(v.x), a1 = hi(v.x), a2 = lo(v.y), a3 = hi(v.y);
+        const float b0 = lo(v.z), b1 = hi(v.z), b2 = lo(v.w), b3 = hi(v.w);
+        return make_float4(fmaf(w, b0 - a0, a0), fmaf(w, b1 - a1, a1), fmaf(w, b2 - a2, a2), fmaf(w, b3 - a3, a3));
+    }
+};
+
+// A workgroup of a launch over n_slow blocks of P frames: blockIdx.x = slow * n_blk + b, n_blk = ceil(n_f / 256) workgroups per
+// image, b through das_workgroup()'s rule on n_blk.  n_frames: the frames of the launch; the rows of the absent frames of its last
+// block do not exist and are not written.
+template <int P>
+struct HmcFrames {
+    typedef std::conditional_t<P == 4, HmcSum4, HmcSum<2, false>> Sum;
+    int n_frames, n_blk;
+    __device__ __forceinline__ int slow() const { return blockIdx.x / n_blk; }
+    __device__ __forceinline__ int block() const
+    {
+        const int b = blockIdx.x - slow() * n_blk, per = (n_blk + 7) >> 3;
+        return (n_blk & 7) ? b : (b & 7) * per + (b >> 3);            // (ragged grids keep the plain order)
+    }
+    __device__ __forceinline__ const float* records(const HmcArgs& a, size_t len) const
+    {
+        const size_t n_pairs = (size_t)a.n_e * ((size_t)a.n_e + 1) / 2;
+        return a.hmc + (size_t)slow() * (n_pairs * len);
+    }
+    __device__ __forceinline__ void store(const HmcArgs& a, int f, const Sum& sum) const
+    {
+        const size_t nf = (size_t)a.n_f;
+        const int have = n_frames - P * slow();
+        float* img = a.image + (size_t)(P * slow()) * nf + f;
+        if constexpr (P == 4) {
+            img[0] = sum.s0;
+            if (have > 1) img[nf] = sum.s1;
+            if (have > 2) img[2 * nf] = sum.s2;
+            if (have > 3) img[3 * nf] = sum.s3;
+        } else {
+            img[0] = sum.re;
+            if (have > 1) img[nf] = sum.im;
+        }
+    }
+};
+
+template <bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_frames_hmc_i16_kernel(HmcArgs a, HmcFrames<4> frames)
+{
+    __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
+    hmc_body<2, false, TWO>(a, tile, DasQuadI16(), frames);
+}
+
+// float32 pairs: the analytic body itself (each plane rtus_tfm_hmc of that plane) with the frames' base and epilogue
+template <bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_frames_hmc_f32_kernel(HmcArgs a, HmcFrames<2> frames)
+{
+    __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
+    hmc_body<2, false, TWO>(a, tile, DasLerp(), frames);
 }
 
 static HmcArgs hmc_args(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
@@ -299,4 +407,46 @@ hipError_t rtus_launch_tfm_iq_hmc(const float* an, int n_e, int n_t, double fs, 
     else if (two) hipLaunchKernelGGL((rtus_tfm_hmc_iq_kernel<false, true>), grid, block, 0, s, a, iq);
     else hipLaunchKernelGGL((rtus_tfm_hmc_iq_kernel<false, false>), grid, block, 0, s, a, iq);
     return hipGetLastError();
+}
+
+long long rtus_tfm_frames_blocks(int n_slow, int n_f);                // rtus_tfm_frames.hip
+
+// P frames per block (2: float32 pairs, 4: int16 quads), the blocks cut into launches by rtus_tfm_frames.hip's rule: about 2304
+// workgroups per launch, one block per launch from 1153 workgroups per image on.  packed: [n_slow][n_pairs][n_t][P], in 8-byte
+// sample positions either way.  No bit depends on the cut: a lane's sums depend on its focal point and its plane only.
+#define RTUS_HMCF_LAUNCH_BLOCKS 2304
+template <int P>
+static hipError_t hmc_frames_launch(const float* packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                    const double* tt_rx, int n_f, float* images, hipStream_t s)
+{
+    const int n_blk = (int)rtus_tfm_frames_blocks(1, n_f), n_slow = (n_frames + P - 1) / P;
+    int m = RTUS_HMCF_LAUNCH_BLOCKS / n_blk > 1 ? RTUS_HMCF_LAUNCH_BLOCKS / n_blk : 1;
+    m = m < n_slow ? m : n_slow;
+    const size_t block_len = (size_t)n_e * ((size_t)n_e + 1) / 2 * (size_t)n_t * 2;   // floats per block
+    for (int q0 = 0; q0 < n_slow; q0 += m) {                          // blocks [q0, q0 + m): frames P q0 .. of the stack
+        const int frames = n_frames - P * q0 < P * m ? n_frames - P * q0 : P * m;
+        const HmcArgs a = hmc_args(packed + (size_t)q0 * block_len, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images + (size_t)(P * q0) * n_f, nullptr);
+        const HmcFrames<P> where = {frames, n_blk};
+        const dim3 grid((unsigned)rtus_tfm_frames_blocks((frames + P - 1) / P, n_f)), block(RTUS_BLOCK);
+        if constexpr (P == 4) {
+            if (tt_tx == tt_rx) hipLaunchKernelGGL(rtus_tfm_frames_hmc_i16_kernel<false>, grid, block, 0, s, a, where);
+            else hipLaunchKernelGGL(rtus_tfm_frames_hmc_i16_kernel<true>, grid, block, 0, s, a, where);
+        } else {
+            if (tt_tx == tt_rx) hipLaunchKernelGGL(rtus_tfm_frames_hmc_f32_kernel<false>, grid, block, 0, s, a, where);
+            else hipLaunchKernelGGL(rtus_tfm_frames_hmc_f32_kernel<true>, grid, block, 0, s, a, where);
+        }
+    }
+    return hipGetLastError();
+}
+
+hipError_t rtus_launch_tfm_frames_hmc_i16(const short* packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                          const double* tt_rx, int n_f, float* images, hipStream_t s)
+{
+    return hmc_frames_launch<4>((const float*)packed, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, s);
+}
+
+hipError_t rtus_launch_tfm_frames_hmc(const float* packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx,
+                                      const double* tt_rx, int n_f, float* images, hipStream_t s)
+{
+    return hmc_frames_launch<2>(packed, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, s);
 }

@@ -548,6 +548,45 @@ def tfm_hmc_dev(hmc, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
     return out
 
 
+def _tfm_frames_hmc_dev(entry, per, dtype, packed, n_frames, fs, tt_tx, tt_rx, t0, out):
+    """tfm_frames_hmc_i16_dev (per = 4 frames a block) and tfm_frames_hmc_dev (per = 2)"""
+    _chk(packed, "packed", dtype); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_frames = int(n_frames)
+    what = f"packed [n_blocks, n_pairs, n_t, {per}]"
+    if packed.dim() != 4 or packed.shape[3] != per or packed.shape[0] < 1 or (n_frames + per - 1) // per != packed.shape[0] or n_frames < 1:
+        raise ValueError(f"need {what} and n_frames in [{per} n_blocks - {per - 1}, {per} n_blocks]")
+    ok = tt_tx.dim() == 2 and tt_rx.dim() == 2 and tt_tx.shape == tt_rx.shape
+    n_e = tt_tx.shape[0] if ok else 0
+    if not ok or n_e < 1 or n_e * (n_e + 1) // 2 != packed.shape[1]:
+        raise ValueError(f"need {what} with n_pairs = n_e (n_e + 1) / 2, tt_tx [n_e, n], tt_rx [n_e, n]")
+    n_f = tt_tx.shape[1]
+    out = _result(out, (n_frames, n_f), packed, torch.float32)
+    if not (out.device == packed.device == tt_tx.device == tt_rx.device):
+        raise ValueError("out must be on the device of packed / tt_tx / tt_rx")
+    st = getattr(_lib.lib(), entry)(_p(packed), n_frames, n_e, packed.shape[2], float(fs), float(t0), _p(tt_tx), _p(tt_rx), n_f, _p(out),
+                                    _stream(packed))
+    _lib.check(st, entry)
+    return out
+
+
+def tfm_frames_hmc_i16_dev(packed, n_frames, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
+    """TFM over a stack of int16 half-matrix frames on device (rtus_tfm_frames_hmc_i16_dev; api.tfm_frames(hmc=True)'s definition):
+    ``packed`` int16 [n_quads, n_pairs, n_t, 4] — fmc_pack_frames_i16_dev(stack.view(n_frames, 1, n_pairs, n_t))[:, 0] makes it —
+    ``n_frames`` in [4 n_quads - 3, 4 n_quads], tt_tx / tt_rx [n_e, n_f] (default: tt_tx — one table: every record gathered once) ->
+    out float32 [n_frames, n_f]; row k has tfm_hmc_dev's bits on frame k converted to float32.  One call, a few launches;
+    asynchronous on the current stream (capturable with a pre-allocated output)."""
+    return _tfm_frames_hmc_dev("rtus_tfm_frames_hmc_i16_dev", 4, torch.int16, packed, n_frames, fs, tt_tx, tt_rx, t0, out)
+
+
+def tfm_frames_hmc_dev(packed, n_frames, fs, tt_tx, tt_rx=None, t0=0.0, out=None):
+    """TFM over a stack of float32 half-matrix frames on device (rtus_tfm_frames_hmc_dev): ``packed`` float32
+    [n_fpairs, n_pairs, n_t, 2] — fmc_pack_frames_dev(stack.view(n_frames, 1, n_pairs, n_t))[:, 0] makes it — ``n_frames`` =
+    2 n_fpairs or 2 n_fpairs - 1, tables as tfm_frames_hmc_i16_dev -> out float32 [n_frames, n_f]; row k has tfm_hmc_dev's bits on
+    frame k.  Asynchronous on the current stream (capturable with a pre-allocated output)."""
+    return _tfm_frames_hmc_dev("rtus_tfm_frames_hmc_dev", 2, torch.float32, packed, n_frames, fs, tt_tx, tt_rx, t0, out)
+
+
 def tfm_analytic_hmc_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None):
     """Envelope TFM over a half-matrix capture on device (rtus_tfm_analytic_hmc_dev; api.tfm_analytic_hmc's definition): analytic
     float32 [n_pairs, n_t, 2], tt_tx / tt_rx [n_e, n_f] (default: tt_tx) -> out float32 [n_f, 2] (the complex sum); ``cf``: an

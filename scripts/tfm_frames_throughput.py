@@ -12,7 +12,15 @@ In the child: CUDA events around each route, outputs preallocated, a warm-up of 
 timed in turn WITHIN each repetition, so that a drift of the clocks falls on all of them alike.  One JSON line per shape: median and
 [5 %, 95 %] of each route in us, the ratios of the medians, whether the stack calls gave the loops' bits, and the pass bar: a stack
 route is "no slower" when its median is within the run-to-run spread of its loop, i.e. not above the loop's 95th percentile.
-    python scripts/tfm_frames_throughput.py [--reps 50] [--rf-only] > profiles/tfm_frames_kernel.txt"""
+    python scripts/tfm_frames_throughput.py [--reps 50] [--rf-only] > profiles/tfm_frames_kernel.txt
+
+--hmc: the half-matrix stack instead (rtus_tfm_frames_hmc_i16_dev, rtus_tfm_frames_hmc_dev): n_frames captures of the 2080 records
+with tx <= rx, int16, the same six shapes, one table and two (an equal copy through another pointer).  Routes:  (a) n_frames calls of
+tfm_hmc_dev on the float32 frames;  (b) tfm_frames_i16_dev on the stack expanded to full matrices, already packed (and with its pack);
+(h) int16 pack + tfm_frames_hmc_i16_dev, and on an already packed stack;  (f) float32 pack + tfm_frames_hmc_dev, and packed.  The bar:
+(h) with its pack below (a) and (b) with one table at 8 and 32 frames.  --host-twins: the wall time of tfm_frames(hmc=True) on int16
+against a loop of tfm_hmc on float32 frames and tfm_frames on the expanded int16 stack, 8 frames.
+    python scripts/tfm_frames_throughput.py --hmc --host-twins > profiles/tfm_frames_hmc_kernel.txt"""
 import argparse
 import json
 import os
@@ -29,6 +37,7 @@ ap.add_argument("--rf-only", action="store_true", help="skip the envelope routes
 ap.add_argument("--limit", type=int, default=240, help="seconds a shape's child process may take")
 ap.add_argument("--frames", type=int, nargs="+", help="stack lengths instead of 8, 9 and 32")
 ap.add_argument("--host-twins", action="store_true", help="also time the host twins, float32 against int16, on the 8-frame shapes")
+ap.add_argument("--hmc", action="store_true", help="measure the half-matrix stack routes instead")
 ap.add_argument("--shape", type=int, nargs=2, metavar=("N_FRAMES", "N"), help="(child) measure this one shape")
 a = ap.parse_args()
 
@@ -38,7 +47,7 @@ if a.shape is None:
     for n_frames, n in SHAPES:
         cmd = [sys.executable, os.path.abspath(__file__), "--shape", str(n_frames), str(n), "--elements", str(a.elements),
                "--samples", str(a.samples), "--reps", str(a.reps)] + (["--rf-only"] if a.rf_only else []) \
-            + (["--host-twins"] if a.host_twins else [])
+            + (["--host-twins"] if a.host_twins else []) + (["--hmc"] if a.hmc else [])
         try:
             r = subprocess.run(cmd, timeout=a.limit)
         except subprocess.TimeoutExpired:
@@ -56,8 +65,9 @@ n_frames, n = a.shape
 n_e, n_t = a.elements, a.samples
 fs, c1 = 50e6, 1480.0
 g = torch.Generator(device="cuda").manual_seed(1)
-stack_i16 = torch.randint(-32768, 32768, (n_frames, n_e, n_e, n_t), generator=g, dtype=torch.int16, device="cuda")
-stack = stack_i16.to(torch.float32)
+if not a.hmc:
+    stack_i16 = torch.randint(-32768, 32768, (n_frames, n_e, n_e, n_t), generator=g, dtype=torch.int16, device="cuda")
+    stack = stack_i16.to(torch.float32)
 xe = ((torch.arange(n_e, dtype=torch.float64, device="cuda") - (n_e - 1) / 2) * 0.25e-3).contiguous()
 ze = torch.zeros(n_e, dtype=torch.float64, device="cuda")
 x0, dx, z_lo, dz = -0.008, 0.016 / (n - 1), 0.004, 0.016 / (n - 1)           # the record holds 30 mm of water: all inside
@@ -66,6 +76,114 @@ pz = (z_lo + dz * torch.arange(n, dtype=torch.float64, device="cuda"))[None, :].
 tt = (torch.hypot(xe[:, None] - px[None, :], ze[:, None] - pz[None, :]) / c1).contiguous()         # straight-ray table, one for both legs
 n_f = n * n
 new = lambda *shape: torch.empty(shape, dtype=torch.float32, device="cuda")   # noqa: E731
+
+
+def pct(v, q):
+    v = sorted(v)
+    return v[min(len(v) - 1, max(0, round(q * (len(v) - 1))))]
+
+
+def measure(routes):
+    """every route once (code objects loaded, buffers touched), once more, then a.reps repetitions with the routes timed in turn -> us"""
+    for _ in range(2):
+        for fn in routes.values():
+            fn()
+        torch.cuda.synchronize()
+    runs = {k: [] for k in routes}
+    for _ in range(a.reps):
+        for k, fn in routes.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            fn()
+            t1.record()
+            t1.synchronize()
+            runs[k].append(t0.elapsed_time(t1) * 1e3)
+    return runs
+
+
+if a.hmc:
+    n_pairs = n_e * (n_e + 1) // 2
+    hmc_i16 = torch.randint(-32768, 32768, (n_frames, n_pairs, n_t), generator=g, dtype=torch.int16, device="cuda")
+    hmc_f32 = hmc_i16.to(torch.float32)
+    iu = torch.triu_indices(n_e, n_e, device="cuda")
+    rec = torch.empty((n_e, n_e), dtype=torch.long, device="cuda")
+    rec[iu[0], iu[1]] = torch.arange(n_pairs, device="cuda")
+    rec[iu[1], iu[0]] = torch.arange(n_pairs, device="cuda")
+    full = hmc_i16[:, rec.reshape(-1)].view(n_frames, n_e, n_e, n_t)             # (b)'s input: the stack expanded to full matrices, once
+    full_packed = dev.fmc_pack_frames_i16_dev(full)
+    q16 = dev.fmc_pack_frames_i16_dev(hmc_i16[:, None])
+    q32 = dev.fmc_pack_frames_dev(hmc_f32[:, None])
+    result = dict(lib=os.environ.get("RTUS_LIB", "in-tree"), mode="hmc", elements=n_e, samples=n_t, n_frames=n_frames, pixels=f"{n}x{n}", reps=a.reps,
+                  device_MB=dict(hmc_int16_packed=round(q16.numel() * 2 / 1e6, 1), hmc_float32_frames=round(hmc_f32.numel() * 4 / 1e6, 1),
+                                 full_int16_packed=round(full_packed.numel() * 2 / 1e6, 1)))
+    for tables, tr in (("one_table", None), ("two_tables", tt.clone())):
+        out = {k: new(n_frames, n_f) for k in ("a", "b", "b_pack", "h", "h_packed", "f", "f_packed")}
+
+        def a_loop():
+            for k in range(n_frames):
+                dev.tfm_hmc_dev(hmc_f32[k], fs, tt, tr, out=out["a"][k])
+
+        def b_with_pack():
+            dev.fmc_pack_frames_i16_dev(full, out=full_packed)
+            dev.tfm_frames_i16_dev(full_packed, n_frames, fs, tt, tr, out=out["b_pack"])
+
+        def h_with_pack():
+            dev.fmc_pack_frames_i16_dev(hmc_i16[:, None], out=q16)
+            dev.tfm_frames_hmc_i16_dev(q16[:, 0], n_frames, fs, tt, tr, out=out["h"])
+
+        def f_with_pack():
+            dev.fmc_pack_frames_dev(hmc_f32[:, None], out=q32)
+            dev.tfm_frames_hmc_dev(q32[:, 0], n_frames, fs, tt, tr, out=out["f"])
+        routes = {"a_loop_of_tfm_hmc_dev": a_loop,
+                  "b_tfm_frames_i16_dev_full_matrix_packed": lambda: dev.tfm_frames_i16_dev(full_packed, n_frames, fs, tt, tr, out=out["b"]),
+                  "b_full_matrix_pack_and_tfm_frames_i16_dev": b_with_pack,
+                  "h_i16_pack_and_tfm_frames_hmc_i16_dev": h_with_pack,
+                  "h_tfm_frames_hmc_i16_dev_packed": lambda: dev.tfm_frames_hmc_i16_dev(q16[:, 0], n_frames, fs, tt, tr, out=out["h_packed"]),
+                  "f_pack_and_tfm_frames_hmc_dev": f_with_pack,
+                  "f_tfm_frames_hmc_dev_packed": lambda: dev.tfm_frames_hmc_dev(q32[:, 0], n_frames, fs, tt, tr, out=out["f_packed"])}
+        runs = measure(routes)
+        med = {k: pct(v, 0.5) for k, v in runs.items()}
+        h, a_, b_ = med["h_i16_pack_and_tfm_frames_hmc_i16_dev"], med["a_loop_of_tfm_hmc_dev"], med["b_tfm_frames_i16_dev_full_matrix_packed"]
+        result[tables] = dict(
+            per_frame_us={k: round(v / n_frames, 1) for k, v in med.items()},
+            p05_p95_per_frame_us={k: [round(pct(v, 0.05) / n_frames, 1), round(pct(v, 0.95) / n_frames, 1)] for k, v in runs.items()},
+            ratio=dict(h_over_a=round(h / a_, 3), h_over_b=round(h / b_, 3),
+                       h_packed_over_a=round(med["h_tfm_frames_hmc_i16_dev_packed"] / a_, 3),
+                       h_packed_over_b=round(med["h_tfm_frames_hmc_i16_dev_packed"] / b_, 3),
+                       f_over_a=round(med["f_pack_and_tfm_frames_hmc_dev"] / a_, 3),
+                       f_packed_over_a=round(med["f_tfm_frames_hmc_dev_packed"] / a_, 3)),
+            bits_equal_the_loop={k: bool(torch.equal(out[k], out["a"])) for k in ("h", "h_packed", "f", "f_packed")},
+            # rounding differs between the half- and the full-matrix order of summation: (b) is compared by its size only
+            b_relative_difference=float(((out["b"] - out["a"]).abs().max() / out["a"].abs().max()).item()))
+    if a.host_twins and n_frames == 8:
+        import time
+        import numpy as np
+        rtus = import_module("ray-tracing-ultrasound_amd")
+        h_i16, full_i16 = hmc_i16.cpu().numpy(), full.cpu().numpy()
+        h_f32, h_tt = h_i16.astype(np.float32), tt.cpu().numpy()
+        h_out = {k: np.empty((n_frames, n_f), dtype=np.float32) for k in ("hmc_int16", "loop_of_tfm_hmc_float32", "full_matrix_int16")}
+
+        def loop_of_tfm_hmc():
+            for k in range(n_frames):
+                rtus.tfm_hmc(h_f32[k], fs, h_tt, out=h_out["loop_of_tfm_hmc_float32"][k])
+        calls = {"hmc_int16": lambda: rtus.tfm_frames(h_i16, fs, h_tt, hmc=True, out=h_out["hmc_int16"]),
+                 "loop_of_tfm_hmc_float32": loop_of_tfm_hmc,
+                 "full_matrix_int16": lambda: rtus.tfm_frames(full_i16, fs, h_tt, out=h_out["full_matrix_int16"])}
+        wall = {k: [] for k in calls}
+        for r in range(7):                                                   # (the first two: the arena grows, pages are touched)
+            for k, fn in calls.items():
+                t = time.perf_counter()
+                fn()
+                if r >= 2:
+                    wall[k].append((time.perf_counter() - t) * 1e3)
+        result.update(host_twin_wall_ms={k: round(pct(v, 0.5), 2) for k, v in wall.items()},
+                      host_twin_wall_ms_min_max={k: [round(min(v), 2), round(max(v), 2)] for k, v in wall.items()},
+                      host_twin_bits_equal=bool(np.array_equal(h_out["hmc_int16"], h_out["loop_of_tfm_hmc_float32"])),
+                      host_twin_upload_MB={"hmc_int16": round(h_i16.nbytes / 1e6, 1), "loop_of_tfm_hmc_float32": round(h_f32.nbytes / 1e6, 1),
+                                           "full_matrix_int16": round(full_i16.nbytes / 1e6, 1)})
+    print(json.dumps(result), flush=True)
+    sys.exit(0)
+
 packed = dev.fmc_pack_frames_dev(stack)
 packed_i16 = dev.fmc_pack_frames_i16_dev(stack_i16)
 loop_out, stack_out, packed_out = new(n_frames, n_f), new(n_frames, n_f), new(n_frames, n_f)
@@ -121,11 +239,6 @@ for _ in range(a.reps):
         t1.record()
         t1.synchronize()
         runs[k].append(t0.elapsed_time(t1) * 1e3)                            # us
-
-
-def pct(v, q):
-    v = sorted(v)
-    return v[min(len(v) - 1, max(0, round(q * (len(v) - 1))))]
 
 
 med = {k: pct(v, 0.5) for k, v in runs.items()}
