@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 123 /* 0.1.22: rtus_tfm_frames_hmc[_i16] (TFM over a stack of half-matrix frames) */
+#define RTUS_VERSION 124 /* 0.1.23: rtus_tfm_phase_hmc, rtus_tfm_weighted_hmc (phase coherence and weighted TFM over a half matrix) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -1481,6 +1481,85 @@ int rtus_skip_reflector_dev(const double *d_tt_down, int n_e, const double *d_xb
                             double *d_tt, double *d_pos, int *d_n_min, void *stream);
 int rtus_skip_reflector(const double *tt_down, int n_e, const double *xb, const double *zb, int n_p, double c_up,
                         const double *xf, const double *zf, int n_f, double *tt, double *pos, int *n_min, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_phase_hmc: rtus_tfm_phase over a HALF-MATRIX CAPTURE — rtus_tfm_analytic_hmc's delay-and-sum over the packed triangle
+ * with the vector and sign coherence factors.  NOT IN THE REFERENCE; checked against tests/tfm_hmc_ext_numpy.py and against
+ * rtus_tfm_phase on the unpacked capture.
+ *   a [n_pairs][n_t][2], n_e, n_t, fs, t0, tt_tx, tt_rx [n_e][n_f] (the two may be one table), n_f: rtus_tfm_analytic_hmc's.
+ *   The sample positions, the interpolation, the edge rules, the no-path rule, the pair rule and the order of summation are exactly
+ *           rtus_tfm_analytic_hmc's (blocks of 16 columns; the rows above a block, then the block's triangle).
+ *   image   [n_f][2]  BIT-IDENTICAL to rtus_tfm_analytic_hmc's image, whichever of the other outputs are asked for.
+ *   Per record (i, j), i < j: the two samples p1 = a_ij(s_ij) and p2 = a_ij(s_ji); the diagonal has p1 = a_ii(s_ii) only.
+ *   N = T R, rtus_tfm_analytic_hmc's count (R = T with one table).  As in rtus_tfm_phase a leg pair with a path whose position is
+ *           outside the record counts in N with a zero phasor and a zero sign.
+ *   U       accumulates u(p1) + u(p2) — the two of a pair added to each other FIRST, then to the running sum as one term; the
+ *           diagonal u(p1) — in fp32 in the fixed order; u is rtus_tfm_phase's unit phasor (the same statements).
+ *   One table (tt_tx == tt_rx as pointers): p1 == p2 bit for bit, so the record is gathered ONCE and U = fmaf(wgt, u(p1), U) with
+ *           wgt = 2 off the diagonal, 1 on it: U + (u + u) in one rounding, the bits of the two-table form called with two equal
+ *           tables.
+ *   B       accumulates sign(Re p1) + sign(Re p2) (the diagonal sign(Re p1)) as an int32, exact; with one table the one sign is
+ *           added twice off the diagonal.
+ *   vcf, scf [n_f] float32, counts [n_f][2] int32 (B, N), all nullable: rtus_tfm_phase's formulas, clamps and NaN rule, formed in
+ *           fp64 from the sums.  An output that is not asked for costs nothing in the gather loop.
+ *   Consequence: counts and scf are BIT FOR BIT rtus_tfm_phase's on the unpacked capture (record (i, j) at [i][j] and [j][i]) with
+ *           the same table(s), for any finite data: every pair's sample has the same bits in both forms — the same fp32 position,
+ *           the same two loaded samples, the same fmaf — and B and N are integers, whose sums have no order.  vcf differs by the
+ *           order of the fp32 sum of U alone.
+ *   Determinism: the bits of a focal point depend only on its own columns of the tables; no output's bits depend on which other
+ *           outputs are asked for.
+ *   Limits: rtus_tfm_analytic_hmc's (image required; vcf, scf, counts nullable) and n_e^2 <= 2^30 (the sign sum is an int32; with
+ *           n_e <= 32768 that is always so): -1 for invalid arguments, -5 past a limit, before any HIP call.  The _dev entry
+ *           allocates nothing and does not synchronise (capturable).  The host twin stages through the arena (one table uploaded
+ *           when tt_tx == tt_rx, only the outputs asked for downloaded).
+ *
+ * rtus_tfm_weighted_hmc: rtus_tfm_weighted over a half-matrix capture — ray-amplitude weighting and the sensitivity P, which put
+ * the views of a multi-view inspection on one scale (|S| / P).  NOT IN THE REFERENCE; checked against tests/tfm_hmc_ext_numpy.py
+ * and against rtus_tfm_weighted on the unpacked capture.
+ *   a, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f: rtus_tfm_analytic_hmc's;  w_tx, w_rx [n_e][n_f][2] interleaved complex float32, both
+ *           required (they may be one table);  image [n_f][2];  sens [n_f] float32, nullable.
+ *   Legs:   element i's transmit leg has a path only if tt_tx[i] has one (rtus_tfm's rule) AND both parts of w_tx[i] are finite;
+ *           its receive leg likewise from tt_rx[i] and w_rx[i].  A leg without a path contributes nothing and cannot poison the
+ *           pixel: its weight counts as 0 (and, with two delay tables, its delay as the no-path value).
+ *   Terms:  W_ij = w_tx[i] w_rx[j];  c_ii = W_ii a_ii(s_ii);  c_ij = W_ij a_ij(s_ij) + W_ji a_ij(s_ji) for i < j — the pair's two
+ *           terms added to each other FIRST, then to the running sum.  S = the sum of the c in rtus_tfm_hmc's order (blocks of 16
+ *           columns).  In exact arithmetic this is rtus_tfm_weighted on the symmetric full matrix.
+ *   The fp32 statements (every product and sum rounded by itself but inside an fmaf; a = (ar, ai), b = (br, bi)):
+ *             a b  :  re = fmaf(-ai, bi, ar br);   im = (ar bi) + (ai br)        — symmetric in a and b: a b == b a bit for bit,
+ *                                                                                  so ONE weight table for both legs gives W_ij == W_ji
+ *             W p  :  re = fmaf(-Wi, pi, Wr pr);   im = fmaf(Wr, pi, Wi pr)
+ *           two delay tables:  c = (W_ij p1) + (W_ji p2), each part one addition;  S.re += c.re;  S.im += c.im
+ *           one delay table (tt_tx == tt_rx as pointers; the weight tables may differ — every same-leg view "A-A", whose down and up
+ *           amplitudes are different tables): s_ij == s_ji bit for bit, the record is gathered ONCE:
+ *                              W = W_ij + W_ji, each part one addition (the diagonal: W = W_ii);  c = W p;  S += c as above.
+ *   sens    P = (sum over the transmit legs with a path of |w_tx|^2) (sum over the receive legs with a path of |w_rx|^2): BIT FOR
+ *           BIT rtus_tfm_weighted's sens on the same tables and weights — each sum the chain fmaf(wi, wi, fmaf(wr, wr, sum)) over
+ *           the elements ascending, in fp32; the product in fp64, rounded once.  Passing sens does not change the bits of image.
+ *   Determinism: the bits of a focal point depend only on its own columns of the tables and of the weights, and not on the size of
+ *           the kernel's tile.
+ *   Limits: rtus_tfm_analytic_hmc's; w_tx or w_rx null: -1.  The _dev entry allocates nothing and does not synchronise
+ *           (capturable).  The host twin stages through the arena (one delay table and one weight table uploaded where the
+ *           pointers are equal).
+ * Measured on MI355X (2026-10-21; DESIGN.md §4 "Half-matrix capture", profiles/tfm_hmc_phase_weighted_kernel.txt; CUDA-event timing;
+ * x = time / the full-matrix twin, rtus_tfm_phase_dev / rtus_tfm_weighted_dev on the unpacked capture with the same outputs, in the
+ * SAME run; rtus_tfm_analytic_hmc_dev in that run: 143.8 us and 1.052 ms): 64 elements x 2048 samples, one delay table, 256^2 focal
+ * points: phase image alone 143 us (0.53x), vcf 152 us (0.54x), scf 149 us (0.55x), all outputs 168 us (0.56x); weighted 233-235 us
+ * (0.56x), with sens 237 us (0.61-0.62x); 1024^2: phase 1.03 / 1.43 / 1.12 / 1.61 ms (0.53-0.55x); weighted 1.89-1.99 ms
+ * (0.62-0.68x).  Two delay tables: phase 0.75-1.10x; weighted 0.70-0.77x at 256^2 and 1.46-1.55x (slower than the twin) at 1024^2,
+ * where one workgroup per CU (96 KiB of LDS) binds.  Not measured: counters, kernel durations under a profiler.
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tfm_phase_hmc_dev(const float *d_a, int n_e, int n_t, double fs, double t0,
+                           const double *d_tt_tx, const double *d_tt_rx, int n_f,
+                           float *d_image, float *d_vcf, float *d_scf, int *d_counts, void *stream);
+int rtus_tfm_phase_hmc(const float *a, int n_e, int n_t, double fs, double t0,
+                       const double *tt_tx, const double *tt_rx, int n_f,
+                       float *image, float *vcf, float *scf, int *counts, int device);
+int rtus_tfm_weighted_hmc_dev(const float *d_a, int n_e, int n_t, double fs, double t0,
+                              const double *d_tt_tx, const double *d_tt_rx, const float *d_w_tx, const float *d_w_rx, int n_f,
+                              float *d_image, float *d_sens, void *stream);
+int rtus_tfm_weighted_hmc(const float *a, int n_e, int n_t, double fs, double t0,
+                          const double *tt_tx, const double *tt_rx, const float *w_tx, const float *w_rx, int n_f,
+                          float *image, float *sens, int device);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits, 
                   backwall_echo_layers, backwall_echo_surface, bore_echo_pipe, fit_reflector, measure_reflector,
                   skip_travel_time_reflector, reflector_mask, skip_travel_time_layers_profile, skip_travel_time_surface_profile,
                   view_legs_layers_profile, view_legs_surface_profile, backwall_profile,
-                  hmc_index, hmc_pack, hmc_unpack, hmc_analytic, tfm_hmc, tfm_analytic_hmc, tfm_iq, tfm_iq_hmc,
+                  hmc_index, hmc_pack, hmc_unpack, hmc_analytic, tfm_hmc, tfm_analytic_hmc, tfm_iq, tfm_iq_hmc, tfm_phase_hmc, tfm_weighted_hmc,
                   centre_frequency, frames_pack, frames_unpack, tfm_frames, frames_pack_i16, frames_unpack_i16)
 
 __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "solve_path", "SOLVE_PATHS", "focal_delays", "tfm_image", "fmc_analytic",
@@ -30,6 +30,6 @@ __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hi
            "backwall_echo_layers", "backwall_echo_surface", "bore_echo_pipe", "fit_reflector", "measure_reflector",
            "skip_travel_time_reflector", "reflector_mask", "skip_travel_time_layers_profile", "skip_travel_time_surface_profile",
            "view_legs_layers_profile", "view_legs_surface_profile", "backwall_profile", "hmc_index", "hmc_pack",
-           "hmc_unpack", "hmc_analytic", "tfm_hmc", "tfm_analytic_hmc", "tfm_iq", "tfm_iq_hmc", "centre_frequency", "frames_pack",
+           "hmc_unpack", "hmc_analytic", "tfm_hmc", "tfm_analytic_hmc", "tfm_iq", "tfm_iq_hmc", "tfm_phase_hmc", "tfm_weighted_hmc", "centre_frequency", "frames_pack",
            "frames_unpack", "tfm_frames", "frames_pack_i16", "frames_unpack_i16", "Params",
            "configure", "reference_elements", "ALPHA_MAX", "KEYS", "build", "lib", "RtusError"]

@@ -207,6 +207,11 @@ PROTOTYPES = (
     # skip legs off a sampled backwall
     ("rtus_skip_reflector_dev", i, [vp, i, vp, vp, i, dd, vp, vp, i, vp, vp, vp, vp], 117),
     ("rtus_skip_reflector", i, [vp, i, vp, vp, i, dd, vp, vp, i, vp, vp, vp, i], 117),
+    # phase coherence and weighted TFM over a half-matrix capture
+    ("rtus_tfm_phase_hmc_dev", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, vp], 124),
+    ("rtus_tfm_phase_hmc", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, i], 124),
+    ("rtus_tfm_weighted_hmc_dev", i, [vp, i, i, dd, dd, vp, vp, vp, vp, i, vp, vp, vp], 124),
+    ("rtus_tfm_weighted_hmc", i, [vp, i, i, dd, dd, vp, vp, vp, vp, i, vp, vp, i], 124),
 )
 EXPORTS = tuple(p[0] for p in PROTOTYPES)
 

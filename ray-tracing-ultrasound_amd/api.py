@@ -928,11 +928,12 @@ def _complex_hmc(a):
 def tfm_analytic_hmc(analytic_hmc, fs, tt_tx, tt_rx=None, *, t0=0.0, coherence=False, out=None, device=0):
     """tfm_analytic over a half-matrix capture: complex64 [n_pairs, n_t] (hmc_analytic's, or float32 [n_pairs, n_t, 2]) -> complex64
     image [n_f], each plane tfm_hmc of that plane bit for bit; with ``coherence=True`` (or "cf") -> (image, cf float32 [n_f]), the
-    coherence factor of tfm_analytic with E summed over both legs of every record.  "vcf" / "scf" raise ValueError: the
-    phase-coherence kernel has no half-matrix form.  Definition: include/rtus.h (rtus_tfm_analytic_hmc).  Not in the reference."""
+    coherence factor of tfm_analytic with E summed over both legs of every record.  "vcf" / "scf" raise ValueError here: call
+    tfm_phase_hmc, which returns the same image bits with both phase-coherence factors.  Definition: include/rtus.h
+    (rtus_tfm_analytic_hmc).  Not in the reference."""
     mode = _coherence(coherence)
     if mode in ("vcf", "scf"):
-        raise ValueError(f"coherence={mode!r} is not available on a half-matrix capture (tfm_phase has no HMC form): use 'cf'")
+        raise ValueError(f"coherence={mode!r} is not available from tfm_analytic_hmc: use 'cf', or call tfm_phase_hmc")
     a = _complex_hmc(analytic_hmc)
     n_e, tt_tx, tt_rx, n_f = _hmc_tables(a.shape[0], tt_tx, tt_rx)
     img = _out(out, (n_f,), np.complex64)
@@ -997,6 +998,26 @@ def _tfm_phase(analytic, fs, tt_tx, tt_rx, t0, want, counts, out, device):
     st = _lib.lib().rtus_tfm_phase(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f,
                                    _ptr(img), _ptr(r.get("vcf")), _ptr(r.get("scf")), _ptr(cnt), int(device))
     _lib.check(st, "rtus_tfm_phase")
+    if counts:
+        r["sign_sum"], r["n_pairs"] = np.ascontiguousarray(cnt[:, 0]), np.ascontiguousarray(cnt[:, 1])
+    return r
+
+
+def tfm_phase_hmc(analytic_hmc, fs, tt_tx, tt_rx=None, *, t0=0.0, counts=False, out=None, device=0):
+    """tfm_phase over a half-matrix capture: tfm_analytic_hmc's inputs (complex64 [n_pairs, n_t] or float32 [n_pairs, n_t, 2];
+    tt_tx / tt_rx [n_e, n_f], tt_rx defaults to tt_tx: one table, every record gathered once) and image bits, tfm_phase's returns:
+    -> dict(image complex64 [n_f], vcf float32 [n_f], scf float32 [n_f]); with ``counts=True`` also sign_sum (B) and n_pairs (N),
+    int32 [n_f].  Every record counts for (i, j) and for (j, i): the unit phasors and signs of its two samples (one on the
+    diagonal) go into U and B, N = T R.  sign_sum, n_pairs and scf are tfm_phase's on hmc_unpack(analytic_hmc) bit for bit; vcf
+    differs by the order of an fp32 sum.  Definition: include/rtus.h (rtus_tfm_phase_hmc).  Not in the reference."""
+    a = _complex_hmc(analytic_hmc)
+    n_e, tt_tx, tt_rx, n_f = _hmc_tables(a.shape[0], tt_tx, tt_rx)
+    img = _out(out, (n_f,), np.complex64)
+    r = {"image": img, "vcf": np.empty(n_f, dtype=np.float32), "scf": np.empty(n_f, dtype=np.float32)}
+    cnt = np.empty((n_f, 2), dtype=np.int32) if counts else None
+    st = _lib.lib().rtus_tfm_phase_hmc(_ptr(a), n_e, a.shape[1], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f, _ptr(img),
+                                       _ptr(r["vcf"]), _ptr(r["scf"]), _ptr(cnt), int(device))
+    _lib.check(st, "rtus_tfm_phase_hmc")
     if counts:
         r["sign_sum"], r["n_pairs"] = np.ascontiguousarray(cnt[:, 0]), np.ascontiguousarray(cnt[:, 1])
     return r
@@ -1264,15 +1285,16 @@ def tfm_views(fmc, fs, legs, views=VIEWS, *, t0=0.0, envelope=False, coherence=F
     each view is beamformed by tfm_weighted with w_tx = conj(down[A]) and w_rx = conj(up[reverse_leg(B)]) and the value is |S| / P,
     P the view's sensitivity (NaN where P = 0): a unit point scatterer reads 1 in every view that sees it, so views share one scale.
     ``hmc=True``: ``fmc`` is a half-matrix capture [n_pairs, n_t] (hmc_pack) and every view goes through tfm_hmc / tfm_analytic_hmc;
-    ``amplitudes`` and ``coherence="vcf"`` / ``"scf"`` have no half-matrix form and raise ValueError.
+    ``amplitudes`` and ``coherence="vcf"`` / ``"scf"`` raise ValueError with it: loop over the views with tfm_weighted_hmc (its
+    docstring shows the loop) or tfm_phase_hmc on hmc_analytic(fmc) instead.
     ``f_demod`` [Hz]: every view goes through tfm_iq / tfm_iq_hmc (carrier-aware interpolation) instead; it needs ``envelope=True``
     and raises ValueError together with ``amplitudes`` or ``coherence="vcf"`` / ``"scf"``.  None: exactly the paths above.
     An unknown view or a leg missing from ``legs`` (or ``amplitudes``) raises ValueError before any GPU call."""
     coherence = _coherence(coherence)
     if hmc and amplitudes is not None:
-        raise ValueError("amplitude weighting is not available on a half-matrix capture (tfm_weighted has no HMC form)")
+        raise ValueError("tfm_views does not weight a half-matrix capture: loop over the views with tfm_weighted_hmc")
     if hmc and coherence in ("vcf", "scf"):
-        raise ValueError(f"coherence={coherence!r} is not available on a half-matrix capture (tfm_phase has no HMC form)")
+        raise ValueError(f"tfm_views has no coherence={coherence!r} on a half-matrix capture: loop over the views with tfm_phase_hmc")
     if coherence and not envelope:
         raise ValueError("the coherence factor needs envelope=True")
     if amplitudes is not None and not envelope:
@@ -1423,6 +1445,46 @@ def tfm_weighted(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, *, t0=0.0, se
     st = _lib.lib().rtus_tfm_weighted(_ptr(a), a.shape[0], a.shape[1], a.shape[2], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx),
                                       _ptr(w_tx), _ptr(w_rx), n_f, _ptr(img), _ptr(sens), int(device))
     _lib.check(st, "rtus_tfm_weighted")
+    return (img, sens) if sensitivity else img
+
+
+def _hmc_weights(w, n_e, n_f, name):
+    """a weight table of tfm_weighted_hmc -> complex64 [n_e, n_f]; a real array is refused (it is not a view's amplitude)"""
+    w = np.asarray(w)
+    if not np.iscomplexobj(w):
+        raise ValueError(f"{name} must be complex64 [{n_e}, {n_f}] (got dtype {w.dtype})")
+    return _weights(w, n_e, n_f, name)
+
+
+def tfm_weighted_hmc(analytic_hmc, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, *, t0=0.0, sensitivity=False, out=None, device=0):
+    """tfm_weighted over a half-matrix capture: ``analytic_hmc`` complex64 [n_pairs, n_t] (hmc_analytic's, or float32
+    [n_pairs, n_t, 2]); tt_tx / tt_rx float64 [n_e, n_f]; w_tx / w_rx complex64 [n_e, n_f]; tt_rx and w_rx default to tt_tx and w_tx.
+    S[f] = sum over the records of W_ii a_ii(s_ii) and, for i < j, W_ij a_ij(s_ij) + W_ji a_ij(s_ji) with W_ij = w_tx[i] w_rx[j] —
+    tfm_weighted of hmc_unpack(analytic_hmc) up to the order of the fp32 sum; a leg with a non-finite weight contributes nothing.
+    With ONE delay table (tt_rx None or tt_tx itself; the weight tables may differ: every view "A-A") each record is gathered once
+    and weighted by W_ij + W_ji.  -> complex64 image [n_f]; with ``sensitivity=True`` -> (image, P float32 [n_f]), tfm_weighted's P
+    bit for bit.  Multi-view imaging of a packed capture, on one scale (tfm_views' ``amplitudes=`` for the full matrix)::
+
+        legs, amps = view_amplitudes_surface(...)            # {leg: tt}, {leg: (down, up)}
+        analytic = hmc_analytic(hmc)
+        for view in views:
+            a, b = view_tables(view)                         # the transmit leg A, reverse_leg(B)
+            w_tx, w_rx = np.conj(amps[a][0]), np.conj(amps[b][1])
+            # (a view "A-A": legs[b] is legs[a] — one delay table, two weight tables, every record gathered once)
+            S, P = tfm_weighted_hmc(analytic, fs, legs[a], w_tx, legs[b], w_rx, sensitivity=True)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                image[view] = np.where(P > 0, np.abs(S) / P, np.nan)
+
+    Definition: include/rtus.h (rtus_tfm_weighted_hmc).  Not in the reference."""
+    a = _complex_hmc(analytic_hmc)
+    n_e, tt_tx, tt_rx, n_f = _hmc_tables(a.shape[0], tt_tx, tt_rx)
+    w_tx = _hmc_weights(w_tx, n_e, n_f, "w_tx")
+    w_rx = w_tx if w_rx is None else _hmc_weights(w_rx, n_e, n_f, "w_rx")
+    img = _out(out, (n_f,), np.complex64)
+    sens = np.empty(n_f, dtype=np.float32) if sensitivity else None
+    st = _lib.lib().rtus_tfm_weighted_hmc(_ptr(a), n_e, a.shape[1], float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), _ptr(w_tx),
+                                          _ptr(w_rx), n_f, _ptr(img), _ptr(sens), int(device))
+    _lib.check(st, "rtus_tfm_weighted_hmc")
     return (img, sens) if sensitivity else img
 
 

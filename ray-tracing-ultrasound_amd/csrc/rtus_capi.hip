@@ -106,6 +106,10 @@ hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t
                                     hipStream_t s);
 hipError_t rtus_launch_tfm_phase(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                  const double* tt_rx, int n_f, float* image, float* vcf, float* scf, int* counts, hipStream_t s);
+hipError_t rtus_launch_tfm_phase_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                                     int n_f, float* image, float* vcf, float* scf, int* counts, hipStream_t s);
+hipError_t rtus_launch_tfm_weighted_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                                        const float* w_tx, const float* w_rx, int n_f, float* image, float* sens, hipStream_t s);
 hipError_t rtus_launch_leg_amp_surface(double x0, double dx, const double* zs, int n_s, double c1, double rho1, double c_l, double c_t,
                                        double rho2, double z_back, int leg, int up, double width, double f_c, const double* xe,
                                        const double* ze, int n_e, const double* xf, const double* zf, int n_f, const double* x_entry,
@@ -1808,6 +1812,91 @@ int rtus_tfm_weighted(const float* a, int n_tx, int n_rx, int n_t, double fs, do
     S.out(dsens, sens, n_f);
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tfm_weighted(da, n_tx, n_rx, n_t, fs, t0, dtx, drx, dwt, dwr, n_f, dimg, dsens, S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- phase-coherence and weighted TFM over a half matrix
+static int check_tfm_phase_hmc(const void* a, int n_e, int n_t, double fs, double t0, const void* tt_tx, const void* tt_rx, int n_f,
+                               const void* image)
+{
+    int st = check_tfm_hmc(a, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, true);         // (vcf, scf, counts are nullable)
+    if (st) return st;
+    if ((long long)n_e * n_e > (1LL << 30)) return RTUS_ERR_UNSUPPORTED;                 // the sign sum is an int32
+    return RTUS_OK;
+}
+
+int rtus_tfm_phase_hmc_dev(const float* d_a, int n_e, int n_t, double fs, double t0, const double* d_tt_tx, const double* d_tt_rx,
+                           int n_f, float* d_image, float* d_vcf, float* d_scf, int* d_counts, void* stream)
+{
+    int st = check_tfm_phase_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_phase_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, d_image, d_vcf, d_scf, d_counts,
+                                         (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_phase_hmc(const float* a, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
+                       float* image, float* vcf, float* scf, int* counts, int device)
+{
+    int st = check_tfm_phase_hmc(a, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image);
+    if (st) return st;
+    const size_t n_pairs = (size_t)n_e * ((size_t)n_e + 1) / 2;
+    const bool same = tt_tx == tt_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    float *da, *dimg, *dvcf, *dscf;
+    int* dcnt;
+    double *dtx, *drx = nullptr;
+    S.in(da, a, n_pairs * n_t * 2);
+    S.in(dtx, tt_tx, (size_t)n_e * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_e * n_f);
+    S.out(dimg, image, 2 * (size_t)n_f);
+    S.out(dvcf, vcf, n_f);
+    S.out(dscf, scf, n_f);
+    S.out(dcnt, counts, 2 * (size_t)n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tfm_phase_hmc(da, n_e, n_t, fs, t0, dtx, same ? dtx : drx, n_f, dimg, dvcf, dscf, dcnt, S.a->stream));
+    return S.finish();
+}
+
+static int check_tfm_weighted_hmc(const void* a, int n_e, int n_t, double fs, double t0, const void* tt_tx, const void* tt_rx,
+                                  const void* w_tx, const void* w_rx, int n_f, const void* image)
+{
+    if (!w_tx || !w_rx) return RTUS_ERR_INVALID_ARG;
+    return check_tfm_hmc(a, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, true);           // (sens is nullable)
+}
+
+int rtus_tfm_weighted_hmc_dev(const float* d_a, int n_e, int n_t, double fs, double t0, const double* d_tt_tx, const double* d_tt_rx,
+                              const float* d_w_tx, const float* d_w_rx, int n_f, float* d_image, float* d_sens, void* stream)
+{
+    int st = check_tfm_weighted_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, d_w_tx, d_w_rx, n_f, d_image);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tfm_weighted_hmc(d_a, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, d_w_tx, d_w_rx, n_f, d_image, d_sens,
+                                            (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tfm_weighted_hmc(const float* a, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                          const float* w_tx, const float* w_rx, int n_f, float* image, float* sens, int device)
+{
+    int st = check_tfm_weighted_hmc(a, n_e, n_t, fs, t0, tt_tx, tt_rx, w_tx, w_rx, n_f, image);
+    if (st) return st;
+    const size_t n_pairs = (size_t)n_e * ((size_t)n_e + 1) / 2, n = (size_t)n_e * n_f;
+    const bool same = tt_tx == tt_rx, same_w = w_tx == w_rx;          // one upload each; the one-delay-table kernel on `same`
+    Session S;
+    if ((st = S.open(device))) return st;
+    float *da, *dwt, *dwr = nullptr, *dimg, *dsens;
+    double *dtx, *drx = nullptr;
+    S.in(da, a, n_pairs * n_t * 2);
+    S.in(dtx, tt_tx, n);
+    if (!same) S.in(drx, tt_rx, n);
+    S.in(dwt, w_tx, 2 * n);
+    if (!same_w) S.in(dwr, w_rx, 2 * n);
+    S.out(dimg, image, 2 * (size_t)n_f);
+    S.out(dsens, sens, n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tfm_weighted_hmc(da, n_e, n_t, fs, t0, dtx, same ? dtx : drx, dwt, same_w ? dwt : dwr, n_f, dimg, dsens,
+                                            S.a->stream));
     return S.finish();
 }
 

@@ -155,3 +155,21 @@ __device__ __forceinline__ void das_batch(int n_t, At&& at, Accum&& accum)
 #pragma unroll
     for (int k = 0; k < RTUS_DAS_GROUP; ++k) accum(k, v[k], w[k]);
 }
+
+// What rtus_tfm_phase_kernel / rtus_tfm_weighted_kernel (rtus_tfm.hip) and their half-matrix forms (rtus_tfm_hmc.hip) share.
+// p / |p| for every non-zero finite p, (0, 0) for p = 0.  |p|^2 under- or overflows in fp32 from |p| ~ 1e-19 / 1e19 on, so both
+// parts are first scaled by the power of two that brings max(|re|, |im|) into [0.5, 1): exact (the smaller part may lose bits
+// below 2^-126 of the larger: nothing against 0.25 <= x^2 + y^2 < 2).  One v_rsq_f32 (1 ulp), two products.  No contraction: the
+// bits do not depend on what the compiler would fuse.
+__device__ __forceinline__ float2 tfmp_unit(float2 p)
+{
+#pragma clang fp contract(off)
+    const float m = fmaxf(fabsf(p.x), fabsf(p.y));
+    const int e = __builtin_amdgcn_frexp_expf(m);                     // m = [0.5, 1) x 2^e (0 for m = 0)
+    const float x = __builtin_amdgcn_ldexpf(p.x, -e), y = __builtin_amdgcn_ldexpf(p.y, -e);
+    const float r = m > 0.0f ? __builtin_amdgcn_rsqf(fmaf(y, y, x * x)) : 0.0f;   // rsq(0) 0 would be NaN
+    return make_float2(x * r, y * r);
+}
+
+// a weight that a leg of rtus_tfm_weighted can carry: both parts finite
+__device__ __forceinline__ bool tfmw_finite(float2 w) { return fabsf(w.x) <= 3.4e38f && fabsf(w.y) <= 3.4e38f; }   // NaN fails

@@ -285,20 +285,7 @@ struct TfmpArgs {
     double fs, half_t0s;
 };
 
-// p / |p| for every non-zero finite p, (0, 0) for p = 0.  |p|^2 under- or overflows in fp32 from |p| ~ 1e-19 / 1e19 on, so both
-// parts are first scaled by the power of two that brings max(|re|, |im|) into [0.5, 1): exact (the smaller part may lose bits
-// below 2^-126 of the larger: nothing against 0.25 <= x^2 + y^2 < 2).  One v_rsq_f32 (1 ulp), two products.  No contraction: the
-// bits do not depend on what the compiler would fuse.
-__device__ __forceinline__ float2 tfmp_unit(float2 p)
-{
-#pragma clang fp contract(off)
-    const float m = fmaxf(fabsf(p.x), fabsf(p.y));
-    const int e = __builtin_amdgcn_frexp_expf(m);                     // m = [0.5, 1) x 2^e (0 for m = 0)
-    const float x = __builtin_amdgcn_ldexpf(p.x, -e), y = __builtin_amdgcn_ldexpf(p.y, -e);
-    const float r = m > 0.0f ? __builtin_amdgcn_rsqf(fmaf(y, y, x * x)) : 0.0f;   // rsq(0) 0 would be NaN
-    return make_float2(x * r, y * r);
-}
-
+// (tfmp_unit, the unit phasor p / |p|: rtus_das.h — the half-matrix form sums the same phasors)
 template <bool PHASOR, bool SIGN>
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_phase_kernel(TfmpArgs a)
 {
@@ -404,8 +391,7 @@ struct TfmwArgs {
     double fs, half_t0s;
 };
 
-__device__ __forceinline__ bool tfmw_finite(float2 w) { return fabsf(w.x) <= 3.4e38f && fabsf(w.y) <= 3.4e38f; }   // NaN fails
-
+// (tfmw_finite, a weight that a leg can carry: rtus_das.h)
 template <bool SENS>
 __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_weighted_kernel(TfmwArgs a)
 {

@@ -83,10 +83,20 @@ template <> struct HmcTau<true> { typedef float2 type; };
 // stream (the walk itself costs ~25 scalar and 2 vector instructions per record).
 // lerp: the step from a loaded pair to the interpolated sample (rtus_das.h: DasLerp, or DasIq for the carrier-aware kernels).
 // Sum: the focal point's sums, one(sample, wgt) / two(sample, sample, kind) on what lerp returns (HmcSum, or HmcSum4 for a quad).
-template <int C, bool TWO, bool TRI, int NR = 0, class Sum, class Lerp>
+// Wts: the legs' weights beside the delays (HmcWts: rtus_tfm_hmc_weighted_kernel), or none (HmcNoWts: every other kernel, whose
+// instruction stream is what it was).  With weights a slot also keeps its (r, c) — wave-uniform, constants where the walk is
+// unrolled — and the sum gets one(sample, kind, row's weights, column's weights) / two(sample, sample, kind, ...): the column's
+// from the tile, the row's from the tile (TRI) or from the caller (a row above the block), read when the sample is consumed.
+struct HmcNoWts { static constexpr bool ON = false; };
+struct HmcWts {
+    static constexpr bool ON = true;
+    const float4 (*tile)[RTUS_BLOCK];                                 // (w_tx.re, w_tx.im, w_rx.re, w_rx.im) of the block's columns
+    float4 row;                                                       // the row's, where it is not one of the block's (!TRI)
+};
+template <int C, bool TWO, bool TRI, int NR = 0, class Sum, class Lerp, class Wts = HmcNoWts>
 __device__ __forceinline__ void hmc_walk(Sum& sum, const float* rec, size_t len, size_t step, int n_t, int nr_,
                                          const typename HmcTau<TWO>::type (*tile)[RTUS_BLOCK], int lane, typename HmcTau<TWO>::type tr,
-                                         const Lerp& lerp)
+                                         const Lerp& lerp, const Wts& wts = Wts())
 {
     constexpr int PER = TWO ? RTUS_DAS_GROUP / 2 : RTUS_DAS_GROUP;    // records per batch
     const int nr = NR ? NR : nr_;
@@ -97,7 +107,9 @@ __device__ __forceinline__ void hmc_walk(Sum& sum, const float* rec, size_t len,
         constexpr bool LAST = decltype(last)::value;
         int kind[PER];
         float wgt[PER];                                               // one table: 2, 1 or -0 by the record's kind
+        int ri[PER], ci[PER];                                         // (with weights only)
         auto open = [&](int m) {
+            if constexpr (Wts::ON) { ri[m] = r; ci[m] = c; }
             kind[m] = LAST && m >= left ? HMC_NONE : TRI && r == c ? HMC_DIAG : HMC_PAIR;
             // (in a scalar register: 1.0f's bits plus one exponent step off the diagonal, c - r >= 1 there)
             if constexpr (LAST || !TRI) wgt[m] = kind[m] == HMC_PAIR ? 2.0f : kind[m] == HMC_DIAG ? 1.0f : -0.0f;
@@ -131,7 +143,8 @@ __device__ __forceinline__ void hmc_walk(Sum& sum, const float* rec, size_t len,
                 return LAST && kind[k] == HMC_NONE ? 2.0f * RTUS_DAS_NO_PATH : tr + tc;
             };
             das_batch<C>(n_t, at, [&](int k, auto v, float w) {
-                sum.one(lerp(v, w), wgt[k]);
+                if constexpr (Wts::ON) sum.one(lerp(v, w), kind[k], TRI ? wts.tile[ri[k]][lane] : wts.row, wts.tile[ci[k]][lane]);
+                else sum.one(lerp(v, w), wgt[k]);
             });
         } else {
             decltype(lerp(das_load2<C>(rec, n_t, 0), 0.0f)) first;
@@ -154,6 +167,8 @@ __device__ __forceinline__ void hmc_walk(Sum& sum, const float* rec, size_t len,
             };
             das_batch<C>(n_t, at, [&](int k, auto v, float w) {
                 if (!(k & 1)) first = lerp(v, w);
+                else if constexpr (Wts::ON)
+                    sum.two(first, lerp(v, w), kind[k >> 1], TRI ? wts.tile[ri[k >> 1]][lane] : wts.row, wts.tile[ci[k >> 1]][lane]);
                 else sum.two(first, lerp(v, w), kind[k >> 1]);
             });
         }
@@ -172,6 +187,7 @@ __device__ __forceinline__ void hmc_walk(Sum& sum, const float* rec, size_t len,
 template <int C, bool CF>
 struct HmcImage {
     typedef HmcSum<C, CF> Sum;
+    static constexpr bool COUNT = false;                              // (HmcPhase: T and R are counted and handed to finish())
     __device__ __forceinline__ int block() const { return das_workgroup(); }
     __device__ __forceinline__ const float* records(const HmcArgs& a, size_t) const { return a.hmc; }
     __device__ __forceinline__ void store(const HmcArgs& a, int f, const Sum& sum) const
@@ -201,15 +217,16 @@ __device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>:
     };
     const float* records = where.records(a, len);                     // record (0, 0) of the workgroup's capture
     typename Where::Sum sum;
-    int n_tx_ok = 0, n_rx_ok = 0;                                     // T[f], R[f] (CF only)
+    constexpr bool COUNT = CF || Where::COUNT;
+    int n_tx_ok = 0, n_rx_ok = 0;                                     // T[f], R[f] (COUNT only)
     for (int r0 = 0; r0 < a.n_e; r0 += TILE) {
         const int nr = min(TILE, a.n_e - r0);
         __syncthreads();                                              // the previous tile is no longer read
         for (int r = 0; r < nr; ++r) {
             const Tau v = tau(r0 + r);
             tile[r][lane] = v;
-            if constexpr (CF && TWO) { n_tx_ok += tfm_has_path(v.x); n_rx_ok += tfm_has_path(v.y); }
-            else if constexpr (CF) n_tx_ok += tfm_has_path(v);
+            if constexpr (COUNT && TWO) { n_tx_ok += tfm_has_path(v.x); n_rx_ok += tfm_has_path(v.y); }
+            else if constexpr (COUNT) n_tx_ok += tfm_has_path(v);
         }
         __syncthreads();
         // the tile's columns in blocks of RTUS_DAS_GROUP: a row above a block meets it in ONE batch of fixed shape (the record
@@ -233,6 +250,7 @@ __device__ __forceinline__ void hmc_body(const HmcArgs& a, typename HmcTau<TWO>:
     }
     if (!live) return;
     where.store(a, f, sum);
+    if constexpr (Where::COUNT) where.finish(f, sum, n_tx_ok, TWO ? n_rx_ok : n_tx_ok);
     if constexpr (CF) {
         // as rtus_tfm_analytic_kernel: |S|^2 exact in fp64, N = T R, clamped to 1
         if constexpr (!TWO) n_rx_ok = n_tx_ok;
@@ -316,6 +334,7 @@ struct DasQuadI16 {
 template <int P>
 struct HmcFrames {
     typedef std::conditional_t<P == 4, HmcSum4, HmcSum<2, false>> Sum;
+    static constexpr bool COUNT = false;
     int n_frames, n_blk;
     __device__ __forceinline__ int slow() const { return blockIdx.x / n_blk; }
     __device__ __forceinline__ int block() const
@@ -358,6 +377,211 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_frames_hmc_f32_kernel(Hmc
 {
     __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
     hmc_body<2, false, TWO>(a, tile, DasLerp(), frames);
+}
+
+// ---------------------------------------------------------------------------------------------- phase coherence: vcf, scf
+// rtus_tfm_phase_hmc (include/rtus.h): rtus_tfm_analytic_hmc_kernel's body — the same walk and the same two statements for S, so
+// the image has its bits — with rtus_tfm_phase_kernel's sums fed per record: with PHASOR the unit phasors of the record's one or two
+// samples (tfmp_unit, rtus_das.h), the pair's two added first; with SIGN the signs of their real parts as an integer.  One table:
+// the one sample's phasor and sign count twice off the diagonal, U = fmaf(wgt, u, U) as S.  T and R are counted while the tile is
+// filled (hmc_body, Where::COUNT); vcf and scf are rtus_tfm_phase_kernel's epilogue.
+// Resources (code-object metadata, gfx950): no scratch in any of the eight instantiations; LDS 64 KiB as the other half-matrix
+// kernels: two workgroups per CU, two waves per SIMD, which every count below allows (<= 256).  VGPRs <PHASOR, SIGN, TWO>:
+//   <0,0,0> 120   <1,0,0> 124   <0,1,0> 223   <1,1,0> 231   <0,0,1> 135   <1,0,1> 140   <0,1,1> 151   <1,1,1> 151
+// (<0,0,*> are rtus_tfm_analytic_hmc_kernel<false, *>'s instruction streams; with SIGN and one table the scheduler keeps more of the
+// unrolled triangle's loads in flight; <*,1,1> park one VGPR in an accumulation register, not in memory).
+template <bool PHASOR, bool SIGN>
+struct HmcPhaseSum {
+    float re = 0.0f, im = 0.0f, ure = 0.0f, uim = 0.0f;
+    int sgn = 0;                                                      // B[f]: |B| <= n_e^2 <= 2^30
+    static __device__ __forceinline__ int sign(float x) { return (x > 0.0f) - (x < 0.0f); }
+    __device__ __forceinline__ void one(float2 p, float wgt)
+    {
+        re = fmaf(wgt, p.x, re);
+        im = fmaf(wgt, p.y, im);
+        if (PHASOR) {
+            const float2 u = tfmp_unit(p);
+            ure = fmaf(wgt, u.x, ure);
+            uim = fmaf(wgt, u.y, uim);
+        }
+        if (SIGN) sgn += (int)wgt * sign(p.x);                        // wgt: 2, 1 or -0
+    }
+    __device__ __forceinline__ void two(float2 p, float2 q, int kind)
+    {
+        re += HmcSum<2, false>::term(p.x, q.x, kind);
+        im += HmcSum<2, false>::term(p.y, q.y, kind);
+        if (PHASOR) {
+            const float2 u = tfmp_unit(p), v = tfmp_unit(q);
+            ure += HmcSum<2, false>::term(u.x, v.x, kind);
+            uim += HmcSum<2, false>::term(u.y, v.y, kind);
+        }
+        if (SIGN) sgn += kind == HMC_PAIR ? sign(p.x) + sign(q.x) : kind == HMC_DIAG ? sign(p.x) : 0;
+    }
+};
+
+template <bool PHASOR, bool SIGN>
+struct HmcPhase {
+    typedef HmcPhaseSum<PHASOR, SIGN> Sum;
+    static constexpr bool COUNT = PHASOR || SIGN;
+    float* __restrict__ vcf;             // [n_f] (PHASOR only; not null there)
+    float* __restrict__ scf;             // [n_f] (SIGN only, nullable)
+    int2* __restrict__ counts;           // [n_f] (B, N) (SIGN only, nullable)
+    __device__ __forceinline__ int block() const { return das_workgroup(); }
+    __device__ __forceinline__ const float* records(const HmcArgs& a, size_t) const { return a.hmc; }
+    __device__ __forceinline__ void store(const HmcArgs& a, int f, const Sum& sum) const { ((float2*)a.image)[f] = make_float2(sum.re, sum.im); }
+    // rtus_tfm_phase_kernel's epilogue on the half matrix's sums
+    __device__ __forceinline__ void finish(int f, const Sum& sum, int n_tx_ok, int n_rx_ok) const
+    {
+#pragma clang fp contract(off)
+        const int n = n_tx_ok * n_rx_ok;                              // <= n_e^2 <= 2^30 (checked by the C entries)
+        if (PHASOR) {
+            double c = NAN;                                           // no pair with a path
+            if (n > 0) {
+                c = sqrt((double)sum.ure * (double)sum.ure + (double)sum.uim * (double)sum.uim) / (double)n;
+                c = c > 1.0 ? 1.0 : c;
+            }
+            vcf[f] = (float)c;
+        }
+        if (SIGN) {
+            if (scf) {
+                double c = NAN;
+                if (n > 0) {
+                    const double q = (double)sum.sgn / (double)n;     // |q| <= 1: |B| <= N
+                    c = 1.0 - sqrt(1.0 - q * q);
+                }
+                scf[f] = (float)c;
+            }
+            if (counts) counts[f] = make_int2(sum.sgn, n);
+        }
+    }
+};
+
+template <bool PHASOR, bool SIGN, bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_hmc_phase_kernel(HmcArgs a, HmcPhase<PHASOR, SIGN> where)
+{
+    __shared__ typename HmcTau<TWO>::type tile[TWO ? RTUS_HMC_TILE2 : RTUS_HMC_TILE][RTUS_BLOCK];
+    hmc_body<2, false, TWO>(a, tile, DasLerp(), where);
+}
+
+// ---------------------------------------------------------------------------------------------- weighted envelope TFM + sensitivity
+// rtus_tfm_weighted_hmc (include/rtus.h): S[f] = the sum over the records of c_ii = W_ii a_ii(s_ii), c_ij = W_ij a_ij(s_ij) +
+// W_ji a_ij(s_ji), W_ij = w_tx[i] w_rx[j], in rtus_tfm_hmc's order.  hmc_walk with weights (HmcWts): a record's sample meets the
+// weights of its row and of its column when it is consumed.
+// The tile: an element carries its delay(s) and BOTH its weights, (w_tx, w_rx) as a float4 — 20 B per element and lane with one
+// delay table, 24 B with two: 5 / 6 KiB per element of the 160 KiB a CU has.  A tile must be a whole number of column blocks
+// (RTUS_DAS_GROUP = 16 elements: 80 / 96 KiB); two blocks would be 160 / 192 KiB, the whole CU or more.  So the tile IS one column
+// block: one workgroup per CU with two delay tables (96 KiB), and with one (80 KiB: two would need the CU's last byte).  Rows above the
+// block (i < c0) take their delay and weights from memory: 24 / 32 B per row and block against 16 gathers of 16 B — at 64 elements 96
+// such rows per focal point, 2.3 / 3 KiB beside 33 KiB of gathers.
+// A leg has a path only if its time has one and its weight is finite.  Two delay tables: such a leg's delay becomes the no-path value
+// and its weight 0, as rtus_tfm_weighted_kernel does.  One delay table: element i's ONE delay serves its transmit and its receive
+// leg, which can differ (w_tx[i] finite, w_rx[i] not), so the delay stays (no path only if the time has none) and the leg's weight
+// alone becomes 0: W = 0 exactly, and 0 times the finite sample adds nothing.
+// Resources (code-object metadata, gfx950): no scratch, no spills.  <SENS, TWO>: <0,0> 180 VGPRs, 80 KiB LDS; <1,0> 182, 80 KiB;
+// <0,1> 186, 96 KiB; <1,1> 188, 96 KiB.  One workgroup per CU — one wave per SIMD — by LDS in all four (whether the hardware places two
+// 80 KiB workgroups in a CU's 160 KiB was not measured); the registers would allow two.
+struct HmcwArgs {
+    HmcArgs a;                           // (cf unused)
+    const float2* __restrict__ w_tx;     // [n_e][n_f]
+    const float2* __restrict__ w_rx;     // [n_e][n_f]
+    float* __restrict__ sens;            // [n_f] (read by the SENS instantiations only)
+};
+
+// The fp32 statements of include/rtus.h (rtus_tfm_weighted_hmc), nothing contracted beyond the fmaf's written here.
+struct HmcwSum {
+    float re = 0.0f, im = 0.0f;
+    // a b, symmetric in its operands: the products commute and so does the sum of the imaginary part's two
+    static __device__ __forceinline__ float2 cmul(float2 a, float2 b)
+    {
+#pragma clang fp contract(off)
+        const float t = a.x * b.y, u = a.y * b.x;
+        return make_float2(fmaf(-a.y, b.y, a.x * b.x), t + u);
+    }
+    static __device__ __forceinline__ float2 times(float2 g, float2 p)   // W a(s)
+    {
+#pragma clang fp contract(off)
+        return make_float2(fmaf(-g.y, p.y, g.x * p.x), fmaf(g.x, p.y, g.y * p.x));
+    }
+    static __device__ __forceinline__ float2 w_tx(float4 g) { return make_float2(g.x, g.y); }
+    static __device__ __forceinline__ float2 w_rx(float4 g) { return make_float2(g.z, g.w); }
+    // one gather for both legs: c = (W_ij + W_ji) a, the weights' sum first; the diagonal W_ii a; an unused slot nothing
+    __device__ __forceinline__ void one(float2 p, int kind, float4 gr, float4 gc)
+    {
+        const float2 wij = cmul(w_tx(gr), w_rx(gc)), wji = cmul(w_tx(gc), w_rx(gr));
+        float2 g;
+        g.x = kind == HMC_PAIR ? wij.x + wji.x : kind == HMC_DIAG ? wij.x : 0.0f;
+        g.y = kind == HMC_PAIR ? wij.y + wji.y : kind == HMC_DIAG ? wij.y : 0.0f;
+        const float2 c = times(g, p);
+        re += c.x;
+        im += c.y;
+    }
+    // two gathers: c = W_ij a(s_ij) + W_ji a(s_ji), the pair first
+    __device__ __forceinline__ void two(float2 p, float2 q, int kind, float4 gr, float4 gc)
+    {
+        const float2 c1 = times(cmul(w_tx(gr), w_rx(gc)), p), c2 = times(cmul(w_tx(gc), w_rx(gr)), q);
+        re += kind == HMC_PAIR ? c1.x + c2.x : kind == HMC_DIAG ? c1.x : 0.0f;
+        im += kind == HMC_PAIR ? c1.y + c2.y : kind == HMC_DIAG ? c1.y : 0.0f;
+    }
+};
+
+#define RTUS_HMCW_TILE RTUS_DAS_GROUP
+template <bool SENS, bool TWO>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tfm_hmc_weighted_kernel(HmcwArgs g)
+{
+    typedef typename HmcTau<TWO>::type Tau;
+    __shared__ Tau tile[RTUS_HMCW_TILE][RTUS_BLOCK];                  // 16 / 32 KiB
+    __shared__ float4 wtile[RTUS_HMCW_TILE][RTUS_BLOCK];              // 64 KiB
+    const HmcArgs& a = g.a;
+    const int lane = threadIdx.x;
+    const int f_raw = das_workgroup() * RTUS_BLOCK + lane;
+    const bool live = f_raw < a.n_f;
+    const int f = live ? f_raw : a.n_f - 1;
+    const size_t nf = (size_t)a.n_f, ne = (size_t)a.n_e;
+    const size_t len = (size_t)a.n_t * 2;                             // floats per record
+    float ptx = 0.0f, prx = 0.0f;
+    // element e's delay(s) and weights under the leg rule; sens: its share of P is counted (once per element: the tile's fill)
+    auto elem = [&](int e, Tau& tau, float4& w, bool sens) {
+        const size_t o = (size_t)e * nf + f;
+        const float tt = tfm_tau(a.tt_tx[o], a.fs, a.half_t0s);
+        const float tr = TWO ? tfm_tau(a.tt_rx[o], a.fs, a.half_t0s) : tt;
+        const float2 gt = g.w_tx[o], gr = g.w_rx[o];
+        const bool ok_t = tfm_has_path(tt) && tfmw_finite(gt), ok_r = tfm_has_path(tr) && tfmw_finite(gr);
+        if constexpr (TWO) tau = make_float2(ok_t ? tt : RTUS_DAS_NO_PATH, ok_r ? tr : RTUS_DAS_NO_PATH);
+        else tau = tt;
+        w = make_float4(ok_t ? gt.x : 0.0f, ok_t ? gt.y : 0.0f, ok_r ? gr.x : 0.0f, ok_r ? gr.y : 0.0f);
+        if (SENS && sens) {
+            if (ok_t) ptx = fmaf(gt.y, gt.y, fmaf(gt.x, gt.x, ptx));
+            if (ok_r) prx = fmaf(gr.y, gr.y, fmaf(gr.x, gr.x, prx));
+        }
+    };
+    HmcwSum sum;
+    const DasLerp lerp;
+    for (int c0 = 0; c0 < a.n_e; c0 += RTUS_HMCW_TILE) {              // the tile is the column block [c0, c0 + nb)
+        const int nb = min(RTUS_HMCW_TILE, a.n_e - c0);
+        __syncthreads();                                              // the previous tile is no longer read
+        for (int r = 0; r < nb; ++r) {
+            Tau t;
+            float4 w;
+            elem(c0 + r, t, w, true);
+            tile[r][lane] = t;
+            wtile[r][lane] = w;
+        }
+        __syncthreads();
+        const float* row = a.hmc + (size_t)c0 * len;                  // record (i, c0): p(i, c0) = i n_e - i (i + 1) / 2 + c0
+        size_t down = (ne - 1) * len;                                 // from (i, c0) to (i + 1, c0): n_e - 1 - i records
+        HmcWts wts = {wtile, make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
+        for (int i = 0; i < c0; ++i, row += down, down -= len) {      // the rows above the block: delay and weights from memory
+            Tau t;
+            elem(i, t, wts.row, false);
+            hmc_walk<2, TWO, false>(sum, row, len, 0, a.n_t, nb, tile, lane, t, lerp, wts);
+        }
+        const size_t past = (ne - (size_t)(c0 + nb)) * len;           // the block's own triangle from (c0, c0) on
+        if (nb == RTUS_DAS_GROUP) hmc_walk<2, TWO, true, RTUS_DAS_GROUP>(sum, row, len, past, a.n_t, nb, tile, lane, Tau(), lerp, wts);
+        else hmc_walk<2, TWO, true>(sum, row, len, past, a.n_t, nb, tile, lane, Tau(), lerp, wts);
+    }
+    if (!live) return;
+    ((float2*)a.image)[f] = make_float2(sum.re, sum.im);
+    if (SENS) g.sens[f] = (float)((double)ptx * (double)prx);
 }
 
 static HmcArgs hmc_args(const float* hmc, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx, int n_f,
@@ -449,4 +673,38 @@ hipError_t rtus_launch_tfm_frames_hmc(const float* packed, int n_frames, int n_e
                                       const double* tt_rx, int n_f, float* images, hipStream_t s)
 {
     return hmc_frames_launch<2>(packed, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, s);
+}
+
+// an output that is not asked for is not computed: vcf null -> no phasor, scf and counts null -> no sign sum
+template <bool TWO>
+static void hmc_phase_launch(const HmcArgs& a, float* vcf, float* scf, int2* counts, dim3 grid, dim3 block, hipStream_t s)
+{
+    const bool sign = scf || counts;
+    if (vcf && sign) hipLaunchKernelGGL((rtus_tfm_hmc_phase_kernel<true, true, TWO>), grid, block, 0, s, a, HmcPhase<true, true>{vcf, scf, counts});
+    else if (vcf) hipLaunchKernelGGL((rtus_tfm_hmc_phase_kernel<true, false, TWO>), grid, block, 0, s, a, HmcPhase<true, false>{vcf, scf, counts});
+    else if (sign) hipLaunchKernelGGL((rtus_tfm_hmc_phase_kernel<false, true, TWO>), grid, block, 0, s, a, HmcPhase<false, true>{vcf, scf, counts});
+    else hipLaunchKernelGGL((rtus_tfm_hmc_phase_kernel<false, false, TWO>), grid, block, 0, s, a, HmcPhase<false, false>{vcf, scf, counts});
+}
+
+hipError_t rtus_launch_tfm_phase_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                                     int n_f, float* image, float* vcf, float* scf, int* counts, hipStream_t s)
+{
+    const HmcArgs a = hmc_args(an, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, nullptr);
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    if (tt_tx == tt_rx) hmc_phase_launch<false>(a, vcf, scf, (int2*)counts, grid, block, s);
+    else hmc_phase_launch<true>(a, vcf, scf, (int2*)counts, grid, block, s);
+    return hipGetLastError();
+}
+
+hipError_t rtus_launch_tfm_weighted_hmc(const float* an, int n_e, int n_t, double fs, double t0, const double* tt_tx, const double* tt_rx,
+                                        const float* w_tx, const float* w_rx, int n_f, float* image, float* sens, hipStream_t s)
+{
+    const HmcwArgs g = {hmc_args(an, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, image, nullptr), (const float2*)w_tx, (const float2*)w_rx, sens};
+    const dim3 grid((n_f + RTUS_BLOCK - 1) / RTUS_BLOCK), block(RTUS_BLOCK);
+    const bool two = tt_tx != tt_rx;
+    if (sens && two) hipLaunchKernelGGL((rtus_tfm_hmc_weighted_kernel<true, true>), grid, block, 0, s, g);
+    else if (sens) hipLaunchKernelGGL((rtus_tfm_hmc_weighted_kernel<true, false>), grid, block, 0, s, g);
+    else if (two) hipLaunchKernelGGL((rtus_tfm_hmc_weighted_kernel<false, true>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((rtus_tfm_hmc_weighted_kernel<false, false>), grid, block, 0, s, g);
+    return hipGetLastError();
 }

@@ -643,6 +643,49 @@ def tfm_phase_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, vcf=None, s
     return (out, *given) if given else out
 
 
+def tfm_phase_hmc_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, vcf=None, scf=None, counts=None):
+    """Phase-coherence TFM over a half-matrix capture on device (rtus_tfm_phase_hmc_dev; api.tfm_phase_hmc's definition):
+    tfm_analytic_hmc_dev's tensors -> out float32 [n_f, 2] (tfm_analytic_hmc_dev's bits); ``vcf`` / ``scf`` / ``counts``: the optional
+    outputs of tfm_phase_dev (float32 [n_f], float32 [n_f], int32 [n_f, 2]).  -> out, or the tuple of out followed by the optional
+    tensors given (in that order).  Asynchronous on the current stream (capturable with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    n_e, n_f = _hmc_tables(tt_tx, tt_rx, analytic, True)
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, vcf=vcf, scf=scf)
+    _optional(2 * n_f, torch.int32, counts=counts)
+    given = [t for t in (vcf, scf, counts) if t is not None]
+    if not all(t.device == analytic.device for t in (tt_tx, tt_rx, out, *given)):
+        raise ValueError("analytic, tt_tx, tt_rx, out, vcf, scf and counts must be on one device")
+    st = _lib.lib().rtus_tfm_phase_hmc_dev(_p(analytic), n_e, analytic.shape[1], float(fs), float(t0), _p(tt_tx), _p(tt_rx), n_f,
+                                           _p(out), _p(vcf), _p(scf), _p(counts), _stream(analytic))
+    _lib.check(st, "rtus_tfm_phase_hmc_dev")
+    return (out, *given) if given else out
+
+
+def tfm_weighted_hmc_dev(analytic, fs, tt_tx, w_tx, tt_rx=None, w_rx=None, t0=0.0, out=None, sens=None):
+    """Weighted envelope TFM over a half-matrix capture on device (rtus_tfm_weighted_hmc_dev; api.tfm_weighted_hmc's definition):
+    analytic float32 [n_pairs, n_t, 2], tt_tx / tt_rx float64 [n_e, n_f], w_tx / w_rx float32 [n_e, n_f, 2] (complex); tt_rx and w_rx
+    default to tt_tx and w_tx (tt_rx None or tt_tx itself: one delay table, every record gathered once) -> out float32 [n_f, 2];
+    ``sens``: an optional float32 [n_f] tensor that receives the sensitivity (then -> (out, sens)).  Asynchronous on the current
+    stream (capturable with pre-allocated outputs)."""
+    _chk(analytic, "analytic", torch.float32); _chk(tt_tx, "tt_tx"); _chk(w_tx, "w_tx", torch.float32)
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    w_rx = w_tx if w_rx is None else _chk(w_rx, "w_rx", torch.float32)
+    n_e, n_f = _hmc_tables(tt_tx, tt_rx, analytic, True)
+    if tuple(w_tx.shape) != (n_e, n_f, 2) or tuple(w_rx.shape) != (n_e, n_f, 2):
+        raise ValueError(f"w_tx / w_rx must be float32 [{n_e}, {n_f}, 2]")
+    out = _result(out, (n_f, 2), analytic, torch.float32)
+    _optional(n_f, torch.float32, sens=sens)
+    devs = {t.device for t in (analytic, tt_tx, tt_rx, w_tx, w_rx, out) + ((sens,) if sens is not None else ())}
+    if len(devs) != 1:
+        raise ValueError("analytic, the tables, the weights, out and sens must be on one device")
+    st = _lib.lib().rtus_tfm_weighted_hmc_dev(_p(analytic), n_e, analytic.shape[1], float(fs), float(t0), _p(tt_tx), _p(tt_rx),
+                                              _p(w_tx), _p(w_rx), n_f, _p(out), _p(sens), _stream(analytic))
+    _lib.check(st, "rtus_tfm_weighted_hmc_dev")
+    return out if sens is None else (out, sens)
+
+
 class LayersPlan:
     """Pre-bound ``rtus_tt_layers_dev`` call for repeated solves of one shape: ``run()`` is a single
     ctypes call (no argument checking, no allocation, no sync) — capturable in a hipGraph."""
