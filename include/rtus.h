@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 124 /* 0.1.23: rtus_tfm_phase_hmc, rtus_tfm_weighted_hmc (phase coherence and weighted TFM over a half matrix) */
+#define RTUS_VERSION 125 /* 0.1.24: rtus_tfm_envelope_frames_hmc[_i16], rtus_fmc_analytic_i16 (envelope TFM over half-matrix frame stacks) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -868,6 +868,79 @@ int rtus_tfm_frames_hmc_dev(const float *d_packed, int n_frames, int n_e, int n_
                             const double *d_tt_tx, const double *d_tt_rx, int n_f, float *d_images, void *stream);
 int rtus_tfm_frames_hmc(const float *hmc, int n_frames, int n_e, int n_t, double fs, double t0,
                         const double *tt_tx, const double *tt_rx, int n_f, float *images, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * rtus_tfm_envelope_frames_hmc[_i16]: ENVELOPE TFM over a stack of half-matrix frames, the analytic signal formed on the device —
+ * raw int16 (or float32) samples up, complex or magnitude images down, nothing in between touches the host.  NOT IN THE REFERENCE;
+ * held bit for bit to the frame-by-frame route through rtus_fmc_analytic and rtus_tfm_analytic_hmc / rtus_tfm_iq_hmc.
+ *   A stack: hmc [n_frames][n_pairs][n_t], int16 or float32, frame-major, the records in rtus_tfm_hmc's order.  n_taps: the Hilbert
+ *           transformer's (rtus_fmc_analytic), odd in [3, 255].  fs, t0, tt_tx, tt_rx [n_e][n_f]: as in rtus_tfm_hmc.  f_demod in
+ *           [0, fs / 2): 0 interpolates linearly, > 0 is rtus_tfm_iq's carrier-aware step.  flags: 0 or RTUS_ENV_MAGNITUDE.
+ *           images [n_frames][n_f][2] float32 (8-byte aligned), or [n_frames][n_f] with RTUS_ENV_MAGNITUDE; cf [n_frames][n_f] or null.
+ *   The contract.  Frame k's complex image is, BIT FOR BIT, what rtus_tfm_analytic_hmc returns on rtus_fmc_analytic of frame k
+ *           converted to float32 (exact), called with (n_tx, n_rx) = (1, n_pairs) and the same n_taps; with f_demod > 0 it is
+ *           rtus_tfm_iq_hmc's image; cf is the coherence factor of that same call.  No bit depends on n_frames, on a frame's partners
+ *           in a quad or pair, on how the stack is cut into calls or launches, on whether cf is asked for, or on which internal
+ *           route ran.  tt_tx == tt_rx AS POINTERS selects the one-table kernels, as in rtus_tfm_frames_hmc.
+ *   RTUS_ENV_MAGNITUDE: m = (float) sqrt((double) re * re + (double) im * im) of the complex image — the products exact in fp64,
+ *           one rounding in the sum, a correctly rounded fp64 sqrt, one rounding to float; in NumPy
+ *           np.sqrt(re.astype(f8)**2 + im.astype(f8)**2).astype(f4).  Half the download; no intermediate overflows.
+ *   Routes.  int16 frames with f_demod == 0 and cf null take the SPLIT-PLANE route: rtus_tfm_analytic_hmc's image is, plane by plane,
+ *           rtus_tfm_hmc of that plane; the real plane of an analytic int16 frame is the frame, so the real parts of four frames come
+ *           from one gather per record (rtus_tfm_frames_hmc_i16's kernel on the raw quads) and the imaginary parts from the float32
+ *           pair kernel on the Hilbert planes, which the transformer writes pair-packed: three 16-byte gathers per record and four
+ *           frames where the complex kernel issues four; a streaming kernel joins the planes.  Every other case takes the COMPLEX
+ *           route: frame by frame, the transformer into one frame's block of the workspace, then rtus_tfm_analytic_hmc's /
+ *           rtus_tfm_iq_hmc's kernel on that block: two launches per frame, the parent's kernels for the image.
+ *   rtus_fmc_analytic_i16[_dev]: rtus_fmc_analytic on int16 samples: out has its bits on the samples as float32 (d_out 8-byte aligned).
+ *   rtus_fmc_hilbert_pairs_i16_dev: the Hilbert planes alone of a frame-major int16 stack [n_frames][n_scans][n_t], in the float32
+ *           pair-packed layout d_packed [n_fpairs][n_scans][n_t][2] that rtus_tfm_frames_hmc_dev reads: plane c of pair p is the
+ *           imaginary part of rtus_fmc_analytic of frame 2 p + c; the absent frame of an odd stack is +0.0.  d_packed 8-byte aligned,
+ *           not overlapping d_fmc (-1); more than 2^31 - 1 workgroups, n_fpairs n_scans ceil(n_t / 1024): -5.
+ *   rtus_tfm_envelope_frames_hmc_workspace_bytes: the bytes the _dev entries need for these sizes (i16: 1 for the int16 entry;
+ *           want_cf: 1 when cf is not null); 0 for a size that is not positive, n_e > 32768, an unknown flag, f_demod negative or
+ *           not finite, or a sum past 2^62.  The _dev entries take the FRAME-MAJOR stack and pack inside d_work (64-byte aligned),
+ *           allocate nothing and do not synchronise (capturable).  The host twins upload the stack in its own type and work in the arena.
+ *   Limits: rtus_tfm_frames_hmc's (-1: a null pointer, a non-positive size, n_e > 32768, n_t < 2, fs not positive and finite, t0 not
+ *           finite; -5: n_t > 2^26, or more than 2^31 - 1 workgroups), and: n_taps not odd in [3, 255], f_demod outside [0, fs / 2),
+ *           an unknown flag, a misaligned pointer: -1; more than 2^31 - 1 A-scan tiles, n_frames n_pairs ceil(n_t / 1024): -5; a
+ *           workspace that is null, not 64-byte aligned or too small: -4.  All before any HIP call.
+ * Kernels, resources and the figures: DESIGN.md §4 "Envelope TFM over half-matrix frame stacks" (profiles/
+ *           tfm_envelope_frames_hmc_kernel.txt).
+ * Measured on MI355X, 2026-10-21, 64 elements (2080 records) x 2048 int16 samples, medians of 50 alternating repetitions, two separate
+ * runs (with one table they differ by at most 0.002 in a ratio, with two by 0.034; run 1 quoted), time per frame, against (L) a device loop per frame of
+ * rtus_fmc_analytic_dev and rtus_tfm_analytic_hmc_dev on float32 frames in the same run.  ESTIMATED before the measurement, composed
+ * from figures of separate runs: the split-plane route about 0.8x of (L) at 256^2 focal points and 0.9x at 1024^2, the complex route
+ * about 1.0x.
+ *   one table, 256^2, 8 / 9 / 32 frames: (L) 162 / 162 / 161 us; the int16 _dev entry on its split-plane route, pack, Hilbert and
+ *           combine included, 119 / 140 / 118 us (0.74x / 0.86x / 0.73x), the same with the magnitude output; with cf (the complex
+ *           route) 162 / 162 / 163 us (1.00x / 1.00x / 1.01x).
+ *   one table, 1024^2: (L) 1.05 / 1.05 / 1.05 ms; split-plane 0.93 / 1.11 / 0.93 ms (0.89x / 1.06x / 0.88x: nine frames are
+ *           three quads and five pairs with the last ones a quarter and half full — slower than the loop there); complex route
+ *           1.08 / 1.09 / 1.08 ms (1.03x / 1.04x / 1.03x).
+ *   two tables (reported, 8 and 32 frames): split-plane 0.67 to 0.69x at 256^2, 0.85 to 0.87x at 1024^2; complex route 1.05x, 1.01 to 1.02x.
+ *   The host twin on 8 frames from pageable memory against the Python loop route (widen, rtus_fmc_analytic, rtus_tfm_analytic_hmc per
+ *           frame), wall time, which depends on the host's pageable copies: 3.07 ms (102 MB up, 4 MB down) against 46.51 ms
+ *           (677 MB up, 277 MB down) at 256^2, 20.92 ms against 126.02 ms at 1024^2; with the magnitude output 2.97 and 20.27 ms.
+ * ---------------------------------------------------------------------------------------- */
+#define RTUS_ENV_MAGNITUDE 1
+int rtus_fmc_analytic_i16_dev(const short *d_fmc, int n_tx, int n_rx, int n_t, int n_taps, float *d_out, void *stream);
+int rtus_fmc_analytic_i16(const short *fmc, int n_tx, int n_rx, int n_t, int n_taps, float *out, int device);
+int rtus_fmc_hilbert_pairs_i16_dev(const short *d_fmc, int n_frames, int n_scans, int n_t, int n_taps, float *d_packed, void *stream);
+size_t rtus_tfm_envelope_frames_hmc_workspace_bytes(int n_frames, int n_e, int n_t, int n_f, int i16, double f_demod, int want_cf,
+                                                    int flags);
+int rtus_tfm_envelope_frames_hmc_i16_dev(const short *d_hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0,
+                                         double f_demod, const double *d_tt_tx, const double *d_tt_rx, int n_f, int flags,
+                                         float *d_images, float *d_cf, void *d_work, size_t work_bytes, void *stream);
+int rtus_tfm_envelope_frames_hmc_i16(const short *hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0,
+                                     double f_demod, const double *tt_tx, const double *tt_rx, int n_f, int flags,
+                                     float *images, float *cf, int device);
+int rtus_tfm_envelope_frames_hmc_dev(const float *d_hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0,
+                                     double f_demod, const double *d_tt_tx, const double *d_tt_rx, int n_f, int flags,
+                                     float *d_images, float *d_cf, void *d_work, size_t work_bytes, void *stream);
+int rtus_tfm_envelope_frames_hmc(const float *hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0,
+                                 double f_demod, const double *tt_tx, const double *tt_rx, int n_f, int flags,
+                                 float *images, float *cf, int device);
 
 /* ------------------------------------------------------------------------------------------
  * Plane-wave imaging (PWI): a few dozen plane waves, each fired by the whole aperture with a linear delay law and received on every

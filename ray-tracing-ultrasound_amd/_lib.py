@@ -160,6 +160,15 @@ PROTOTYPES = (
     ("rtus_tfm_frames_hmc_i16", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, i], 123),
     ("rtus_tfm_frames_hmc_dev", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, vp], 123),
     ("rtus_tfm_frames_hmc", i, [vp, i, i, i, dd, dd, vp, vp, i, vp, i], 123),
+    # envelope TFM over a stack of half-matrix frames
+    ("rtus_fmc_analytic_i16_dev", i, [vp, i, i, i, i, vp, vp], 125),
+    ("rtus_fmc_analytic_i16", i, [vp, i, i, i, i, vp, i], 125),
+    ("rtus_fmc_hilbert_pairs_i16_dev", i, [vp, i, i, i, i, vp, vp], 125),
+    ("rtus_tfm_envelope_frames_hmc_workspace_bytes", sz, [i, i, i, i, i, dd, i, i], 125),
+    ("rtus_tfm_envelope_frames_hmc_i16_dev", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, i, vp, vp, vp, sz, vp], 125),
+    ("rtus_tfm_envelope_frames_hmc_i16", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, i, vp, vp, i], 125),
+    ("rtus_tfm_envelope_frames_hmc_dev", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, i, vp, vp, vp, sz, vp], 125),
+    ("rtus_tfm_envelope_frames_hmc", i, [vp, i, i, i, i, dd, dd, dd, vp, vp, i, i, vp, vp, i], 125),
     # plane-wave imaging
     ("rtus_pw_layers_dev", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, vp], 107),
     ("rtus_pw_layers", i, [vp, vp, i, vp, i, dd, dd, dd, vp, vp, i, vp, i], 107),

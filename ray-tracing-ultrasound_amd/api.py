@@ -775,8 +775,8 @@ def tfm_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, envelope=False, coherenc
     gather per record).  Row k is tfm_hmc(stack[k] as float32, ...) bit for bit; int16 frames go four per gather
     (rtus_tfm_frames_hmc_i16), float32 frames two (rtus_tfm_frames_hmc).  The packed layouts the device entries read are
     frames_pack_i16(stack[:, None])[:, 0] and frames_pack(stack[:, None])[:, 0]; device.fmc_pack_frames[_i16]_dev make them on the
-    GPU from a [n_frames, 1, n_pairs, n_t] view.  ``envelope``, ``coherence`` and ``f_demod`` have no stacked half-matrix form
-    (ValueError: tfm_analytic_hmc frame by frame).
+    GPU from a [n_frames, 1, n_pairs, n_t] view.  ``envelope``, ``coherence`` and ``f_demod`` raise ValueError with ``hmc=True``:
+    envelope images of a half-matrix stack are tfm_envelope_frames' (which forms the analytic signal on the device).
     Definition: include/rtus.h (rtus_tfm_frames, rtus_tfm_analytic_frames, rtus_tfm_frames_hmc).  Not in the reference."""
     if hmc:
         return _tfm_frames_hmc(stack, fs, tt_tx, tt_rx, t0, envelope, coherence, f_demod, max_frames, out, device)
@@ -835,6 +835,63 @@ def _tfm_frames_hmc(stack, fs, tt_tx, tt_rx, t0, envelope, coherence, f_demod, m
         st = fn(_ptr(stack[k:k + n]), n, n_e, n_t, float(fs), float(t0), _ptr(tt_tx), _ptr(tt_rx), n_f, _ptr(imgs[k:k + n]), int(device))
         _lib.check(st, entry)
     return imgs
+
+
+ENV_MAGNITUDE = 1                                                     # RTUS_ENV_MAGNITUDE (include/rtus.h)
+
+
+def _n_taps(n_taps):
+    """the Hilbert transformer's length -> int; ValueError unless odd in [3, 255]"""
+    if isinstance(n_taps, (bool, np.bool_)) or int(n_taps) != n_taps or not 3 <= int(n_taps) <= 255 or not int(n_taps) & 1:
+        raise ValueError("n_taps must be odd in [3, 255]")
+    return int(n_taps)
+
+
+def fmc_analytic_i16(fmc_i16, n_taps=63, *, out=None, device=0):
+    """fmc_analytic on int16 samples [n_tx, n_rx, n_t], uploaded as int16 -> complex64 [n_tx, n_rx, n_t] with fmc_analytic's bits on
+    the samples as float32.  Definition: include/rtus.h (rtus_fmc_analytic_i16).  Not in the reference."""
+    fmc = np.ascontiguousarray(fmc_i16)
+    if fmc.dtype != np.int16 or fmc.ndim != 3:
+        raise ValueError("fmc_i16 must be int16 [n_tx, n_rx, n_t]")
+    a = _out(out, fmc.shape, np.complex64)
+    st = _lib.lib().rtus_fmc_analytic_i16(_ptr(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], int(n_taps), _ptr(a), int(device))
+    _lib.check(st, "rtus_fmc_analytic_i16")
+    return a
+
+
+def tfm_envelope_frames(stack, fs, tt_tx, tt_rx=None, *, t0=0.0, n_taps=63, coherence=False, f_demod=None, magnitude=False,
+                        max_frames=None, out=None, device=0):
+    """Envelope TFM over a stack of half-matrix frames in one call: ``stack`` [n_frames, n_pairs, n_t], int16 or float32 (other
+    dtypes go to float32), the records in hmc_index's order; tt_tx / tt_rx [n_e, n_f], ``tt_rx`` None or ``tt_tx`` itself means one
+    table.  The raw samples are uploaded in their own type and the analytic signal (``n_taps`` Hilbert taps) is formed on the device
+    -> complex64 [n_frames, n_f]; row k is tfm_analytic_hmc(hmc_analytic(stack[k] as float32, n_taps), ...) bit for bit, with
+    ``f_demod`` [Hz] tfm_iq_hmc's.  ``coherence=True`` (or "cf") -> (images, cf float32 [n_frames, n_f]), the same images; "vcf" /
+    "scf" raise ValueError.  ``magnitude=True`` -> float32 [n_frames, n_f] instead: the magnitude of the complex images
+    (np.sqrt(re.astype(f8)**2 + im.astype(f8)**2).astype(f4): one rounding in the sum, one in the conversion), formed
+    on the device (half the download).  ``max_frames``: the stack is run in chunks of that many frames, which bounds device memory;
+    no bit depends on it, nor on the dtype's route (int16 frames without ``f_demod`` and ``coherence`` are imaged plane by plane:
+    three gathers per record and four frames, not four).  ``out``: the images' buffer.
+    Definition: include/rtus.h (rtus_tfm_envelope_frames_hmc).  Not in the reference."""
+    mode = _iq_coherence(coherence)
+    f_demod = 0.0 if f_demod is None else _f_demod(f_demod, fs)
+    n_taps = _n_taps(n_taps)
+    i16 = getattr(stack, "dtype", None) == np.int16
+    stack = np.ascontiguousarray(stack, dtype=np.int16 if i16 else np.float32)
+    if stack.ndim != 3 or stack.shape[0] < 1:
+        raise ValueError("the stack must be [n_frames, n_pairs, n_t] with at least one frame")
+    n_frames, n_pairs, n_t = stack.shape
+    n_e, tt_tx, tt_rx, n_f = _hmc_tables(n_pairs, tt_tx, tt_rx)
+    per = _max_frames(max_frames, n_frames)
+    imgs = _out(out, (n_frames, n_f), np.float32 if magnitude else np.complex64)
+    cf = np.empty((n_frames, n_f), dtype=np.float32) if mode else None
+    entry = "rtus_tfm_envelope_frames_hmc_i16" if i16 else "rtus_tfm_envelope_frames_hmc"
+    fn = getattr(_lib.lib(), entry)
+    for k in range(0, n_frames, per):
+        n = min(per, n_frames - k)
+        st = fn(_ptr(stack[k:k + n]), n, n_e, n_t, n_taps, float(fs), float(t0), f_demod, _ptr(tt_tx), _ptr(tt_rx), n_f,
+                ENV_MAGNITUDE if magnitude else 0, _ptr(imgs[k:k + n]), None if cf is None else _ptr(cf[k:k + n]), int(device))
+        _lib.check(st, entry)
+    return (imgs, cf) if mode else imgs
 
 
 # ---------------------------------------------------------------------------------------------- half-matrix capture

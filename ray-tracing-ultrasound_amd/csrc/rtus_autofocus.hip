@@ -4,7 +4,8 @@
 // (rtus_fmc_analytic, rtus_surface_find, rtus_echo_pick).
 //
 //   * rtus_analytic_kernel: one workgroup = RTUS_ANA_TILE samples of one A-scan plus the filter's halo in LDS; streams the FMC
-//     (4 B in, 8 B out per sample) -> HBM roofline, a small share of the chain.
+//     (4 B in, 8 B out per sample) -> HBM roofline, a small share of the chain.  rtus_analytic_i16_kernel: the same on int16
+//     samples (2 B in), also writing the Hilbert planes alone, pair-packed, for rtus_tfm_envelope_frames_hmc_i16.
 //   * rtus_surface_find_kernel: the delay-and-sum core of rtus_das.h on complex samples, with straight-ray delays formed in the
 //     kernel instead of read from a table: 16 B of L2 traffic per (pair, pixel).  The roof is the L2 gather rate, as for rtus_tfm
 //     (DESIGN §4).
@@ -49,17 +50,99 @@ __global__ __launch_bounds__(RTUS_BLOCK) void rtus_analytic_kernel(AnaArgs a)
     }
 }
 
+// the taps of every launcher of the transformer, formed in ONE place (fp64, rounded to fp32): -> M; h[i] = tap 2 i + 1
+static int ana_taps(int n_taps, float h[(RTUS_ANA_MAX_HALF + 1) / 2])
+{
+    const int M = (n_taps - 1) / 2;
+    for (int i = 0; i < (RTUS_ANA_MAX_HALF + 1) / 2; ++i) {
+        const int m = 2 * i + 1;                             // h[m] = 2 / (pi m) w[m], w the Hamming window over -M..M
+        h[i] = m <= M ? (float)(2.0 / (M_PI * m) * (0.54 + 0.46 * cos(M_PI * m / M))) : 0.0f;
+    }
+    return M;
+}
+
 hipError_t rtus_launch_fmc_analytic(const float* fmc, long long n_pairs, int n_t, int n_taps, float2* out, hipStream_t s)
 {
     AnaArgs a;
     a.x = fmc; a.out = out; a.n_t = n_t;
     a.n_tiles = (n_t + RTUS_ANA_TILE - 1) / RTUS_ANA_TILE;
-    a.M = (n_taps - 1) / 2;
-    for (int i = 0; i < (RTUS_ANA_MAX_HALF + 1) / 2; ++i) {
-        const int m = 2 * i + 1;                             // h[m] = 2 / (pi m) w[m], w the Hamming window over -M..M
-        a.h[i] = m <= a.M ? (float)(2.0 / (M_PI * m) * (0.54 + 0.46 * cos(M_PI * m / a.M))) : 0.0f;
-    }
+    a.M = ana_taps(n_taps, a.h);
     hipLaunchKernelGGL(rtus_analytic_kernel, dim3((unsigned)(n_pairs * a.n_tiles)), dim3(RTUS_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// The transformer on INT16 samples (include/rtus.h: rtus_fmc_analytic_i16, rtus_fmc_hilbert_pairs_i16_dev): rtus_analytic_kernel's
+// tile, halo and sum on the samples converted to fp32 when the tile is filled — the conversion is exact and so is the difference
+// of two converted values (|d| <= 65535 < 2^24), so y has the bits of rtus_analytic_kernel on the float32 copy.  One body, two
+// output forms:
+//   PAIRS = false: out [n_rows][n_t][2] = (x, Hx) of the n_rows A-scans of the stack, rtus_analytic_kernel's output;
+//   PAIRS = true:  the Hilbert planes ALONE in the float32 pair-packed layout of rtus_tfm_frames_hmc_dev, out [n_fpairs][n_scans][n_t][2]:
+//                  plane c of pair p is H of frame 2 p + c.  A workgroup takes the same tile of BOTH frames of a pair and stores
+//                  float2 (8-byte stores, contiguous per wave); the absent frame of an odd stack fills its tile with zeros, whose
+//                  sum is fmaf(h, +0 - +0, +0) = +0.0 for either sign of h: the plane pack_frames writes.
+struct AnaI16Args {
+    const short* __restrict__ x;                             // [n_frames][n_scans][n_t]
+    float2* __restrict__ out;
+    int n_t, n_tiles, M;
+    int n_frames, n_scans;                                   // (PAIRS only)
+    float h[(RTUS_ANA_MAX_HALF + 1) / 2];                    // h[i] = tap 2 i + 1
+};
+
+template <bool PAIRS>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_analytic_i16_kernel(AnaI16Args a)
+{
+    constexpr int P = PAIRS ? 2 : 1;
+    __shared__ float xs[P][RTUS_ANA_TILE + 2 * RTUS_ANA_MAX_HALF];
+    const size_t row = blockIdx.x / (unsigned)a.n_tiles;     // PAIRS: pair * n_scans + scan; else the A-scan
+    const int n0 = (int)(blockIdx.x % (unsigned)a.n_tiles) * RTUS_ANA_TILE;
+    const int M = a.M;
+#pragma unroll
+    for (int c = 0; c < P; ++c) {
+        size_t scan = row;
+        bool have = true;
+        if constexpr (PAIRS) {
+            const size_t frame = 2 * (row / (unsigned)a.n_scans) + c;
+            have = frame < (size_t)a.n_frames;               // (an absent frame's record does not exist and is not read)
+            scan = frame * (unsigned)a.n_scans + row % (unsigned)a.n_scans;
+        }
+        const short* rec = a.x + scan * (size_t)a.n_t;
+        for (int i = threadIdx.x; i < RTUS_ANA_TILE + 2 * M; i += RTUS_BLOCK) {   // samples outside the record are zero
+            const int n = n0 - M + i;
+            xs[c][i] = (have && n >= 0 && n < a.n_t) ? (float)rec[n] : 0.0f;
+        }
+    }
+    __syncthreads();
+    float2* o = a.out + row * (size_t)a.n_t;
+#pragma unroll
+    for (int q = 0; q < RTUS_ANA_TILE / RTUS_BLOCK; ++q) {
+        const int l = q * RTUS_BLOCK + threadIdx.x, n = n0 + l;
+        if (n >= a.n_t) break;
+        float y[P];
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            const float* t = xs[c] + l + M;                  // t[0] = x[n]
+            y[c] = 0.0f;
+            for (int i = 0; 2 * i + 1 <= M; ++i) y[c] = fmaf(a.h[i], t[-(2 * i + 1)] - t[2 * i + 1], y[c]);
+        }
+        if constexpr (PAIRS) o[n] = make_float2(y[0], y[1]);
+        else o[n] = make_float2(xs[0][l + M], y[0]);
+    }
+}
+
+// n_frames stacks of n_scans A-scans; pairs: the pair-packed Hilbert planes, else (x, Hx) of every A-scan.  The C entries have
+// checked that the grid fits.
+hipError_t rtus_launch_fmc_analytic_i16(const short* stack, int n_frames, long long n_scans, int n_t, int n_taps, bool pairs, float* out,
+                                        hipStream_t s)
+{
+    AnaI16Args a;
+    a.x = stack; a.out = (float2*)out; a.n_t = n_t;
+    a.n_tiles = (n_t + RTUS_ANA_TILE - 1) / RTUS_ANA_TILE;
+    a.M = ana_taps(n_taps, a.h);
+    a.n_frames = n_frames; a.n_scans = (int)n_scans;
+    const long long rows = pairs ? (n_frames + 1LL) / 2 * n_scans : n_frames * n_scans;
+    const dim3 grid((unsigned)(rows * a.n_tiles)), block(RTUS_BLOCK);
+    if (pairs) hipLaunchKernelGGL(rtus_analytic_i16_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(rtus_analytic_i16_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 

@@ -101,6 +101,9 @@ hipError_t rtus_launch_tfm_frames_hmc_i16(const short* packed, int n_frames, int
                                           const double* tt_rx, int n_f, float* images, hipStream_t s);
 hipError_t rtus_launch_tfm_frames_hmc(const float* packed, int n_frames, int n_e, int n_t, double fs, double t0, const double* tt_tx,
                                       const double* tt_rx, int n_f, float* images, hipStream_t s);
+hipError_t rtus_launch_fmc_analytic_i16(const short* stack, int n_frames, long long n_scans, int n_t, int n_taps, bool pairs, float* out,
+                                        hipStream_t s);
+hipError_t rtus_launch_envelope_combine(const float* re, const float* im, size_t n, bool mag, float* out, hipStream_t s);
 hipError_t rtus_launch_tfm_weighted(const float* an, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                                     const double* tt_rx, const float* w_tx, const float* w_rx, int n_f, float* image, float* sens,
                                     hipStream_t s);
@@ -1001,14 +1004,14 @@ int rtus_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0
 // ---------------------------------------------------------------------------- adaptive TFM: analytic FMC, surface from the couplant image
 #define RTUS_ANALYTIC_MAX_TAPS 255
 #define RTUS_ANALYTIC_MAX_SAMPLES (1 << 26)
-static int check_analytic(const void* fmc, int n_tx, int n_rx, int n_t, int n_taps, const void* out)
+static int check_analytic(const void* fmc, int n_tx, int n_rx, int n_t, int n_taps, const void* out, int in_bytes = 4)   // (2: int16 samples)
 {
     if (!fmc || !out || n_tx <= 0 || n_rx <= 0 || n_t <= 0) return RTUS_ERR_INVALID_ARG;
     if (n_taps < 3 || n_taps > RTUS_ANALYTIC_MAX_TAPS || !(n_taps & 1)) return RTUS_ERR_INVALID_ARG;
     if (n_t > RTUS_ANALYTIC_MAX_SAMPLES) return RTUS_ERR_UNSUPPORTED;
     const long long n_pairs = (long long)n_tx * n_rx, n_tiles = (n_t + 1023) / 1024;
     if (n_pairs * n_tiles > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;          // one workgroup per (pair, 1024 samples)
-    const uintptr_t i0 = (uintptr_t)fmc, i1 = i0 + (uintptr_t)(4 * n_pairs * n_t), o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(8 * n_pairs * n_t);
+    const uintptr_t i0 = (uintptr_t)fmc, i1 = i0 + (uintptr_t)(in_bytes * n_pairs * n_t), o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(8 * n_pairs * n_t);
     if (i0 < o1 && o0 < i1) return RTUS_ERR_INVALID_ARG;                        // the output must not overlap the input
     return RTUS_OK;
 }
@@ -1728,6 +1731,209 @@ int rtus_tfm_frames_hmc(const float* hmc, int n_frames, int n_e, int n_t, double
                         int n_f, float* images, int device)
 {
     return tfm_frames_hmc_host(hmc, false, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, device);
+}
+
+// ---------------------------------------------------------------------------- envelope TFM over a stack of half-matrix frames
+int rtus_fmc_analytic_i16_dev(const short* d_fmc, int n_tx, int n_rx, int n_t, int n_taps, float* d_out, void* stream)
+{
+    int st = check_analytic(d_fmc, n_tx, n_rx, n_t, n_taps, d_out, 2);
+    if (st) return st;
+    if (((uintptr_t)d_fmc & 1) || ((uintptr_t)d_out & 7)) return RTUS_ERR_INVALID_ARG;   // 2-byte loads, 8-byte stores
+    LAUNCH_TRY(rtus_launch_fmc_analytic_i16(d_fmc, 1, (long long)n_tx * n_rx, n_t, n_taps, false, d_out, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_fmc_analytic_i16(const short* fmc, int n_tx, int n_rx, int n_t, int n_taps, float* out, int device)
+{
+    int st = check_analytic(fmc, n_tx, n_rx, n_t, n_taps, out, 2);
+    if (st) return st;
+    const size_t n = (size_t)n_tx * n_rx * n_t;
+    Session S;
+    if ((st = S.open(device))) return st;
+    short* din;
+    float* dout;
+    S.in(din, fmc, n);
+    S.out(dout, out, 2 * n);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_fmc_analytic_i16(din, 1, (long long)n_tx * n_rx, n_t, n_taps, false, dout, S.a->stream));
+    return S.finish();
+}
+
+int rtus_fmc_hilbert_pairs_i16_dev(const short* d_fmc, int n_frames, int n_scans, int n_t, int n_taps, float* d_packed, void* stream)
+{
+    if (!d_fmc || !d_packed || n_frames <= 0 || n_scans <= 0 || n_t <= 0) return RTUS_ERR_INVALID_ARG;
+    if (n_taps < 3 || n_taps > RTUS_ANALYTIC_MAX_TAPS || !(n_taps & 1)) return RTUS_ERR_INVALID_ARG;
+    if (((uintptr_t)d_fmc & 1) || ((uintptr_t)d_packed & 7)) return RTUS_ERR_INVALID_ARG;   // 2-byte loads, 8-byte stores
+    if (n_t > RTUS_ANALYTIC_MAX_SAMPLES) return RTUS_ERR_UNSUPPORTED;
+    const long long rows = (n_frames + 1LL) / 2 * n_scans, n_tiles = (n_t + 1023) / 1024;   // one workgroup per (pair, A-scan, 1024 samples)
+    if (rows > 0x7fffffffLL || rows * n_tiles > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    const uintptr_t i0 = (uintptr_t)d_fmc, i1 = i0 + (uintptr_t)(2LL * n_frames * n_scans * n_t);
+    const uintptr_t o0 = (uintptr_t)d_packed, o1 = o0 + (uintptr_t)(8 * rows * n_t);
+    if (i0 < o1 && o0 < i1) return RTUS_ERR_INVALID_ARG;              // the output must not overlap the input
+    LAUNCH_TRY(rtus_launch_fmc_analytic_i16(d_fmc, n_frames, n_scans, n_t, n_taps, true, d_packed, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+// The workspace of rtus_tfm_envelope_frames_hmc[_i16]_dev, laid out by ONE function for the size helper and the entries: segments
+// at multiples of 256 bytes.  split: the split-plane route (int16, f_demod == 0, no cf) — the quads, the pair-packed Hilbert planes
+// and the two sets of image planes; else the complex route — ONE frame's analytic block, reused frame after frame, and with RTUS_ENV_MAGNITUDE the complex images.
+struct EnvWork {
+    bool split;
+    size_t quads, hilbert, re, im;                                    // byte offsets (split)
+    size_t analytic, cimages;                                         // byte offsets (complex route)
+    size_t bytes;                                                     // 0: a size is not positive, or the sum does not fit 2^62
+};
+static EnvWork env_work(int n_frames, int n_e, int n_t, int n_f, bool i16, double f_demod, bool want_cf, int flags)
+{
+    EnvWork w = {};
+    if (n_frames <= 0 || n_e < 1 || n_e > RTUS_HMC_MAX_ELEMENTS || n_t <= 0 || n_f <= 0) return w;
+    w.split = i16 && f_demod == 0.0 && !want_cf;
+    typedef unsigned __int128 u128;
+    const u128 n = (u128)((size_t)n_e * ((size_t)n_e + 1) / 2) * (unsigned)n_t;       // samples per frame
+    const u128 n_img = (u128)(unsigned)n_frames * (unsigned)n_f;
+    u128 end = 0;
+    auto seg = [&](size_t& off, u128 bytes) {
+        off = end >> 62 ? 0 : (size_t)end;
+        end += (bytes + 255) & ~(u128)255;
+    };
+    if (w.split) {
+        seg(w.quads, n * ((unsigned)((n_frames + 3LL) / 4) * 8ULL));
+        seg(w.hilbert, n * ((unsigned)((n_frames + 1LL) / 2) * 8ULL));
+        seg(w.re, n_img * 4);
+        seg(w.im, n_img * 4);
+    } else {
+        seg(w.analytic, n * 8);
+        if (flags & RTUS_ENV_MAGNITUDE) seg(w.cimages, n_img * 8);
+    }
+    w.bytes = end >> 62 ? 0 : (size_t)end;
+    return w;
+}
+
+size_t rtus_tfm_envelope_frames_hmc_workspace_bytes(int n_frames, int n_e, int n_t, int n_f, int i16, double f_demod, int want_cf, int flags)
+{
+    if ((flags & ~RTUS_ENV_MAGNITUDE) || !(f_demod >= 0.0) || !isfinite(f_demod)) return 0;
+    return env_work(n_frames, n_e, n_t, n_f, i16 != 0, f_demod, want_cf != 0, flags).bytes;
+}
+
+static int check_env_frames(const void* stack, bool i16, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                            const void* tt_tx, const void* tt_rx, int n_f, int flags, const void* images, bool want_cf)
+{
+    if (n_taps < 3 || n_taps > RTUS_ANALYTIC_MAX_TAPS || !(n_taps & 1) || (flags & ~RTUS_ENV_MAGNITUDE)) return RTUS_ERR_INVALID_ARG;
+    if (!(fs > 0) || check_f_demod(f_demod, fs)) return RTUS_ERR_INVALID_ARG;
+    const bool split = i16 && f_demod == 0.0 && !want_cf;            // the image kernels' blocks: pairs of frames, or frames
+    int st = check_tfm_frames_hmc(stack, n_frames, n_e, n_t, fs, t0, tt_tx, tt_rx, n_f, images, split ? 2 : 1);
+    if (st) return st;
+    if (((uintptr_t)stack & (i16 ? 1 : 3)) || ((uintptr_t)images & ((flags & RTUS_ENV_MAGNITUDE) ? 3 : 7))) return RTUS_ERR_INVALID_ARG;
+    const long long n_pairs = (long long)n_e * (n_e + 1) / 2, n_tiles = (n_t + 1023) / 1024;   // the transformer's grid
+    if (n_frames * n_pairs > 0x7fffffffLL || n_frames * n_pairs * n_tiles > 0x7fffffffLL) return RTUS_ERR_UNSUPPORTED;
+    return RTUS_OK;
+}
+
+// the launches of a call, on device pointers (the _dev entries' and the twins' after their upload)
+static int env_frames_run(const void* d_stack, bool i16, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                          const double* d_tt_tx, const double* d_tt_rx, int n_f, int flags, float* d_images, float* d_cf, void* d_work,
+                          const EnvWork& w, hipStream_t s)
+{
+    const int n_pairs = n_e * (n_e + 1) / 2;
+    const size_t n = (size_t)n_pairs * n_t, n_img = (size_t)n_frames * n_f;
+    const bool mag = flags & RTUS_ENV_MAGNITUDE;
+    char* work = (char*)d_work;
+    if (w.split) {
+        short* quads = (short*)(work + w.quads);
+        float *hilbert = (float*)(work + w.hilbert), *re = (float*)(work + w.re), *im = (float*)(work + w.im);
+        LAUNCH_TRY(rtus_launch_fmc_pack_frames_i16((const short*)d_stack, n_frames, n, quads, s));
+        LAUNCH_TRY(rtus_launch_tfm_frames_hmc_i16(quads, n_frames, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, re, s));
+        LAUNCH_TRY(rtus_launch_fmc_analytic_i16((const short*)d_stack, n_frames, n_pairs, n_t, n_taps, true, hilbert, s));
+        LAUNCH_TRY(rtus_launch_tfm_frames_hmc(hilbert, n_frames, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, im, s));
+        LAUNCH_TRY(rtus_launch_envelope_combine(re, im, n_img, mag, d_images, s));
+        return RTUS_OK;
+    }
+    float* an = (float*)(work + w.analytic);
+    float* cimages = mag ? (float*)(work + w.cimages) : d_images;
+    // Frame by frame: the transformer into the one block, then one launch of rtus_tfm_analytic_hmc's (f_demod > 0: rtus_tfm_iq_hmc's)
+    // kernel on it — that entry's bits by construction; the stream orders the block's reuse.  The block (8 B per sample) is gathered
+    // while it is still in the last-level cache; with the whole stack transformed first it is not (1.07x / 1.24x of the loop at 256^2
+    // with one / two tables: profiles/tfm_envelope_frames_hmc_variants.txt).
+    for (int k = 0; k < n_frames; ++k) {
+        if (i16) LAUNCH_TRY(rtus_launch_fmc_analytic_i16((const short*)d_stack + (size_t)k * n, 1, n_pairs, n_t, n_taps, false, an, s));
+        else LAUNCH_TRY(rtus_launch_fmc_analytic((const float*)d_stack + (size_t)k * n, n_pairs, n_t, n_taps, (float2*)an, s));
+        float *img = cimages + (size_t)k * n_f * 2, *cf = d_cf ? d_cf + (size_t)k * n_f : nullptr;
+        if (f_demod > 0.0) LAUNCH_TRY(rtus_launch_tfm_iq_hmc(an, n_e, n_t, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, img, cf, s));
+        else LAUNCH_TRY(rtus_launch_tfm_analytic_hmc(an, n_e, n_t, fs, t0, d_tt_tx, d_tt_rx, n_f, img, cf, s));
+    }
+    if (mag) LAUNCH_TRY(rtus_launch_envelope_combine(cimages, nullptr, n_img, true, d_images, s));
+    return RTUS_OK;
+}
+
+static int env_frames_dev(const void* d_hmc, bool i16, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                          const double* d_tt_tx, const double* d_tt_rx, int n_f, int flags, float* d_images, float* d_cf, void* d_work,
+                          size_t work_bytes, void* stream)
+{
+    int st = check_env_frames(d_hmc, i16, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, flags, d_images, d_cf != nullptr);
+    if (st) return st;
+    const EnvWork w = env_work(n_frames, n_e, n_t, n_f, i16, f_demod, d_cf != nullptr, flags);
+    if (!w.bytes) return RTUS_ERR_UNSUPPORTED;
+    if ((st = check_workspace(d_work, work_bytes, w.bytes, 64))) return st;
+    return env_frames_run(d_hmc, i16, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, flags, d_images, d_cf, d_work, w,
+                          (hipStream_t)stream);
+}
+
+int rtus_tfm_envelope_frames_hmc_i16_dev(const short* d_hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                                         const double* d_tt_tx, const double* d_tt_rx, int n_f, int flags, float* d_images, float* d_cf,
+                                         void* d_work, size_t work_bytes, void* stream)
+{
+    return env_frames_dev(d_hmc, true, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, flags, d_images, d_cf, d_work,
+                          work_bytes, stream);
+}
+
+int rtus_tfm_envelope_frames_hmc_dev(const float* d_hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                                     const double* d_tt_tx, const double* d_tt_rx, int n_f, int flags, float* d_images, float* d_cf,
+                                     void* d_work, size_t work_bytes, void* stream)
+{
+    return env_frames_dev(d_hmc, false, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, d_tt_tx, d_tt_rx, n_f, flags, d_images, d_cf, d_work,
+                          work_bytes, stream);
+}
+
+// the two host twins: the frame-major stack uploaded in its own type, the workspace a scratch buffer of the arena
+static int env_frames_host(const void* hmc, bool i16, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                           const double* tt_tx, const double* tt_rx, int n_f, int flags, float* images, float* cf, int device)
+{
+    int st = check_env_frames(hmc, i16, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, tt_tx, tt_rx, n_f, flags, images, cf != nullptr);
+    if (st) return st;
+    const EnvWork w = env_work(n_frames, n_e, n_t, n_f, i16, f_demod, cf != nullptr, flags);
+    if (!w.bytes) return RTUS_ERR_UNSUPPORTED;
+    const size_t n = (size_t)n_e * ((size_t)n_e + 1) / 2 * (size_t)n_t * (size_t)n_frames, n_img = (size_t)n_frames * n_f;
+    const bool same = tt_tx == tt_rx;
+    Session S;
+    if ((st = S.open(device))) return st;
+    short* dstack16 = nullptr;
+    float *dstack = nullptr, *dimg, *dcf;
+    double *dtx, *drx = nullptr;
+    char* dwork;
+    if (i16) S.in(dstack16, (const short*)hmc, n);
+    else S.in(dstack, (const float*)hmc, n);
+    S.in(dtx, tt_tx, (size_t)n_e * n_f);
+    if (!same) S.in(drx, tt_rx, (size_t)n_e * n_f);
+    S.out(dimg, images, (flags & RTUS_ENV_MAGNITUDE) ? n_img : 2 * n_img);
+    S.out(dcf, cf, n_img);
+    S.scratch(dwork, w.bytes);
+    if ((st = S.flush())) return st;
+    st = env_frames_run(i16 ? (const void*)dstack16 : (const void*)dstack, i16, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, dtx,
+                        same ? dtx : drx, n_f, flags, dimg, dcf, dwork, w, S.a->stream);
+    if (st) return st;
+    return S.finish();
+}
+
+int rtus_tfm_envelope_frames_hmc_i16(const short* hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                                     const double* tt_tx, const double* tt_rx, int n_f, int flags, float* images, float* cf, int device)
+{
+    return env_frames_host(hmc, true, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, tt_tx, tt_rx, n_f, flags, images, cf, device);
+}
+
+int rtus_tfm_envelope_frames_hmc(const float* hmc, int n_frames, int n_e, int n_t, int n_taps, double fs, double t0, double f_demod,
+                                 const double* tt_tx, const double* tt_rx, int n_f, int flags, float* images, float* cf, int device)
+{
+    return env_frames_host(hmc, false, n_frames, n_e, n_t, n_taps, fs, t0, f_demod, tt_tx, tt_rx, n_f, flags, images, cf, device);
 }
 
 // ---------------------------------------------------------------------------- phase-coherence TFM: vcf, scf

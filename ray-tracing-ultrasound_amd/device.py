@@ -587,6 +587,85 @@ def tfm_frames_hmc_dev(packed, n_frames, fs, tt_tx, tt_rx=None, t0=0.0, out=None
     return _tfm_frames_hmc_dev("rtus_tfm_frames_hmc_dev", 2, torch.float32, packed, n_frames, fs, tt_tx, tt_rx, t0, out)
 
 
+def fmc_analytic_i16_dev(fmc, n_taps=63, out=None):
+    """fmc_analytic_dev on int16 samples (rtus_fmc_analytic_i16_dev): fmc int16 [n_tx, n_rx, n_t] -> out float32 [n_tx, n_rx, n_t, 2]
+    with fmc_analytic_dev's bits on the samples as float32.  Asynchronous on the current stream."""
+    _chk(fmc, "fmc", torch.int16)
+    if fmc.dim() != 3:
+        raise ValueError("fmc must be [n_tx, n_rx, n_t]")
+    out = _result(out, (*fmc.shape, 2), fmc, torch.float32)
+    if out.device != fmc.device:
+        raise ValueError("out must be on the device of fmc")
+    st = _lib.lib().rtus_fmc_analytic_i16_dev(_p(fmc), fmc.shape[0], fmc.shape[1], fmc.shape[2], int(n_taps), _p(out), _stream(fmc))
+    _lib.check(st, "rtus_fmc_analytic_i16_dev")
+    return out
+
+
+def fmc_hilbert_pairs_i16_dev(stack, n_taps=63, out=None):
+    """The Hilbert planes of a frame-major int16 stack [n_frames, n_scans, n_t], pair-packed (rtus_fmc_hilbert_pairs_i16_dev;
+    api.frames_pack's layout on the imaginary parts) -> out float32 [n_fpairs, n_scans, n_t, 2]: what tfm_frames_hmc_dev reads, plane c of pair p the
+    imaginary part of fmc_analytic_i16_dev of frame 2 p + c, the absent frame of an odd stack +0.0.  Asynchronous on the current
+    stream (capturable with a pre-allocated output)."""
+    _chk(stack, "stack", torch.int16)
+    if stack.dim() != 3 or stack.shape[0] < 1:
+        raise ValueError("stack must be [n_frames, n_scans, n_t] with at least one frame")
+    n_frames, n_scans, n_t = stack.shape
+    out = _result(out, ((n_frames + 1) // 2, n_scans, n_t, 2), stack, torch.float32)
+    if out.device != stack.device:
+        raise ValueError("out must be on the device of stack")
+    st = _lib.lib().rtus_fmc_hilbert_pairs_i16_dev(_p(stack), n_frames, n_scans, n_t, int(n_taps), _p(out), _stream(stack))
+    _lib.check(st, "rtus_fmc_hilbert_pairs_i16_dev")
+    return out
+
+
+def tfm_envelope_frames_hmc_workspace_bytes(n_frames, n_e, n_t, n_f, *, i16, f_demod=0.0, want_cf=False, magnitude=False):
+    """the bytes of the ``ws`` tensor of tfm_envelope_frames_hmc[_i16]_dev for these sizes (0: refused)"""
+    return int(_lib.lib().rtus_tfm_envelope_frames_hmc_workspace_bytes(int(n_frames), int(n_e), int(n_t), int(n_f), int(bool(i16)),
+                                                                        float(f_demod), int(bool(want_cf)),
+                                                                        _api.ENV_MAGNITUDE if magnitude else 0))
+
+
+def _tfm_envelope_frames_hmc_dev(entry, dtype, stack, fs, tt_tx, tt_rx, t0, n_taps, f_demod, magnitude, out, cf, ws):
+    """tfm_envelope_frames_hmc_i16_dev (int16 frames) and tfm_envelope_frames_hmc_dev (float32 frames)"""
+    f_demod = _f_demod(f_demod, fs)
+    _chk(stack, "stack", dtype); _chk(tt_tx, "tt_tx")
+    tt_rx = tt_tx if tt_rx is None else _chk(tt_rx, "tt_rx")
+    if stack.dim() != 3 or stack.shape[0] < 1:
+        raise ValueError("stack must be [n_frames, n_pairs, n_t] with at least one frame")
+    n_frames, n_t = stack.shape[0], stack.shape[2]
+    n_e, n_f = _hmc_tables(tt_tx, tt_rx, stack[0], False)
+    out = _result(out, (n_frames, n_f) if magnitude else (n_frames, n_f, 2), stack, torch.float32)
+    _optional(n_frames * n_f, torch.float32, cf=cf)
+    need = tfm_envelope_frames_hmc_workspace_bytes(n_frames, n_e, n_t, n_f, i16=dtype == torch.int16, f_demod=f_demod,
+                                                   want_cf=cf is not None, magnitude=magnitude)
+    ws = _workspace(ws, need, stack)
+    if not (out.device == stack.device == tt_tx.device == tt_rx.device == ws.device and (cf is None or cf.device == stack.device)):
+        raise ValueError("stack, tt_tx, tt_rx, out, cf and ws must be on one device")
+    st = getattr(_lib.lib(), entry)(_p(stack), n_frames, n_e, n_t, int(n_taps), float(fs), float(t0), f_demod, _p(tt_tx), _p(tt_rx), n_f,
+                                    _api.ENV_MAGNITUDE if magnitude else 0, _p(out), _p(cf), _p(ws), ws.numel(), _stream(stack))
+    _lib.check(st, entry)
+    return out if cf is None else (out, cf)
+
+
+def tfm_envelope_frames_hmc_i16_dev(stack, fs, tt_tx, tt_rx=None, t0=0.0, n_taps=63, f_demod=0.0, magnitude=False, out=None, cf=None,
+                                    ws=None):
+    """Envelope TFM over a stack of int16 half-matrix frames on device (rtus_tfm_envelope_frames_hmc_i16_dev;
+    api.tfm_envelope_frames' definition): ``stack`` int16 [n_frames, n_pairs, n_t], FRAME-MAJOR (the packing happens in ``ws``),
+    tt_tx / tt_rx [n_e, n_f] (default: tt_tx — one table) -> out float32 [n_frames, n_f, 2], or [n_frames, n_f] with
+    ``magnitude=True``; ``cf``: an optional float32 [n_frames, n_f] tensor that receives the coherence factors (then -> (out, cf)).
+    ``ws``: a uint8 workspace of tfm_envelope_frames_hmc_workspace_bytes(...) bytes, allocated here when None.  Asynchronous on the
+    current stream (capturable with pre-allocated out, cf and ws)."""
+    return _tfm_envelope_frames_hmc_dev("rtus_tfm_envelope_frames_hmc_i16_dev", torch.int16, stack, fs, tt_tx, tt_rx, t0, n_taps, f_demod,
+                                        magnitude, out, cf, ws)
+
+
+def tfm_envelope_frames_hmc_dev(stack, fs, tt_tx, tt_rx=None, t0=0.0, n_taps=63, f_demod=0.0, magnitude=False, out=None, cf=None, ws=None):
+    """tfm_envelope_frames_hmc_i16_dev for float32 frames (rtus_tfm_envelope_frames_hmc_dev): ``stack`` float32
+    [n_frames, n_pairs, n_t]; the same tensors, returns and bits."""
+    return _tfm_envelope_frames_hmc_dev("rtus_tfm_envelope_frames_hmc_dev", torch.float32, stack, fs, tt_tx, tt_rx, t0, n_taps, f_demod,
+                                        magnitude, out, cf, ws)
+
+
 def tfm_analytic_hmc_dev(analytic, fs, tt_tx, tt_rx=None, t0=0.0, out=None, cf=None):
     """Envelope TFM over a half-matrix capture on device (rtus_tfm_analytic_hmc_dev; api.tfm_analytic_hmc's definition): analytic
     float32 [n_pairs, n_t, 2], tt_tx / tt_rx [n_e, n_f] (default: tt_tx) -> out float32 [n_f, 2] (the complex sum); ``cf``: an
