@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 125 /* 0.1.24: rtus_tfm_envelope_frames_hmc[_i16], rtus_fmc_analytic_i16 (envelope TFM over half-matrix frame stacks) */
+#define RTUS_VERSION 126 /* 0.1.25: rtus_tt_layers3[_dev] (matrix arrays: element x point travel times in three dimensions through horizontal layers) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -1633,6 +1633,47 @@ int rtus_tfm_weighted_hmc_dev(const float *d_a, int n_e, int n_t, double fs, dou
 int rtus_tfm_weighted_hmc(const float *a, int n_e, int n_t, double fs, double t0,
                           const double *tt_tx, const double *tt_rx, const float *w_tx, const float *w_rx, int n_f,
                           float *image, float *sens, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Matrix (2-D) arrays: element x focal-point Fermat travel times in THREE dimensions through horizontal layers — the table that
+ * volumetric TFM needs.  NOT IN THE REFERENCE; checked against oracle/ per element, closed forms and tests/layers3d_numpy.py.
+ * Every consumer of a table [n_e][n_f] (rtus_tfm*, rtus_focal_delays, rtus_fmc_sim, the multi-view entries) takes this one as it
+ * is: the focal points are a flat list, the n_e = n_x n_y elements of a matrix array are rows.
+ *
+ *   z_if, c, n_if   the stack, rtus_tt_layers's conventions (HOST memory; n_if <= RTUS_MAX_LAYERS)
+ *   xe,ye,ze [n_e]  elements, at any depth (also below the first interface)
+ *   xf,yf,zf [n_f]  focal points, at any depth
+ *   tt [n_e][n_f]   least travel time [s]; NaN where zf <= ze or where any of the pair's six coordinates is not finite
+ *   flags           must be 0 (RTUS_ERR_INVALID_ARG otherwise): no tau-p tier, no table-served path
+ *
+ * Definition.  Horizontal layers are symmetric about the vertical axis: the ray from an element to a point lies in the vertical
+ * plane through both, and its time is the planar time (rtus_tt_layers, default tier: <= 1e-13 relative) at the lateral reach
+ *       r = sqrt(dx dx + dy dy),   dx = xf - xe,   dy = yf - ye
+ * in fp64 with a correctly rounded square root, between the depths ze and zf.  With dy = 0, r is |dx| exactly.
+ * Each entry depends on its own pair only.  Every solve starts from a bound formed from its own reach and depths; nothing is carried
+ * from element to element.  The bits of tt[e][f] do not change when elements or points are permuted, duplicated, added or removed,
+ * or when the call is split into calls over blocks of rows or columns.  Row shards and several GPUs therefore need no entry of
+ * their own: a slice of the inputs gives the slice of the table.
+ * Launch shape (what a test of the tile seams needs): one workgroup = RTUS_TT_LAYERS3_POINTS points (one per lane) x
+ * RTUS_TT_LAYERS3_ROWS consecutive elements.
+ * Limits: n_f < 2^29 (a row's byte offsets are 32-bit; row offsets are 64-bit, n_e n_f 8 may pass 4 GiB) and
+ * ceil(n_f / RTUS_TT_LAYERS3_POINTS) ceil(n_e / RTUS_TT_LAYERS3_ROWS) < 2^31: RTUS_ERR_UNSUPPORTED beyond.  Null pointers, non-positive
+ * sizes, a bad stack: as rtus_tt_layers.  The _dev entry allocates nothing and does not synchronise (capturable); the host twin stages
+ * through the arena.
+ * Measured on MI355X (2026-10-21; DESIGN.md section 4 "Matrix arrays", profiles/layers3d_kernel.txt; CUDA-event timing, two interfaces):
+ * 16 x 16 elements x 64 x 64 x 32 points 152 us, 32 x 32 x 64^3 1.04 ms: 2.2-2.6e11 solves/s, 1.9-2.0x the time of rtus_tt_layers_dev
+ * (default tier) at equal n_e and n_f in the same run — every solve starts cold.  Not measured: counters.
+ * ---------------------------------------------------------------------------------------- */
+#define RTUS_TT_LAYERS3_POINTS 256
+#define RTUS_TT_LAYERS3_ROWS 16
+int rtus_tt_layers3_dev(const double *z_if, const double *c, int n_if,
+                        const double *d_xe, const double *d_ye, const double *d_ze, int n_e,
+                        const double *d_xf, const double *d_yf, const double *d_zf, int n_f,
+                        double *d_tt, unsigned flags, void *stream);
+int rtus_tt_layers3(const double *z_if, const double *c, int n_if,
+                    const double *xe, const double *ye, const double *ze, int n_e,
+                    const double *xf, const double *yf, const double *zf, int n_f,
+                    double *tt, unsigned flags, int device);
 
 #ifdef __cplusplus
 }

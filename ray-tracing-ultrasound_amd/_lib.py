@@ -221,6 +221,9 @@ PROTOTYPES = (
     ("rtus_tfm_phase_hmc", i, [vp, i, i, dd, dd, vp, vp, i, vp, vp, vp, vp, i], 124),
     ("rtus_tfm_weighted_hmc_dev", i, [vp, i, i, dd, dd, vp, vp, vp, vp, i, vp, vp, vp], 124),
     ("rtus_tfm_weighted_hmc", i, [vp, i, i, dd, dd, vp, vp, vp, vp, i, vp, vp, i], 124),
+    # matrix arrays: travel times in three dimensions through horizontal layers
+    ("rtus_tt_layers3_dev", i, [vp, vp, i, vp, vp, vp, i, vp, vp, vp, i, vp, u, vp], 126),
+    ("rtus_tt_layers3", i, [vp, vp, i, vp, vp, vp, i, vp, vp, vp, i, vp, u, i], 126),
 )
 EXPORTS = tuple(p[0] for p in PROTOTYPES)
 

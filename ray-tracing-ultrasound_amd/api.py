@@ -1316,6 +1316,98 @@ def view_legs_layers(z_if, c_above, c_l, c_t, z_back, xe, ze, xf, zf, *, legs=LE
     return out
 
 
+# ---------------------------------------------------------------------------------------------- matrix arrays: three dimensions
+LAYERS3_POINTS = 256        # RTUS_TT_LAYERS3_POINTS: focal points per workgroup of the kernel (tests of its tile seams)
+LAYERS3_ROWS = 16           # RTUS_TT_LAYERS3_ROWS:   elements per workgroup
+
+
+def matrix_array(n_x, n_y, pitch_x, pitch_y=None, z=0.0):
+    """The elements of an ``n_x`` x ``n_y`` matrix array -> (xe, ye, ze), each [n_x * n_y]: centred on x = y = 0, x fastest
+    (element ``j * n_x + i`` is column i of row j), all at depth ``z``.  ``pitch_y`` defaults to ``pitch_x``."""
+    n_x, n_y = int(n_x), int(n_y)
+    if n_x < 1 or n_y < 1:
+        raise ValueError("need n_x >= 1 and n_y >= 1")
+    pitch_y = pitch_x if pitch_y is None else pitch_y
+    x = (np.arange(n_x, dtype=np.float64) - 0.5 * (n_x - 1)) * np.float64(pitch_x)
+    y = (np.arange(n_y, dtype=np.float64) - 0.5 * (n_y - 1)) * np.float64(pitch_y)
+    return np.tile(x, n_y), np.repeat(y, n_x), np.full(n_x * n_y, float(z))
+
+
+def volume_grid(xs, ys, zs):
+    """The focal points of a volume -> (xf, yf, zf, shape): every (x, y, z) of the three axes as flat vectors, x fastest, then y,
+    then z; ``shape`` = (n_z, n_y, n_x), so an image over the points reads ``image.reshape(shape)[iz, iy, ix]``."""
+    xs, ys, zs = _f64(xs, "xs"), _f64(ys, "ys"), _f64(zs, "zs")
+    shape = (zs.size, ys.size, xs.size)
+    zf, yf, xf = (np.ascontiguousarray(np.broadcast_to(v, shape).reshape(-1))
+                  for v in (zs[:, None, None], ys[None, :, None], xs[None, None, :]))
+    return xf, yf, zf, shape
+
+
+def _points_3d(xe, ye, ze, xf, yf, zf):
+    """Elements and focal points in three dimensions as float64 vectors, xe/ye/ze and xf/yf/zf of one length each."""
+    xe, ye, ze = _f64(xe, "xe"), _f64(ye, "ye"), _f64(ze, "ze")
+    xf, yf, zf = _f64(xf, "xf"), _f64(yf, "yf"), _f64(zf, "zf")
+    if not (xe.shape == ye.shape == ze.shape and xf.shape == yf.shape == zf.shape):
+        raise ValueError("xe/ye/ze and xf/yf/zf must pair up")
+    return xe, ye, ze, xf, yf, zf
+
+
+def travel_time_layers_3d(z_if, c, xe, ye, ze, xf, yf, zf, *, out=None, device=0):
+    """Element x focal-point Fermat travel times in three dimensions through horizontal layers -> tt[n_e, n_f]: the table of a
+    matrix (2-D) array over the points of a volume, which every consumer of a table (tfm_image, tfm_analytic, tfm_views,
+    simulate_fmc, focal_delays ...) takes as it is.
+
+    The stack is travel_time_layers's; elements and points may lie at any depth.  An entry is the planar time at the lateral reach
+    r = sqrt((xf - xe)^2 + (yf - ye)^2) (<= 1e-13 relative), NaN where zf <= ze or a coordinate of the pair is not finite.  Each
+    entry depends on its own pair only: a slice of the elements or of the points gives that slice of the table bit for bit, so
+    row shards and several GPUs are slices of the inputs (include/rtus.h, rtus_tt_layers3).  ``out``: optional float64
+    [n_e, n_f] result buffer.  Not in the reference."""
+    z_if, c = _medium(z_if, c)
+    xe, ye, ze, xf, yf, zf = _points_3d(xe, ye, ze, xf, yf, zf)
+    tt = _out(out, (xe.size, xf.size), np.float64)
+    st = _lib.lib().rtus_tt_layers3(_ptr(z_if) if z_if.size else None, _ptr(c), z_if.size, _ptr(xe), _ptr(ye), _ptr(ze), xe.size,
+                                    _ptr(xf), _ptr(yf), _ptr(zf), xf.size, _ptr(tt), 0, int(device))
+    _lib.check(st, "rtus_tt_layers3")
+    return tt
+
+
+def skip_travel_time_layers_3d(z_if, c, z_back, xe, ye, ze, xf, yf, zf, *, c_up=None, out=None, device=0):
+    """skip_travel_time_layers for a matrix array: the SKIP leg down through ``z_if`` / ``c``, off the planar backwall at ``z_back``
+    and up at ``c_up`` (default ``c[-1]``) to the point — a planar backwall keeps the symmetry about the vertical axis, so the time
+    is travel_time_layers_3d(z_if + [z_back], c + [c_up], ..., 2 z_back - zf), and NaN outside z_if[-1] < zf < z_back."""
+    z_if, c = _medium(z_if, c)
+    z_back = float(z_back)
+    c_up = float(c[-1]) if c_up is None else float(c_up)
+    front = float(z_if[-1]) if z_if.size else -np.inf
+    if not (z_back > front):
+        raise ValueError("the backwall must lie below the last interface (z_back > z_if[-1])")
+    if z_if.size + 1 > MAX_LAYERS:
+        raise ValueError(f"a skip leg adds an interface: at most {MAX_LAYERS - 1} interfaces above the backwall")
+    zf = _f64(zf, "zf")
+    tt = travel_time_layers_3d(np.r_[z_if, z_back], np.r_[c, c_up], xe, ye, ze, xf, yf, 2.0 * z_back - zf, out=out, device=device)
+    tt[:, ~((zf > front) & (zf < z_back))] = np.nan
+    return tt
+
+
+def view_legs_layers_3d(z_if, c_above, c_l, c_t, z_back, xe, ye, ze, xf, yf, zf, *, legs=LEGS, device=0):
+    """view_legs_layers for a matrix array -> {leg: tt [n_e, n_f]} for ``legs`` (default all six), in the shape tfm_views takes:
+    multi-view TFM of a volume.  Direct legs: travel_time_layers_3d; skip legs: skip_travel_time_layers_3d."""
+    legs = _legs_wanted(legs)
+    z_if = list(np.atleast_1d(np.asarray(z_if, dtype=np.float64)))
+    c_above = list(np.atleast_1d(np.asarray(c_above, dtype=np.float64)))
+    if len(c_above) != len(z_if):
+        raise ValueError("need len(c_above) == len(z_if)")
+    sp = {"L": float(c_l), "T": float(c_t)}
+    out = {}
+    for g in legs:
+        if len(g) == 1:
+            out[g] = travel_time_layers_3d(z_if, c_above + [sp[g]], xe, ye, ze, xf, yf, zf, device=device)
+        else:
+            out[g] = skip_travel_time_layers_3d(z_if, c_above + [sp[g[0]]], z_back, xe, ye, ze, xf, yf, zf, c_up=sp[g[1]],
+                                                device=device)
+    return out
+
+
 def view_legs_surface(x0, dx, zs, c1, c_l, c_t, z_back, xe, ze, xf, zf, *, legs=LEGS, device=0):
     """The leg tables of multi-view TFM through ONE measured front surface (travel_time_surface's profile; couplant ``c1``) ->
     {leg: tt [n_e, n_f]} for ``legs`` (default all six).  The part has speeds ``c_l`` / ``c_t`` and a planar backwall at

@@ -46,6 +46,8 @@ size_t rtus_layers_sort_ws_bytes(int n_e);
 hipError_t rtus_launch_tt_layers_sorted(const double* z_if, const double* c, int n_if, const double* xe, const double* ze, int n_e,
                                         const double* xf, const double* zf, int n_f, double* tt, void* ws, const int* presorted_row_of,
                                         unsigned flags, hipStream_t s);
+hipError_t rtus_launch_tt_layers3(const double* z_if, const double* c, int n_if, const double* xe, const double* ye, const double* ze,
+                                  int n_e, const double* xf, const double* yf, const double* zf, int n_f, double* tt, hipStream_t s);
 
 hipError_t rtus_launch_tt_lens_f64(const rtus_lens& L, double a_lo, double a_hi, const double* xe, const double* ze,
                                    int n_e, const double* xf, const double* zf, int n_f, double* tt,
@@ -844,6 +846,48 @@ int rtus_tt_layers(const double* z_if, const double* c, int n_if, const double* 
                    const double* xf, const double* zf, int n_f, double* tt, uint8_t* iters, int device)
 {
     return rtus_tt_layers_ex(z_if, c, n_if, xe, ze, n_e, xf, zf, n_f, tt, iters, 0u, device);
+}
+
+// matrix arrays (three dimensions): rtus_tt_layers's checks + the y vectors, the kernel's own limits, flags = 0
+static int check_layers3(const double* z_if, const double* c, int n_if, const void* xe, const void* ye, const void* ze, int n_e,
+                         const void* xf, const void* yf, const void* zf, int n_f, const void* tt, unsigned flags)
+{
+    if (!ye || !yf) return RTUS_ERR_INVALID_ARG;
+    const int st = check_layers(z_if, c, n_if, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    if (flags) return RTUS_ERR_INVALID_ARG;
+    if (n_f >= (1 << 29)) return RTUS_ERR_UNSUPPORTED;                        // a row's byte offsets are 32-bit
+    const long long gx = (n_f + RTUS_TT_LAYERS3_POINTS - 1) / RTUS_TT_LAYERS3_POINTS, gy = (n_e + RTUS_TT_LAYERS3_ROWS - 1) / RTUS_TT_LAYERS3_ROWS;
+    return gx * gy > 0x7fffffffLL ? RTUS_ERR_UNSUPPORTED : RTUS_OK;           // one workgroup per work item in grid.x
+}
+
+int rtus_tt_layers3_dev(const double* z_if, const double* c, int n_if, const double* d_xe, const double* d_ye, const double* d_ze, int n_e,
+                        const double* d_xf, const double* d_yf, const double* d_zf, int n_f, double* d_tt, unsigned flags, void* stream)
+{
+    const int st = check_layers3(z_if, c, n_if, d_xe, d_ye, d_ze, n_e, d_xf, d_yf, d_zf, n_f, d_tt, flags);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tt_layers3(z_if, c, n_if, d_xe, d_ye, d_ze, n_e, d_xf, d_yf, d_zf, n_f, d_tt, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tt_layers3(const double* z_if, const double* c, int n_if, const double* xe, const double* ye, const double* ze, int n_e,
+                    const double* xf, const double* yf, const double* zf, int n_f, double* tt, unsigned flags, int device)
+{
+    int st = check_layers3(z_if, c, n_if, xe, ye, ze, n_e, xf, yf, zf, n_f, tt, flags);
+    if (st) return st;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dxe, *dye, *dze, *dxf, *dyf, *dzf, *dtt;
+    S.in(dxe, xe, n_e);
+    S.in(dye, ye, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dyf, yf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, (size_t)n_e * n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tt_layers3(z_if, c, n_if, dxe, dye, dze, n_e, dxf, dyf, dzf, n_f, dtt, S.a->stream));
+    return S.finish();
 }
 
 // ---------------------------------------------------------------------------- one curved interface: a sampled profile

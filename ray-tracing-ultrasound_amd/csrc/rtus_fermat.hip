@@ -1109,3 +1109,133 @@ hipError_t rtus_launch_tt_layers_sorted(const double* z_if, const double* c, int
     hipLaunchKernelGGL(rtus_rank_kernel, dim3((n_e + 3) / 4), dim3(256), 0, s, xe, ze, n_e, w.xs, w.zs, w.row_of);
     return launch_layers(z_if, c, n_if, w.xs, w.zs, n_e, xf, zf, n_f, tt, nullptr, 1, 0, 0, 0, 0, n_e, flags, w.row_of, s);
 }
+
+// ---- Matrix arrays: elements (xe, ye, ze) x points (xf, yf, zf) ---------------------------------------------------------------
+// Horizontal layers are symmetric about the vertical axis: the ray from an element to a point lies in the vertical plane through
+// both, and its time is the planar time at lateral reach r = sqrt(dx dx + dy dy), dx = xf - xe, dy = yf - ye, between the depths ze
+// and zf.  The mathematics is the planar solver's (layer_setup, the fp32 Newton loop clamped to the root's lower bound, the fp64
+// tail with the second-order Fermat term); none of its speed machinery carries over — the predictor along a linear aperture, HOLD
+// and the row table all lean on xf - xe being signed and linear along the element index.
+// EVERY SOLVE STARTS COLD, from the lower bound that its own reach gives: nothing is carried from element to element, so the bits of
+// tt[e][f] are a function of the pair (and the medium) alone — not of the order of the elements or points, of what else the call
+// holds, or of how a table is cut into calls.  (A lane that is done does not take its step and re-derives the same dq while its
+// wave goes on: the wave's trip count does not reach the bits.  layer_setup is a pure function of (ze, zf): re-using it while the
+// depth repeats gives what running it again gives.)
+// Launch shape: a workgroup = RTUS_TT_LAYERS3_POINTS points (one per lane: a row's stores are contiguous) x RTUS_TT_LAYERS3_ROWS
+// consecutive elements (loop); the elements' coordinates sit in LDS and are broadcast.  Work items are flattened into grid.x, the
+// columns of points fastest.
+static_assert(RTUS_TT_LAYERS3_POINTS == RTUS_BLOCK, "one point per lane of the workgroup");
+
+struct Layers3Args {
+    LayerArgs a;                       // the medium, xe / ze / xf / zf / tt, n_e, n_f (the planar launch's fields are unused)
+    const double* __restrict__ ye;
+    const double* __restrict__ yf;
+    int gx;                            // columns of points
+};
+
+// The travel time at reach X >= 0 through the lane's layers: Newton from the lower bound of the root (solve_elem's cold start), then
+// the default tier's tail.  A function of (X, L) alone.
+template <int NL>
+__device__ __forceinline__ double solve_reach(const Lane<NL>& L, double X)
+{
+    const float Xf = (float)X;
+    const float lb = fmaxf(fmaxf(Xf * L.rs0f, (Xf - L.asymf) * L.rhmf), 0.0f);
+    float q = lb, y[NL], rS3 = 0.0f;
+    for (int trip = 0; trip < 64; ++trip) {                 // wave-uniform trip count, ballot exit
+        const float q2 = q * q;
+        float S1 = L.hr0f, S3 = L.hr0f;                     // slot 0: k = 0, y = 1
+#pragma unroll
+        for (int i = 1; i < NL; ++i) {
+            y[i] = __builtin_amdgcn_rsqf(fmaf(L.kkf[i], q2, 1.0f));
+            const float hw = L.hrf[i] * y[i];
+            S1 += hw;
+            S3 = fmaf(hw, y[i] * y[i], S3);
+        }
+        rS3 = __builtin_amdgcn_rcpf(S3);
+        const float dq = fmaf(-S1, q, Xf) * rS3;
+        const bool big = fabsf(dq) > L.tau * q;             // tau = +inf on lanes without a path, NaN on a non-finite reach: never a step
+        if (!__builtin_amdgcn_ballot_w64(big)) break;
+        q = big ? fmaxf(q + dq, lb) : q;                    // a lane that is done keeps its q: y[] and rS3 stay those of its q
+    }
+    // T(root) = T(q) + p dXr + (1/2) (dp/dX) dXr^2 + O(dXr^3), dXr = X - X(q) in fp64: see solve_elem
+    const double qd = (double)q, q2 = qd * qd, a1 = 1.0 + q2;
+    const float us = __builtin_amdgcn_rsqf(fmaf(q, q, 1.0f));
+    const double u = rsqrt_refine(a1, (double)us);
+    double A1 = L.hr0, ST = L.hc0;
+#pragma unroll
+    for (int i = 1; i < NL; ++i) {
+        const double w = rsqrt_refine(fma(L.kk[i], q2, 1.0), (double)y[i]);
+        A1 = fma(L.hr[i], w, A1);
+        ST = fma(L.hc[i], w, ST);
+    }
+    const double dXr = fma(-A1, qd, X);
+    const float s2 = (0.5f * us) * (us * rS3);
+    return u * fma(L.inv_cm, dXr * fma((double)s2, dXr, qd), a1 * ST);
+}
+
+template <int NL>
+__global__ __launch_bounds__(RTUS_BLOCK) void rtus_tt_layers3_kernel(Layers3Args g)
+{
+    __shared__ double ex[RTUS_TT_LAYERS3_ROWS], ey[RTUS_TT_LAYERS3_ROWS], ez[RTUS_TT_LAYERS3_ROWS];
+    const LayerArgs& a = g.a;
+    const int bx = (int)(blockIdx.x % (unsigned)g.gx), by = (int)(blockIdx.x / (unsigned)g.gx);
+    const int e0 = by * RTUS_TT_LAYERS3_ROWS, ne = min(RTUS_TT_LAYERS3_ROWS, a.n_e - e0);
+    if ((int)threadIdx.x < ne) {
+        ex[threadIdx.x] = a.xe[e0 + threadIdx.x];
+        ey[threadIdx.x] = g.ye[e0 + threadIdx.x];
+        ez[threadIdx.x] = a.ze[e0 + threadIdx.x];
+    }
+    // lanes beyond the last point redo the last one and store to its address: no index leaves the buffers
+    const int f = min(bx * RTUS_BLOCK + (int)threadIdx.x, a.n_f - 1);
+    const unsigned f8 = (unsigned)f * 8u;                   // (n_f < 2^29: the launcher checks)
+    const double xf = a.xf[f], yf = g.yf[f];
+    __syncthreads();
+    const unsigned row_bytes = (unsigned)a.n_f * 8u;
+    double* __restrict__ row = a.tt + (size_t)e0 * (size_t)a.n_f;   // 64-bit: n_e n_f 8 passes 4 GiB at production sizes
+    Lane<NL> L;
+    for (int i = 0; i < ne; ++i, row += a.n_f) {
+        const double ze = ez[i];
+        // the layer table depends on (ze, zf): a flat matrix array sets up once per lane (wave-uniform: the depths are the block's)
+        if (i == 0 || __builtin_amdgcn_readfirstlane((int)!(ze == ez[i - 1]))) {
+            layer_setup<NL>(a, ze, a.zf, f8, L);
+            // a depth that is not finite has no path (layer_setup knows zf <= ze and NaN, not +-inf)
+            L.hc0 = isfinite(a.zf[f] - ze) ? L.hc0 : NAN;
+        }
+        const double dx = xf - ex[i], dy = yf - ey[i];
+        const double r = sqrt(dx * dx + dy * dy);           // IEEE: correctly rounded (-fno-fast-math); dy = 0: |dx| exactly
+        double T = solve_reach<NL>(L, r);
+        T = isfinite(r) ? T : NAN;
+        // one descriptor per row (extent: the row), each lane a 32-bit byte offset inside it
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(row, 0, row_bytes, 0x00020000);
+        const u32x2 bits = {(unsigned)__double2loint(T), (unsigned)__double2hiint(T)};
+        __builtin_amdgcn_raw_buffer_store_b64(bits, rs, f8, 0, 0);
+    }
+}
+
+hipError_t rtus_launch_tt_layers3(const double* z_if, const double* c, int n_if, const double* xe, const double* ye, const double* ze,
+                                  int n_e, const double* xf, const double* yf, const double* zf, int n_f, double* tt, hipStream_t s)
+{
+    Layers3Args g = {};
+    LayerArgs& a = g.a;
+    for (int i = 0; i < RTUS_MAX_LAYERS; ++i) a.z_if[i] = i < n_if ? z_if[i] : INFINITY;
+    for (int i = 0; i <= RTUS_MAX_LAYERS; ++i) { a.c[i] = i <= n_if ? c[i] : 1.0; a.inv_c[i] = 1.0 / a.c[i]; }
+    a.n_if = n_if; a.xe = xe; a.ze = ze; a.xf = xf; a.zf = zf; a.tt = tt; a.n_e = n_e; a.n_f = n_f;
+    g.ye = ye; g.yf = yf;
+    g.gx = (n_f + RTUS_BLOCK - 1) / RTUS_BLOCK;
+    const long long wgs = (long long)g.gx * ((n_e + RTUS_TT_LAYERS3_ROWS - 1) / RTUS_TT_LAYERS3_ROWS);
+    if (n_f >= (1 << 29) || wgs > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)wgs), block(RTUS_BLOCK);
+    switch (n_if + 1) {
+        case 1: hipLaunchKernelGGL(rtus_tt_layers3_kernel<1>, grid, block, 0, s, g); break;
+        case 2: hipLaunchKernelGGL(rtus_tt_layers3_kernel<2>, grid, block, 0, s, g); break;
+        case 3: hipLaunchKernelGGL(rtus_tt_layers3_kernel<3>, grid, block, 0, s, g); break;
+        case 4: hipLaunchKernelGGL(rtus_tt_layers3_kernel<4>, grid, block, 0, s, g); break;
+        case 5: hipLaunchKernelGGL(rtus_tt_layers3_kernel<5>, grid, block, 0, s, g); break;
+        case 6: hipLaunchKernelGGL(rtus_tt_layers3_kernel<6>, grid, block, 0, s, g); break;
+        case 7: hipLaunchKernelGGL(rtus_tt_layers3_kernel<7>, grid, block, 0, s, g); break;
+        case 8: hipLaunchKernelGGL(rtus_tt_layers3_kernel<8>, grid, block, 0, s, g); break;
+        case 9: hipLaunchKernelGGL(rtus_tt_layers3_kernel<9>, grid, block, 0, s, g); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}

@@ -233,6 +233,24 @@ def tt_layers_sorted_dev(z_if, c, xe, ze, xf, zf, out=None, ws=None, taup=False)
     return out
 
 
+def tt_layers3_dev(z_if, c, xe, ye, ze, xf, yf, zf, out=None):
+    """Matrix arrays: Fermat travel times in three dimensions through horizontal layers (rtus_tt_layers3_dev) -> [n_e, n_f];
+    z_if/c are small HOST sequences, the six coordinate vectors float64 CUDA tensors on one device.  Each entry depends on its own
+    pair only, so a slice of the elements or of the points gives that slice of the table bit for bit.  Runs on the current stream
+    of the tensors' device; with ``out`` given nothing is allocated, and nothing synchronises (capturable)."""
+    z_if, c = _api._medium(z_if, c, flat=True)
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    if _chk(ye, "ye").numel() != n_e or _chk(yf, "yf").numel() != n_f:
+        raise ValueError("xe/ye/ze and xf/yf/zf must pair up")
+    out = _result(out, (n_e, n_f), xe)
+    if any(t.device != xe.device for t in (ye, ze, xf, yf, zf, out)):
+        raise ValueError("xe, ye, ze, xf, yf, zf and out must be on one device")
+    st = _lib.lib().rtus_tt_layers3_dev(z_if.ctypes.data if z_if.size else None, c.ctypes.data, z_if.size, _p(xe), _p(ye), _p(ze), n_e,
+                                        _p(xf), _p(yf), _p(zf), n_f, _p(out), 0, _stream(xe))
+    _lib.check(st, "rtus_tt_layers3_dev")
+    return out
+
+
 def rows_per_block(n_rows_total, n_f, dtype=torch.float64):
     """Rows the table kernels solve per workgroup for a table of this size: shard boundaries that are multiples of it
     reproduce the one-launch table bit for bit (rtus_table_rows_per_block)."""
