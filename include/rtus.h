@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RTUS_VERSION 126 /* 0.1.25: rtus_tt_layers3[_dev] (matrix arrays: element x point travel times in three dimensions through horizontal layers) */
+#define RTUS_VERSION 127 /* 0.1.26: rtus_tt_aniso_surface[_dev], rtus_tt_aniso_direct[_dev] (travel times into an anisotropic part: the group slowness as a series in the ray angle) */
 
 typedef enum rtus_status {
     RTUS_OK = 0,
@@ -1674,6 +1674,63 @@ int rtus_tt_layers3(const double *z_if, const double *c, int n_if,
                     const double *xe, const double *ye, const double *ze, int n_e,
                     const double *xf, const double *yf, const double *zf, int n_f,
                     double *tt, unsigned flags, int device);
+
+/* ------------------------------------------------------------------------------------------
+ * Travel times into a homogeneous ANISOTROPIC part (austenitic weld metal, cladding, carbon-fibre laminate): the speed depends on
+ * the ray's direction.  NOT IN THE REFERENCE — "parity unpinned"; checked against tests/aniso_numpy.py, with an isotropic series
+ * against rtus_tt_surface, and with an elliptical one under a flat surface against rtus_tt_layers at stretched depths.
+ *
+ * The medium is its GROUP SLOWNESS over the ray's direction, a Fourier series of period pi:
+ *
+ *     S(psi) = a[0] + sum over k = 1 .. K of ( a[k] cos 2k psi + b[k] sin 2k psi ),    0 <= K <= 16,   b[0] is ignored
+ *
+ *   psi           the ray's angle from the +z axis (depth, down), positive towards +x: a leg from P to F has
+ *                 psi = atan2(F_x - P_x, F_z - P_z); its sign is immaterial (the period).  The time along a straight leg of
+ *                 length L is L S(psi).  K = 0, a[0] = 1 / c2 is the isotropic medium.
+ *   a, b [K + 1]  HOST memory in both twins (passed to the kernels by value).  -1 (RTUS_ERR_INVALID_ARG) for K outside 0 .. 16,
+ *                 for a coefficient that is not finite, and for a series that is not positive at one of the 4096 angles
+ *                 psi_i = i pi / 4096.  The medium IS the series: how a series is fitted to a crystal's group slowness is the
+ *                 host's business (the Python package: group_slowness_ti, fit_group_slowness, elliptical_slowness).
+ *
+ * rtus_tt_aniso_surface: through ONE measured surface, the couplant (c1) above it.  x0, dx, zs, n_s, c1, xe, ze, xf, zf, tt,
+ *   x_entry, the workspace and the limits are rtus_tt_surface's, and so is the definition with the second leg changed:
+ *
+ *     T(x) = |E - S(x)| / c1 + |F - S(x)| S(psi(x)),    S(x) = (x, s(x)),  psi(x) the direction from S(x) to F
+ *
+ *   the entry is the LEAST T OVER THE INTERIOR LOCAL MINIMA of T; NaN without one, for an element with ze >= min s, for a focal
+ *   point outside the extent or with zf <= s(xf), and for non-finite coordinates.  Occlusion is not checked.
+ *   Guarantee: every interior local minimum whose basin spans at least one profile segment dx centred on it is found — the basin
+ *   running from the minimum to its neighbouring stationary points of T or to the ends of the extent; a minimum qualifies when
+ *   each neighbouring STATIONARY point is at least dx / 2 away (an end of the extent always does).  Narrower minima may be
+ *   missed; a missed minimum can only make the reported time later (or NaN), never earlier.  The entry is the least T over the
+ *   found minima where there are at most three of them.  With four or more, the three are chosen by a lower bound of each one's T
+ *   taken at a scan point next to it (spacing dx / 4: within T'' (dx / 4)^2 of the minimum's own T, ~2e-8 s on a 1 mm grid); the
+ *   least minimum can be left out where it is within that of the third chosen one, and the entry is then late by at most that much.
+ *   Determinism: an entry depends only on its element, its focal point, the profile, c1 and the coefficients — not on which other
+ *   elements or focal points share the call (the bits of a row block or a focal-point subset are those of the whole table).
+ *   The _dev entry runs rtus_tt_surface's set-up kernel (into d_workspace: rtus_tt_surface_workspace_bytes(n_s) bytes, 256-byte
+ *   aligned, -4 otherwise) and the table kernel on `stream`: no allocation, no host synchronisation (capturable).
+ *
+ * rtus_tt_aniso_direct: CONTACT, the probe on the part and no couplant path: the ray is straight, tt[e][f] = |F - E| S(psi), psi
+ *   the direction from E to F.  Any relative position is accepted (a point above the element: the period); 0 at zero distance;
+ *   NaN for a non-finite coordinate.  n_e <= 65535 (-5 beyond).  Each entry depends on its own pair and the coefficients only.
+ * ---------------------------------------------------------------------------------------- */
+int rtus_tt_aniso_surface_dev(double x0, double dx, const double *d_zs, int n_s, double c1,
+                              const double *a, const double *b, int K,
+                              const double *d_xe, const double *d_ze, int n_e,
+                              const double *d_xf, const double *d_zf, int n_f,
+                              double *d_tt, double *d_x_entry, void *d_workspace, size_t workspace_bytes, void *stream);
+int rtus_tt_aniso_surface(double x0, double dx, const double *zs, int n_s, double c1,
+                          const double *a, const double *b, int K,
+                          const double *xe, const double *ze, int n_e,
+                          const double *xf, const double *zf, int n_f,
+                          double *tt, double *x_entry, int device);
+int rtus_tt_aniso_direct_dev(const double *a, const double *b, int K,
+                             const double *d_xe, const double *d_ze, int n_e,
+                             const double *d_xf, const double *d_zf, int n_f, double *d_tt, void *stream);
+int rtus_tt_aniso_direct(const double *a, const double *b, int K,
+                         const double *xe, const double *ze, int n_e,
+                         const double *xf, const double *zf, int n_f, double *tt, int device);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,8 @@ from .api import (ALPHA_MAX, KEYS, Params, configure, match_elements, ray_hits, 
                   centre_frequency, frames_pack, frames_unpack, tfm_frames, frames_pack_i16, frames_unpack_i16,
                   tfm_envelope_frames, fmc_analytic_i16,
                   travel_time_layers_3d, skip_travel_time_layers_3d, view_legs_layers_3d, matrix_array, volume_grid)
+from .aniso import (travel_time_surface_aniso, travel_time_aniso, group_slowness_ti, fit_group_slowness,  # noqa: F401
+                    elliptical_slowness, eval_group_slowness)
 
 __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hits", "travel_time_layers", "travel_time_lens", "travel_time_surface", "fmc_table_layers", "solve_travel_times", "solve_path", "SOLVE_PATHS", "focal_delays", "tfm_image", "fmc_analytic",
            "measure_surface", "adaptive_tfm", "tfm_analytic", "tfm_phase", "pw_delays", "pw_travel_time_layers", "pw_travel_time_surface",
@@ -35,5 +37,6 @@ __all__ = ["shoot_rays", "shoot_batch", "sweep_batch", "match_elements", "ray_hi
            "hmc_unpack", "hmc_analytic", "tfm_hmc", "tfm_analytic_hmc", "tfm_iq", "tfm_iq_hmc", "tfm_phase_hmc", "tfm_weighted_hmc", "centre_frequency", "frames_pack",
            "frames_unpack", "tfm_frames", "frames_pack_i16", "frames_unpack_i16", "tfm_envelope_frames",
            "fmc_analytic_i16", "travel_time_layers_3d", "skip_travel_time_layers_3d", "view_legs_layers_3d", "matrix_array",
-           "volume_grid", "Params",
+           "volume_grid", "travel_time_surface_aniso", "travel_time_aniso", "group_slowness_ti", "fit_group_slowness",
+           "elliptical_slowness", "eval_group_slowness", "Params",
            "configure", "reference_elements", "ALPHA_MAX", "KEYS", "build", "lib", "RtusError"]

@@ -224,6 +224,11 @@ PROTOTYPES = (
     # matrix arrays: travel times in three dimensions through horizontal layers
     ("rtus_tt_layers3_dev", i, [vp, vp, i, vp, vp, vp, i, vp, vp, vp, i, vp, u, vp], 126),
     ("rtus_tt_layers3", i, [vp, vp, i, vp, vp, vp, i, vp, vp, vp, i, vp, u, i], 126),
+    # an anisotropic part: the group slowness as a series in the ray angle
+    ("rtus_tt_aniso_surface_dev", i, [dd, dd, vp, i, dd, vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, vp, sz, vp], 127),
+    ("rtus_tt_aniso_surface", i, [dd, dd, vp, i, dd, vp, vp, i, vp, vp, i, vp, vp, i, vp, vp, i], 127),
+    ("rtus_tt_aniso_direct_dev", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, vp], 127),
+    ("rtus_tt_aniso_direct", i, [vp, vp, i, vp, vp, i, vp, vp, i, vp, i], 127),
 )
 EXPORTS = tuple(p[0] for p in PROTOTYPES)
 

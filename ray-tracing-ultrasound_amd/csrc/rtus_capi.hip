@@ -63,6 +63,12 @@ size_t rtus_surface_ws_bytes(int n_s);
 hipError_t rtus_launch_tt_surface_skip(double x0, double dx, const double* zs, int n_s, double c1, double c_down, double c_up, double z_back,
                                        const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
                                        double* xent, double* xback, void* ws, hipStream_t s);
+hipError_t rtus_launch_tt_aniso_surface(double x0, double dx, const double* zs, int n_s, double c1, const double* a, const double* b, int K,
+                                        const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f,
+                                        double* tt, double* xent, void* ws, hipStream_t s);
+hipError_t rtus_launch_tt_aniso_direct(const double* a, const double* b, int K, const double* xe, const double* ze, int n_e,
+                                       const double* xf, const double* zf, int n_f, double* tt, hipStream_t s);
+bool rtus_aniso_series_ok(const double* a, const double* b, int K);
 hipError_t rtus_launch_focal_delays(const double* tt, int n_e, int n_f, double* delays, hipStream_t s);
 hipError_t rtus_launch_tfm(const float* fmc, int n_tx, int n_rx, int n_t, double fs, double t0, const double* tt_tx,
                            const double* tt_rx, int n_f, float* image, hipStream_t s);
@@ -981,6 +987,86 @@ int rtus_tt_surface_skip(double x0, double dx, const double* zs, int n_s, double
     if ((st = S.flush())) return st;
     LAUNCH_TRY(rtus_launch_tt_surface_skip(x0, dx, dzs, n_s, c1, c_down, c_up, z_back, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, dxb, ws,
                                            S.a->stream));
+    return S.finish();
+}
+
+// ---------------------------------------------------------------------------- an anisotropic part: the group slowness as a series
+// rtus_tt_surface's checks (1 / a[0] in c2's place once the series is known to be positive) and the series' own
+static int check_aniso_surface(double x0, double dx, const void* zs, int n_s, double c1, const double* a, const double* b, int K,
+                               const void* xe, const void* ze, int n_e, const void* xf, const void* zf, int n_f, const void* tt)
+{
+    if (!rtus_aniso_series_ok(a, b, K)) return RTUS_ERR_INVALID_ARG;
+    return check_surface(x0, dx, zs, n_s, c1, 1.0 / a[0], xe, ze, n_e, xf, zf, n_f, tt);
+}
+
+int rtus_tt_aniso_surface_dev(double x0, double dx, const double* d_zs, int n_s, double c1, const double* a, const double* b, int K,
+                              const double* d_xe, const double* d_ze, int n_e, const double* d_xf, const double* d_zf, int n_f,
+                              double* d_tt, double* d_x_entry, void* d_workspace, size_t workspace_bytes, void* stream)
+{
+    int st = check_aniso_surface(x0, dx, d_zs, n_s, c1, a, b, K, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    if ((st = check_workspace(d_workspace, workspace_bytes, rtus_surface_ws_bytes(n_s), 256))) return st;
+    LAUNCH_TRY(rtus_launch_tt_aniso_surface(x0, dx, d_zs, n_s, c1, a, b, K, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, d_x_entry, d_workspace,
+                                            (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tt_aniso_surface(double x0, double dx, const double* zs, int n_s, double c1, const double* a, const double* b, int K,
+                          const double* xe, const double* ze, int n_e, const double* xf, const double* zf, int n_f, double* tt,
+                          double* x_entry, int device)
+{
+    int st = check_aniso_surface(x0, dx, zs, n_s, c1, a, b, K, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    const size_t tot = (size_t)n_e * n_f;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dzs, *dxe, *dze, *dxf, *dzf, *dtt, *dxn;
+    char* ws;
+    S.in(dzs, zs, n_s);
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, tot);
+    S.out(dxn, x_entry, tot);
+    S.scratch(ws, rtus_surface_ws_bytes(n_s));
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tt_aniso_surface(x0, dx, dzs, n_s, c1, a, b, K, dxe, dze, n_e, dxf, dzf, n_f, dtt, dxn, ws, S.a->stream));
+    return S.finish();
+}
+
+// contact: the probe on the part
+static int check_aniso_direct(const double* a, const double* b, int K, const void* xe, const void* ze, int n_e, const void* xf,
+                              const void* zf, int n_f, const void* tt)
+{
+    if (!xe || !ze || !xf || !zf || !tt || n_e <= 0 || n_f <= 0 || !rtus_aniso_series_ok(a, b, K)) return RTUS_ERR_INVALID_ARG;
+    return n_e > 65535 ? RTUS_ERR_UNSUPPORTED : RTUS_OK;                      // grid.y: one element per workgroup row
+}
+
+int rtus_tt_aniso_direct_dev(const double* a, const double* b, int K, const double* d_xe, const double* d_ze, int n_e, const double* d_xf,
+                             const double* d_zf, int n_f, double* d_tt, void* stream)
+{
+    const int st = check_aniso_direct(a, b, K, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt);
+    if (st) return st;
+    LAUNCH_TRY(rtus_launch_tt_aniso_direct(a, b, K, d_xe, d_ze, n_e, d_xf, d_zf, n_f, d_tt, (hipStream_t)stream));
+    return RTUS_OK;
+}
+
+int rtus_tt_aniso_direct(const double* a, const double* b, int K, const double* xe, const double* ze, int n_e, const double* xf,
+                         const double* zf, int n_f, double* tt, int device)
+{
+    int st = check_aniso_direct(a, b, K, xe, ze, n_e, xf, zf, n_f, tt);
+    if (st) return st;
+    Session S;
+    if ((st = S.open(device))) return st;
+    double *dxe, *dze, *dxf, *dzf, *dtt;
+    S.in(dxe, xe, n_e);
+    S.in(dze, ze, n_e);
+    S.in(dxf, xf, n_f);
+    S.in(dzf, zf, n_f);
+    S.out(dtt, tt, (size_t)n_e * n_f);
+    if ((st = S.flush())) return st;
+    LAUNCH_TRY(rtus_launch_tt_aniso_direct(a, b, K, dxe, dze, n_e, dxf, dzf, n_f, dtt, S.a->stream));
     return S.finish();
 }
 

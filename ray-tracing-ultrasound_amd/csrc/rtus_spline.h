@@ -11,6 +11,16 @@ size_t rtus_surface_ws_bytes(int n_s);
 // the set-up kernel alone: the spline's coefficients [n_s - 1][4] land in the workspace at *coef (the scan points are written too, as
 // for a table launch)
 hipError_t rtus_launch_surface_setup(const double* zs, int n_s, double x0, double dx, void* ws, const double** coef, hipStream_t s);
+// ... for a table kernel in another file (rtus_aniso.hip): also where the set-up leaves the m scan points P_j = x0 + j dx / 4 as
+// fp32 (x - xo, s - zo, s', 0) and the profile's least and greatest depth (smin[0], smin[1])
+struct RtusSurfaceScan {
+    const double* coef;
+    const float4* pts;
+    const double* smin;
+    double xo, zo;
+    int m;
+};
+hipError_t rtus_launch_surface_setup_scan(const double* zs, int n_s, double x0, double dx, void* ws, RtusSurfaceScan* scan, hipStream_t s);
 
 // s, s', s'' at x (x clamped to the extent's segments: outside it the end segments' cubics continue)
 __device__ __forceinline__ void spline_eval(const double* __restrict__ coef, int n_s, double x0, double dx, double inv_dx, double x,

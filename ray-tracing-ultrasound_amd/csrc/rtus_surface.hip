@@ -566,3 +566,12 @@ hipError_t rtus_launch_surface_setup(const double* zs, int n_s, double x0, doubl
     hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, surf_xo(x0, dx, n_s), surf_zo, w);
     return hipGetLastError();
 }
+
+// ... and where it leaves the scan points and the depth extremes (rtus_spline.h)
+hipError_t rtus_launch_surface_setup_scan(const double* zs, int n_s, double x0, double dx, void* ws, RtusSurfaceScan* scan, hipStream_t s)
+{
+    const SurfWs w = surf_ws(ws, n_s);
+    *scan = RtusSurfaceScan{w.coef, w.pts, w.smin, surf_xo(x0, dx, n_s), surf_zo, surf_points(n_s)};
+    hipLaunchKernelGGL(rtus_surface_setup_kernel, dim3(1), dim3(RTUS_BLOCK), 0, s, zs, n_s, x0, dx, scan->xo, scan->zo, w);
+    return hipGetLastError();
+}

@@ -329,6 +329,39 @@ def tt_surface_dev(x0, dx, zs, c1, c2, xe, ze, xf, zf, out=None, x_entry=None):
     return out
 
 
+def tt_surface_aniso_dev(x0, dx, zs, c1, slowness, xe, ze, xf, zf, out=None, x_entry=None):
+    """Travel times through one curved interface into an anisotropic part (rtus_tt_aniso_surface_dev;
+    aniso.travel_time_surface_aniso's definition) on float64 CUDA tensors -> out [n_e, n_f] (and x_entry [n_e, n_f] when a tensor
+    is given for it).  ``slowness`` = (a, b): host vectors, the group slowness's series.  The spline's workspace is allocated here;
+    asynchronous on the current stream."""
+    from .aniso import _series
+    _chk(zs, "zs")
+    a, b, K = _series(slowness)
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
+    _optional(n_e * n_f, x_entry=x_entry)
+    need = int(_lib.lib().rtus_tt_surface_workspace_bytes(zs.numel()))
+    ws = _workspace(None, need, xe)
+    st = _lib.lib().rtus_tt_aniso_surface_dev(float(x0), float(dx), _p(zs), zs.numel(), float(c1), a.ctypes.data, b.ctypes.data, K,
+                                              _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(out), _p(x_entry), _p(ws), need, _stream(xe))
+    _lib.check(st, "rtus_tt_aniso_surface_dev")
+    return out
+
+
+def tt_aniso_dev(slowness, xe, ze, xf, zf, out=None):
+    """Contact travel times inside an anisotropic part (rtus_tt_aniso_direct_dev; aniso.travel_time_aniso's definition) on float64
+    CUDA tensors -> out [n_e, n_f].  ``slowness`` = (a, b): host vectors.  No allocation beyond ``out``; asynchronous on the
+    current stream."""
+    from .aniso import _series
+    a, b, K = _series(slowness)
+    n_e, n_f = _pair(xe, ze, xf, zf)
+    out = _result(out, (n_e, n_f), xe)
+    st = _lib.lib().rtus_tt_aniso_direct_dev(a.ctypes.data, b.ctypes.data, K, _p(xe), _p(ze), n_e, _p(xf), _p(zf), n_f, _p(out),
+                                             _stream(xe))
+    _lib.check(st, "rtus_tt_aniso_direct_dev")
+    return out
+
+
 def focal_delays_dev(tt, out=None):
     """delays[e, f] = max_e' tt[e', f] - tt[e, f] on device (NaN-aware); ``out`` may be ``tt`` itself."""
     _chk(tt, "tt")
